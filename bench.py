@@ -173,6 +173,7 @@ def bench_tsn(args, rank, world, device, stream):
     import torch.distributed as dist
 
     gather_events = []
+    gathered = [feat]                                        # what a caller of the step receives: the (gathered) feature rows
 
     def step(timed=False):
         model.forward_device(crops.data_ptr(), n_crops, T_SEG, tsn_net.RGB_MEAN)
@@ -180,7 +181,7 @@ def bench_tsn(args, rank, world, device, stream):
             if timed:                                        # the collective's own time: events on the stream it is ordered on
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-            all_gather_rows(feat, world * B_CLIPS)           # RCCL over xGMI: per-GPU feature blocks
+            gathered[0] = all_gather_rows(feat, world * B_CLIPS)     # RCCL over xGMI: per-GPU feature blocks
             if timed:
                 e1.record(stream)
                 gather_events.append((e0, e1))
@@ -214,6 +215,17 @@ def bench_tsn(args, rank, world, device, stream):
     rank_ms = dt_rank / args.steps * 1e3
     gather_ms = float(np.mean([a.elapsed_time(b) for a, b in gather_events])) if gather_events else None
     feats = feat.clone()
+    outputs = None
+    if args.dump_outputs:                                    # the last timed step's results, as the caller of the step gets them
+        _, ps_ptr = model.feat_devptr()
+        outputs = {"features": gathered[0].detach().cpu().numpy().astype(np.float64),
+                   "per_snippet_global_pool": dev_tensor(ps_ptr, (n_crops, model.feature_dim), "<f4", device).cpu().numpy().astype(np.float32)}
+    if not args.full:                                        # a plain run: the headline only, no one-stream region, no per-kernel figures
+        roof = {"rank_ms_per_step": rank_ms, "flops_per_step": model.flops_per_crop() * n_crops}
+        if gather_ms is not None:
+            roof["all_gather_ms_per_step"] = gather_ms
+        _save_tiles(args, rank, model, n_crops)
+        return dt, roof, model, crops, feats, outputs
     # The same K steps once more, ALL on one stream, `every`-th step with events on every launch: the timed mode of rounds 1-4,
     # reported beside `value` (never instead of it) -- and the region every per-kernel figure of the line comes from.
     single_ms = float("nan")
@@ -262,11 +274,23 @@ def bench_tsn(args, rank, world, device, stream):
             roof["pmc_source"] = "profiles/%s: SQ_INSTS_MFMA x 64 / SIMD-cycles per kernel family (tools/pmc_mfma.sh), committed, not collected in this run" % name
             break
     model.set_profile(0)
+    _save_tiles(args, rank, model, n_crops)
+    return dt, roof, model, crops, feats, outputs
+
+
+def _save_tiles(args, rank, model, n_crops):
     if args.tiles and rank == 0 and not os.path.exists(args.tiles):
         os.makedirs(os.path.dirname(os.path.abspath(args.tiles)), exist_ok=True)
         with open(args.tiles, "w") as f:
             json.dump({"n_crops": n_crops, "tiles": model.layer_tiles(n_crops).tolist()}, f)
-    return dt, roof, model, crops, feats
+
+
+def dump_outputs(outdir, outputs):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float32 / float64) of what the timed path computed in its last step."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def bench_two_stream(args, device, stream, with_cpu):
@@ -1109,13 +1133,17 @@ def compact(out):
                                     "launches_per_step", "conv_ms_per_step", "other_kernels_ms_per_step", "all_gather_ms_per_step", "profiled_steps",
                                     "traffic_per_step"])
     line["roofline"].setdefault("traffic", None)
-    line["roofline"]["kernel"] = "%d conv launches/step: conv_igemm(_pipe) / pool_gemm + wino_f2x2_3x3 kernels, v_mfma_f32_32x32x2" % roof["launches_per_step"]
-    line["roofline"]["families"] = {k: _pick(v, ["matrix_pipe_frac", "ms_per_step", "launches"]) for k, v in roof.get("families", {}).items()}
+    if "launches_per_step" in roof:
+        line["roofline"]["kernel"] = "%d conv launches/step: conv_igemm(_pipe) / pool_gemm + wino_f2x2_3x3 kernels, v_mfma_f32_32x32x2" % roof["launches_per_step"]
+    if "families" in roof:
+        line["roofline"]["families"] = {k: _pick(v, ["matrix_pipe_frac", "ms_per_step", "launches"]) for k, v in roof["families"].items()}
     if isinstance(roof.get("rank_ms_per_step"), dict):
         line["roofline"]["rank_ms_per_step"] = _pick(roof["rank_ms_per_step"], ["min", "max", "all"])
     if "pmc_matrix_pipe_utilisation" in roof:
         line["roofline"]["pmc_matrix_pipe"] = roof["pmc_matrix_pipe_utilisation"]
-    line["config"]["timed_mode"] = "vq_tsn_forward default: 2 sub-batch streams, no events; per-kernel fields: " + str(roof.get("kernel_fields_from"))
+    line["config"]["timed_mode"] = "vq_tsn_forward default: 2 sub-batch streams, no events"
+    if "kernel_fields_from" in roof:
+        line["config"]["timed_mode"] += "; per-kernel fields: " + str(roof["kernel_fields_from"])
     if "single_stream" in out:
         line["single_stream"] = _pick(out["single_stream"], ["value", "ms_per_step", "frac", "profiled_steps"])
         line["single_stream"].update(_pick(out["single_stream"].get("kernels") or {}, ["conv_ms_per_step", "kernel_frac", "matrix_pipe_frac"]))
@@ -1237,7 +1265,18 @@ def main():
                                                         "itself; tools/profile_round.sh shares one directory between its runs so that the "
                                                         "run under rocprofv3 traces no autotune launch)")
     ap.add_argument("--tiles", default=None, help="JSON file: load the conv tiling table if it exists, else write it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the one-stream region and its per-kernel roofline, CPU baselines and live parity, "
+                         "configs[2] two-stream, the similarity scan, query rounds, flow, JPEG and the end-to-end command lines (the --skip-* "
+                         "and --profile-* options narrow it; --profile-* imply it).  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy: features.npy (fp64 consensus features "
+                         "[n_gpus x 32, 1024], as the step's caller gets them) and per_snippet_global_pool.npy (fp32 [96, 1024], rank 0); "
+                         "the inputs are seeded, so runs with the same arguments compare output for output")
     args = ap.parse_args()
+    if args.profile_only or args.profile_two_stream:        # profiler runs are about the per-kernel figures
+        args.full = True
     rc = self_launch(args)                                   # before ANY GPU call of this process
     if rc is not None:
         sys.exit(rc)
@@ -1280,7 +1319,9 @@ def main():
                      "devices_visible": torch.cuda.device_count(), "rank0_device": torch.cuda.get_device_name(device),
                      "rehearsal_on_one_gpu": rehearse}
 
-    dt, roof, model, crops, feats = bench_tsn(args, rank, world, device, stream)
+    dt, roof, model, crops, feats, outputs = bench_tsn(args, rank, world, device, stream)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1303,6 +1344,20 @@ def main():
     # algorithmic FLOPs of a step (per GPU) over the whole timed step
     roof["achieved"] = roof["flops_per_step"] / out["ms_per_step"] / 1e9
     roof["frac"] = roof["achieved"] / PEAK_FP32_MFMA_TFLOPS
+    if not args.full:
+        roof.update({"bound": "mfma", "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "traffic": None})
+        out["config"]["timed_mode"] = "vq_tsn_forward's default: 2 sub-batches on 2 HIP streams, no launch carries an event"
+        model.close()
+        del crops
+        if rank == 0:
+            if args.details:
+                os.makedirs(os.path.dirname(os.path.abspath(args.details)) or ".", exist_ok=True)
+                with open(args.details, "w") as f:
+                    json.dump(out, f)
+            print(json.dumps(out if args.verbose else compact(out), separators=(",", ":")), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     out["config"]["timed_mode"] = ("all steps on one stream (--profile-only)" if args.profile_only else
                                    "vq_tsn_forward's default: 2 sub-batches on 2 HIP streams, no launch carries an event; per-kernel fields from the " + roof["kernel_fields_from"])
     up = torch.tensor([roof.pop("single_stream_ms_per_step")], dtype=torch.float64, device=device)

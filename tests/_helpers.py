@@ -19,6 +19,21 @@ def golden_npy(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+def reference_features(dest):
+    """The reference's shipped feature CSVs (tests/golden/reference_features, xz-compressed) unpacked byte for byte under ``dest``,
+    in their data/features layout; returns ``dest``."""
+    import lzma
+    src = os.path.join(GOLDEN, "reference_features")
+    for dirpath, _dirs, files in os.walk(src):
+        for fn in files:
+            if fn.endswith(".xz"):
+                out = os.path.join(dest, os.path.relpath(os.path.join(dirpath, fn[:-3]), src))
+                os.makedirs(os.path.dirname(out), exist_ok=True)
+                with lzma.open(os.path.join(dirpath, fn)) as f, open(out, "wb") as g:
+                    g.write(f.read())
+    return dest
+
+
 def records_from_dense(x, clip_ids, splits, present=None, order="split_major", extra=()):
     """[N,S,E,D] -> API feature records (the wire format of ticket.py:374-381)."""
     n, s, e, d = x.shape

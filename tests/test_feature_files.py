@@ -9,8 +9,7 @@ import pytest
 import tsn_oracle as to
 from video_query_algorithms_amd.tsn import feature_csv, frames
 
-REF_CSV = ("/root/reference/data/features/stock-video-clips_features/DowntownBrooklynDrive_480p/UCF101_split1/"
-           "rgb_global_pool_features.csv")
+REF_CSV = "stock-video-clips_features/DowntownBrooklynDrive_480p/UCF101_split1/rgb_global_pool_features.csv"
 
 
 def test_writer_layout_and_number_format(tmp_path):
@@ -34,16 +33,17 @@ def test_writer_layout_and_number_format(tmp_path):
     assert nsplit == 2 and set(streams) == {"rgb", "warped_optical_flow"}
 
 
-REF_CSV_G12 = ("/root/reference/data/features/SHRP2_Forward_clips_features/S06NDS_Sample_120406_1451_00186_Forward/"
+REF_CSV_G12 = ("SHRP2_Forward_clips_features/S06NDS_Sample_120406_1451_00186_Forward/"
                "UCF101_split2/warped_optical_flow_global_pool_features.csv")
 
 
-@pytest.mark.parametrize("path,number_format", [(REF_CSV, "repr"), (REF_CSV_G12, "g12")])
+@pytest.mark.parametrize("path,number_format", [(REF_CSV, "repr"), (REF_CSV_G12, "g12")],
+                         ids=["stock_split1_rgb-repr", "shrp2_split2_flow-g12"])
 def test_writer_reproduces_a_shipped_reference_file_byte_for_byte(tmp_path, path, number_format):
     """The reference ships files of both numpy float-str generations (feature_csv docstring); each is reproduced
-    byte for byte by the matching number_format."""
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present (GPU box)")
+    byte for byte by the matching number_format.  The files: tests/golden/reference_features (oracle/gen_golden_reference.py)."""
+    from _helpers import reference_features
+    path = os.path.join(reference_features(str(tmp_path / "ref")), path)
     meta, clips, feats = feature_csv.read_features(path)
     raw = open(path, "rb").read()
     header = raw.split(b"\n", 1)[0].decode()
@@ -338,16 +338,17 @@ def test_feature_store_round_trip_and_csv_tree_import(tmp_path):
         fs.save_store(str(tmp_path / "s3"), x, [1, 1, 2, 3, 4], ("rgb", "warped_optical_flow"), (1, 2, 3))
 
 
-REF_TREE = "/root/reference/data/features/stock-video-clips_features"
+REF_TREE = "stock-video-clips_features"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TREE), reason="the reference checkout (build container only) is not here")
 def test_store_from_the_reference_csv_tree_matches_the_golden_subset(tmp_path):
-    """The shipped data/features tree of the reference -> binary store (fp64): the 24 golden clips (tests/golden/
-    real_subset_x.npy, written by oracle/gen_golden.py from the same files) come back value for value."""
+    """The shipped data/features tree of the reference (tests/golden/reference_features) -> binary store (fp64): the 24 golden clips
+    (tests/golden/real_subset_x.npy, written by oracle/gen_golden.py from the same files) come back value for value."""
     import video_query_algorithms_amd  # noqa: F401
+    from _helpers import reference_features
     from video_query_algorithms_amd import feature_store as fs
-    out = fs.store_from_csv_tree(REF_TREE, str(tmp_path / "store"), dtype=np.float64)
+    tree = os.path.join(reference_features(str(tmp_path / "ref")), REF_TREE)
+    out = fs.store_from_csv_tree(tree, str(tmp_path / "store"), dtype=np.float64)
     meta, feats, ids, present = fs.open_store(out)
     assert meta["splits"] == [1, 2, 3] and meta["dim"] == 1024 and present is None          # dense: 87 clips x 2 x 3
     clips = json.load(open(os.path.join(out, "clips.json")))
@@ -453,21 +454,21 @@ def test_native_row_formatter_prints_like_str_of_numpy_float64():
 
 
 def _reference_rgb_and_flow_values():
-    """Feature values of the reference's own shipped CSVs in their lossless (17-digit) number format: read from /root/reference
-    where it exists (the build container), and always the committed 24-clip extract of the same files (tests/golden/real_subset_x.npy,
-    exact fp64, written by oracle/gen_golden.py)."""
+    """Feature values of the reference's own shipped CSVs in their lossless (17-digit) number format: the whole stock-video-clips tree
+    (tests/golden/reference_features) and the 24-clip extract of the same files (tests/golden/real_subset_x.npy, exact fp64, written by
+    oracle/gen_golden.py)."""
+    import lzma
     out = {"committed extract": np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "real_subset_x.npy"), allow_pickle=False).reshape(-1)}
-    root = "/root/reference/data/features/stock-video-clips_features"
-    if os.path.isdir(root):
-        vals = []
-        for dirpath, _dirs, files in sorted(os.walk(root)):
-            for f in sorted(files):
-                if f.endswith("_global_pool_features.csv"):
-                    with open(os.path.join(dirpath, f)) as fh:
-                        fh.readline()
-                        vals += [float(t) for line in fh for t in line.strip().split(",")[1:]]
-        assert len(vals) == 6 * 87 * 1024
-        out["reference CSVs"] = np.array(vals)
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_features", REF_TREE)
+    vals = []
+    for dirpath, _dirs, files in sorted(os.walk(root)):
+        for f in sorted(files):
+            if f.endswith("_global_pool_features.csv.xz"):
+                with lzma.open(os.path.join(dirpath, f), "rt") as fh:
+                    fh.readline()
+                    vals += [float(t) for line in fh for t in line.strip().split(",")[1:]]
+    assert len(vals) == 6 * 87 * 1024
+    out["reference CSVs"] = np.array(vals)
     return out
 
 

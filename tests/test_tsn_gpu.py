@@ -915,8 +915,8 @@ def test_bench_two_rank_control_flow_rehearsal(tsn):
     env = dict(os.environ, VQ_BENCH_REHEARSE="1")
     for world, port in ((2, "29533"), (4, "29535")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-               "--master-port", port, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--skip-sim",
-               "--skip-cpu"]
+               "--master-port", port, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full",
+               "--skip-sim", "--skip-cpu"]
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -940,7 +940,7 @@ def test_bench_two_rank_control_flow_rehearsal(tsn):
         assert len(lines[0]) < 4096                                 # the driver's record keeps the whole line
     # ``python bench.py --gpus 2`` with NO launcher starts its own ranks (before any GPU call) and prints the same one line
     plain = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--skip-cpu"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--skip-cpu"]
     p = subprocess.run(cmd, env=plain, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -955,6 +955,37 @@ def test_bench_two_rank_control_flow_rehearsal(tsn):
     p = subprocess.run(cmd + ["--skip-sim"], env=dict(plain, VQ_BENCH_FAIL_INIT_RANK="1"), capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "told to fail" in p.stderr and time.perf_counter() - t0 < 120
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(tsn, tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps and the one line -- nothing of what --full adds.  --dump-outputs
+    writes what the last timed step computed: the consensus features are the fp64 means of the per-snippet global_pool rows, and two
+    runs with the same arguments give the same bits (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumped = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["metric"] == "clips/sec TSN feature-extract" and line["unit"] == "clips/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+        assert line["value"] == pytest.approx(32 / line["ms_per_step"] * 1e3, rel=1e-3)
+        assert abs(line["roofline"]["frac"] * line["roofline"]["peak"] * line["ms_per_step"] - 390.06) < 0.5
+        assert not {"single_stream", "cpu_baseline", "two_stream", "similarity", "rounds", "flow", "jpeg", "e2e_cli"} & set(line)
+        feats = np.load(str(out_dir / "features.npy"))
+        ps = np.load(str(out_dir / "per_snippet_global_pool.npy"))
+        assert feats.dtype == np.float64 and feats.shape == (32, 1024) and ps.dtype == np.float32 and ps.shape == (96, 1024)
+        assert np.isfinite(feats).all() and (feats >= 0).all() and feats.max() > 0
+        assert (feats == to.consensus(ps, 3)).all()
+        dumped.append((feats, ps))
+    assert (dumped[0][0] == dumped[1][0]).all() and (dumped[0][1] == dumped[1][1]).all()
 
 
 def test_tiling_tables_survive_the_process(tsn, monkeypatch, tmp_path):

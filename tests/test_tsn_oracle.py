@@ -1,6 +1,7 @@
 """CPU: pins the pieces of the hot-path-A oracle that CAN be pinned here -- the torch calls against loop-level
 restatements of the Caffe layer rules, the driver logic against calcSig_wOF.py's documented cases, and the
-built-in graph against the reference's own prototxt (when the reference checkout is present)."""
+built-in graph against the reference's own prototxt (as parsed, pinned by digest under tests/golden)."""
+import json
 import os
 
 import numpy as np
@@ -8,7 +9,7 @@ import pytest
 
 import tsn_oracle as to
 
-REF_PROTO = "/root/reference/src/features_GPU_compute/models/ucf101/tsn_bn_inception_%s_deploy.prototxt"
+REF_PROTO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_prototxt.json")
 
 
 def test_frame_ticks_follow_calcsig():
@@ -66,12 +67,19 @@ def test_consensus_is_fp64_mean_of_fp32_snippets():
 
 
 def test_builtin_graph_equals_reference_prototxt():
-    if not os.path.exists(REF_PROTO % "rgb"):
-        pytest.skip("reference checkout not present (GPU box)")
+    """The reference's two deploy prototxts as load_prototxt parsed them are pinned by a digest of the layer list and the input
+    shape (tests/golden/reference_prototxt.json, oracle/gen_golden_reference.py): the built-in graph has the same digest, and so
+    has the graph parsed back from the prototxt written from it."""
+    from gen_golden_reference import layers_digest
     from video_query_algorithms_amd.tsn import bn_inception as bi
+    with open(REF_PROTO) as f:
+        ref = json.load(f)
     for name, c in (("rgb", 3), ("flow", 10)):
-        ref = bi.load_prototxt(REF_PROTO % name)
-        assert ref.layers == bi.bn_inception(c).layers and ref.input_shape == (c, 224, 224)
+        g = bi.bn_inception(c)
+        back = bi.parse_prototxt(bi.to_prototxt(g))
+        assert back.layers == g.layers and back.input_shape == g.input_shape
+        assert len(g.layers) == ref[name]["layers"] and layers_digest(g.layers) == ref[name]["layers_sha256"]
+        assert g.input_shape == tuple(ref[name]["input_shape"]) == (c, 224, 224)
 
 
 def test_plan_matches_survey_appendix_a():

@@ -4,9 +4,9 @@
 TAG=${1:-r06}
 OUT=gpurun_out/${TAG}_bench_repeat.txt
 mkdir -p gpurun_out
-echo "# python3 bench.py --steps 20 --warmup 5 --skip-cpu --skip-flow, three fresh processes on one box: cfg 2 value (product mode), single_stream, cfg 3, scan, rounds" > $OUT
+echo "# python3 bench.py --full --steps 20 --warmup 5 --skip-cpu --skip-flow, three fresh processes on one box: cfg 2 value (product mode), single_stream, cfg 3, scan, rounds" > $OUT
 for i in 1 2 3; do
-python3 bench.py --steps 20 --warmup 5 --skip-cpu --skip-flow 2>/dev/null | python3 -c "
+python3 bench.py --full --steps 20 --warmup 5 --skip-cpu --skip-flow 2>/dev/null | python3 -c "
 import json,sys
 l=json.loads([x for x in sys.stdin if x.startswith('{')][0])
 print('run $i: value %.1f clips/s (%.4f ms, frac %.4f)  single_stream %.1f (%.4f ms)  cfg3 %.1f (single %.1f)  scan %.2f q/s  query %.4f ms  weight_updates %.4f ms' % (

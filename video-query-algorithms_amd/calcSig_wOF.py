@@ -90,20 +90,22 @@ def _join_world(device: int):
     """(rank, world) of this process.  Under torchrun the rank binds its GPU BEFORE the communicator exists
     (``set_device`` + ``device_id``: RCCL then builds the communicator on that device instead of guessing at the first
     collective); backend "nccl" = RCCL, or gloo on a box without GPUs / with VQ_DIST_BACKEND=gloo (a rehearsal of the
-    N > 1 path on one card)."""
+    N > 1 path on one card).  The third value says whether this call made the process group (the command then tears it down
+    before it returns: a gloo group left to the interpreter's exit can abort the process after the work is done)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "RANK" not in os.environ or world <= 1:
-        return 0, 1
+        return 0, 1, False
     import torch
     import torch.distributed as dist
-    if not dist.is_initialized():
+    created = not dist.is_initialized()
+    if created:
         backend = os.environ.get("VQ_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         if backend == "nccl":
             torch.cuda.set_device(device)
             dist.init_process_group("nccl", device_id=torch.device("cuda", device))
         else:
             dist.init_process_group(backend)
-    return dist.get_rank(), dist.get_world_size()
+    return dist.get_rank(), dist.get_world_size(), created
 
 
 def _stack_rows(blocks, width):
@@ -199,7 +201,7 @@ def _main(argv=None, net_factory=None, program=None):
     device = gpu_list[local % len(gpu_list)] if gpu_list else local                    # calcSig_wOF.py:50-55
     if fanout.is_child() and "VQ_FANOUT_DEVICE" in os.environ:                         # the GPU the parent mapped this rank to
         device = int(os.environ["VQ_FANOUT_DEVICE"])
-    rank, world = _join_world(device)
+    rank, world, own_group = _join_world(device)
     if world == 1 and "torch" not in sys.modules:
         # one rank: nothing here needs torch (device buffers and streams come from the library, tsn/devmem.py) -- 0.8 s of import for a
         # process that takes 2.3 s for 256 clips.  Decided before the library is loaded: it must share ONE HIP runtime with torch if torch
@@ -440,6 +442,9 @@ def _main(argv=None, net_factory=None, program=None):
         job.result()                                                     # a writer's exception is the command's
     io_pool.shutdown()
     stamp("feature files written (torch imported: %s)" % ("torch" in sys.modules))
+    if own_group:
+        import torch.distributed as dist
+        dist.destroy_process_group()
     return 0
 
 
