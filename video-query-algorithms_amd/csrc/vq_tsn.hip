@@ -466,7 +466,7 @@ void conv_igemm_pipe_kernel(ConvArgs a) {
     const int ks = a.ksplit > 1 ? (int)blockIdx.x / n_tiles : 0;            // K slice of this workgroup (uniform)
     const int kbeg = ks * a.k_per;
     const int tile = xcd_remap(blockIdx.x - ks * n_tiles, n_tiles);
-    // Which pixels, which channels: on the scalar unit, with reciprocals from the host (launch_conv_pipe_t).  An integer division costs
+    // Which pixels, which channels: on the scalar unit, with reciprocals from the host (launch_conv_t).  An integer division costs
     // ~30 vector instructions, a third of them at a quarter of the rate, and the vector unit's time is the matrix pipe's: the prologue
     // of a K = 256 tile used to be 11 % of its issue slots.
     const int tm = (int)magic_div((unsigned)tile, a.m_tiles_n);
@@ -492,7 +492,7 @@ void conv_igemm_pipe_kernel(ConvArgs a) {
         a_row[i] = c / CPR;
         a_col[i] = c % CPR;
         const bool ok = m0 + a_row[i] < a.M && a_row[i] < BM;
-        // the a_row-th pixel behind the tile's first one: a walk of < BM pixels (every factor below 2^24, launch_conv_pipe_t)
+        // the a_row-th pixel behind the tile's first one: a walk of < BM pixels (every factor below 2^24, launch_conv_t)
         const unsigned lin = ow0 + (unsigned)a_row[i];
         const unsigned q1 = umul24(lin, a.s_wo) >> kRecipShift;
         const unsigned ly = oh0 + q1;
@@ -994,12 +994,6 @@ static inline double first_layer_k2c(const vq_input_desc& in, const vq_layer_des
 static inline bool is_wino(int op) { return op == VQ_OP_CONV_WINOGRAD || op == VQ_OP_CONV_WINOGRAD16; }
 static inline bool is_conv(int op) { return op == VQ_OP_CONV || is_wino(op); }
 
-struct ConvTile {
-    int bm, bn, bk;
-    int pipe;   // 1 = software-pipelined kernel (aligned Cin only); 3 = pool_gemm_kernel (pooled-input 1x1 layers only; bk is its
-                // k-group of 8).  2 is taken: vq_tsn_layer_tiles reports the Winograd form with it
-};
-
 // One kernel launch of a forward: a single layer, or the Winograd convolutions of one graph level together.
 struct LaunchItem {
     int kind = 0;              // 0 = one layer, 1 = Winograd group
@@ -1117,34 +1111,12 @@ static void tsn_free(vq_tsn* net) {
     if (net->feat_dev) (void)hipFree(net->feat_dev);
 }
 
-template <int BM, int BN, int WM, int WN, int BK, bool SMALL>
-static int launch_conv_t(vq_tsn* net, ConvArgs& a) {
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_n = cdiv(a.Cout, BN);
-    auto kern = conv_igemm_kernel<BM, BN, WM, WN, BK, SMALL>;
-    const size_t lds = sizeof(ConvSmem<BM, BN, BK>);
-    VQ_DYN_LDS(kern, lds);            // per instantiation and device
-    VQ_LAUNCH(kern, a.tiles_m * a.tiles_n * a.ksplit, 256, lds, net->ls, net->ev_start, net->ev_stop, a);
-    VQ_CHECK_LAUNCH();
-    return VQ_OK;
-}
+// The kernels of a direct convolution: the plain kernel, the software-pipelined one, the plain kernel with the pooled-input
+// loader, and the two-phase pool_gemm_kernel
+enum : int { kConv = 1, kPipe = 2, kPool = 4, kGemm = 8 };
 
-// Candidate tilings (BM x BN x BK).  Every candidate sums each output element's K terms in the same order, so
-// the choice never changes a result bit; it is made per layer and batch size by timing (autotune) or, with
-// VQ_TSN_AUTOTUNE=0, by the occupancy heuristic below.
-static const ConvTile kTiles[] = {
-    {128, 128, 32, 0}, {128, 128, 16, 0}, {128, 96, 32, 0}, {128, 96, 16, 0}, {128, 64, 32, 0}, {128, 64, 16, 0},
-    {64, 128, 32, 0},  {64, 128, 16, 0},  {64, 64, 32, 0},  {64, 64, 16, 0},  {128, 32, 32, 0}, {128, 32, 16, 0},
-    {32, 128, 32, 0},  {32, 128, 16, 0},
-    {128, 128, 32, 1}, {128, 128, 16, 1}, {128, 96, 32, 1}, {128, 96, 16, 1}, {128, 64, 32, 1}, {128, 64, 16, 1},
-    {64, 128, 32, 1},  {64, 128, 16, 1},  {64, 64, 32, 1},  {64, 64, 16, 1},  {128, 32, 32, 1}, {128, 32, 16, 1},
-    {32, 128, 32, 1},  {32, 128, 16, 1},
-    // (round 6: 256 x 64 tilings -- four waves of 64 x 64 one above the other, for the 64-channel stem with its short K -- were built, tested
-    // against the oracle and offered to the sweep: never chosen, conv1 stays at 0.233-0.238 ms on 128 x 64; removed again.)
-    // pooled-input 1x1 layers only: ONE column tile for up to 256 output columns (every pooling window is read once), and the
-    // two-phase kernel
-    {64, 256, 16, 0}, {64, 256, 8, 3}, {64, 64, 8, 3}, {128, 64, 8, 3}};
-constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+constexpr size_t kPoolGemmMaxLds = 64 * 1024;                  // pool_gemm_kernel: BM x (K + 4) floats, two or three workgroups per unit
+static size_t pool_gemm_lds(int bm, int K) { return std::max((size_t)bm * (K + 4) * sizeof(float), (size_t)4 * 32 * 36 * sizeof(float)); }
 
 // The pipelined kernel decodes pixels with host-made reciprocals on 24-bit multiplies: what the shapes must satisfy
 static bool pixel_walk_ok(const ConvArgs& a) {
@@ -1153,103 +1125,118 @@ static bool pixel_walk_ok(const ConvArgs& a) {
            recip22_ok((unsigned)a.Wo, (unsigned)a.Wo + 128u) && recip22_ok((unsigned)a.Ho, (unsigned)a.Ho + 130u);
 }
 
-template <int BM, int BN, int WM, int WN, int BK, bool SMALL>
-static int launch_conv_pipe_t(vq_tsn* net, ConvArgs& a) {
+template <int BM, int BN, int WM, int WN, int BK, int KERNEL, bool SMALL>
+static int launch_conv_t(vq_tsn* net, ConvArgs& a) {
     a.tiles_m = cdiv(a.M, BM);
     a.tiles_n = cdiv(a.Cout, BN);
-    VQ_REQUIRE(pixel_walk_ok(a) && (unsigned long long)a.tiles_m * a.tiles_n * a.tiles_n < 0x100000000ull,
-               "pipelined convolution: shape outside the range of its reciprocal divisions");
-    a.m_tiles_n = a.tiles_n == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.tiles_n) + 1u;
-    a.d_howo = full_div_for((unsigned)(a.Ho * a.Wo));
-    a.d_wo = full_div_for((unsigned)a.Wo);
-    a.s_wo = recip22((unsigned)a.Wo);
-    a.s_ho = recip22((unsigned)a.Ho);
-    auto kern = conv_igemm_pipe_kernel<BM, BN, WM, WN, BK, SMALL>;
-    const size_t lds = sizeof(ConvSmem<BM, BN, BK>);
-    VQ_DYN_LDS(kern, lds);            // per instantiation and device
+    void (*kern)(ConvArgs);
+    size_t lds = sizeof(ConvSmem<BM, BN, BK>), lds_max = lds;
+    if constexpr (KERNEL == kPipe) {
+        VQ_REQUIRE(pixel_walk_ok(a) && (unsigned long long)a.tiles_m * a.tiles_n * a.tiles_n < 0x100000000ull,
+                   "pipelined convolution: shape outside the range of its reciprocal divisions");
+        a.m_tiles_n = a.tiles_n == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.tiles_n) + 1u;
+        a.d_howo = full_div_for((unsigned)(a.Ho * a.Wo));
+        a.d_wo = full_div_for((unsigned)a.Wo);
+        a.s_wo = recip22((unsigned)a.Wo);
+        a.s_ho = recip22((unsigned)a.Ho);
+        kern = conv_igemm_pipe_kernel<BM, BN, WM, WN, BK, SMALL>;
+    } else if constexpr (KERNEL == kGemm) {
+        VQ_REQUIRE(a.pool_k == 3 && a.Cin % 32 == 0 && a.Kp == a.Cin, "pool_gemm_kernel: a 3x3 window over a multiple of 32 channels");
+        kern = pool_gemm_kernel<BM, BN, WM, WN>;
+        lds = pool_gemm_lds(BM, a.Cin);                     // a launch asks for what its K needs
+        lds_max = kPoolGemmMaxLds;
+    } else {
+        kern = conv_igemm_kernel<BM, BN, WM, WN, BK, SMALL, KERNEL == kPool>;
+    }
+    VQ_DYN_LDS(kern, lds_max);            // per instantiation and device
     VQ_LAUNCH(kern, a.tiles_m * a.tiles_n * a.ksplit, 256, lds, net->ls, net->ev_start, net->ev_stop, a);
     VQ_CHECK_LAUNCH();
     return VQ_OK;
 }
 
-template <bool SMALL>
-static int launch_conv_pipe(vq_tsn* net, ConvArgs& a, const ConvTile& t) {
-#define P_(BM_, BN_, WM_, WN_, BK_) \
-    if (t.bm == BM_ && t.bn == BN_ && t.bk == BK_) return launch_conv_pipe_t<BM_, BN_, WM_, WN_, BK_, SMALL>(net, a);
-    P_(128, 128, 2, 2, 32) P_(128, 128, 2, 2, 16) P_(128, 96, 4, 1, 32) P_(128, 96, 4, 1, 16) P_(128, 64, 2, 2, 32)
-    P_(128, 64, 2, 2, 16) P_(64, 128, 2, 2, 32) P_(64, 128, 2, 2, 16) P_(64, 64, 2, 2, 32) P_(64, 64, 2, 2, 16)
-    P_(128, 32, 4, 1, 32) P_(128, 32, 4, 1, 16) P_(32, 128, 1, 4, 32) P_(32, 128, 1, 4, 16)
-#undef P_
-    return fail(VQ_E_INVALID, "no pipelined kernel for tile %dx%dx%d", t.bm, t.bn, t.bk);
-}
+typedef int (*ConvLaunch)(vq_tsn*, ConvArgs&);
 
-// The pooled loader keeps 8 extra window taps per staged chunk in registers: tilings that stage at most two chunks per thread.
-static bool pool_only_tile(const ConvTile& t) { return t.bn > 128 || t.pipe == 3; }      // instantiated for pooled-input layers only
-constexpr size_t kPoolGemmMaxLds = 64 * 1024;                  // pool_gemm_kernel: BM x (K + 4) floats, two or three workgroups per unit
-static size_t pool_gemm_lds(int bm, int K) { return std::max((size_t)bm * (K + 4) * sizeof(float), (size_t)4 * 32 * 36 * sizeof(float)); }
-static bool pool_tile_ok(const ConvTile& t, int K) {
-    if (t.pipe == 3) return pool_gemm_lds(t.bm, K) <= kPoolGemmMaxLds;
-    return !t.pipe && t.bm >= 64 && t.bm <= 128 && (t.bk == 16 || (t.bm == 64 && t.bn <= 128));
-}
+struct ConvTile {
+    int bm, bn, bk;
+    int pipe;                // 0 = plain kernel; 1 = software-pipelined kernel (aligned Cin only); 3 = pool_gemm_kernel (pooled-input 1x1
+                             // layers only; bk is its k-group of 8).  2 is taken: vq_tsn_layer_tiles reports the Winograd form with it
+    ConvLaunch conv[2];      // plain kernel, aligned / small Cin (also in a pipelined tiling: shapes outside its reciprocal range)
+    ConvLaunch piped[2];     // pipelined kernel, aligned / small Cin
+    ConvLaunch pooled;       // pooled-input layers: the plain kernel's pooled loader, or pool_gemm_kernel
+};
 
-template <int BM, int BN, int WM, int WN, int BK>
-static int launch_conv_pool_t(vq_tsn* net, ConvArgs& a) {
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_n = cdiv(a.Cout, BN);
-    auto kern = conv_igemm_kernel<BM, BN, WM, WN, BK, false, true>;
-    const size_t lds = sizeof(ConvSmem<BM, BN, BK>);
-    VQ_DYN_LDS(kern, lds);            // per instantiation and device
-    VQ_LAUNCH(kern, a.tiles_m * a.tiles_n, 256, lds, net->ls, net->ev_start, net->ev_stop, a);
-    VQ_CHECK_LAUNCH();
-    return VQ_OK;
-}
-
-template <int BM, int BN, int WM, int WN>
-static int launch_pool_gemm_t(vq_tsn* net, ConvArgs& a) {
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_n = cdiv(a.Cout, BN);
-    auto kern = pool_gemm_kernel<BM, BN, WM, WN>;
-    VQ_DYN_LDS(kern, kPoolGemmMaxLds);            // per instantiation and device; a launch asks for what its K needs
-    VQ_LAUNCH(kern, a.tiles_m * a.tiles_n, 256, pool_gemm_lds(BM, a.Cin), net->ls, net->ev_start, net->ev_stop, a);
-    VQ_CHECK_LAUNCH();
-    return VQ_OK;
-}
-
-static int launch_conv_pool(vq_tsn* net, ConvArgs& a, const ConvTile& t) {
-    if (t.pipe == 3) {
-        VQ_REQUIRE(a.pool_k == 3 && a.Cin % 32 == 0 && a.Kp == a.Cin && pool_tile_ok(t, a.Cin), "pool_gemm_kernel: a 3x3 window over a multiple of 32 channels");
-        if (t.bm == 64 && t.bn == 256) return launch_pool_gemm_t<64, 256, 1, 4>(net, a);
-        if (t.bm == 64 && t.bn == 64) return launch_pool_gemm_t<64, 64, 2, 2>(net, a);
-        if (t.bm == 128 && t.bn == 64) return launch_pool_gemm_t<128, 64, 2, 2>(net, a);
-        return fail(VQ_E_INVALID, "no pool_gemm kernel for tile %dx%d", t.bm, t.bn);
+// An entry of kTiles: the tiling and launches of the kernels HAS names (kPipe brings the plain kernel along)
+template <int BM, int BN, int BK, int WM, int WN, int HAS>
+constexpr ConvTile tiling() {
+    ConvTile t{BM, BN, BK, (HAS & kGemm) ? 3 : (HAS & kPipe) ? 1 : 0, {}, {}, nullptr};
+    if constexpr ((HAS & (kConv | kPipe)) != 0) {
+        t.conv[0] = launch_conv_t<BM, BN, WM, WN, BK, kConv, false>;
+        t.conv[1] = launch_conv_t<BM, BN, WM, WN, BK, kConv, true>;
     }
-#define T_(BM_, BN_, WM_, WN_, BK_) \
-    if (t.bm == BM_ && t.bn == BN_ && t.bk == BK_) return launch_conv_pool_t<BM_, BN_, WM_, WN_, BK_>(net, a);
-    T_(128, 128, 2, 2, 16) T_(128, 96, 4, 1, 16) T_(128, 64, 2, 2, 16) T_(64, 128, 2, 2, 32) T_(64, 128, 2, 2, 16)
-    T_(64, 64, 2, 2, 32) T_(64, 64, 2, 2, 16) T_(128, 32, 4, 1, 16) T_(64, 256, 1, 4, 16)
-#undef T_
-    return fail(VQ_E_INVALID, "no pooled-input kernel for tile %dx%dx%d", t.bm, t.bn, t.bk);
+    if constexpr ((HAS & kPipe) != 0) {
+        t.piped[0] = launch_conv_t<BM, BN, WM, WN, BK, kPipe, false>;
+        t.piped[1] = launch_conv_t<BM, BN, WM, WN, BK, kPipe, true>;
+    }
+    if constexpr ((HAS & kPool) != 0) t.pooled = launch_conv_t<BM, BN, WM, WN, BK, kPool, false>;
+    if constexpr ((HAS & kGemm) != 0) t.pooled = launch_conv_t<BM, BN, WM, WN, BK, kGemm, false>;
+    return t;
 }
 
-template <bool SMALL>
-static int launch_conv(vq_tsn* net, ConvArgs& a, const ConvTile& t) {
-#define T_(BM_, BN_, WM_, WN_, BK_) \
-    if (t.bm == BM_ && t.bn == BN_ && t.bk == BK_) return launch_conv_t<BM_, BN_, WM_, WN_, BK_, SMALL>(net, a);
-    T_(128, 128, 2, 2, 32) T_(128, 128, 2, 2, 16) T_(128, 96, 4, 1, 32) T_(128, 96, 4, 1, 16) T_(128, 64, 2, 2, 32)
-    T_(128, 64, 2, 2, 16) T_(64, 128, 2, 2, 32) T_(64, 128, 2, 2, 16) T_(64, 64, 2, 2, 32) T_(64, 64, 2, 2, 16)
-    T_(128, 32, 4, 1, 32) T_(128, 32, 4, 1, 16) T_(32, 128, 1, 4, 32) T_(32, 128, 1, 4, 16)
-#undef T_
-    return fail(VQ_E_INVALID, "no kernel for tile %dx%dx%d", t.bm, t.bn, t.bk);
+// Candidate tilings: BM x BN x BK on four waves of WM x WN, and the kernels each has.  Every candidate sums each output element's
+// K terms in the same order, so the choice never changes a result bit; it is made per layer and batch size by timing (autotune) or,
+// with VQ_TSN_AUTOTUNE=0, by the occupancy heuristic below.  Both take the first of equals in this order.
+// The pooled loader keeps 8 extra window taps per staged chunk in registers: tilings that stage at most two chunks per thread have it.
+static constexpr ConvTile kTiles[] = {
+    tiling<128, 128, 32, 2, 2, kConv>(), tiling<128, 128, 16, 2, 2, kConv | kPool>(),
+    tiling<128, 96, 32, 4, 1, kConv>(),  tiling<128, 96, 16, 4, 1, kConv | kPool>(),
+    tiling<128, 64, 32, 2, 2, kConv>(),  tiling<128, 64, 16, 2, 2, kConv | kPool>(),
+    tiling<64, 128, 32, 2, 2, kConv | kPool>(), tiling<64, 128, 16, 2, 2, kConv | kPool>(),
+    tiling<64, 64, 32, 2, 2, kConv | kPool>(),  tiling<64, 64, 16, 2, 2, kConv | kPool>(),
+    tiling<128, 32, 32, 4, 1, kConv>(),  tiling<128, 32, 16, 4, 1, kConv | kPool>(),
+    tiling<32, 128, 32, 1, 4, kConv>(),  tiling<32, 128, 16, 1, 4, kConv>(),
+    tiling<128, 128, 32, 2, 2, kPipe>(), tiling<128, 128, 16, 2, 2, kPipe>(),
+    tiling<128, 96, 32, 4, 1, kPipe>(),  tiling<128, 96, 16, 4, 1, kPipe>(),
+    tiling<128, 64, 32, 2, 2, kPipe>(),  tiling<128, 64, 16, 2, 2, kPipe>(),
+    tiling<64, 128, 32, 2, 2, kPipe>(),  tiling<64, 128, 16, 2, 2, kPipe>(),
+    tiling<64, 64, 32, 2, 2, kPipe>(),   tiling<64, 64, 16, 2, 2, kPipe>(),
+    tiling<128, 32, 32, 4, 1, kPipe>(),  tiling<128, 32, 16, 4, 1, kPipe>(),
+    tiling<32, 128, 32, 1, 4, kPipe>(),  tiling<32, 128, 16, 1, 4, kPipe>(),
+    // (round 6: 256 x 64 tilings -- four waves of 64 x 64 one above the other, for the 64-channel stem with its short K -- were built, tested
+    // against the oracle and offered to the sweep: never chosen, conv1 stays at 0.233-0.238 ms on 128 x 64; removed again.)
+    // pooled-input 1x1 layers only: ONE column tile for up to 256 output columns (every pooling window is read once), and the
+    // two-phase kernel
+    tiling<64, 256, 16, 1, 4, kPool>(), tiling<64, 256, 8, 1, 4, kGemm>(), tiling<64, 64, 8, 2, 2, kGemm>(), tiling<128, 64, 8, 2, 2, kGemm>()};
+constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+
+// The entry of the external form [bm, bn, bk, pipe] of a tiling (vq_tsn_set_tiles, VQ_TSN_TILE); -1: none
+static int tile_index(int bm, int bn, int bk, int pipe) {
+    for (int i = 0; i < kNumTiles; ++i)
+        if (kTiles[i].bm == bm && kTiles[i].bn == bn && kTiles[i].bk == bk && kTiles[i].pipe == pipe) return i;
+    return -1;
 }
 
-static int heuristic_tile(int M, int N, int cus) {
+// A pooled-input layer of K channels has a kernel under tiling t
+static bool pooled_ok(const ConvTile& t, int K) { return t.pooled && (t.pipe != 3 || pool_gemm_lds(t.bm, K) <= kPoolGemmMaxLds); }
+
+// May layer L be given tiling t: by the sweep (timed), which tries every tiling with a kernel for the layer, or by the occupancy
+// heuristic, which scores the plain kernel's BK = 32 tilings (conv_launch then finds a pooled-input layer its substitute)
+static bool tile_candidate(const vq_layer_desc& L, const ConvTile& t, bool timed) {
+    if (!timed) return t.pipe == 0 && t.bk == 32 && t.conv[0];
+    if (L.pre_pool_k > 0 ? !pooled_ok(t, L.cin) : !t.conv[0]) return false;
+    return t.bn < 2 * ((L.cout + 63) / 64 * 64);     // a column tile that is mostly padding cannot win: do not let a timing fluke choose it
+}
+
+static int heuristic_tile(const vq_tsn* net, int li, int n_crops) {
+    const vq_layer_desc& L = net->layers[li];
+    const vq_tensor_desc& td = net->tensors[L.dst];
+    const int M = n_crops * td.h * td.w, N = L.cout;
     int best = 0;
     double bs = -1;
     for (int i = 0; i < kNumTiles; ++i) {
         const ConvTile& t = kTiles[i];
-        if (t.bk != 32 || t.pipe || pool_only_tile(t)) continue;
+        if (!tile_candidate(L, t, false)) continue;
         const long long tiles = (long long)cdiv(M, t.bm) * cdiv(N, t.bn);
-        const double per_cu = (double)tiles / cus;
+        const double per_cu = (double)tiles / net->cus;
         const double balance = per_cu / std::ceil(per_cu);                      // tail quantisation
         const double padding = ((double)M * N) / ((double)tiles * t.bm * t.bn); // ragged edges
         const double area = (double)t.bm * t.bn;
@@ -1261,6 +1248,24 @@ static int heuristic_tile(int M, int N, int cus) {
         }
     }
     return best;
+}
+
+// The launch that runs tiling ti on layer li with arguments a (after launch_conv_layer's row folding); nullptr: none.  Every
+// substitute gives the same bits.
+static ConvLaunch conv_launch(const vq_tsn* net, int li, const ConvArgs& a, bool stem_rows, int ti) {
+    const ConvTile* t = &kTiles[ti];
+    if (net->layers[li].pre_pool_k > 0) {
+        // max-pool folded into the loader: any tiling gives the same bits, so an unsupported choice (heuristic, VQ_TSN_TILE)
+        // is replaced by the BK = 16 tiling of the same shape
+        if (!pooled_ok(*t, a.Cin)) ti = tile_index(std::min(t->bm, 128), std::min(t->bn, 128), 16, 0);
+        return ti < 0 ? nullptr : kTiles[ti].pooled;
+    }
+    if (stem_rows) ti = tile_index(t->bm, t->bn, 16, t->pipe);   // four chunk columns = four kernel rows: BK = 16 tilings only (same bits for all)
+    if (ti < 0) return nullptr;
+    t = &kTiles[ti];
+    const bool small = (a.Cin % t->bk) != 0;
+    // (shapes outside the pipelined kernel's reciprocal range run the plain kernel of the same tiling: same bits)
+    return t->piped[small] && pixel_walk_ok(a) ? t->piped[small] : t->conv[small];
 }
 
 static void fill_conv_args(vq_tsn* net, int li, int n_crops, ConvArgs& a) {
@@ -1330,50 +1335,34 @@ static int launch_conv_layer(vq_tsn* net, int li, int n_crops, int tile_idx) {
         a.kw = 1;
         a.Cin = L.k * L.cin;
     }
-    if (L.pre_pool_k > 0) {
-        // max-pool folded into the loader: any tiling gives the same bits, so an unsupported choice (heuristic, VQ_TSN_TILE)
-        // is replaced by the BK = 16 tiling of the same shape
-        ConvTile t = kTiles[tile_idx];
-        if (!pool_tile_ok(t, a.Cin)) t = ConvTile{std::min(t.bm, 128), std::min(t.bn, 128), 16, 0};
-        return launch_conv_pool(net, a, t);
-    }
-    if (stem_rows) {                                   // four chunk columns = four kernel rows: BK = 16 tilings only (same bits for all)
-        ConvTile t = kTiles[tile_idx];
-        t.bk = 16;
-        return t.pipe && pixel_walk_ok(a) ? launch_conv_pipe<false>(net, a, t) : launch_conv<false>(net, a, t);
-    }
-    const bool small = (a.Cin % kTiles[tile_idx].bk) != 0;
-    if (net->ksplit[li] > 1) {
-        // K slices into the scratch planes (zero bias, no ReLU: the slice tables say so), then the combine pass into the
-        // layer's destination.  The profiling events bracket the pair.
-        const hipEvent_t e0 = net->ev_start, e1 = net->ev_stop;
-        a.ksplit = net->ksplit[li];
-        a.k_per = a.Kp / a.ksplit;
-        a.seg_stride = (L.cout + 31) / 32;
-        a.bias = net->zero_bias;
-        // Sub-batches of one forward run on separate streams and may be at DIFFERENT split layers at the same moment: every
-        // crop owns a fixed stretch of each scratch plane (split_crop_floats, room for the largest split layer), and a
-        // launch writes its [M][Cout] partial sums at the first whole row inside the stretch of its first crop.
-        a.out_row0 = (int)cdiv((int64_t)net->crop_off * (int64_t)net->split_crop_floats, (int64_t)L.cout);
-        net->ev_stop = nullptr;
-        int rc = kTiles[tile_idx].pipe == 1 && pixel_walk_ok(a) ? launch_conv_pipe<false>(net, a, kTiles[tile_idx])
-                                                                 : launch_conv<false>(net, a, kTiles[tile_idx]);
-        net->ev_stop = e1;
-        if (rc != VQ_OK) return rc;
-        net->ev_start = nullptr;
-        const vq_tensor_desc& td = net->tensors[L.dst];
-        float* out = net->slots[L.dst] + (size_t)net->crop_off * td.h * td.w * td.c + L.dst_coff;
-        const int64_t work = (int64_t)a.M * (L.cout / 4);
-        VQ_LAUNCH(splitk_combine_kernel, (unsigned)cdiv(work, 256), 256, 0, net->ls, net->ev_start, net->ev_stop,
-                  net->split_scratch + (size_t)a.out_row0 * L.cout, a.ksplit, net->split_slice_floats, a.M, L.cout, net->blob + L.b_off, L.relu, out, td.c);
-        net->ev_start = e0;
-        VQ_CHECK_LAUNCH();
-        return VQ_OK;
-    }
-    // (shapes outside the pipelined kernel's reciprocal range run the plain kernel of the same tiling: same bits)
-    if (kTiles[tile_idx].pipe == 1 && pixel_walk_ok(a))
-        return small ? launch_conv_pipe<true>(net, a, kTiles[tile_idx]) : launch_conv_pipe<false>(net, a, kTiles[tile_idx]);
-    return small ? launch_conv<true>(net, a, kTiles[tile_idx]) : launch_conv<false>(net, a, kTiles[tile_idx]);
+    const ConvLaunch run = conv_launch(net, li, a, stem_rows, tile_idx);
+    const ConvTile& t = kTiles[tile_idx];
+    if (!run) return fail(VQ_E_INVALID, "layer %d: no kernel for tile %dx%dx%d pipe=%d", li, t.bm, t.bn, t.bk, t.pipe);
+    if (net->ksplit[li] == 1) return run(net, a);
+    // K slices into the scratch planes (zero bias, no ReLU: the slice tables say so), then the combine pass into the
+    // layer's destination.  The profiling events bracket the pair.
+    const hipEvent_t e0 = net->ev_start, e1 = net->ev_stop;
+    a.ksplit = net->ksplit[li];
+    a.k_per = a.Kp / a.ksplit;
+    a.seg_stride = (L.cout + 31) / 32;
+    a.bias = net->zero_bias;
+    // Sub-batches of one forward run on separate streams and may be at DIFFERENT split layers at the same moment: every
+    // crop owns a fixed stretch of each scratch plane (split_crop_floats, room for the largest split layer), and a
+    // launch writes its [M][Cout] partial sums at the first whole row inside the stretch of its first crop.
+    a.out_row0 = (int)cdiv((int64_t)net->crop_off * (int64_t)net->split_crop_floats, (int64_t)L.cout);
+    net->ev_stop = nullptr;
+    int rc = run(net, a);
+    net->ev_stop = e1;
+    if (rc != VQ_OK) return rc;
+    net->ev_start = nullptr;
+    const vq_tensor_desc& td = net->tensors[L.dst];
+    float* out = net->slots[L.dst] + (size_t)net->crop_off * td.h * td.w * td.c + L.dst_coff;
+    const int64_t work = (int64_t)a.M * (L.cout / 4);
+    VQ_LAUNCH(splitk_combine_kernel, (unsigned)cdiv(work, 256), 256, 0, net->ls, net->ev_start, net->ev_stop,
+              net->split_scratch + (size_t)a.out_row0 * L.cout, a.ksplit, net->split_slice_floats, a.M, L.cout, net->blob + L.b_off, L.relu, out, td.c);
+    net->ev_start = e0;
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
 }
 
 static void fill_wino_job(vq_tsn* net, int li, int n_crops, WinoJob& a, int variant) {
@@ -1572,10 +1561,7 @@ static int autotune(vq_tsn* net, int n_crops, bool paired) {
         std::vector<std::pair<float, int>> seen;
         const int n_wino = net->layers[li].op == VQ_OP_CONV_WINOGRAD16 ? 2 * kWinoVariants : kWinoVariants;     // + the 16-tile units
         for (int t = 0; t < (wino ? n_wino : kNumTiles); ++t) {
-            if (!wino && net->layers[li].pre_pool_k > 0 && !pool_tile_ok(kTiles[t], net->layers[li].cin)) continue;
-            if (!wino && net->layers[li].pre_pool_k == 0 && pool_only_tile(kTiles[t])) continue;
-            // a column tile that is mostly padding cannot win: do not let a timing fluke choose it
-            if (!wino && kTiles[t].bn >= 2 * ((net->layers[li].cout + 63) / 64 * 64)) continue;
+            if (!wino && !tile_candidate(net->layers[li], kTiles[t], true)) continue;
             for (int m : it.layers) pick[m] = t;               // a grouped launch runs one variant for all its members
             float ms = 0.f;
             const int rc = timed(it, 3, &ms);
@@ -1636,7 +1622,7 @@ static int run_layer(vq_tsn* net, int li, int n_crops, int tune_key) {
         int t = net->forced_tile;   // VQ_TSN_TILE (read at creation): test / tuning aid
         if (t < 0) {
             auto it = net->tuned.find(tune_key);
-            t = it != net->tuned.end() ? it->second[li] : heuristic_tile(n_crops * td.h * td.w, L.cout, net->cus);
+            t = it != net->tuned.end() ? it->second[li] : heuristic_tile(net, li, n_crops);
         }
         return launch_conv_layer(net, li, n_crops, t);
     }
@@ -2030,9 +2016,7 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
         if (const char* po = getenv("VQ_TSN_POISON")) net->poison = atoi(po) != 0;
         if (const char* force = getenv("VQ_TSN_TILE")) {
             int bm = 0, bn = 0, bk = 32, pipe = 0;   // "BMxBN", "BMxBNxBK" or "BMxBNxBKxP" (P = 1: pipelined kernel)
-            if (sscanf(force, "%dx%dx%dx%d", &bm, &bn, &bk, &pipe) >= 2)
-                for (int i = 0; i < kNumTiles; ++i)
-                    if (kTiles[i].bm == bm && kTiles[i].bn == bn && kTiles[i].bk == bk && kTiles[i].pipe == pipe) net->forced_tile = i;
+            if (sscanf(force, "%dx%dx%dx%d", &bm, &bn, &bk, &pipe) >= 2) net->forced_tile = tile_index(bm, bn, bk, pipe);
         }
         const char* sp = getenv("VQ_TSN_SPLIT");
         if (sp && strchr(sp, ',')) {                   // "2,1": sub-batches of 2/3 and 1/3 of the crops
@@ -2427,8 +2411,7 @@ int vq_tsn_get_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, int32_t* tile
             continue;
         }
         if (net->layers[i].op != VQ_OP_CONV) continue;
-        const vq_tensor_desc& td = net->tensors[net->layers[i].dst];
-        const int t = it != net->tuned.end() ? it->second[i] : heuristic_tile(n_crops * td.h * td.w, net->layers[i].cout, net->cus);
+        const int t = it != net->tuned.end() ? it->second[i] : heuristic_tile(net, i, n_crops);
         tiles[4 * i] = kTiles[t].bm;
         tiles[4 * i + 1] = kTiles[t].bn;
         tiles[4 * i + 2] = kTiles[t].bk;
@@ -2463,11 +2446,7 @@ int vq_tsn_set_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, const int32_t
             continue;
         }
         if (net->layers[i].op != VQ_OP_CONV) continue;
-        int found = -1;
-        for (int t = 0; t < kNumTiles; ++t)
-            if (kTiles[t].bm == tiles[4 * i] && kTiles[t].bn == tiles[4 * i + 1] && kTiles[t].bk == tiles[4 * i + 2] &&
-                kTiles[t].pipe == tiles[4 * i + 3])
-                found = t;
+        const int found = tile_index(tiles[4 * i], tiles[4 * i + 1], tiles[4 * i + 2], tiles[4 * i + 3]);
         VQ_REQUIRE(found >= 0, "layer %d: no kernel for tile %dx%dx%d pipe=%d", i, tiles[4 * i], tiles[4 * i + 1], tiles[4 * i + 2],
                    tiles[4 * i + 3]);
         choice[i] = found;
