@@ -532,13 +532,19 @@ class TsnNet:
         call("vq_tsn_feat_devptr", self._h, C.byref(f), C.byref(p))
         return f.value, p.value
 
+    def read_tensor(self, slot: int, n_crops: int) -> np.ndarray:
+        """Tensor slot `slot` of the plan (all its channels) from the last forward, NHWC [n_crops, h, w, c] as the device holds it
+        (slot 0 in its packed form: read_blob undoes that)."""
+        h, w = self._tensor_hw[slot]
+        buf = np.empty((n_crops, h, w, self._tensor_c[slot]), dtype=np.float32)
+        call("vq_tsn_read_tensor", self._h, slot, n_crops, buf.ctypes.data_as(C.c_void_p))
+        return buf
+
     def read_blob(self, name: str, n_crops: int) -> np.ndarray:
         """Activation of blob `name` from the last forward, NHWC [n_crops, h, w, c] (per-layer parity)."""
         slot, coff, c = self.plan.blob_loc[name]
         h, w = self._tensor_hw[slot]
-        cs = self._tensor_c[slot]
-        buf = np.empty((n_crops, h, w, cs), dtype=np.float32)
-        call("vq_tsn_read_tensor", self._h, slot, n_crops, buf.ctypes.data_as(C.c_void_p))
+        buf = self.read_tensor(slot, n_crops)
         if slot == 0 and self.stem_s2d:                   # undo the space-to-depth packing of the input slot
             pad = [op for op in self.plan.ops if op.src == 0][0].pad
             ci = self.in_channels
