@@ -67,8 +67,9 @@ extern "C" {
  * 10 (round 5): + vq_dev_malloc / vq_dev_free / vq_stream_create / vq_stream_destroy / vq_stream_synchronize / vq_dev_read.
  * 11 (round 6): + vq_tsn_tile_tables / vq_tsn_get_tiles / vq_tsn_set_tiles / vq_tsn_tune / vq_tsn_set_split / vq_device_pool_trim; VQ_OP_CONV_WINOGRAD16 (a tiling table is keyed by (batch size, timed side by side on
  *      the sub-batch streams | alone)); vq_db_query_round / vq_db_round_layout / vq_host_alloc / vq_host_free (a query round in one call); vq_db_loss_surface;
- *      vq_stream_create_priority. */
-#define VQ_ABI_VERSION 11
+ *      vq_stream_create_priority.
+ * 12: + vq_flow_tile_cut (which cut of a level vq_flow_tvl1 runs for a number of pairs: tests of the tile kernel name the cuts they ran). */
+#define VQ_ABI_VERSION 12
 
 enum {
     VQ_OK = 0,
@@ -494,6 +495,10 @@ int vq_flow_create(int32_t max_pairs, int32_t h, int32_t w, const vq_tvl1_params
 int vq_flow_destroy(vq_flow* flow);
 /* Pyramid actually used: *n_levels and (h, w) of the first min(*n_levels, cap) levels, finest first. */
 int vq_flow_levels(vq_flow* flow, int32_t* n_levels, int32_t* sizes_hw, int32_t cap);
+/* The cut of pyramid level `level` (0 = finest, as in vq_flow_levels) into tiles that vq_flow_tvl1 runs for a batch of n_pairs pairs on
+ * this handle's device: out = nx, ny (tiles across / down = workgroups per pair), tw, th (own pixels of a tile), ew, eh (cells of a tile,
+ * halo included).  Chosen by the same function as in vq_flow_tvl1; the cut never changes a bit of the result (tested). */
+int vq_flow_tile_cut(vq_flow* flow, int32_t level, int32_t n_pairs, int32_t out[6]);
 /* Flow from frames0[p] to frames1[p] (uint8 grey [n_pairs][h][w], host or device) for every pair of the batch.
  * homographies_host (optional, [n_pairs][9] row-major fp64): frames1[p] is first warped by it (cv::warpPerspective
  * semantics, bilinear, replicated border).  Outputs, all optional, host: u1 / u2 = dx / dy fp32 [n_pairs][h][w];

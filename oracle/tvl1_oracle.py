@@ -22,7 +22,7 @@ Everything is float32 with the operation order written out, so that a device ker
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -99,26 +99,34 @@ def warp_bilinear(img: np.ndarray, u1: np.ndarray, u2: np.ndarray) -> np.ndarray
 
 
 def tvl1_level(i0: np.ndarray, i1: np.ndarray, u1: np.ndarray, u2: np.ndarray, warps: int = WARPS, iterations: int = ITERATIONS,
-               epsilon: float = EPSILON, tau: float = TAU, lam: float = LAMBDA, theta: float = THETA):
-    """One pyramid level of IPOL Algorithm 1.  Returns (u1, u2, inner iterations actually run per warp)."""
+               epsilon: float = EPSILON, tau: float = TAU, lam: float = LAMBDA, theta: float = THETA,
+               schedule: Optional[Sequence[int]] = None, trace: bool = False, case_counts: Optional[np.ndarray] = None):
+    """One pyramid level of IPOL Algorithm 1.  Returns (u1, u2, inner iterations actually run per warp).
+    schedule: per warp, the number of inner iterations to run INSTEAD of the stopping rule's (epsilon and iterations then decide
+    nothing; the error is still computed).  trace: additionally return, per warp, the fp64 mean squared update of every iteration
+    that ran.  case_counts: int64 [4], incremented by the cells of every iteration that took each case of the thresholding step
+    (rho < -l_t |grad|^2; rho > l_t |grad|^2; in between with a gradient; in between without one)."""
     i0, i1 = i0.astype(F), i1.astype(F)
     u1, u2 = u1.astype(F).copy(), u2.astype(F).copy()
     tau, lam, theta, epsilon = float(F(tau)), float(F(lam)), float(F(theta)), float(F(epsilon))   # the C ABI carries float32 parameters
     l_t, taut, th = F(lam * theta), F(tau / theta), F(theta)
     i1x, i1y = centered_gradient(i1)
     p11, p12, p21, p22 = (np.zeros_like(u1) for _ in range(4))
-    ran = []
-    for _ in range(warps):
+    ran, errors = [], []
+    for wp in range(warps):
         i1w, i1wx, i1wy = warp_bilinear(i1, u1, u2), warp_bilinear(i1x, u1, u2), warp_bilinear(i1y, u1, u2)
         grad = (i1wx * i1wx + i1wy * i1wy).astype(F)
         rho_c = (i1w - i1wx * u1 - i1wy * u2 - i0).astype(F)
         n = 0
         error = np.inf
-        while error > epsilon * epsilon and n < iterations:
+        errors.append([])
+        while (n < int(schedule[wp])) if schedule is not None else (error > epsilon * epsilon and n < iterations):
             n += 1
             rho = (rho_c + (i1wx * u1 + i1wy * u2)).astype(F)
             lo, hi = rho < -l_t * grad, rho > l_t * grad
             mid = ~lo & ~hi & (grad > F(GRAD_IS_ZERO))
+            if case_counts is not None:
+                case_counts += np.array([lo.sum(), (~lo & hi).sum(), mid.sum(), (~lo & ~hi & ~mid).sum()], dtype=np.int64)
             fi = np.where(mid, -rho / np.where(mid, grad, F(1)), F(0)).astype(F)
             d1 = np.where(lo, l_t * i1wx, np.where(hi, -l_t * i1wx, fi * i1wx)).astype(F)
             d2 = np.where(lo, l_t * i1wy, np.where(hi, -l_t * i1wy, fi * i1wy)).astype(F)
@@ -127,6 +135,7 @@ def tvl1_level(i0: np.ndarray, i1: np.ndarray, u1: np.ndarray, u2: np.ndarray, w
             n2 = (v2 + th * divergence(p21, p22)).astype(F)
             d = (n1 - u1) * (n1 - u1) + (n2 - u2) * (n2 - u2)
             error = float(d.astype(np.float64).sum()) / d.size          # mean squared update, accumulated in fp64
+            errors[-1].append(error)
             u1, u2 = n1, n2
             u1x, u1y = forward_gradient(u1)
             u2x, u2y = forward_gradient(u2)
@@ -135,13 +144,16 @@ def tvl1_level(i0: np.ndarray, i1: np.ndarray, u1: np.ndarray, u2: np.ndarray, w
             p11, p12 = ((p11 + taut * u1x) / ng1).astype(F), ((p12 + taut * u1y) / ng1).astype(F)
             p21, p22 = ((p21 + taut * u2x) / ng2).astype(F), ((p22 + taut * u2y) / ng2).astype(F)
         ran.append(n)
-    return u1, u2, ran
+    return (u1, u2, ran, errors) if trace else (u1, u2, ran)
 
 
 def tvl1_flow(frame0: np.ndarray, frame1: np.ndarray, nscales: int = NSCALES, warps: int = WARPS, iterations: int = ITERATIONS,
-              epsilon: float = EPSILON, scale_step: float = SCALE_STEP, **kw):
+              epsilon: float = EPSILON, scale_step: float = SCALE_STEP, schedule: Optional[Sequence[Sequence[int]]] = None,
+              trace: bool = False, **kw):
     """Flow (u1 = dx, u2 = dy) from grey uint8 (or float, 0..255) frame0 to frame1: coarse-to-fine over the pyramid, the
-    flow of a level resized to the next finer one and divided by scale_step."""
+    flow of a level resized to the next finer one and divided by scale_step.  Returns (u1, u2, counts [level][warp], coarsest
+    level first).  schedule: counts in that same layout to run instead of the stopping rule's; trace: additionally return the
+    fp64 mean squared updates [level][warp][iteration] (see tvl1_level)."""
     f0, f1 = frame0.astype(F), frame1.astype(F)
     scale_step = float(F(scale_step))
     sizes = pyramid_sizes(f0.shape[0], f0.shape[1], nscales, scale_step)
@@ -151,15 +163,19 @@ def tvl1_flow(frame0: np.ndarray, frame1: np.ndarray, nscales: int = NSCALES, wa
         pyr1.append(resize_bilinear(pyr1[-1], h, w))
     u1 = np.zeros(sizes[-1], dtype=F)
     u2 = np.zeros(sizes[-1], dtype=F)
-    counts = []
+    counts, errors = [], []
+    if schedule is not None and (len(schedule) != len(sizes) or any(len(lvl) != warps for lvl in schedule)):
+        raise ValueError("schedule must be [%d levels][%d warps]" % (len(sizes), warps))
     for s in range(len(sizes) - 1, -1, -1):
-        u1, u2, ran = tvl1_level(pyr0[s], pyr1[s], u1, u2, warps, iterations, epsilon, **kw)
+        u1, u2, ran, err = tvl1_level(pyr0[s], pyr1[s], u1, u2, warps, iterations, epsilon, trace=True,
+                                      schedule=None if schedule is None else schedule[len(sizes) - 1 - s], **kw)
         counts.append(ran)
+        errors.append(err)
         if s > 0:
             h, w = sizes[s - 1]
             inv = F(1.0 / scale_step)
             u1, u2 = (resize_bilinear(u1, h, w) * inv).astype(F), (resize_bilinear(u2, h, w) * inv).astype(F)
-    return u1, u2, counts
+    return (u1, u2, counts, errors) if trace else (u1, u2, counts)
 
 
 def flow_to_image(flow: np.ndarray, bound: float = 20.0) -> np.ndarray:

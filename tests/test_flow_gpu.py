@@ -87,9 +87,10 @@ def test_blocked_tiles_against_the_oracle_on_every_cut(flow_mod):
     ran past the stop).  With a fixed iteration count (epsilon = 0) the kernel follows the oracle operation for operation: 1e-4 px
     (observed ~1e-6) on shapes that exercise the cut -- iteration counts that are and are not multiples of the block (the tail block
     runs fewer), frames smaller than a tile and larger than several, a single row / column of tiles, tiles wider than 64 cells -- and
-    the cut itself (it depends on the level AND on the number of pairs in the batch) never changes a bit: a pair alone, in a batch
-    of 3 and in a batch of 9 gives the same fields.  (Rounds 2-4 also kept the un-blocked two-launch form and the square-tile form
-    in the library and compared them with this kernel bit for bit; they were removed in round 5.)"""
+    the cut itself (it depends on the level AND on the number of pairs in the batch) never changes a bit: a pair gives the same fields
+    alone, in its batch and in a batch whose number of pairs is CHOSEN (Tvl1Flow.tile_cuts) for a cut that differs from its batch's on at
+    least one level -- for these frames most small pair counts share one cut.  (Rounds 2-4 also kept the un-blocked two-launch form and
+    the square-tile form in the library and compared them with this kernel bit for bit; they were removed in round 5.)"""
     rng = np.random.default_rng(31)
     for (h, w, iters, warps, scales, n) in ((64, 80, 7, 2, 3, 3), (100, 132, 12, 3, 2, 1), (256, 340, 6, 1, 5, 9), (48, 50, 9, 2, 2, 2), (40, 300, 5, 1, 1, 3),
                                             (131, 174, 8, 1, 1, 4)):
@@ -101,9 +102,15 @@ def test_blocked_tiles_against_the_oracle_on_every_cut(flow_mod):
         for i in (0, n - 1):
             u1, u2, _ = tv.tvl1_flow(f0[i], f1[i], nscales=scales, warps=warps, iterations=iters, epsilon=0.0)
             assert np.abs(r["u1"][i] - u1).max() <= 1e-4 and np.abs(r["u2"][i] - u2).max() <= 1e-4, (h, w, i)
-        solo = m.flow(f0[n - 1:], f1[n - 1:])                       # another number of pairs = another cut of every level
+        solo = m.flow(f0[n - 1:], f1[n - 1:])                       # another number of pairs; whether it is another cut depends on the level sizes
         assert (solo["u1"][0] == r["u1"][n - 1]).all() and (solo["u2"][0] == r["u2"][n - 1]).all(), (h, w)
         m.close()
+        big = flow_mod.Tvl1Flow(32, h, w, epsilon=0.0, iterations=iters, warps=warps, nscales=scales)
+        other = next(k for k in range(1, 33) if big.tile_cuts(k) != big.tile_cuts(n))      # ... this one IS another cut of at least one level
+        order = [q % n for q in range(other - 1)] + [n - 1]          # the same pair last, the others before it
+        many = big.flow(f0[order], f1[order])
+        assert (many["u1"][-1] == r["u1"][n - 1]).all() and (many["u2"][-1] == r["u2"][n - 1]).all(), (h, w, other)
+        big.close()
     # identical frames stop after exactly one iteration (the first block is replayed with one iteration)
     f = _shifted_pair(96, 128, 0.0, 0.0, seed=7)[0]
     m = flow_mod.Tvl1Flow(2, 96, 128)

@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvqamd.so")
 
-ABI_VERSION = 11                 # include/vq_amd.h: VQ_ABI_VERSION
+ABI_VERSION = 12                 # include/vq_amd.h: VQ_ABI_VERSION
 VQ_F32, VQ_F64 = 0, 1
 VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED = 0, 1
 VQ_OP_CONV, VQ_OP_MAXPOOL, VQ_OP_AVGPOOL, VQ_OP_GLOBAL_AVGPOOL, VQ_OP_CONV_WINOGRAD, VQ_OP_CONV_WINOGRAD16 = 1, 2, 3, 4, 5, 6
@@ -97,7 +97,7 @@ SIGNATURES = {
     "vq_tsn_set_profile": [_P, _I32], "vq_tsn_set_profile_every": [_P, _I32], "vq_tsn_set_profile_split": [_P, _I32], "vq_tsn_layer_times": [_P, _P, _P, _I32],
     "vq_tvl1_default_params": [C.POINTER(Tvl1Params)],
     "vq_flow_create": [_I32, _I32, _I32, C.POINTER(Tvl1Params), _I32, _PP], "vq_flow_destroy": [_P],
-    "vq_flow_levels": [_P, _pI32, _pI32, _I32],
+    "vq_flow_levels": [_P, _pI32, _pI32, _I32], "vq_flow_tile_cut": [_P, _I32, _I32, _pI32],
     "vq_flow_tvl1": [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "vq_flow_last_timing": [_P, _pF64, _pI32],
     "vq_flow_warped": [_P, _P, _P, _I32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],

@@ -905,6 +905,11 @@ static void flow_free(vq_flow* f) {
     if (f->side_ev) (void)hipEventDestroy(f->side_ev);
 }
 
+// The cut of level L for a batch of n_pairs pairs: vq_flow_tvl1 runs it, vq_flow_tile_cut reports it.
+static TileCut level_cut(const vq_flow* f, const Level& L, int n_pairs) {
+    return fit_tiles(L.w, L.h, n_pairs, std::max(1, VQ_FLOW_TILE_WPE * 256 / kTileThreads) * f->n_cus);
+}
+
 extern "C" {
 
 int vq_tvl1_default_params(vq_tvl1_params* p) {
@@ -1023,6 +1028,20 @@ int vq_flow_levels(vq_flow* f, int32_t* n_levels, int32_t* sizes_hw, int32_t cap
     return VQ_OK;
 }
 
+int vq_flow_tile_cut(vq_flow* f, int32_t level, int32_t n_pairs, int32_t out[6]) {
+    VQ_REQUIRE(f && out, "NULL argument");
+    VQ_REQUIRE(level >= 0 && level < (int)f->levels.size(), "level %d outside [0,%d)", level, (int)f->levels.size());
+    VQ_REQUIRE(n_pairs > 0 && n_pairs <= f->max_pairs, "n_pairs %d outside (0,%d]", n_pairs, f->max_pairs);
+    const TileCut cut = level_cut(f, f->levels[level], n_pairs);
+    out[0] = cut.nx;
+    out[1] = cut.ny;
+    out[2] = cut.tw;
+    out[3] = cut.th;
+    out[4] = cut.ew;
+    out[5] = cut.eh;
+    return VQ_OK;
+}
+
 int vq_flow_tvl1(vq_flow* f, const uint8_t* frames0, const uint8_t* frames1, int32_t frames_on_device, int32_t n_pairs,
                  const double* homographies_host, float* u1_host, float* u2_host, uint8_t* flow_x_host, uint8_t* flow_y_host,
                  int32_t* iters_host, void* hip_stream) {
@@ -1093,7 +1112,7 @@ int vq_flow_tvl1(vq_flow* f, const uint8_t* frames0, const uint8_t* frames1, int
         for (float* p : {p11, p12, p21, p22}) VQ_HIP(hipMemsetAsync(p, 0, (size_t)tot * sizeof(float), st));
         const float l_t = (float)((double)P.lambda * (double)P.theta);      // oracle: float32(lam * theta) on the float32 parameters
         const float taut = (float)((double)P.tau / (double)P.theta);
-        const TileCut cut = fit_tiles(L.w, L.h, n_pairs, std::max(1, VQ_FLOW_TILE_WPE * 256 / kTileThreads) * f->n_cus);
+        const TileCut cut = level_cut(f, L, n_pairs);
         const dim3 tgrid((unsigned)cut.nx, (unsigned)cut.ny, (unsigned)n_pairs);
         const size_t tlds = (size_t)6 * cut.eh * cut.ew * sizeof(float);
         BlockArgs ba;

@@ -39,6 +39,16 @@ class Tvl1Flow:
         call("vq_flow_levels", self._h, C.byref(n), sizes.ctypes.data_as(C.POINTER(C.c_int32)), 16)
         self.levels = [tuple(int(v) for v in sizes[i]) for i in range(n.value)]          # (h, w), finest first
 
+    def tile_cuts(self, n_pairs: int):
+        """The cut of every level (finest first, as ``levels``) that ``flow`` runs for a batch of ``n_pairs`` pairs:
+        a list of (nx, ny, tw, th, ew, eh) -- tiles across / down, a tile's own pixels, its cells with the halo."""
+        out = np.zeros(6, dtype=np.int32)
+        cuts = []
+        for level in range(len(self.levels)):
+            call("vq_flow_tile_cut", self._h, level, int(n_pairs), out.ctypes.data_as(C.POINTER(C.c_int32)))
+            cuts.append(tuple(int(v) for v in out))
+        return cuts
+
     def flow(self, frames0: np.ndarray, frames1: np.ndarray, homographies: Optional[np.ndarray] = None, images: bool = True,
              fields: bool = True, iterations: bool = False):
         """frames0 / frames1: uint8 [n, h, w].  Returns a dict with ``u1``, ``u2`` (fp32 dx, dy), ``flow_x``, ``flow_y``
