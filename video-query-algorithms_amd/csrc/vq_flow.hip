@@ -649,7 +649,9 @@ __global__ void corner_strength_kernel(const uint8_t* __restrict__ frames, float
     a *= 0.5f;
     c *= 0.5f;
     const float d = a - c;
-    const float v = (a + c) - __fsqrt_rn(d * d + b * b);
+    // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the intrinsic is the native v_sqrt_f32 (1 ulp), and an ulp in a
+    // strength reorders corners of (nearly) equal strength against the correctly rounded oracle
+    const float v = (a + c) - sqrtf(d * d + b * b);
     if (live) strength[i] = v;
     float top = live ? fmaxf(v, 0.f) : 0.f;
     for (int off = 32; off > 0; off >>= 1) top = fmaxf(top, __shfl_xor(top, off));
