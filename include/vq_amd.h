@@ -337,7 +337,14 @@ enum {
      * instead of (128, 32|64, 8, 2)).  w_off addresses BOTH layouts, one behind the other: the one above, then [cin/16][16][cout][16],
      * slot p of the innermost 16 = input channel {0,2,8,10, 4,6,12,14, 1,3,9,11, 5,7,13,15}[p] of the group (csrc/vq_wino.hip).
      * cin % 16 == 0.  Every form gives the same bits. */
-    VQ_OP_CONV_WINOGRAD16 = 6
+    VQ_OP_CONV_WINOGRAD16 = 6,
+    /* InnerProduct on a 1x1 tensor (the networks' fc-action head): y[n] = bias[n] + sum_k x[k] * W[n][k], fp32, no ReLU.  src / dst are
+     * 1x1 slots; w_off addresses W as [cout][cin] (Caffe's blob order), b_off the bias [cout]; cin, src_coff and w_off are multiples
+     * of 4, cout and dst_coff are free (101 classes).  The bias is always added: has_bias must be 1 (refused otherwise) and b_off is
+     * checked against the blob like w_off.  A launch of its own without tiling choices (its rows of a tiling table are
+     * zeros); the summation order of an output depends on cin alone (csrc/vq_tsn.hip: inner_product_kernel), never on the batch.
+     * Added without a new ABI version: a description that does not use it means what it meant. */
+    VQ_OP_INNER_PRODUCT = 7
 };
 
 /* One executed layer of the frozen network

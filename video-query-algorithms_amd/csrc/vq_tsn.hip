@@ -910,6 +910,64 @@ __global__ void gavgpool_kernel(const float* __restrict__ in, float* __restrict_
     out[(size_t)img * Cs_out + coff_out + c] = acc / (float)HW;
 }
 
+// InnerProduct on 1x1 tensors (fc-action: K = 1024 pooled features -> N = 101 class scores; M = the crops of the launch, 1 .. 960):
+//   y[m][n] = b[n] + sum_k x[m][k] * W[n][k],  W [N][K] as Caffe stores it.
+// A wave-per-rows VALU kernel, not the matrix pipe: the whole layer is 2 x 960 x 1024 x 101 = 0.2 GFLOP at the largest batch (0.02 at the
+// product's 96 crops) against a forward of 200+ GFLOP, so it is bound by launch and load latency, not by arithmetic; the 414 KB of weights
+// and <= 4 MB of inputs sit in L2, both operands are read along K -- the contiguous axis of x AND of W, 16 bytes per lane -- so neither
+// needs LDS staging or a transposed copy, and N = 101 needs no zero-padded rows.  The fp32-input MFMA forms run at the vector fp32 rate on
+// gfx950, and 32 x 32 tiles of v_mfma_f32_32x32x2_f32 would give 120 waves a serial chain of 512 dependent MFMAs each -- an ESTIMATE on
+// paper (64 cycles apiece: ~14 us before any load latency, on 120 of the chip's 1024 SIMDs); that form was not built or timed.
+// One wave computes FC_ROWS crops x FC_COLS outputs (W values reused FC_ROWS times, x values FC_COLS times from registers).
+// SUMMATION ORDER of one output, a function of K alone: lane l owns k = 256 j + 4 l + e (j = 0 .. ceil(K / 256) - 1, e = 0 .. 3) and
+// chains acc = fma(x[k], W[n][k], acc) from 0 over j ascending, e ascending (k >= K: skipped); the 64 lane sums then meet in a butterfly
+// acc += acc[lane ^ s], s = 32, 16, 8, 4, 2, 1 (fp32 addition commutes, so every lane holds the same bits); last + b[n].
+// No accumulator is shared between crops or outputs, rows past M / columns past N recompute the last valid one and store nothing: the
+// bits of y[m][:] do not depend on the batch size, the crop's position, the sub-batch split or the crop range of the launch.
+constexpr int FC_ROWS = 4, FC_COLS = 8;
+__global__ __launch_bounds__(64) void inner_product_kernel(const float* __restrict__ x, int x_stride, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, float* __restrict__ y, int y_stride, int M,
+                                                           int K, int N) {
+    const int lane = threadIdx.x;
+    const int m0 = blockIdx.x * FC_ROWS, n0 = blockIdx.y * FC_COLS;
+    const float* xr[FC_ROWS];
+    const float* wr[FC_COLS];
+#pragma unroll
+    for (int r = 0; r < FC_ROWS; ++r) xr[r] = x + (size_t)min(m0 + r, M - 1) * x_stride;
+#pragma unroll
+    for (int c = 0; c < FC_COLS; ++c) wr[c] = W + (size_t)min(n0 + c, N - 1) * K;
+    float acc[FC_ROWS][FC_COLS];
+#pragma unroll
+    for (int r = 0; r < FC_ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < FC_COLS; ++c) acc[r][c] = 0.f;
+    for (int k = 4 * lane; k < K; k += 256) {             // K % 4 == 0: a lane's four values are all inside or all outside
+        floatx4 xv[FC_ROWS], wv[FC_COLS];
+#pragma unroll
+        for (int r = 0; r < FC_ROWS; ++r) xv[r] = *reinterpret_cast<const floatx4*>(xr[r] + k);
+#pragma unroll
+        for (int c = 0; c < FC_COLS; ++c) wv[c] = *reinterpret_cast<const floatx4*>(wr[c] + k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int r = 0; r < FC_ROWS; ++r)
+#pragma unroll
+                for (int c = 0; c < FC_COLS; ++c) acc[r][c] = __builtin_fmaf(xv[r][e], wv[c][e], acc[r][c]);
+    }
+    float mine = 0.f;                                     // lane r * FC_COLS + c stores output (r, c)
+#pragma unroll
+    for (int r = 0; r < FC_ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < FC_COLS; ++c) {
+            float v = acc[r][c];
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+            if (lane == r * FC_COLS + c) mine = v;
+        }
+    const int m = m0 + lane / FC_COLS, n = n0 + lane % FC_COLS;
+    if (lane < FC_ROWS * FC_COLS && m < M && n < N) y[(size_t)m * y_stride + n] = mine + bias[n];
+}
+
 // Second half of a convolution that was split over K (the 7x7-map layers with long K chains: at M = 49 x crops there
 // are fewer output tiles than compute units, and one wave per SIMD cannot hide its own load latency): the slices' partial
 // sums are added in slice order, then bias and ReLU -- a fixed order for every batch size and tiling, so the rule "which
@@ -1657,6 +1715,14 @@ static int run_layer(vq_tsn* net, int li, int n_crops, int tune_key) {
         VQ_CHECK_LAUNCH();
         return VQ_OK;
     }
+    if (L.op == VQ_OP_INNER_PRODUCT) {
+        const float* xin = net->slots[L.src] + (size_t)net->crop_off * ts.c + L.src_coff;
+        float* yout = net->slots[L.dst] + (size_t)net->crop_off * td.c + L.dst_coff;
+        VQ_LAUNCH(inner_product_kernel, dim3(cdiv(n_crops, FC_ROWS), cdiv(L.cout, FC_COLS)), 64, 0, net->ls, net->ev_start, net->ev_stop, xin, ts.c,
+                  net->blob + L.w_off, net->blob + L.b_off, yout, td.c, n_crops, L.cin, L.cout);
+        VQ_CHECK_LAUNCH();
+        return VQ_OK;
+    }
     return fail(VQ_E_INVALID, "layer %d: unknown op %d", li, L.op);
 }
 
@@ -1859,7 +1925,9 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
             VQ_REQUIRE(sum == L.cout, "layer %d: segments cover %d of %d output channels", i, sum, L.cout);
         }
         VQ_REQUIRE(L.k >= 1 && L.stride >= 1 && L.pad >= 0 && L.pad < L.k, "layer %d: bad kernel/stride/pad", i);
-        VQ_REQUIRE(ts.c % 4 == 0 && td.c % 4 == 0 && L.src_coff % 4 == 0 && L.dst_coff % 4 == 0 && L.cin % 4 == 0 && L.cout % 4 == 0,
+        // (an InnerProduct writes single floats: its destination slot, cout and dst_coff are free -- 101 class scores)
+        const bool fc = L.op == VQ_OP_INNER_PRODUCT;
+        VQ_REQUIRE(ts.c % 4 == 0 && L.src_coff % 4 == 0 && L.cin % 4 == 0 && (fc || (td.c % 4 == 0 && L.dst_coff % 4 == 0 && L.cout % 4 == 0)),
                    "layer %d: channel counts and offsets must be multiples of 4", i);
         if (L.op == VQ_OP_CONV) {
             VQ_REQUIRE(L.k <= 8, "layer %d: conv kernels up to 8x8 (the tap mask is 64 bits)", i);
@@ -1903,6 +1971,14 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
                        "layer %d: pooling output size mismatch (Caffe ceil rule)", i);
         } else if (L.op == VQ_OP_GLOBAL_AVGPOOL) {
             VQ_REQUIRE(L.cin == L.cout && td.h == 1 && td.w == 1, "layer %d: global pool must write a 1x1 slot", i);
+        } else if (L.op == VQ_OP_INNER_PRODUCT) {
+            VQ_REQUIRE(ts.h == 1 && ts.w == 1 && td.h == 1 && td.w == 1, "layer %d: InnerProduct reads and writes 1x1 slots", i);
+            VQ_REQUIRE(L.seg_count == 0 && L.pre_pool_k == 0 && L.relu == 0, "layer %d: InnerProduct has one destination, no pooled input, no ReLU", i);
+            VQ_REQUIRE(L.has_bias == 1, "layer %d: InnerProduct always adds its bias: has_bias must be 1 and b_off address it", i);
+            VQ_REQUIRE(L.w_off >= 0 && L.w_off % 4 == 0 && L.w_off + (int64_t)L.cout * L.cin <= blob_floats, "layer %d: weights outside the blob", i);
+            VQ_REQUIRE(L.b_off >= 0 && L.b_off + L.cout <= blob_floats, "layer %d: bias outside the blob", i);
+            VQ_REQUIRE(L.cout <= 65535 * FC_COLS, "layer %d: InnerProduct with more than %d outputs", i, 65535 * FC_COLS);
+            macs += (double)L.cin * L.cout;
         } else {
             return fail(VQ_E_INVALID, "layer %d: unknown op %d", i, L.op);
         }
@@ -2324,7 +2400,7 @@ int vq_tsn_layer_times(vq_tsn* net, float* ms, double* flops, int32_t n_layers) 
             const vq_layer_desc& L = net->layers[i];
             const vq_tensor_desc& td = net->tensors[L.dst];
             flops[i] = is_conv(L.op) ? 2.0 * net->last_crops * td.h * td.w * L.cout * first_layer_k2c(net->input, L)
-                                          : 0.0;
+                                          : (L.op == VQ_OP_INNER_PRODUCT ? 2.0 * net->last_crops * L.cin * L.cout : 0.0);
         }
     }
     return VQ_OK;

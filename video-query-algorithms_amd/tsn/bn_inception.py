@@ -11,8 +11,10 @@ Two sources give the same ``Graph``:
 
 ``Graph.plan()`` lowers the layer list to what the device executes: Convolution + frozen BN + ReLU
 become one op, Concat disappears (producers write at a channel offset of the concat tensor),
-Dropout is the identity in TEST phase, and ``fc-action`` -- computed by the reference but never read
-by the feature path (calcSig_wOF.py:95 reads ``global_pool``) -- is dropped.
+Dropout is the identity in TEST phase, and an InnerProduct layer on a 1x1 tensor (``fc-action``, the class scores)
+becomes an ``fc`` op.  Only what the feature blob (and the blobs named in ``keep``) needs is planned: the default
+feature path reads ``global_pool`` (calcSig_wOF.py:95), so its plan ends there and carries no ``fc`` op;
+``plan("fc-action")`` is that plan plus the head.
 """
 from __future__ import annotations
 
@@ -47,8 +49,9 @@ class Graph:
     def conv_layers(self) -> List[Layer]:
         return [l for l in self.layers if l.type == "Convolution"]
 
-    def plan(self, feature_blob: str = "global_pool", fuse: bool = True) -> "Plan":
-        p = _lower(self, feature_blob)
+    def plan(self, feature_blob: str = "global_pool", fuse: bool = True, keep: Tuple[str, ...] = ()) -> "Plan":
+        """``keep``: further blobs the device must compute and hold beside the feature blob (read back with ``TsnNet.read_blob``)."""
+        p = _lower(self, feature_blob, tuple(keep))
         return _fuse(p) if fuse else p
 
 
@@ -62,7 +65,7 @@ class Tensor:
 
 @dataclass
 class Op:
-    kind: str                      # conv | maxpool | avgpool | gavgpool
+    kind: str                      # conv | maxpool | avgpool | gavgpool | fc
     name: str                      # name of the producing layer (weights are keyed by it)
     src: int
     dst: int
@@ -107,6 +110,8 @@ class Plan:
             if op.kind == "conv":
                 t = self.tensors[op.segments[0].dst if op.segments else op.dst]
                 total += t.h * t.w * op.cout * op.cin * op.k * op.k
+            elif op.kind == "fc":
+                total += op.cin * op.cout
         return total
 
 
@@ -124,7 +129,7 @@ def pool_out(size: int, k: int, s: int, p: int) -> int:
     return out
 
 
-def _lower(g: Graph, feature_blob: str) -> Plan:
+def _lower(g: Graph, feature_blob: str, keep_blobs: Tuple[str, ...] = ()) -> Plan:
     c0, h0, w0 = g.input_shape
     shapes: Dict[str, Tuple[int, int, int]] = {g.input_name: (c0, h0, w0)}     # blob -> (C,H,W)
     # pass 1: shapes + which blobs live inside a concat output
@@ -158,6 +163,9 @@ def _lower(g: Graph, feature_blob: str) -> Plan:
             raise ValueError("unsupported layer type %s (%s)" % (l.type, l.name))
     if feature_blob not in shapes:
         raise KeyError("feature blob %r is not produced by this network" % feature_blob)
+    for b in keep_blobs:
+        if b not in shapes:
+            raise KeyError("blob %r is not produced by this network" % b)
 
     tensors: List[Tensor] = []
     loc: Dict[str, Tuple[int, int, int]] = {}
@@ -209,26 +217,48 @@ def _lower(g: Graph, feature_blob: str) -> Plan:
         elif l.type == "Dropout":
             if l.tops[0] != l.bottoms[0]:
                 loc[l.tops[0]] = slot_for(l.bottoms[0])
-        elif l.type in ("Concat", "InnerProduct"):
+        elif l.type == "InnerProduct":
+            # source and destination slots are resolved below, and only if the op is kept: a plan without the head is unchanged by it
+            op = Op("fc", l.name, -1, -1, 0, 0, shapes[l.bottoms[0]][0], l.num_output, out_blob=l.tops[0])
+            ops.append(op)
+            by_top[l.tops[0]] = op
+        elif l.type == "Concat":
             pass
-    # resolve destinations now that BN renaming is known; drop ops whose output nobody needs
-    needed = {feature_blob}
+    # resolve destinations now that BN renaming is known; keep an op when its output is the feature blob, one of `keep_blobs`, or
+    # feeds a kept op (e.g. dropped: fc-action under the default feature blob)
+    needed = {feature_blob, *keep_blobs}
+    by_layer = {op.name: op for op in ops}
+    fc_bottom: Dict[str, str] = {}
+    live = set()
+    for l in reversed(g.layers):
+        if l.type in ("Convolution", "Pooling", "InnerProduct"):
+            op = by_layer[l.name]
+            if op.out_blob in needed:
+                live.add(id(op))
+                needed.add(l.bottoms[0])
+                if l.type == "InnerProduct":
+                    fc_bottom[l.name] = l.bottoms[0]
+        elif l.type in ("Concat", "Dropout"):
+            if l.tops[0] in needed:
+                needed.update(l.bottoms)
     keep: List[Op] = []
-    consumers: Dict[str, int] = {}
-    for l in g.layers:
-        if l.type in ("Convolution", "Pooling", "Concat"):
-            for b in l.bottoms:
-                consumers[b] = consumers.get(b, 0) + 1
     for op in ops:
-        blob = op.out_blob
-        if blob != feature_blob and consumers.get(blob, 0) == 0:
-            continue                                             # e.g. nothing: fc-action is not an op
-        d = slot_for(blob)
+        if id(op) not in live:
+            continue
+        if op.kind == "fc":
+            c, h, w = shapes[fc_bottom[op.name]]
+            if h != 1 or w != 1:
+                raise ValueError("InnerProduct %s reads a %dx%d tensor: only 1x1 sources are supported" % (op.name, h, w))
+            src = slot_for(fc_bottom[op.name])
+            op.src, op.src_coff = src[0], src[1]
+        d = slot_for(op.out_blob)
         op.dst, op.dst_coff = d[0], d[1]
         keep.append(op)
     fs = slot_for(feature_blob)
     if fs[1] != 0 or tensors[fs[0]].h != 1 or tensors[fs[0]].w != 1:
         raise ValueError("feature blob must be a 1x1 tensor of its own")
+    if not any(op.dst == fs[0] for op in keep):
+        raise ValueError("feature blob %r is not written by any planned op" % feature_blob)
     return Plan(tensors, keep, fs[0], fs[2], dict(loc))
 
 

@@ -6,6 +6,8 @@ frame_size=(340,256))`` (:94), ``predict_single_flow_stack(flow_stack, score_nam
 ``net._net.blobs[blob].data[0]`` (:95,112).  This class offers the same four, so the reference's per-snippet loop runs
 unchanged on top of it, plus ``extract_clips`` -- the batched path (all B*T crops in one forward) the drop-in
 command line uses.
+Built with ``scores=True`` the two ``predict_*`` methods also do what every other TSN script reads them for: they return the
+``score_name`` blob of the ten over-sampled crops (crop order restated from memory).
 
 Weights: a ``.caffemodel`` (decoded by ``tsn/caffemodel.py`` without Caffe or a protobuf schema; the BN blob order is
 "parity unpinned", see there), an ``.npz`` with ``<layer>/W``, ``<layer>/b`` for convolutions and
@@ -68,38 +70,63 @@ class _NetView:
 
 
 class CaffeNet:
-    def __init__(self, net_proto, net_weights, device_id=0, max_crops=96, feature_blob="global_pool", resize_rule="cv2"):
+    def __init__(self, net_proto, net_weights, device_id=0, max_crops=96, feature_blob="global_pool", resize_rule="cv2", scores=False,
+                 score_name="fc-action"):
         """resize_rule: "cv2" = OpenCV's fixed-point INTER_LINEAR, what the reference's ``cv2.resize(frame, (340, 256))``
-        computes (default); "exact" = exact fp64 bilinear weights (tsn/frames.py)."""
+        computes (default); "exact" = exact fp64 bilinear weights (tsn/frames.py).
+        scores: False (default) = the feature path: ``predict_*`` run crop 0 and return ``None``.  True = pyActionRecog's score
+        interface: the plan also keeps the ``score_name`` blob, ``predict_*`` run the ten over-sampled crops (``over_sample=False``:
+        crop 0 alone) through the device network and return its ``[crops][classes]`` float32 scores; ``_net.blobs`` then holds one
+        row per crop of the feature blob and of the score blob.  The crops are cut on the host (tsn/frames.py:oversample*: order and
+        x-flow inversion restated from memory, parity unpinned)."""
         if resize_rule not in frames.RESIZE_RULES:
             raise ValueError("resize_rule must be 'cv2' or 'exact'")
         self._resize_rule = resize_rule
         self._graph = bn_inception.load_prototxt(net_proto) if isinstance(net_proto, str) else net_proto
         self._blob = feature_blob
+        self._scores = bool(scores)
+        self._score_name = score_name
+        keep = (score_name,) if self._scores and score_name != feature_blob else ()
+        if self._scores:
+            max_crops = max(max_crops, 10)
         self._channels = self._graph.input_shape[0]
         self._mean = RGB_MEAN if self._channels == 3 else tuple([128.0] * self._channels)
         if isinstance(net_weights, str):
             # read (and fold, and lay out) only if the packed form of exactly these weights is not in the cache next to the library
             graph = self._graph
             self._model = TsnNet(graph, lambda: load_weights(graph, net_weights), max_crops=max_crops, device=device_id, feature_blob=feature_blob,
-                                 cache_key=weights_digest(net_weights))
+                                 cache_key=weights_digest(net_weights), keep=keep)
         else:
-            self._model = TsnNet(self._graph, net_weights, max_crops=max_crops, device=device_id, feature_blob=feature_blob)
+            self._model = TsnNet(self._graph, net_weights, max_crops=max_crops, device=device_id, feature_blob=feature_blob, keep=keep)
         self._net = _NetView()
         self._ingest = FrameIngest(self._channels, device_id, resize_rule)
 
     # -- the reference's per-snippet interface ------------------------------------------------------------
+    def _predict(self, crop0, ten, score_name, over_sample):
+        if not self._scores:
+            crops = crop0()[None]                                                                   # crop 0 of the 10-crop over-sample
+            _, ps = self._model.forward(crops, 1, self._mean)
+            self._net.blobs[self._blob] = _Blob(ps.reshape(1, -1, 1, 1))        # .data[0] is what calcSig reads
+            return None
+        name = self._score_name if score_name is None else score_name
+        if name not in self._model.plan.blob_loc or (name != self._score_name and name != self._blob):
+            raise KeyError("score blob %r is not computed by this extractor (built with score_name=%r, feature_blob=%r)"
+                           % (name, self._score_name, self._blob))
+        crops = ten() if over_sample else crop0()[None]
+        n = crops.shape[0]
+        _, ps = self._model.forward(crops, 1, self._mean)
+        self._net.blobs[self._blob] = _Blob(ps.reshape(n, -1, 1, 1))            # one row per crop; .data[0] is crop 0, as without scores
+        score = ps if name == self._blob else np.ascontiguousarray(self._model.read_blob(name, n).reshape(n, -1))
+        self._net.blobs[name] = _Blob(score.reshape(n, -1, 1, 1))
+        return score
+
     def predict_single_frame(self, frame, score_name=None, over_sample=True, frame_size=(340, 256)):
-        crop = frames.crop0(frame[0], frame_size, rule=self._resize_rule)[None]                     # crop 0 of the 10-crop over-sample
-        _, ps = self._model.forward(crop, 1, self._mean)
-        self._net.blobs[self._blob] = _Blob(ps.reshape(1, -1, 1, 1))        # .data[0] is what calcSig reads
-        return None
+        return self._predict(lambda: frames.crop0(frame[0], frame_size, rule=self._resize_rule),
+                             lambda: frames.oversample(frame[0], frame_size, rule=self._resize_rule), score_name, over_sample)
 
     def predict_single_flow_stack(self, frame, score_name=None, over_sample=True, frame_size=(340, 256)):
-        crop = np.stack([frames.crop0(f, frame_size, rule=self._resize_rule) for f in frame], axis=-1)[None]
-        _, ps = self._model.forward(crop, 1, self._mean)
-        self._net.blobs[self._blob] = _Blob(ps.reshape(1, -1, 1, 1))
-        return None
+        return self._predict(lambda: np.stack([frames.crop0(f, frame_size, rule=self._resize_rule) for f in frame], axis=-1),
+                             lambda: frames.oversample_flow_stack(frame, frame_size, rule=self._resize_rule), score_name, over_sample)
 
     # -- the batched path ------------------------------------------------------------------------------------
     def extract_clips(self, crops: np.ndarray, T: int, on_device: bool = False):

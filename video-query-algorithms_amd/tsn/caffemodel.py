@@ -128,6 +128,18 @@ def weights_from_caffemodel(path: str, graph, bn_blob_order=("scale", "shift", "
             if len(blobs) != 4:
                 raise ValueError("BN layer %s: expected 4 blobs (yjxiong caffe fork), got %d" % (l.name, len(blobs)))
             w[l.name] = {k: np.ascontiguousarray(blobs[i].reshape(-1)) for i, k in enumerate(bn_blob_order)}
+        elif l.type == "InnerProduct":
+            # blob 0 = W [num_output][K] (legacy files: [1][1][N][K]), blob 1 = bias.  A file without the head is fine for a plan that
+            # stops at global_pool; a plan that needs it fails in TsnNet with a KeyError naming the layer.
+            if l.name not in layers:
+                continue
+            blobs = layers[l.name]["blobs"]
+            W = blobs[0]
+            if W.size % l.num_output:
+                raise ValueError("InnerProduct %s: weight blob has shape %s for %d outputs" % (l.name, W.shape, l.num_output))
+            W = W.reshape(l.num_output, -1)
+            b = blobs[1].reshape(-1) if len(blobs) > 1 else np.zeros(W.shape[0], dtype=np.float32)
+            w[l.name] = {"W": np.ascontiguousarray(W), "b": np.ascontiguousarray(b)}
     return w
 
 
@@ -152,8 +164,12 @@ def _enc_blob(a: np.ndarray) -> bytes:
     return _enc_ld(7, _enc_ld(1, shape)) + _enc_ld(5, a.tobytes())
 
 
-def write_caffemodel(path: str, graph, weights: Dict[str, Dict[str, np.ndarray]], name: str = "BN-Inception"):
-    """Serialise weights as a NetParameter with the new-style ``layer`` field (what the TSN tooling saves)."""
+_V1_TYPES = {"Convolution": 4, "InnerProduct": 14}           # V1LayerParameter.LayerType values; the fork's BN has none we know: left out
+
+
+def write_caffemodel(path: str, graph, weights: Dict[str, Dict[str, np.ndarray]], name: str = "BN-Inception", v1: bool = False):
+    """Serialise weights as a NetParameter with the new-style ``layer`` field (what the TSN tooling saves), or -- ``v1`` -- with the
+    old ``layers`` records (V1LayerParameter: name 4, type enum 5, blobs 6)."""
     out = bytearray(_enc_ld(1, name.encode()))
     for l in graph.layers:
         if l.name not in weights:
@@ -165,7 +181,13 @@ def write_caffemodel(path: str, graph, weights: Dict[str, Dict[str, np.ndarray]]
         elif l.type == "BN":
             c = d["scale"].shape[0]
             blobs = [d[k].reshape(1, c, 1, 1) for k in ("scale", "shift", "mean", "var")]
+        elif l.type == "InnerProduct":
+            blobs = [d["W"].reshape(d["W"].shape[0], -1), d["b"].reshape(-1)]
         else:
+            continue
+        if v1:
+            kind = _enc_varint((5 << 3) | 0) + _enc_varint(_V1_TYPES[l.type]) if l.type in _V1_TYPES else b""
+            out += _enc_ld(2, _enc_ld(4, l.name.encode()) + kind + b"".join(_enc_ld(6, _enc_blob(b)) for b in blobs))
             continue
         body = _enc_ld(1, l.name.encode()) + _enc_ld(2, l.type.encode()) + b"".join(_enc_ld(7, _enc_blob(b)) for b in blobs)
         out += _enc_ld(100, body)

@@ -210,6 +210,34 @@ def crop0(img: np.ndarray, frame_size=(340, 256), crop=224, rule: str = "cv2") -
     return resize_bilinear(img, frame_size, rule)[:crop, :crop]
 
 
+def oversample_offsets(h: int, w: int, crop: int) -> List[Tuple[int, int]]:
+    """(y, x) of the five un-mirrored crops of pyActionRecog's ten-crop over-sample on an h x w frame, in its order: the four corners
+    (0,0), (0,W-c), (H-c,0), (H-c,W-c), then the centre at trunc(H/2.0 - c/2.0), trunc(W/2.0 - c/2.0).  Restated from memory
+    (SURVEY.md Appendix B): PARITY UNPINNED."""
+    if crop > h or crop > w:
+        raise ValueError("crop %d does not fit a %dx%d frame" % (crop, w, h))
+    return [(0, 0), (0, w - crop), (h - crop, 0), (h - crop, w - crop), (int(h / 2.0 - crop / 2.0), int(w / 2.0 - crop / 2.0))]
+
+
+def oversample(img: np.ndarray, frame_size=(340, 256), crop=224, rule: str = "cv2") -> np.ndarray:
+    """Resize to frame_size (w, h), then the ten over-sample crops [10][crop][crop][C] (a grey image counts as C = 1): the five of
+    ``oversample_offsets``, then their horizontal mirrors.  Crop 0 is ``crop0``."""
+    r = resize_bilinear(img, frame_size, rule)
+    if r.ndim == 2:
+        r = r[..., None]
+    five = [r[y:y + crop, x:x + crop] for y, x in oversample_offsets(r.shape[0], r.shape[1], crop)]
+    return np.ascontiguousarray(np.stack(five + [c[:, ::-1] for c in five]))
+
+
+def oversample_flow_stack(stack, frame_size=(340, 256), crop=224, rule: str = "cv2") -> np.ndarray:
+    """The grey frames of a flow stack (x, y, x, y, ...) -> [10][crop][crop][len(stack)]: each plane over-sampled like an image; the
+    MIRRORED crops of the x planes (even channels) store 255 - v, since a mirrored scene moves the other way along x (same
+    appendix, unpinned)."""
+    out = np.concatenate([oversample(f, frame_size, crop, rule) for f in stack], axis=-1)
+    out[5:, :, :, 0::2] = 255 - out[5:, :, :, 0::2]
+    return out
+
+
 def load_rgb_frames(clip_dir: str, ticks: List[int], rgb_prefix='img_', ext='.jpg') -> np.ndarray:
     """[T, H, W, 3] uint8 BGR: the decoded frames of the snippets, NOT resized (the device does that: vq_resize_crop)."""
     return np.stack([imread(os.path.join(clip_dir, '{}{:05d}{}'.format(rgb_prefix, t, ext)), True) for t in ticks])

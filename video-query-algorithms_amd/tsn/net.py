@@ -23,12 +23,14 @@ BK = 32                      # K granularity of the implicit-GEMM kernel (csrc/v
 RGB_MEAN = (104.0, 117.0, 123.0)      # BGR order, as cv2.imread delivers frames
 FLOW_MEAN = (128.0,) * 10
 _OPS = {"conv": _lib.VQ_OP_CONV, "maxpool": _lib.VQ_OP_MAXPOOL, "avgpool": _lib.VQ_OP_AVGPOOL,
-        "gavgpool": _lib.VQ_OP_GLOBAL_AVGPOOL}
+        "gavgpool": _lib.VQ_OP_GLOBAL_AVGPOOL, "fc": _lib.VQ_OP_INNER_PRODUCT}
 
 
 def synthetic_weights(graph: Graph, seed: int = 2) -> Dict[str, Dict[str, np.ndarray]]:
     """Random-init weights of the right architecture (SURVEY.md 8(d) cfg 2): conv ~ N(0, sqrt(2/fan_in)),
-    small biases, frozen-BN statistics that keep activations O(1) through the 69 layers."""
+    small biases, frozen-BN statistics that keep activations O(1) through the 69 layers.  An InnerProduct layer (the fc-action head)
+    draws W [num_output][cin] ~ N(0, sqrt(2/cin)) and b ~ 0.05 N(0, 1) from a generator of its own, seeded from (seed, layer name): the
+    arrays of every other layer are what they were before the head had weights."""
     rng = np.random.default_rng(seed)
     w: Dict[str, Dict[str, np.ndarray]] = {}
     shapes = {graph.input_name: graph.input_shape[0]}
@@ -50,6 +52,10 @@ def synthetic_weights(graph: Graph, seed: int = 2) -> Dict[str, Dict[str, np.nda
         elif l.type == "Concat":
             shapes[l.tops[0]] = sum(shapes[b] for b in l.bottoms)
         elif l.type == "InnerProduct":
+            cin = shapes[l.bottoms[0]]
+            own = np.random.default_rng([int(seed)] + list(l.name.encode()))
+            w[l.name] = {"W": (own.standard_normal((l.num_output, cin)) * np.sqrt(2.0 / cin)).astype(np.float32),
+                         "b": (own.standard_normal(l.num_output) * 0.05).astype(np.float32)}
             shapes[l.tops[0]] = l.num_output
         else:
             shapes[l.tops[0]] = shapes[l.bottoms[0]]
@@ -246,14 +252,15 @@ class TsnNet:
     def __init__(self, graph: Graph, weights, max_crops: int = 96, device: int = 0,
                  feature_blob: str = "global_pool", bn_eps: float = 1e-5, fuse: bool = True,
                  winograd: bool | None = None, stem_s2d: bool | None = None, cache_key: str | None = None,
-                 tune_cache: str | None = None):
+                 tune_cache: str | None = None, keep: Sequence[str] = ()):
         """``weights``: {layer: {field: array}}, or a function without arguments that returns it (called only when the packed form
         is not in the cache).  ``cache_key``: names the weights' CONTENT (a digest of the file they come from, "synthetic:<seed>");
         with it the packed device blob -- BN folded, GEMM / Winograd layouts, biases -- is kept next to the library
         (``VQ_WEIGHT_CACHE=<dir>`` moves it, ``=0`` disables) under a digest of (key, layer plan, packing options, library ABI), and
-        a later handle of the same network skips reading, folding and transforming the weights (0.3-0.5 s of every command-line run)."""
+        a later handle of the same network skips reading, folding and transforming the weights (0.3-0.5 s of every command-line run).
+        ``keep``: blobs the device computes and holds beside the feature blob (``read_blob``), e.g. ("fc-action",)."""
         self.graph = graph
-        self.plan: Plan = graph.plan(feature_blob, fuse=fuse)
+        self.plan: Plan = graph.plan(feature_blob, fuse=fuse, keep=tuple(keep))
         self.in_channels = graph.input_shape[0]
         self.max_crops = int(max_crops)
         self.device = device
@@ -372,6 +379,24 @@ class TsnNet:
                     d.w_off = off
                     chunks.append(packed.reshape(-1))
                     off += packed.size
+                    d.b_off = off
+                    bias = np.zeros(pad4(op.cout), dtype=np.float32)
+                    bias[:op.cout] = b
+                    chunks.append(bias)
+                    off += bias.size
+                elif op.kind == "fc":                                          # InnerProduct: W [cout][cin] as Caffe stores it, then the bias
+                    if op.name not in weights:
+                        raise KeyError("no weights for InnerProduct layer %r" % op.name)
+                    W = np.asarray(weights[op.name]["W"], dtype=np.float32).reshape(op.cout, -1)
+                    b = np.asarray(weights[op.name]["b"], dtype=np.float32).reshape(-1)
+                    if W.shape != (op.cout, op.cin) or b.shape != (op.cout,):
+                        raise ValueError("weights of %s have shape %s / %s, expected %s" % (op.name, W.shape, b.shape, (op.cout, op.cin)))
+                    d.has_bias = 1
+                    d.w_off = off
+                    chunks.append(np.ascontiguousarray(W).reshape(-1))
+                    off += _round_up(W.size, 4)
+                    if W.size % 4:
+                        chunks.append(np.zeros(-W.size % 4, dtype=np.float32))
                     d.b_off = off
                     bias = np.zeros(pad4(op.cout), dtype=np.float32)
                     bias[:op.cout] = b
