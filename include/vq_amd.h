@@ -68,7 +68,9 @@ extern "C" {
  * 11 (round 6): + vq_tsn_tile_tables / vq_tsn_get_tiles / vq_tsn_set_tiles / vq_tsn_tune / vq_tsn_set_split / vq_device_pool_trim; VQ_OP_CONV_WINOGRAD16 (a tiling table is keyed by (batch size, timed side by side on
  *      the sub-batch streams | alone)); vq_db_query_round / vq_db_round_layout / vq_host_alloc / vq_host_free (a query round in one call); vq_db_loss_surface;
  *      vq_stream_create_priority.
- * 12: + vq_flow_tile_cut (which cut of a level vq_flow_tvl1 runs for a number of pairs: tests of the tile kernel name the cuts they ran). */
+ * 12: + vq_flow_tile_cut (which cut of a level vq_flow_tvl1 runs for a number of pairs: tests of the tile kernel name the cuts they ran).
+ *     Still 12, no new symbol: VQ_OP_INNER_PRODUCT (a value of vq_layer_desc.op); VQ_RESIZE_OVERSAMPLE / VQ_RESIZE_MIRROR_INVERT (flag bits on
+ *     the rule of vq_resize_crop / vq_resize_crop_planes, which a library without them refuses as an unknown rule). */
 #define VQ_ABI_VERSION 12
 
 enum {
@@ -264,9 +266,19 @@ typedef struct vq_tsn vq_tsn;
  * OpenCV's uint8 path (float sample positions, 11-bit fixed-point weights, integer passes; same bytes as
  * tsn/frames.py:resize_cv2_fixed and oracle/frames_oracle.py); VQ_RESIZE_EXACT = the same sampling grid with exact fp64
  * weights, round half to even (tsn/frames.py:resize_exact).  A frame that already has the size is copied.  Both are
- * restated without cv2 at hand: parity unpinned. */
+ * restated without cv2 at hand: parity unpinned.
+ * The low byte of `rule` is the resize rule; two flag bits may be set on it (no other bit: "unknown resize rule", nothing launched):
+ *   VQ_RESIZE_OVERSAMPLE     all ten over-sampled crops, what the two predict_* calls feed the classifier head: crops_dev is
+ *       [n][10][crop][crop][dst_channels]; crop k < 5 is the crop x crop window of the resized frame at
+ *       tsn/frames.py:oversample_offsets(resize_h, resize_w, crop)[k] -- the corners (0,0), (0,W-c), (H-c,0), (H-c,W-c), then the centre
+ *       ((H-c)/2, (W-c)/2) --, crop 5 + k is crop k mirrored along x.  Crop 0 has the bytes of the un-flagged call.
+ *   VQ_RESIZE_MIRROR_INVERT  only with VQ_RESIZE_OVERSAMPLE: the c channels this call writes store 255 - v in crops 5..9 -- the x planes
+ *       of a flow stack, whose motion changes sign under the mirror (tsn/frames.py:oversample_flow_stack).
+ * Crop order and x-inversion are pyActionRecog's restated from memory: parity unpinned. */
 #define VQ_RESIZE_CV2_FIXED 0
 #define VQ_RESIZE_EXACT 1
+#define VQ_RESIZE_OVERSAMPLE 0x100
+#define VQ_RESIZE_MIRROR_INVERT 0x200
 int vq_resize_crop(const uint8_t* frames, int32_t frames_on_device, int32_t n, int32_t h, int32_t w, int32_t c,
                    int32_t resize_w, int32_t resize_h, int32_t crop, int32_t rule, uint8_t* crops_dev, int32_t dst_channels,
                    int32_t dst_channel0, int32_t device, void* hip_stream);
@@ -274,7 +286,10 @@ int vq_resize_crop(const uint8_t* frames, int32_t frames_on_device, int32_t n, i
 /* The same for the ten grey planes of a batch of flow stacks in ONE launch: plane p of frame i at planes_dev + p * plane_stride + i * h * w
  * (what vq_jpeg_decode leaves on the device when the files are handed over plane-major), written as the interleaved crops
  * [n][crop][crop][c].  c must be 10 (predict_single_flow_stack's stack of 5 x/y pairs, calcSig_wOF.py:98-111); crop even.  Same bytes as c
- * calls of vq_resize_crop (tested); a thread computes the taps of its two pixels once for all planes and stores whole words. */
+ * calls of vq_resize_crop (tested); a thread computes the taps of its two pixels once for all planes and stores whole words.
+ * rule | VQ_RESIZE_OVERSAMPLE: the ten crops [n][10][crop][crop][c] of vq_resize_crop's flag; being defined on flow stacks, the call
+ * stores 255 - v in the even channels (the x planes) of crops 5..9 itself and refuses VQ_RESIZE_MIRROR_INVERT.  Same bytes as c calls of
+ * vq_resize_crop with the flag, VQ_RESIZE_MIRROR_INVERT on the even planes (tested). */
 int vq_resize_crop_planes(const uint8_t* planes_dev, int32_t n, int32_t h, int32_t w, int32_t c, int64_t plane_stride, int32_t resize_w,
                           int32_t resize_h, int32_t crop, int32_t rule, uint8_t* crops_dev, int32_t device, void* hip_stream);
 

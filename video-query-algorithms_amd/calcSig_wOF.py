@@ -80,6 +80,11 @@ def build_parser():
                         help="a further ensemble member (repeatable): the SAME pass over the frame tree -- every frame read, decoded and resized "
                              "once -- also runs these weights and writes their <modelname> directories; the three runs of "
                              "calcSig_wOF_ensemble.sh:13-37 become one command with two --ensemble options, byte-identical files")
+    parser.add_argument('--over_sample', action='store_true',
+                        help="every snippet contributes the ten crops of pyActionRecog's over-sample (four corners, centre, their mirrors; cut on "
+                             "the GPU unless --host_resize) instead of crop 0, and the consensus runs over T x 10 crops: the ten-crop feature, "
+                             "or with --featureBlob fc-action the video-level class scores of the TSN test protocol.  A forward takes "
+                             "max(batch_clips x T, 10 T) // (10 T) clips")
     parser.add_argument('--number_format', choices=('repr', 'g12'), default='repr',
                         help="how str(numpy.float64) printed under the numpy the reference ran with: shortest round-trip "
                              "(numpy >= 1.14, lossless) or 12 significant digits (numpy < 1.14); the reference ships files of both kinds")
@@ -143,16 +148,18 @@ class _CropPipeline:
     overlaps the other's device half).  Nothing here needs an extractor: the first batches are prepared while the extractors are
     still being built, and the flow stream's first batches while the RGB stream's last ones are in the network."""
 
-    def __init__(self, ingests, batches, order, load_clip, file_pool, ahead=3):
+    def __init__(self, ingests, batches, order, load_clip, file_pool, ahead=3, over_sample=False):
         from concurrent.futures import ThreadPoolExecutor
         self.ingests, self.batches, self.order, self.load_clip, self.file_pool, self.ahead = ingests, batches, order, load_clip, file_pool, ahead
+        self.over_sample = over_sample                   # --over_sample: the ten crops of every snippet
         self.pool = ThreadPoolExecutor(max_workers=2)
         self.jobs, self.submitted = {}, 0
 
     def _prepare(self, k):
         si, bi = self.order[k]
         lists = [f.result() for f in [self.file_pool.submit(self.load_clip, si, u) for u in self.batches[bi]]]
-        return self.ingests[si].crops_from_jpegs([f for c in lists for f in c], lane=k % 2)
+        ingest = self.ingests[si]
+        return (ingest.oversample_from_jpegs if self.over_sample else ingest.crops_from_jpegs)([f for c in lists for f in c], lane=k % 2)
 
     def start(self):
         self._fill(0)
@@ -260,9 +267,14 @@ def _main(argv=None, net_factory=None, program=None):
     stamp("frame tree parsed: %d videos, %d clips, %d group(s)" % (len(videos), sum(len(u) for u in group_units), len(groups)))
     on_gpu = world > 1                                   # blocks that will be all-gathered never visit the host
     host_rule = {'rule': rule} if args.host_resize else {}             # the host loaders resize; the others hand frames to the GPU
+    # --over_sample: a snippet is ten crops (snippet-major) and the consensus of a clip runs over its 10 T crops; a batch is what ONE
+    # forward takes of them, so every path below works on whole batches as it does without the flag
+    max_crops = max(args.batch_clips * T, 10 * T) if args.over_sample else args.batch_clips * T
+    batch_clips = max_crops // (10 * T) if args.over_sample else args.batch_clips
+    ten = {'over_sample': True} if args.over_sample else {}
 
     def build(s, m):
-        return net_factory(s['net_proto'], m[s['modality']], device, max_crops=args.batch_clips * T, feature_blob=args.featureBlob, resize_rule=rule)
+        return net_factory(s['net_proto'], m[s['modality']], device, max_crops=max_crops, feature_blob=args.featureBlob, resize_rule=rule)
     # both streams' extractors are built side by side: the flow nets' weights are folded and uploaded while the RGB stream is running
     net_jobs = {(s['modality'], mi): build_pool.submit(build, s, m) for s in streamCNN for mi, m in enumerate(members)} if count else {}
 
@@ -271,16 +283,18 @@ def _main(argv=None, net_factory=None, program=None):
         f_info, vid = videos[unit[0]][1], unit[1]
         frame_cnt = f_info[s['cnt_indexer']][vid]
         ticks = frames.frame_ticks(frame_cnt, T, s['stack_depth'])
+        host_rgb, host_flow = ((frames.load_rgb_oversampled, frames.load_flow_oversampled) if args.over_sample else
+                               (frames.load_rgb_snippets, frames.load_flow_snippets))
         if s['modality'] == 'rgb':
-            load = frames.load_rgb_jpegs if device_jpeg else frames.load_rgb_snippets if args.host_resize else frames.load_rgb_frames
+            load = frames.load_rgb_jpegs if device_jpeg else host_rgb if args.host_resize else frames.load_rgb_frames
             return load(f_info[0][vid], ticks, args.rgb_prefix, args.frame_ext, **host_rule)
-        load = frames.load_flow_jpegs if device_jpeg else frames.load_flow_snippets if args.host_resize else frames.load_flow_frames
+        load = frames.load_flow_jpegs if device_jpeg else host_flow if args.host_resize else frames.load_flow_frames
         return load(f_info[0][vid], ticks, frame_cnt, s['stack_depth'], args.flow_x_prefix, args.flow_y_prefix, args.frame_ext, **host_rule)
 
     batches, group_batches = [], []                      # this rank's batches of all groups; per group: their indices
     for units, (first, cnt) in zip(group_units, shards):
-        group_batches.append(list(range(len(batches), len(batches) + -(-cnt // args.batch_clips))))
-        batches += [units[b0:min(b0 + args.batch_clips, first + cnt)] for b0 in range(first, first + cnt, args.batch_clips)]
+        group_batches.append(list(range(len(batches), len(batches) + -(-cnt // batch_clips))))
+        batches += [units[b0:min(b0 + batch_clips, first + cnt)] for b0 in range(first, first + cnt, batch_clips)]
     n_streams = len(streamCNN)
     # The order of the work.  Host decoding: stream by stream, as the reference does (all RGB batches, then all flow batches).
     # --device_jpeg: batch by batch, the RGB and the flow half of a batch behind each other -- the preparation of a flow batch (8 000
@@ -293,7 +307,7 @@ def _main(argv=None, net_factory=None, program=None):
         group_order = [[(si, bi) for bi in gb for si in range(n_streams)] for gb in group_batches]
         order = [x for go in group_order for x in go]
         crop_pipe = _CropPipeline([FrameIngest(3 if s['modality'] == 'rgb' else 2 * s['stack_depth'], device, rule) for s in streamCNN],
-                                  batches, order, load_clip, pool)
+                                  batches, order, load_clip, pool, over_sample=args.over_sample)
         # (building the extractors BEFORE the readers start -- 12 ms alone against 45+ ms beside sixteen reader threads -- was measured in
         # round 5: no difference end to end, 537-545 against 538-561 clips/s on one box: the job is bound by the networks)
         crop_pipe.start()                            # the first batches are read and decoded while the extractors are being built
@@ -401,24 +415,25 @@ def _main(argv=None, net_factory=None, program=None):
                 t0 = time.perf_counter()
                 dev_crops = crop_pipe.get(k)
                 waited[si]['crops'] += time.perf_counter() - t0
-                through_the_nets(si, lambda net: net.extract_clips_from_crops(dev_crops, T, on_device=on_gpu), (si, bi))
+                through_the_nets(si, lambda net: net.extract_clips_from_crops(dev_crops, T, on_device=on_gpu, **ten), (si, bi))
             elif not crops:
                 continue
             elif args.host_resize:
                 block = np.concatenate(crops, axis=0)
-                through_the_nets(si, lambda net: net.extract_clips(block, T, on_device=on_gpu), (si, bi))
+                through_the_nets(si, lambda net: net.extract_clips(block, 10 * T if args.over_sample else T, on_device=on_gpu), (si, bi))
             else:
                 # resize + crop on the GPU, once per batch; clips of different frame sizes in one batch go one by one
                 same_size = [np.concatenate(crops, axis=0)] if len({c.shape[1:] for c in crops}) == 1 else crops
                 for g in same_size:
                     if len(nets[si]) == 1:
-                        through_the_nets(si, lambda net: net.extract_clips_from_frames(g, T, on_device=on_gpu), (si, bi))
+                        through_the_nets(si, lambda net: net.extract_clips_from_frames(g, T, on_device=on_gpu, **ten), (si, bi))
                     else:
-                        per = args.batch_clips * T                      # = max_crops of the extractors
+                        per = batch_clips * T                           # snippets per forward (without --over_sample: max_crops of the extractors)
                         for i in range(0, g.shape[0], per):
-                            dev_crops = nets[si][0].crops_from_frames(g[i:i + per])
+                            cut = nets[si][0].oversample_from_frames if args.over_sample else nets[si][0].crops_from_frames
+                            dev_crops = cut(g[i:i + per])
                             nets[si][0].sync_ingest()
-                            through_the_nets(si, lambda net: net.extract_clips_from_crops(dev_crops, T, on_device=on_gpu), (si, bi))
+                            through_the_nets(si, lambda net: net.extract_clips_from_crops(dev_crops, T, on_device=on_gpu, **ten), (si, bi))
         flush(gi)
     stamp("last batch through the networks")
     if trace:

@@ -11,6 +11,14 @@
 //   VQ_RESIZE_EXACT  the same sampling grid with exact fp64 weights, rounded half to even (tsn/frames.py:resize_exact,
 //       operation for operation, contraction off).
 // Both restate cv2 from memory of imgproc/resize.cpp: "parity unpinned" for lack of cv2 and of the reference's frames.
+//
+// VQ_RESIZE_OVERSAMPLE (a flag bit on `rule`, both entry points): all TEN crops of pyActionRecog's over-sample -- what predict_single_frame /
+// predict_single_flow_stack feed the classifier head, and what the standard TSN test protocol averages -- from one pass over the frame:
+// [n][10][crop][crop][C], crop k < 5 the window of the resized frame at tsn/frames.py:oversample_offsets()[k] (four corners, then the
+// centre), crop 5 + k its mirror along x; VQ_RESIZE_MIRROR_INVERT stores 255 - v in the mirrored crops (the x planes of a flow stack; the
+// planes form does it for its even channels itself).  A thread computes a pixel of one of the five windows ONCE and stores it twice, so a
+// mirror pair is equal by construction; crop 0 has the bytes of the un-flagged call, whose kernels below are untouched.  Order and
+// x-inversion restated from memory: parity unpinned.
 #include "vq_common.h"
 
 using namespace vq;
@@ -179,6 +187,161 @@ __global__ void resize_crop_planes_kernel(PlanesArgs a) {
     for (int q = 0; q < 2 * C / 4; ++q) out[q] = words[q];
 }
 
+// ---- the ten-crop over-sample ---------------------------------------------------------------------------------------------------
+// The crop-0 kernels above stay as they are; these restate their per-pixel arithmetic once, per MODE (0: cv2 fixed point, 1: exact fp64
+// weights, 2: the frame has the size already), evaluated at a coordinate of the RESIZED frame (window offset + position in the crop).
+struct AxisTap {
+    int i0, i1;        // the two source rows / columns
+    int w0, w1;        // MODE 0: their 11-bit weights
+    double f;          // MODE 1: the weight of i1
+};
+
+template <int MODE>
+__device__ inline AxisTap axis_tap(int d, int n_in, int n_out, bool x_axis) {
+    AxisTap t;
+    t.i0 = t.i1 = d;
+    t.w0 = t.w1 = 0;
+    t.f = 0.0;
+    if (MODE == 0) {
+        int s;
+        cv2_taps(d, n_in, n_out, x_axis, s, t.w0, t.w1);
+        if (x_axis) {                                   // taps clamped by cv2_taps
+            t.i0 = s;
+            t.i1 = min(s + 1, n_in - 1);
+        } else {                                        // the weights stay, the ROWS are clipped
+            t.i0 = min(max(s, 0), n_in - 1);
+            t.i1 = min(max(s + 1, 0), n_in - 1);
+        }
+    } else if (MODE == 1) {
+        double ds = ((double)d + 0.5) * (double)n_in / (double)n_out - 0.5;
+        ds = fmin(fmax(ds, 0.0), (double)(n_in - 1));
+        t.i0 = (int)floor(ds);
+        t.i1 = min(t.i0 + 1, n_in - 1);
+        t.f = ds - (double)t.i0;
+    }
+    return t;
+}
+
+template <int MODE>
+__device__ inline int blend(int p00, int p01, int p10, int p11, const AxisTap& ty, const AxisTap& tx) {
+    if (MODE == 0) {
+        const int s0 = p00 * tx.w0 + p01 * tx.w1, s1 = p10 * tx.w0 + p11 * tx.w1;
+        return min(max((((ty.w0 * (s0 >> 4)) >> 16) + ((ty.w1 * (s1 >> 4)) >> 16) + 2) >> 2, 0), 255);
+    }
+    if (MODE == 1) {
+        const double wy = ty.f, wx = tx.f;
+        double v = (double)p00 * (1.0 - wy) * (1.0 - wx);
+        v = v + (double)p01 * (1.0 - wy) * wx;
+        v = v + (double)p10 * wy * (1.0 - wx);
+        v = v + (double)p11 * wy * wx;
+        return (int)fmin(fmax(rint(v), 0.0), 255.0);
+    }
+    return p00;
+}
+
+struct OversampleArgs {
+    const uint8_t* src;   // packed: [n][h][w][c]; planes: plane p of frame n at src + p * plane_stride + n * h * w
+    uint8_t* dst;         // [n][10][crop][crop][dst_c], the packed form's channels at dst_c0
+    int64_t plane_stride, total;   // total: n * 5 * crop * crop (packed), n * 5 * crop * crop / 2 (planes)
+    int h, w, c, rw, rh, crop, dst_c, dst_c0, invert;
+    int oy[5], ox[5];     // the five windows in the resized frame (host: oversample_windows)
+};
+
+// A wave's 64 threads are 64 neighbouring columns of one row of one window: its stores to crop k are contiguous, and those to crop 5 + k
+// the same bytes of that crop's row walked backwards.
+template <int MODE>
+__global__ void oversample_kernel(OversampleArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.total) return;
+    const int64_t area = (int64_t)a.crop * a.crop;
+    const int x = (int)(i % a.crop), y = (int)((i / a.crop) % a.crop), k = (int)((i / area) % 5);
+    const int64_t n = i / (5 * area);
+    int oy = 0, ox = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (k == q) {
+            oy = a.oy[q];
+            ox = a.ox[q];
+        }
+    const AxisTap ty = axis_tap<MODE>(oy + y, a.h, a.rh, false), tx = axis_tap<MODE>(ox + x, a.w, a.rw, true);
+    const uint8_t* img = a.src + n * (int64_t)a.h * a.w * a.c;
+    const uint8_t* r0 = img + (int64_t)ty.i0 * a.w * a.c;
+    const uint8_t* r1 = img + (int64_t)ty.i1 * a.w * a.c;
+    uint8_t* out = a.dst + (((n * 10 + k) * a.crop + y) * (int64_t)a.crop + x) * a.dst_c + a.dst_c0;
+    uint8_t* mir = a.dst + (((n * 10 + 5 + k) * a.crop + y) * (int64_t)a.crop + (a.crop - 1 - x)) * a.dst_c + a.dst_c0;
+    for (int ch = 0; ch < a.c; ++ch) {
+        const int v = blend<MODE>(r0[(int64_t)tx.i0 * a.c + ch], r0[(int64_t)tx.i1 * a.c + ch], r1[(int64_t)tx.i0 * a.c + ch],
+                                  r1[(int64_t)tx.i1 * a.c + ch], ty, tx);
+        out[ch] = (uint8_t)v;
+        mir[ch] = (uint8_t)(a.invert ? 255 - v : v);
+    }
+}
+
+// The C grey planes of a flow stack: a thread owns two adjacent pixels of one of the five windows and all C planes, as resize_crop_planes_kernel
+// does for crop 0.  Their mirror is the pixel pair at column crop - 2 - 2 xp (even, since crop is): the same 2 C bytes with the two pixels
+// swapped and the even channels (the x planes) stored as 255 - v -- whole 32-bit words at both destinations.
+template <int C, int MODE>
+__global__ void oversample_planes_kernel(OversampleArgs a) {
+    static_assert((2 * C) % 4 == 0, "a thread's two pixels are whole 32-bit words");
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.total) return;
+    const int half = a.crop / 2;
+    const int64_t area = (int64_t)half * a.crop;
+    const int xp = (int)(i % half), y = (int)((i / half) % a.crop), k = (int)((i / area) % 5);
+    const int64_t n = i / (5 * area);
+    int oy = 0, ox = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (k == q) {
+            oy = a.oy[q];
+            ox = a.ox[q];
+        }
+    const uint8_t* img = a.src + n * (int64_t)a.h * a.w;
+    uint32_t words[2 * C / 4], mwords[2 * C / 4];
+#pragma unroll
+    for (int q = 0; q < 2 * C / 4; ++q) words[q] = mwords[q] = 0u;
+    const AxisTap ty = axis_tap<MODE>(oy + y, a.h, a.rh, false);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const AxisTap tx = axis_tap<MODE>(ox + 2 * xp + e, a.w, a.rw, true);
+        const int64_t o00 = (int64_t)ty.i0 * a.w + tx.i0, o01 = (int64_t)ty.i0 * a.w + tx.i1;
+        const int64_t o10 = (int64_t)ty.i1 * a.w + tx.i0, o11 = (int64_t)ty.i1 * a.w + tx.i1;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+            const uint8_t* pl = img + ch * a.plane_stride;
+            const int v = MODE == 2 ? (int)pl[o00] : blend<MODE>(pl[o00], pl[o01], pl[o10], pl[o11], ty, tx);
+            const int pos = e * C + ch, mpos = (1 - e) * C + ch;
+            words[pos >> 2] |= (uint32_t)v << (8 * (pos & 3));
+            mwords[mpos >> 2] |= (uint32_t)(ch % 2 == 0 ? 255 - v : v) << (8 * (mpos & 3));
+        }
+    }
+    uint32_t* out = reinterpret_cast<uint32_t*>(a.dst + (((n * 10 + k) * a.crop + y) * (int64_t)a.crop + 2 * xp) * C);
+    uint32_t* mir = reinterpret_cast<uint32_t*>(a.dst + (((n * 10 + 5 + k) * a.crop + y) * (int64_t)a.crop + (a.crop - 2 - 2 * xp)) * C);
+#pragma unroll
+    for (int q = 0; q < 2 * C / 4; ++q) {
+        out[q] = words[q];
+        mir[q] = mwords[q];
+    }
+}
+
+// tsn/frames.py:oversample_offsets: the four corners, then the centre (integer division = its trunc(H / 2.0 - c / 2.0) for H >= c)
+void oversample_windows(OversampleArgs& a) {
+    const int fy = a.rh - a.crop, fx = a.rw - a.crop;
+    const int oy[5] = {0, 0, fy, fy, fy / 2}, ox[5] = {0, fx, 0, fx, fx / 2};
+    for (int k = 0; k < 5; ++k) {
+        a.oy[k] = oy[k];
+        a.ox[k] = ox[k];
+    }
+}
+
+// rule = resize rule in the low byte | flag bits
+bool rule_known(int32_t rule, int32_t flags_allowed) {
+    const int32_t base = rule & 0xff, flags = rule & ~0xff;
+    if (base != VQ_RESIZE_CV2_FIXED && base != VQ_RESIZE_EXACT) return false;
+    if (flags & ~flags_allowed) return false;
+    return !(flags & VQ_RESIZE_MIRROR_INVERT) || (flags & VQ_RESIZE_OVERSAMPLE);
+}
+
 }  // namespace
 
 extern "C" int vq_resize_crop_planes(const uint8_t* planes_dev, int32_t n, int32_t h, int32_t w, int32_t c, int64_t plane_stride, int32_t resize_w,
@@ -189,13 +352,40 @@ extern "C" int vq_resize_crop_planes(const uint8_t* planes_dev, int32_t n, int32
     VQ_REQUIRE(plane_stride >= (int64_t)n * h * w, "plane_stride is smaller than a plane");
     VQ_REQUIRE(resize_w >= crop && resize_h >= crop && crop > 0 && crop % 2 == 0, "crop %d must be even and fit the %dx%d resized frame", crop, resize_w,
                resize_h);
-    VQ_REQUIRE(rule == VQ_RESIZE_CV2_FIXED || rule == VQ_RESIZE_EXACT, "unknown resize rule %d", rule);
+    VQ_REQUIRE(rule_known(rule, VQ_RESIZE_OVERSAMPLE), "unknown resize rule %d", rule);
     VQ_REQUIRE(((uintptr_t)crops_dev & 3u) == 0, "crops_dev must be 4-byte aligned");
     int ndev = 0;
     VQ_HIP(hipGetDeviceCount(&ndev));
     VQ_REQUIRE(device >= 0 && device < ndev, "device %d out of range (%d visible)", device, ndev);
     DeviceGuard g(device);
     hipStream_t st = (hipStream_t)stream;
+    if (rule & VQ_RESIZE_OVERSAMPLE) {
+        OversampleArgs o;
+        o.src = planes_dev;
+        o.dst = crops_dev;
+        o.plane_stride = plane_stride;
+        o.total = (int64_t)n * 5 * crop * (crop / 2);
+        o.h = h;
+        o.w = w;
+        o.c = c;
+        o.rw = resize_w;
+        o.rh = resize_h;
+        o.crop = crop;
+        o.dst_c = c;
+        o.dst_c0 = 0;
+        o.invert = 1;
+        oversample_windows(o);
+        const unsigned oblocks = (unsigned)cdiv(o.total, 256);
+        if (h == resize_h && w == resize_w)
+            oversample_planes_kernel<10, 2><<<oblocks, 256, 0, st>>>(o);
+        else if ((rule & 0xff) == VQ_RESIZE_CV2_FIXED)
+            oversample_planes_kernel<10, 0><<<oblocks, 256, 0, st>>>(o);
+        else
+            oversample_planes_kernel<10, 1><<<oblocks, 256, 0, st>>>(o);
+        const hipError_t oe = hipGetLastError();
+        if (oe != hipSuccess) return fail(VQ_E_HIP, "kernel launch failed: %s", hipGetErrorString(oe));
+        return VQ_OK;
+    }
     PlanesArgs a;
     a.src = planes_dev;
     a.dst = crops_dev;
@@ -224,7 +414,7 @@ extern "C" int vq_resize_crop(const uint8_t* frames, int32_t frames_on_device, i
     VQ_REQUIRE(frames && crops_dev, "NULL argument");
     VQ_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0, "frames must be [n][h][w][c] with positive sizes");
     VQ_REQUIRE(resize_w >= crop && resize_h >= crop && crop > 0, "crop %d does not fit the %dx%d resized frame", crop, resize_w, resize_h);
-    VQ_REQUIRE(rule == VQ_RESIZE_CV2_FIXED || rule == VQ_RESIZE_EXACT, "unknown resize rule %d", rule);
+    VQ_REQUIRE(rule_known(rule, VQ_RESIZE_OVERSAMPLE | VQ_RESIZE_MIRROR_INVERT), "unknown resize rule %d", rule);
     VQ_REQUIRE(dst_channel0 >= 0 && dst_channel0 + c <= dst_channels, "channels [%d,%d) outside the %d-channel crop buffer", dst_channel0,
                dst_channel0 + c, dst_channels);
     int ndev = 0;
@@ -256,7 +446,30 @@ extern "C" int vq_resize_crop(const uint8_t* frames, int32_t frames_on_device, i
     a.crop = crop;
     a.dst_c = dst_channels;
     a.dst_c0 = dst_channel0;
-    if (h == resize_h && w == resize_w)         // a frame that already has the size is copied by either rule (weights 1, 0)
+    if (rule & VQ_RESIZE_OVERSAMPLE) {
+        OversampleArgs o;
+        o.src = src;
+        o.dst = crops_dev;
+        o.plane_stride = 0;
+        o.total = 5 * a.total;
+        o.h = h;
+        o.w = w;
+        o.c = c;
+        o.rw = resize_w;
+        o.rh = resize_h;
+        o.crop = crop;
+        o.dst_c = dst_channels;
+        o.dst_c0 = dst_channel0;
+        o.invert = (rule & VQ_RESIZE_MIRROR_INVERT) ? 1 : 0;
+        oversample_windows(o);
+        const unsigned oblocks = (unsigned)cdiv(o.total, 256);
+        if (h == resize_h && w == resize_w)
+            oversample_kernel<2><<<oblocks, 256, 0, st>>>(o);
+        else if ((rule & 0xff) == VQ_RESIZE_CV2_FIXED)
+            oversample_kernel<0><<<oblocks, 256, 0, st>>>(o);
+        else
+            oversample_kernel<1><<<oblocks, 256, 0, st>>>(o);
+    } else if (h == resize_h && w == resize_w)  // a frame that already has the size is copied by either rule (weights 1, 0)
         crop_copy_kernel<<<cdiv(a.total, 256), 256, 0, st>>>(a);
     else if (rule == VQ_RESIZE_CV2_FIXED)
         resize_crop_cv2_kernel<<<cdiv(a.total, 256), 256, 0, st>>>(a);

@@ -71,20 +71,23 @@ class _NetView:
 
 class CaffeNet:
     def __init__(self, net_proto, net_weights, device_id=0, max_crops=96, feature_blob="global_pool", resize_rule="cv2", scores=False,
-                 score_name="fc-action"):
+                 score_name="fc-action", host_oversample=False):
         """resize_rule: "cv2" = OpenCV's fixed-point INTER_LINEAR, what the reference's ``cv2.resize(frame, (340, 256))``
         computes (default); "exact" = exact fp64 bilinear weights (tsn/frames.py).
         scores: False (default) = the feature path: ``predict_*`` run crop 0 and return ``None``.  True = pyActionRecog's score
         interface: the plan also keeps the ``score_name`` blob, ``predict_*`` run the ten over-sampled crops (``over_sample=False``:
         crop 0 alone) through the device network and return its ``[crops][classes]`` float32 scores; ``_net.blobs`` then holds one
-        row per crop of the feature blob and of the score blob.  The crops are cut on the host (tsn/frames.py:oversample*: order and
-        x-flow inversion restated from memory, parity unpinned)."""
+        row per crop of the feature blob and of the score blob.  The frame or stack is uploaded once and the ten crops are cut on the
+        device (FrameIngest.oversample_from_frames); ``host_oversample=True`` cuts them with numpy and uploads the crops instead
+        (tsn/frames.py:oversample*) -- the same bytes and scores either way (order and x-flow inversion restated from memory, parity
+        unpinned)."""
         if resize_rule not in frames.RESIZE_RULES:
             raise ValueError("resize_rule must be 'cv2' or 'exact'")
         self._resize_rule = resize_rule
         self._graph = bn_inception.load_prototxt(net_proto) if isinstance(net_proto, str) else net_proto
         self._blob = feature_blob
         self._scores = bool(scores)
+        self._host_oversample = bool(host_oversample)
         self._score_name = score_name
         keep = (score_name,) if self._scores and score_name != feature_blob else ()
         if self._scores:
@@ -102,7 +105,7 @@ class CaffeNet:
         self._ingest = FrameIngest(self._channels, device_id, resize_rule)
 
     # -- the reference's per-snippet interface ------------------------------------------------------------
-    def _predict(self, crop0, ten, score_name, over_sample):
+    def _predict(self, crop0, ten, ten_dev, score_name, over_sample):
         if not self._scores:
             crops = crop0()[None]                                                                   # crop 0 of the 10-crop over-sample
             _, ps = self._model.forward(crops, 1, self._mean)
@@ -112,9 +115,16 @@ class CaffeNet:
         if name not in self._model.plan.blob_loc or (name != self._score_name and name != self._blob):
             raise KeyError("score blob %r is not computed by this extractor (built with score_name=%r, feature_blob=%r)"
                            % (name, self._score_name, self._blob))
-        crops = ten() if over_sample else crop0()[None]
-        n = crops.shape[0]
-        _, ps = self._model.forward(crops, 1, self._mean)
+        if over_sample and not self._host_oversample:
+            crops = ten_dev()                                                   # cut on the device: the frame went up, not its ten crops
+            self._ingest.sync()
+            n = crops.shape[0]
+            ps = np.empty((n, self._model.feature_dim), dtype=np.float32)
+            self._model.forward_device(crops.data_ptr(), n, 1, self._mean, per_snippet_out=ps)
+        else:
+            crops = ten() if over_sample else crop0()[None]
+            n = crops.shape[0]
+            _, ps = self._model.forward(crops, 1, self._mean)
         self._net.blobs[self._blob] = _Blob(ps.reshape(n, -1, 1, 1))            # one row per crop; .data[0] is crop 0, as without scores
         score = ps if name == self._blob else np.ascontiguousarray(self._model.read_blob(name, n).reshape(n, -1))
         self._net.blobs[name] = _Blob(score.reshape(n, -1, 1, 1))
@@ -122,11 +132,13 @@ class CaffeNet:
 
     def predict_single_frame(self, frame, score_name=None, over_sample=True, frame_size=(340, 256)):
         return self._predict(lambda: frames.crop0(frame[0], frame_size, rule=self._resize_rule),
-                             lambda: frames.oversample(frame[0], frame_size, rule=self._resize_rule), score_name, over_sample)
+                             lambda: frames.oversample(frame[0], frame_size, rule=self._resize_rule),
+                             lambda: self._ingest.oversample_from_frames(np.asarray(frame[0])[None], frame_size), score_name, over_sample)
 
     def predict_single_flow_stack(self, frame, score_name=None, over_sample=True, frame_size=(340, 256)):
         return self._predict(lambda: np.stack([frames.crop0(f, frame_size, rule=self._resize_rule) for f in frame], axis=-1),
-                             lambda: frames.oversample_flow_stack(frame, frame_size, rule=self._resize_rule), score_name, over_sample)
+                             lambda: frames.oversample_flow_stack(frame, frame_size, rule=self._resize_rule),
+                             lambda: self._ingest.oversample_from_frames(np.stack(frame)[None], frame_size), score_name, over_sample)
 
     # -- the batched path ------------------------------------------------------------------------------------
     def extract_clips(self, crops: np.ndarray, T: int, on_device: bool = False):
@@ -150,6 +162,15 @@ class CaffeNet:
             return torch.cat(out, dim=0)
         return np.concatenate(out, axis=0)
 
+    def _per_forward(self, T: int, over_sample: bool):
+        """(snippets per forward, the T the forward runs with): with ``over_sample`` every snippet is ten crops, snippet-major, and
+        the consensus over T' = 10 T of them is the average over snippets x crops."""
+        Tf = 10 * T if over_sample else T
+        per = (self._model.max_crops // Tf) * T
+        if per == 0:
+            raise ValueError("max_crops (%d) is smaller than %s (%d)" % (self._model.max_crops, "10 T" if over_sample else "T", Tf))
+        return per, Tf
+
     def crops_from_frames(self, frames_: np.ndarray, frame_size=(340, 256), crop=224):
         """Decoded frames -> device crops; see :class:`tsn.ingest.FrameIngest` (this extractor's own instance)."""
         return self._ingest.crops_from_frames(frames_, frame_size, crop)
@@ -161,16 +182,23 @@ class CaffeNet:
         """JPEG file contents -> device crops; see :class:`tsn.ingest.FrameIngest`."""
         return self._ingest.crops_from_jpegs(files, frame_size, crop, lane)
 
-    def extract_clips_from_jpegs(self, files, T: int, frame_size=(340, 256), on_device: bool = False):
-        """JPEG file contents of B*T snippets (flow: * C planes) -> consensus features [B, D]; see crops_from_jpegs."""
+    def oversample_from_frames(self, frames_: np.ndarray, frame_size=(340, 256), crop=224):
+        """Decoded frames -> the ten device crops of every snippet; see :class:`tsn.ingest.FrameIngest`."""
+        return self._ingest.oversample_from_frames(frames_, frame_size, crop)
+
+    def oversample_from_jpegs(self, files, frame_size=(340, 256), crop=224, lane=0):
+        """JPEG file contents -> the ten device crops of every snippet; see :class:`tsn.ingest.FrameIngest`."""
+        return self._ingest.oversample_from_jpegs(files, frame_size, crop, lane)
+
+    def extract_clips_from_jpegs(self, files, T: int, frame_size=(340, 256), on_device: bool = False, over_sample: bool = False):
+        """JPEG file contents of B*T snippets (flow: * C planes) -> consensus features [B, D]; see crops_from_jpegs.  ``over_sample``:
+        the ten crops of every snippet (oversample_from_jpegs), averaged with the snippets (see extract_clips_from_frames)."""
         from . import devmem
         per_snip = 1 if self._channels == 3 else self._channels
-        per = (self._model.max_crops // T) * T
-        if per == 0:
-            raise ValueError("max_crops (%d) is smaller than T (%d)" % (self._model.max_crops, T))
+        per, T = self._per_forward(T, over_sample)
         out = []
         for i in range(0, len(files) // per_snip, per):
-            crops = self.crops_from_jpegs(files[i * per_snip:(i + per) * per_snip], frame_size)
+            crops = (self.oversample_from_jpegs if over_sample else self.crops_from_jpegs)(files[i * per_snip:(i + per) * per_snip], frame_size)
             devmem.synchronize_current(self._model.device)
             nb = crops.shape[0]
             if on_device:
@@ -183,10 +211,13 @@ class CaffeNet:
             return torch.cat(out, dim=0)
         return np.concatenate(out, axis=0)
 
-    def extract_clips_from_crops(self, crops, T: int, on_device: bool = False):
+    def extract_clips_from_crops(self, crops, T: int, on_device: bool = False, over_sample: bool = False):
         """Device crops (torch uint8 [B*T, crop, crop, C], e.g. from ``crops_from_jpegs`` run by another thread for the NEXT batch while
-        this one is in the network) -> consensus features [B, D]."""
+        this one is in the network) -> consensus features [B, D].  ``over_sample``: the crops are the [B*T*10, ...] of
+        ``oversample_from_*`` and the consensus runs over the 10 T crops of a clip."""
         nb = crops.shape[0]
+        if over_sample:
+            T = 10 * T
         if nb > self._model.max_crops or nb % T:
             raise ValueError("%d crops: at most max_crops (%d), a multiple of T (%d)" % (nb, self._model.max_crops, T))
         if on_device:
@@ -196,16 +227,17 @@ class CaffeNet:
         # batches ahead, which other threads have in flight on the ingest streams
         return self._model.forward_device(crops.data_ptr(), nb, T, self._mean, np.empty((nb // T, self._model.feature_dim), dtype=np.float64))
 
-    def extract_clips_from_frames(self, frames_: np.ndarray, T: int, frame_size=(340, 256), on_device: bool = False):
+    def extract_clips_from_frames(self, frames_: np.ndarray, T: int, frame_size=(340, 256), on_device: bool = False, over_sample: bool = False):
         """Decoded frames of B*T snippets -> consensus features [B, D]: resize + crop 0 on the device, then the
-        batched forward on the resident crops (no host-side image processing at all).  ``on_device``: see extract_clips."""
+        batched forward on the resident crops (no host-side image processing at all).  ``on_device``: see extract_clips.
+        ``over_sample``: every snippet contributes its ten over-sampled crops (cut on the device, snippet-major) and the forward runs
+        with T' = 10 T, max_crops // (10 T) clips at a time: the fp64 average over snippets x crops -- the ten-crop feature under
+        ``global_pool``, the video-level class scores of the TSN test protocol under ``fc-action``."""
         from . import devmem
-        per = (self._model.max_crops // T) * T
-        if per == 0:
-            raise ValueError("max_crops (%d) is smaller than T (%d)" % (self._model.max_crops, T))
+        per, T = self._per_forward(T, over_sample)
         out = []
         for i in range(0, frames_.shape[0], per):
-            crops = self.crops_from_frames(frames_[i:i + per], frame_size)
+            crops = (self.oversample_from_frames if over_sample else self.crops_from_frames)(frames_[i:i + per], frame_size)
             devmem.synchronize_current(self._model.device)
             nb = crops.shape[0]
             if on_device:

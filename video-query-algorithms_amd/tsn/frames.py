@@ -132,6 +132,9 @@ def write_pnm(path: str, img: np.ndarray):
 
 RESIZE_CV2, RESIZE_EXACT = 0, 1            # include/vq_amd.h: VQ_RESIZE_CV2_FIXED / VQ_RESIZE_EXACT
 RESIZE_RULES = {"cv2": RESIZE_CV2, "exact": RESIZE_EXACT}
+# flag bits on the rule argument of vq_resize_crop / vq_resize_crop_planes (VQ_RESIZE_OVERSAMPLE / VQ_RESIZE_MIRROR_INVERT): all ten crops of
+# ``oversample`` from one call; 255 - v in the mirrored crops of the channels the call writes (the x planes of ``oversample_flow_stack``)
+RESIZE_OVERSAMPLE, RESIZE_MIRROR_INVERT = 0x100, 0x200
 
 
 def _cv2_linear_taps(n_in: int, n_out: int, clamp_taps: bool):
@@ -299,3 +302,21 @@ def load_flow_snippets(clip_dir: str, ticks: List[int], frame_cnt: int, stk_dept
             stack.append(crop0(imread(os.path.join(clip_dir, '{}{:05d}{}'.format(flow_y_prefix, idx, ext)), False), rule=rule))
         out.append(np.stack(stack, axis=-1))
     return np.stack(out)
+
+
+def load_rgb_oversampled(clip_dir: str, ticks: List[int], rgb_prefix='img_', ext='.jpg', rule: str = "cv2") -> np.ndarray:
+    """[T * 10, 224, 224, 3] uint8 BGR: the ten over-sampled crops of every snippet, snippet-major (``oversample``)."""
+    return np.concatenate([oversample(imread(os.path.join(clip_dir, '{}{:05d}{}'.format(rgb_prefix, t, ext)), True), rule=rule) for t in ticks])
+
+
+def load_flow_oversampled(clip_dir: str, ticks: List[int], frame_cnt: int, stk_depth=5, flow_x_prefix='flow_x_',
+                          flow_y_prefix='flow_y_', ext='.jpg', rule: str = "cv2") -> np.ndarray:
+    """[T * 10, 224, 224, 10] uint8: the ten over-sampled crops of every snippet's flow stack, snippet-major (``oversample_flow_stack``)."""
+    out = []
+    for tick in ticks:
+        stack = []
+        for idx in flow_stack_indices(tick, frame_cnt, stk_depth):
+            stack.append(imread(os.path.join(clip_dir, '{}{:05d}{}'.format(flow_x_prefix, idx, ext)), False))
+            stack.append(imread(os.path.join(clip_dir, '{}{:05d}{}'.format(flow_y_prefix, idx, ext)), False))
+        out.append(oversample_flow_stack(stack, rule=rule))
+    return np.concatenate(out)

@@ -2,6 +2,8 @@
 ``[n, 224, 224, C]``, the form the network's first kernel reads.  What the reference does per snippet on the host --
 ``cv2.imread`` (calcSig_wOF.py:92,105-106) and, inside ``predict_single_frame`` / ``predict_single_flow_stack(...,
 frame_size=(340, 256))`` (:94,111), ``cv2.resize`` + crop 0 of the 10-crop over-sample -- runs on the GPU for whole batches.
+``oversample_from_*`` cut all ten crops there (``[n * 10, 224, 224, C]``, snippet-major: what the class scores of the TSN test protocol
+are averaged over).
 
 A :class:`FrameIngest` depends on the stream's channel count, the device and the resize rule only -- not on any weights -- so the
 command line creates it before (and prepares batches while) the extractors are being built, keeps preparing the next stream's
@@ -89,6 +91,36 @@ class FrameIngest:
                      crop, frames.RESIZE_RULES[self._resize_rule], C.c_void_p(out.data_ptr()), self._channels, k, self.device, C.c_void_p(stream))
         return out
 
+    def oversample_from_frames(self, frames_: np.ndarray, frame_size=(340, 256), crop=224):
+        """Decoded frames -> the ten over-sampled crops of every snippet on the device (torch uint8 [n * 10, crop, crop, C], row
+        10 * i + k = crop k of snippet i): the frames are uploaded once (a tenth of the crops' bytes) and cut by vq_resize_crop with
+        VQ_RESIZE_OVERSAMPLE.  RGB frames [n, H, W, 3]: one call; flow planes [n, C, H, W]: a call per plane, the x planes (even) with
+        VQ_RESIZE_MIRROR_INVERT.  Same bytes as frames.oversample / frames.oversample_flow_stack."""
+        import ctypes as C
+        from .._lib import call
+        from . import devmem
+        f = np.ascontiguousarray(frames_, dtype=np.uint8)
+        if f.ndim != 4:
+            raise ValueError("frames must be [n,H,W,3] (RGB) or [n,C,H,W] (flow planes)")
+        n = f.shape[0]
+        out = devmem.empty_u8((n * 10, crop, crop, self._channels), self.device)
+        stream = devmem.current_stream_handle(self.device)
+        rule = frames.RESIZE_RULES[self._resize_rule] | frames.RESIZE_OVERSAMPLE
+        if self._channels == 3:
+            if f.shape[3] != 3:
+                raise ValueError("RGB frames must be [n,H,W,3]")
+            call("vq_resize_crop", f.ctypes.data_as(C.c_void_p), 0, n, f.shape[1], f.shape[2], 3, frame_size[0], frame_size[1], crop, rule,
+                 C.c_void_p(out.data_ptr()), 3, 0, self.device, C.c_void_p(stream))
+        else:
+            if f.shape[1] != self._channels:
+                raise ValueError("flow planes must be [n,%d,H,W]" % self._channels)
+            for k in range(self._channels):
+                plane = np.ascontiguousarray(f[:, k])
+                call("vq_resize_crop", plane.ctypes.data_as(C.c_void_p), 0, n, f.shape[2], f.shape[3], 1, frame_size[0], frame_size[1], crop,
+                     rule | (0 if k % 2 else frames.RESIZE_MIRROR_INVERT), C.c_void_p(out.data_ptr()), self._channels, k, self.device,
+                     C.c_void_p(stream))
+        return out
+
     def sync(self):
         """Wait for the resize / crop work of ``crops_from_frames`` (queued on torch's current stream) before an extractor's own
         stream reads the crops."""
@@ -113,9 +145,8 @@ class FrameIngest:
         with st["lock"]:                                 # a lane's decoder buffer and stream serve one call at a time
             return self._crops_from_jpegs_on(st, files, n, ch, frame_size, crop, out)
 
-    def _crops_from_jpegs_on(self, st, files, n, ch, frame_size, crop, out):
-        import ctypes as C
-        from .._lib import call
+    def _lane_decoder(self, st, files):
+        """A lane's stream and a decoder that holds the frames of ``files`` -> (stream, decoder, files per decoder call, h, w)."""
         from . import devmem, jpeg
         # a stream of its own (non-blocking): the call may run in a thread of its own for a LATER batch while the network works on the
         # current one on the default stream -- decoding a batch of flow files keeps a few CUs busy for tens of milliseconds
@@ -126,7 +157,6 @@ class FrameIngest:
             prio = {"low": -1, "normal": 0, "high": 1}.get(os.environ.get("VQ_INGEST_PRIORITY", "normal"), 0)
             st["stream"] = devmem.new_stream(self.device, prio)
         ingest = st["stream"]
-        stream = ingest.cuda_stream
         h, w, _ = jpeg.info(files[0])
         # files per decoder call (its buffers grow to what a call needs; a call addresses its component planes with 32 bits)
         cap = max(1, min(8192, int(3.0e9 // (2 * (h + 16) * (w + 16)))))
@@ -135,7 +165,13 @@ class FrameIngest:
             if dec is not None:
                 dec.close()
             dec = st["jpeg"] = _take_decoder(self.device, h, w) or jpeg.JpegDecoder(cap, h, w, self.device)
-        cap = min(cap, dec.max_frames)
+        return ingest, dec, min(cap, dec.max_frames), h, w
+
+    def _crops_from_jpegs_on(self, st, files, n, ch, frame_size, crop, out):
+        import ctypes as C
+        from .._lib import call
+        ingest, dec, cap, h, w = self._lane_decoder(st, files)
+        stream = ingest.cuda_stream
         same_size = (w, h) == tuple(frame_size) and crop % 2 == 0 and crop <= min(h, w)
         if same_size and ch in (3, 10):
             # frames as build_wof_clips.py writes them: resize is the identity, crop 0 the top-left pixels -- decoded and cropped without the
@@ -171,6 +207,47 @@ class FrameIngest:
                         call("vq_resize_crop", C.c_void_p(ptr + k * m * h * w), 1, m, h, w, 1, frame_size[0], frame_size[1], crop,
                              frames.RESIZE_RULES[self._resize_rule], C.c_void_p(out[i:i + m].data_ptr()), ch, k, self.device, C.c_void_p(stream))
                 ingest.synchronize()
+        return out
+
+    def oversample_from_jpegs(self, files, frame_size=(340, 256), crop=224, lane=0):
+        """JPEG files -> the ten over-sampled crops of every snippet on the device (torch uint8 [n * 10, crop, crop, C], snippet-major):
+        ``crops_from_jpegs``' decode (same file order, lanes, streams and decoder buffers), then the over-sample cut straight from the
+        decoder's device buffer -- the packed call for RGB, the one-launch planes form for the ten planes of a flow stack with an even
+        crop, a call per plane otherwise.  Frames that already have ``frame_size`` are copied by the same kernels.  Same bytes as
+        decoding on the host + frames.oversample / frames.oversample_flow_stack."""
+        import ctypes as C
+        from .._lib import call
+        from . import devmem
+        ch = self._channels
+        per_snip = 1 if ch == 3 else ch
+        if len(files) % per_snip:
+            raise ValueError("flow net: %d files is not a multiple of the %d planes of a snippet" % (len(files), ch))
+        n = len(files) // per_snip
+        out = devmem.empty_u8((n * 10, crop, crop, ch), self.device)
+        rule = frames.RESIZE_RULES[self._resize_rule] | frames.RESIZE_OVERSAMPLE
+        st = self._lanes.setdefault(lane, {"stream": None, "jpeg": None, "lock": threading.Lock()})
+        with st["lock"]:                                 # a lane's decoder buffer and stream serve one call at a time
+            ingest, dec, cap, h, w = self._lane_decoder(st, files)
+            stream = ingest.cuda_stream
+            per = cap if ch == 3 else max(1, cap // ch)
+            for i in range(0, n, per):
+                m = min(per, n - i)
+                dst = C.c_void_p(out[10 * i:10 * (i + m)].data_ptr())
+                if ch == 3:
+                    ptr, _ = dec.decode_to_device(files[i:i + m], color=True, stream=stream)
+                    call("vq_resize_crop", C.c_void_p(ptr), 1, m, h, w, 3, frame_size[0], frame_size[1], crop, rule, dst, 3, 0, self.device,
+                         C.c_void_p(stream))
+                else:
+                    group = [f for k in range(ch) for f in files[i * ch + k:(i + m) * ch:ch]]          # plane-major, as crops_from_jpegs
+                    ptr, _ = dec.decode_to_device(group, color=False, stream=stream)
+                    if ch == 10 and crop % 2 == 0:
+                        call("vq_resize_crop_planes", C.c_void_p(ptr), m, h, w, ch, m * h * w, frame_size[0], frame_size[1], crop, rule, dst,
+                             self.device, C.c_void_p(stream))
+                    else:
+                        for k in range(ch):
+                            call("vq_resize_crop", C.c_void_p(ptr + k * m * h * w), 1, m, h, w, 1, frame_size[0], frame_size[1], crop,
+                                 rule | (0 if k % 2 else frames.RESIZE_MIRROR_INVERT), dst, ch, k, self.device, C.c_void_p(stream))
+                ingest.synchronize()                                  # the decoder's buffer is reused by its next call
         return out
 
     def close(self):
