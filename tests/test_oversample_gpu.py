@@ -135,6 +135,22 @@ def test_one_plane_into_a_ten_channel_buffer(dev):
     assert (np.delete(got, 3, axis=-1) == SENTINEL).all()
 
 
+@pytest.mark.parametrize("src,rule", [((23, 31), "cv2"), ((23, 31), "exact"), ((29, 37), "cv2")], ids=["fixed", "exact", "copy"])
+def test_one_plane_into_a_ten_channel_buffer_unflagged(dev, src, rule):
+    """The un-flagged call of the kernel that also serves the ten-crop cut, c = 1 into dst_channels = 10 at dst_channel0 = 3, n = 3, crop 15
+    (675 threads: a partial last block), in its three modes, into a buffer as large as the flagged call's (n * 10 crops): channel 3 of the
+    first n crops is crop 0 of the pixel loops and every other byte keeps the sentinel -- the other nine channels, and the crops behind the
+    first n, where the mirror store of the flagged instantiation would land (crop row + 5 * crop) if the un-flagged one carried it."""
+    fr, torch = dev.frames, dev.torch
+    x, want = _packed_case(src, 1, FRAME, 15, rule)
+    out = torch.full((30, 15, 15, 10), SENTINEL, dtype=torch.uint8, device="cuda")
+    got = _resize_crop(dev, x, FRAME, 15, fr.RESIZE_RULES[rule], 1, dst_channels=10, c0=3, out=out)
+    assert got.shape == (30, 15, 15, 10)
+    assert (got[:3, ..., 3:4] == want[:, 0]).all()
+    assert (np.delete(got[:3], 3, axis=-1) == SENTINEL).all()
+    assert (got[3:] == SENTINEL).all()
+
+
 @pytest.mark.parametrize("rule", ["cv2", "exact"])
 @pytest.mark.parametrize("src", PLANES_SOURCES)
 def test_planes_form_against_the_pixel_loops_and_the_per_plane_calls(dev, src, rule):
@@ -155,7 +171,7 @@ def test_planes_form_against_the_pixel_loops_and_the_per_plane_calls(dev, src, r
 
 
 def test_crop0_control(dev):
-    """The un-flagged calls (the crop-0 kernels, which over-sampling leaves alone) give crop 0 of the pixel loops."""
+    """The un-flagged calls (the TEN = false instantiations of the two kernel templates) give crop 0 of the pixel loops."""
     fr = dev.frames
     for rule in ("cv2", "exact"):
         for src in SOURCES:

@@ -190,15 +190,15 @@ class CaffeNet:
         """JPEG file contents -> the ten device crops of every snippet; see :class:`tsn.ingest.FrameIngest`."""
         return self._ingest.oversample_from_jpegs(files, frame_size, crop, lane)
 
-    def extract_clips_from_jpegs(self, files, T: int, frame_size=(340, 256), on_device: bool = False, over_sample: bool = False):
-        """JPEG file contents of B*T snippets (flow: * C planes) -> consensus features [B, D]; see crops_from_jpegs.  ``over_sample``:
-        the ten crops of every snippet (oversample_from_jpegs), averaged with the snippets (see extract_clips_from_frames)."""
+    def _extract_batched(self, source: str, items, per_snip: int, T: int, frame_size, on_device: bool, over_sample: bool):
+        """The loop of extract_clips_from_jpegs / _from_frames (``source``: "jpegs" / "frames"): the device crops of a forward's snippets,
+        ``per_snip`` items each, from crops_from_<source> or oversample_from_<source>."""
+        produce = getattr(self, ("oversample_from_" if over_sample else "crops_from_") + source)
         from . import devmem
-        per_snip = 1 if self._channels == 3 else self._channels
         per, T = self._per_forward(T, over_sample)
         out = []
-        for i in range(0, len(files) // per_snip, per):
-            crops = (self.oversample_from_jpegs if over_sample else self.crops_from_jpegs)(files[i * per_snip:(i + per) * per_snip], frame_size)
+        for i in range(0, len(items) // per_snip, per):
+            crops = produce(items[i * per_snip:(i + per) * per_snip], frame_size)
             devmem.synchronize_current(self._model.device)
             nb = crops.shape[0]
             if on_device:
@@ -210,6 +210,11 @@ class CaffeNet:
             import torch
             return torch.cat(out, dim=0)
         return np.concatenate(out, axis=0)
+
+    def extract_clips_from_jpegs(self, files, T: int, frame_size=(340, 256), on_device: bool = False, over_sample: bool = False):
+        """JPEG file contents of B*T snippets (flow: * C planes) -> consensus features [B, D]; see crops_from_jpegs.  ``over_sample``:
+        the ten crops of every snippet (oversample_from_jpegs), averaged with the snippets (see extract_clips_from_frames)."""
+        return self._extract_batched("jpegs", files, 1 if self._channels == 3 else self._channels, T, frame_size, on_device, over_sample)
 
     def extract_clips_from_crops(self, crops, T: int, on_device: bool = False, over_sample: bool = False):
         """Device crops (torch uint8 [B*T, crop, crop, C], e.g. from ``crops_from_jpegs`` run by another thread for the NEXT batch while
@@ -233,22 +238,7 @@ class CaffeNet:
         ``over_sample``: every snippet contributes its ten over-sampled crops (cut on the device, snippet-major) and the forward runs
         with T' = 10 T, max_crops // (10 T) clips at a time: the fp64 average over snippets x crops -- the ten-crop feature under
         ``global_pool``, the video-level class scores of the TSN test protocol under ``fc-action``."""
-        from . import devmem
-        per, T = self._per_forward(T, over_sample)
-        out = []
-        for i in range(0, frames_.shape[0], per):
-            crops = (self.oversample_from_frames if over_sample else self.crops_from_frames)(frames_[i:i + per], frame_size)
-            devmem.synchronize_current(self._model.device)
-            nb = crops.shape[0]
-            if on_device:
-                self._model.forward_device(crops.data_ptr(), nb, T, self._mean)
-                out.append(self._model.features_tensor(nb // T).clone())
-            else:
-                out.append(self._model.forward_device(crops.data_ptr(), nb, T, self._mean, np.empty((nb // T, self._model.feature_dim), dtype=np.float64)))
-        if on_device:
-            import torch
-            return torch.cat(out, dim=0)
-        return np.concatenate(out, axis=0)
+        return self._extract_batched("frames", frames_, 1, T, frame_size, on_device, over_sample)
 
     @property
     def feature_dim(self):
