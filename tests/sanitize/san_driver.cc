@@ -9,12 +9,14 @@
 //   san_driver csv             vq_format_feature_rows on values of every kind
 //   san_driver corners         the corner selection of the warped-flow step, 24 frames over host threads
 //   san_driver pool            the device-block pool's bookkeeping hammered from 8 threads
+//   san_driver plan            the TSN executor's plan checks, launch sequence, K split, batch cut on a hand-built inception level
 #include <dirent.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 #include <thread>
@@ -23,6 +25,7 @@
 #include "vq_block_pool.h"
 #include "vq_corners.h"
 #include "vq_jpeg_host.h"
+#include "vq_tsn_plan.h"
 
 namespace vq {
 std::string& last_error_ref() {
@@ -265,6 +268,304 @@ static int run_pool() {
     return 0;
 }
 
+// ---- the TSN executor's plan decisions (csrc/host/vq_tsn_plan.cc) on one inception-style level built by hand --------------------
+namespace plan_test {
+using vq::TsnPlan;
+
+struct PlanIn {
+    std::vector<vq_tensor_desc> t;
+    std::vector<vq_layer_desc> l;
+    std::vector<vq_conv_segment> s;
+    vq_input_desc in = {8, 8, 32, -1, 0, 0};
+    int64_t blob_floats = 0;
+    int feature_slot = 8, max_crops = 4;
+    bool null_tensors = false, null_segments = false;
+};
+
+static int validate(const PlanIn& p, TsnPlan* plan) {
+    static const float blob = 0.f;                              // validate_plan looks at the pointer only
+    return vq::validate_plan(p.null_tensors ? nullptr : p.t.data(), (int)p.t.size(), p.l.data(), (int)p.l.size(), p.null_segments ? nullptr : p.s.data(),
+                             (int)p.s.size(), &blob, p.blob_floats, &p.in, p.feature_slot, p.max_crops, plan);
+}
+
+enum { L_RED_A, L_RED_B, L_MERGED, L_POOL, L_WINO, L_WINO16, L_POOLED, L_K1024, L_GPOOL, L_FC };
+
+// slots: 0 module input 8x8x32 | 1, 2 the reductions | 3 the module's output (concat of 4 x 32) | 4 a second destination of the merged
+// convolution | 5 pooled-input convolution 6x6x64 | 6 -> 7: the 1 024-channel 1x1 on 7x7 | 8 feature | 9 class scores
+static PlanIn inception_level() {
+    PlanIn p;
+    p.t = {{8, 8, 32}, {8, 8, 32}, {8, 8, 32}, {8, 8, 128}, {8, 8, 32}, {6, 6, 64}, {7, 7, 1024}, {7, 7, 128}, {1, 1, 128}, {1, 1, 101}};
+    p.s = {{32, 3, 0, 1}, {32, 4, 0, 1}};
+    int64_t off = 0;
+    auto take = [&](int64_t n) {
+        const int64_t at = off;
+        off += (n + 3) / 4 * 4;
+        return at;
+    };
+    auto layer = [&](int op, int src, int dst, int src_coff, int dst_coff, int cin, int cout, int k, int stride, int pad, int64_t w_floats) {
+        vq_layer_desc L = {};
+        L.op = op, L.src = src, L.dst = dst, L.src_coff = src_coff, L.dst_coff = dst_coff, L.cin = cin, L.cout = cout, L.k = k, L.stride = stride, L.pad = pad;
+        L.relu = 1, L.ceil_mode = 1;
+        if (w_floats > 0) {
+            L.has_bias = 1;
+            L.w_off = take(w_floats);
+            L.b_off = take(cout);
+        }
+        p.l.push_back(L);
+    };
+    layer(VQ_OP_CONV, 0, 1, 0, 0, 32, 32, 1, 1, 0, 32 * 32);
+    layer(VQ_OP_CONV, 0, 2, 0, 0, 32, 32, 1, 1, 0, 32 * 32);
+    layer(VQ_OP_CONV, 0, 3, 0, 0, 32, 64, 1, 1, 0, 64 * 32);
+    p.l.back().seg_first = 0, p.l.back().seg_count = 2;
+    layer(VQ_OP_MAXPOOL, 0, 3, 0, 96, 32, 32, 3, 1, 1, 0);
+    layer(VQ_OP_CONV_WINOGRAD, 1, 3, 0, 32, 32, 32, 3, 1, 1, 16 * 32 * 32);
+    layer(VQ_OP_CONV_WINOGRAD16, 2, 3, 0, 64, 32, 32, 3, 1, 1, 2 * 16 * 32 * 32);
+    layer(VQ_OP_CONV, 3, 5, 0, 0, 128, 64, 1, 1, 0, 64 * 128);
+    p.l.back().pre_pool_k = 3, p.l.back().pre_pool_stride = 1;
+    layer(VQ_OP_CONV, 6, 7, 0, 0, 1024, 128, 1, 1, 0, 128 * 1024);
+    layer(VQ_OP_GLOBAL_AVGPOOL, 7, 8, 0, 0, 128, 128, 7, 1, 0, 0);
+    layer(VQ_OP_INNER_PRODUCT, 8, 9, 0, 0, 128, 101, 1, 1, 0, 101 * 128);
+    p.l.back().relu = 0;
+    p.blob_floats = off;
+    return p;
+}
+
+struct Mutation {
+    int site;                 // which `require` of validate_plan it must trip, in source order
+    int layer;                // the layer the message must name; -1: a check of the call's own arguments
+    const char* text;         // ... and a piece of that message
+    void (*apply)(PlanIn&);
+};
+
+static void s2d(PlanIn& p, int c, int pad, int order) { p.in.c = c, p.in.s2d_pad = pad, p.in.s2d_kernel = 7, p.in.s2d_order = order; }
+
+static const Mutation kMutations[] = {
+    {1, -1, "NULL argument", [](PlanIn& p) { p.null_tensors = true; }},
+    {2, -1, "sizes must be positive", [](PlanIn& p) { p.max_crops = 0; }},
+    {3, -1, "bad segment table", [](PlanIn& p) { p.null_segments = true; }},
+    {4, -1, "feature_slot out of range", [](PlanIn& p) { p.feature_slot = 10; }},
+    {5, -1, "feature slot must be 1x1xD", [](PlanIn& p) { p.feature_slot = 7; }},
+    {6, -1, "input slot channels", [](PlanIn& p) { p.t[0].c = 30; }},
+    {7, -1, "input crops must be", [](PlanIn& p) { p.in.w = 0; }},
+    {8, -1, "input slot is 8x8 but the crops are 9x8", [](PlanIn& p) { p.in.h = 9; }},
+    {9, -1, "does not fit", [](PlanIn& p) { p.in.c = 27; }},
+    {10, -1, "space-to-depth input slot needs 4 x 3", [](PlanIn& p) { s2d(p, 3, 3, 0); }},
+    {11, -1, "space-to-depth shift out of range", [](PlanIn& p) { s2d(p, 8, 65, 0); }},
+    {12, -1, "s2d_order must be 0 or 1", [](PlanIn& p) { s2d(p, 8, 3, 2); }},
+    {13, L_WINO, "bad tensor slots", [](PlanIn& p) { p.l[L_WINO].dst = p.l[L_WINO].src; }},
+    {14, L_RED_A, "exceeds 2 GiB", [](PlanIn& p) { p.t[1] = {8192, 8192, 32}; }},
+    {15, L_RED_A, "reads channels [4,36)", [](PlanIn& p) { p.l[L_RED_A].src_coff = 4; }},
+    {16, L_WINO, "writes channels [100,132)", [](PlanIn& p) { p.l[L_WINO].dst_coff = 100; }},
+    {17, L_MERGED, "segments outside the table", [](PlanIn& p) { p.l[L_MERGED].seg_first = 1; }},
+    {18, L_MERGED, "segment 1: bad slot", [](PlanIn& p) { p.s[1].dst = 0; }},
+    {19, L_MERGED, "segment 0: channels", [](PlanIn& p) { p.s[0].cout = 16; }},
+    {20, L_MERGED, "segment 1: spatial size differs", [](PlanIn& p) { p.s[1].dst = 5; }},
+    {21, L_MERGED, "segments cover 64 of 96", [](PlanIn& p) { p.l[L_MERGED].cout = 96; }},
+    {22, L_RED_A, "bad kernel/stride/pad", [](PlanIn& p) { p.l[L_RED_A].pad = 1; }},
+    {23, L_RED_A, "multiples of 4", [](PlanIn& p) { p.l[L_RED_A].cin = 30; }},
+    {24, L_K1024, "conv kernels up to 8x8", [](PlanIn& p) { p.l[L_K1024].k = 9; }},
+    {25, L_POOLED, "3x3 max window with stride 1..3", [](PlanIn& p) { p.l[L_POOLED].pre_pool_stride = 4; }},
+    {26, L_POOLED, "multiple of 32 channels", [](PlanIn& p) { p.l[L_POOLED].cin = 48; }},
+    {27, L_POOLED, "pooled-input size mismatch", [](PlanIn& p) { p.l[L_POOLED].pre_pool_stride = 2; }},
+    {28, L_RED_A, "conv output size mismatch", [](PlanIn& p) { p.l[L_RED_A].stride = 2; }},
+    {29, L_RED_A, "x-major space-to-depth stem", [](PlanIn& p) { s2d(p, 8, 3, 1); }},
+    {30, L_RED_A, "weights outside the blob", [](PlanIn& p) { p.l[L_RED_A].w_off = p.blob_floats - 4; }},
+    {31, L_RED_A, "bias outside the blob", [](PlanIn& p) { p.l[L_RED_A].b_off = p.blob_floats; }},
+    {32, L_RED_A, "small-Cin convolution must read a whole slot", [](PlanIn& p) { p.l[L_RED_A].cin = 4, p.l[L_RED_A].src_coff = 4; }},
+    {33, L_RED_A, "small-Cin convolution must read a whole slot", [](PlanIn& p) { p.l[L_RED_A].cin = 4; }},
+    {34, L_WINO, "Winograd form is 3x3", [](PlanIn& p) { p.l[L_WINO].stride = 2; }},
+    {35, L_WINO, "Winograd form needs Cin", [](PlanIn& p) { p.l[L_WINO].cin = 28; }},
+    {36, L_WINO, "conv output size mismatch", [](PlanIn& p) { p.l[L_WINO].dst = 5, p.l[L_WINO].dst_coff = 0; }},
+    {37, L_WINO, "transformed filters outside the blob", [](PlanIn& p) { p.l[L_WINO].w_off = p.blob_floats - 4; }},
+    {38, L_WINO, "bias outside the blob", [](PlanIn& p) { p.l[L_WINO].b_off = p.blob_floats; }},
+    {39, L_POOL, "pooling keeps the channel count", [](PlanIn& p) { p.l[L_POOL].cout = 16; }},
+    {40, L_POOL, "pooling bias outside the blob", [](PlanIn& p) { p.l[L_POOL].op = VQ_OP_AVGPOOL, p.l[L_POOL].has_bias = 1, p.l[L_POOL].b_off = -4; }},
+    {41, L_POOL, "pooling output size mismatch", [](PlanIn& p) { p.l[L_POOL].stride = 2; }},
+    {42, L_GPOOL, "global pool must write a 1x1 slot", [](PlanIn& p) { p.l[L_GPOOL].dst = 7, p.l[L_GPOOL].src = 6, p.l[L_GPOOL].cin = 128; }},
+    {43, L_FC, "InnerProduct reads and writes 1x1 slots", [](PlanIn& p) { p.l[L_FC].src = 7; }},
+    {44, L_FC, "no ReLU", [](PlanIn& p) { p.l[L_FC].relu = 1; }},
+    {45, L_FC, "has_bias must be 1", [](PlanIn& p) { p.l[L_FC].has_bias = 0; }},
+    {46, L_FC, "weights outside the blob", [](PlanIn& p) { p.l[L_FC].w_off = p.blob_floats - 4; }},
+    {47, L_FC, "bias outside the blob", [](PlanIn& p) { p.l[L_FC].b_off = p.blob_floats; }},
+    {48, L_FC, "InnerProduct with more than", [](PlanIn& p) { p.t[9].c = 1 << 20, p.l[L_FC].cout = 65535 * 8 + 4, p.blob_floats = 1ll << 40; }},
+    {49, L_POOL, "unknown op 99", [](PlanIn& p) { p.l[L_POOL].op = 99; }},
+    // further ways into sites already counted (the count below takes distinct sites)
+    {13, L_RED_A, "bad tensor slots", [](PlanIn& p) { p.l[L_RED_A].src = 10; }},
+    {35, L_WINO16, "Winograd form needs Cin", [](PlanIn& p) { p.l[L_WINO16].cin = 24; }},       // % 8 == 0, % 16 != 0
+    {26, L_POOLED, "1x1 convolution over a multiple of 32", [](PlanIn& p) { p.l[L_POOLED].pad = 0, p.l[L_POOLED].stride = 2; }},
+    {44, L_FC, "one destination", [](PlanIn& p) { p.l[L_FC].seg_count = 1; }},
+};
+
+struct Range {
+    int slot, c0, c1;
+};
+static bool meet(const std::vector<Range>& x, const std::vector<Range>& y) {
+    for (const Range& a : x)
+        for (const Range& b : y)
+            if (a.slot == b.slot && a.c0 < b.c1 && b.c0 < a.c1) return true;
+    return false;
+}
+
+// items is a launch order of all layers: nothing reads what its own or a later launch writes, every layer is in one item
+static bool valid_schedule(const TsnPlan& plan) {
+    const int n = (int)plan.layers.size();
+    std::vector<std::vector<Range>> rd((size_t)n), wr((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const vq_layer_desc& L = plan.layers[i];
+        const bool whole = L.op == VQ_OP_CONV && L.cin % 32 != 0;
+        rd[i].push_back(whole ? Range{L.src, 0, plan.tensors[L.src].c} : Range{L.src, L.src_coff, L.src_coff + L.cin});
+        if (L.op == VQ_OP_CONV && L.seg_count > 0)
+            for (int q = 0; q < L.seg_count; ++q) wr[i].push_back(Range{plan.segments[L.seg_first + q].dst, plan.segments[L.seg_first + q].dst_coff, plan.segments[L.seg_first + q].dst_coff + plan.segments[L.seg_first + q].cout});
+        else
+            wr[i].push_back(Range{L.dst, L.dst_coff, L.dst_coff + L.cout});
+    }
+    std::vector<int> seen((size_t)n, 0);
+    for (size_t q = 0; q < plan.items.size(); ++q)
+        for (int x : plan.items[q].layers) {
+            if (x < 0 || x >= n || plan.item_of_layer[x] != (int)q) return false;
+            ++seen[x];
+            for (size_t r = q; r < plan.items.size(); ++r)
+                for (int y : plan.items[r].layers)
+                    if (y != x && meet(rd[x], wr[y])) return false;
+        }
+    for (int i = 0; i < n; ++i)
+        if (seen[i] != 1) return false;
+    return true;
+}
+
+static size_t crop_bytes(const TsnPlan& plan, int slot) { return (size_t)plan.tensors[slot].h * plan.tensors[slot].w * plan.tensors[slot].c * sizeof(float); }
+
+#define PLAN_CHECK(cond)                                                      \
+    do {                                                                      \
+        if (!(cond)) {                                                        \
+            fprintf(stderr, "plan: line %d: %s\n", __LINE__, #cond);          \
+            return 20;                                                        \
+        }                                                                     \
+    } while (0)
+
+static int run() {
+    const PlanIn good = inception_level();
+    TsnPlan plan;
+    // 1. the plan is accepted; the FLOP count is the sum of the same formulas
+    if (validate(good, &plan) != VQ_OK) {
+        fprintf(stderr, "plan: refused: %s\n", vq::last_error_ref().c_str());
+        return 20;
+    }
+    const double macs = 64.0 * (32 + 32 + 64) * 32 /* the three 1x1 on the 8x8x32 input */ + 2 * 64.0 * 32 * 32 * 9 /* Winograd, direct-form count */ +
+                        36.0 * 64 * 128 /* pooled-input */ + 49.0 * 128 * 1024 + 128.0 * 101 /* InnerProduct */;
+    PLAN_CHECK(plan.flops_per_crop == 2.0 * macs && plan.D == 128 && plan.consensus_layer == L_GPOOL && plan.layers.size() == 10 && plan.segments.size() == 2);
+    // 2. one mutation per `require` of validate_plan: each refused, by that check
+    std::vector<int> hit((size_t)vq::kValidatePlanRequires + 1, 0);
+    int distinct = 0;
+    for (const Mutation& m : kMutations) {
+        PlanIn bad = good;
+        m.apply(bad);
+        TsnPlan out;
+        vq::last_error_ref().clear();
+        const int rc = validate(bad, &out);
+        const std::string& err = vq::last_error_ref();
+        char name[32];
+        snprintf(name, sizeof name, "layer %d", m.layer);
+        if (rc != VQ_E_INVALID || err.empty() || err.find(m.text) == std::string::npos || (m.layer >= 0 && err.compare(0, strlen(name), name) != 0) ||
+            (m.layer >= 0 && err[strlen(name)] != ':' && err[strlen(name)] != ' ')) {
+            fprintf(stderr, "plan: mutation of site %d (\"%s\"): rc %d, message \"%s\"\n", m.site, m.text, rc, err.c_str());
+            return 21;
+        }
+        PLAN_CHECK(m.site >= 1 && m.site <= vq::kValidatePlanRequires);
+        if (hit[(size_t)m.site]++ == 0) ++distinct;
+    }
+    PLAN_CHECK(distinct == vq::kValidatePlanRequires);                  // no check goes untested
+    // 3. the launch sequence
+    for (int group_pool = 0; group_pool < 2; ++group_pool) {
+        vq::build_items(plan, true, group_pool != 0);
+        PLAN_CHECK(valid_schedule(plan));
+        const std::vector<int>& of = plan.item_of_layer;
+        PLAN_CHECK(of[L_WINO] != of[L_WINO16]);                          // two filter layouts: two launches
+        PLAN_CHECK(plan.items[of[L_WINO]].kind == 1 && plan.items[of[L_WINO16]].kind == 1 && plan.items[of[L_WINO16]].layers.size() == 1);
+        PLAN_CHECK(of[L_WINO] < of[L_WINO16] && of[L_WINO16] < of[L_POOLED] && of[L_GPOOL] < of[L_FC] && of[L_K1024] < of[L_GPOOL]);
+        if (group_pool) {
+            PLAN_CHECK(of[L_POOL] == of[L_WINO] && plan.items[of[L_WINO]].layers == (std::vector<int>{L_WINO, L_POOL}) && plan.items.size() == 9);
+        } else {
+            PLAN_CHECK(plan.items[of[L_POOL]].kind == 0 && plan.items[of[L_POOL]].layers.size() == 1 && of[L_POOL] < of[L_WINO] && plan.items.size() == 10);
+        }
+        for (const vq::LaunchItem& it : plan.items) {
+            size_t worst = 1;
+            for (int li : it.layers) {
+                const vq_layer_desc& L = plan.layers[li];
+                worst = std::max(worst, crop_bytes(plan, L.src));
+                if (L.op == VQ_OP_CONV && L.seg_count > 0)
+                    for (int q = 0; q < L.seg_count; ++q) worst = std::max(worst, crop_bytes(plan, plan.segments[L.seg_first + q].dst));
+                else
+                    worst = std::max(worst, crop_bytes(plan, L.dst));
+            }
+            PLAN_CHECK(it.max_crops == (int)(0x7FFFFFF0u / worst));
+        }
+    }
+    PLAN_CHECK(plan.items[plan.item_of_layer[L_K1024]].max_crops == (int)(0x7FFFFFF0u / (49 * 1024 * 4)));
+    {
+        TsnPlan single = plan;
+        vq::build_items(single, false, true);
+        PLAN_CHECK(valid_schedule(single) && single.items.size() == single.layers.size());
+        for (const vq::LaunchItem& it : single.items) PLAN_CHECK(it.kind == 0 && it.layers.size() == 1);
+        // a Winograd layer on a 4-channel-wide 56x56 slot: the 2^23-pixel cap of the kernel's 24-bit multiplies, far below the byte cap
+        TsnPlan narrow;
+        narrow.tensors = {{56, 56, 4}, {56, 56, 4}};
+        vq_layer_desc L = {};
+        L.op = VQ_OP_CONV_WINOGRAD, L.src = 0, L.dst = 1, L.cin = 4, L.cout = 4, L.k = 3, L.stride = 1, L.pad = 1;
+        narrow.layers = {L};
+        vq::build_items(narrow, true, true);
+        PLAN_CHECK(narrow.items.size() == 1 && narrow.items[0].kind == 1 && narrow.items[0].max_crops == ((1 << 23) - 1) / (56 * 56));
+        PLAN_CHECK(narrow.items[0].max_crops < (int)(0x7FFFFFF0u / (56 * 56 * 4 * 4)));
+    }
+    // 4. split-K and the batch cut
+    vq::choose_ksplit(plan, true);
+    for (int i = 0; i < (int)plan.layers.size(); ++i) PLAN_CHECK(plan.ksplit[(size_t)i] == (i == L_K1024 ? 2 : 1));     // 32 K-steps: min(4, 32 / 16)
+    PLAN_CHECK(plan.split_crop_floats == (size_t)49 * 128 + 128 && plan.max_cout == 128);
+    {
+        TsnPlan wide = plan;                                           // the same layer on a 14x14 map: enough tiles already
+        wide.tensors[6].h = wide.tensors[6].w = wide.tensors[7].h = wide.tensors[7].w = 14;
+        vq::choose_ksplit(wide, true);
+        TsnPlan off = plan;
+        vq::choose_ksplit(off, false);
+        for (size_t i = 0; i < plan.layers.size(); ++i) PLAN_CHECK(wide.ksplit[i] == 1 && off.ksplit[i] == 1);
+        PLAN_CHECK(wide.split_crop_floats == 0 && off.split_crop_floats == 0);
+    }
+    typedef std::vector<int> V;
+    const V halves = {1, 1}, thirds = {2, 1};
+    PLAN_CHECK(vq::parts_sum(halves) == 2 && vq::parts_sum(thirds) == 3);
+    vq::BatchCut c = vq::cut_batch(plan, 96, 3, halves, 2, false);
+    PLAN_CHECK(c.sub == (V{48, 48}) && c.sub_off == (V{0, 48}) && c.fused_consensus);
+    c = vq::cut_batch(plan, 96, 3, thirds, 3, false);
+    PLAN_CHECK(c.sub == (V{64, 32}) && c.sub_off == (V{0, 64}) && !c.fused_consensus);        // 64 crops are not whole clips of 3
+    c = vq::cut_batch(plan, 96, 4, thirds, 3, false);
+    PLAN_CHECK(c.sub == (V{64, 32}) && c.fused_consensus);
+    c = vq::cut_batch(plan, 97, 1, thirds, 3, false);
+    PLAN_CHECK(c.sub == (V{97}) && c.sub_off == (V{0}) && c.fused_consensus);
+    c = vq::cut_batch(plan, 96, 3, halves, 2, true);
+    PLAN_CHECK(c.sub == (V{96}) && c.sub_off == (V{0}) && c.fused_consensus);
+    c = vq::cut_batch(plan, 34, 17, halves, 2, false);                                           // kMaxFusedT is 16
+    PLAN_CHECK(c.sub == (V{17, 17}) && !c.fused_consensus);
+    PLAN_CHECK(vq::cut_batch(plan, 32, 16, halves, 2, false).fused_consensus);
+    const int cap = plan.items[(size_t)plan.item_of_layer[L_GPOOL]].max_crops;                 // 85 598 crops of 7x7x128: even, no multiple of 3
+    PLAN_CHECK(cap == (int)(0x7FFFFFF0u / (49 * 128 * 4)) && cap % 3 != 0 && cap % 2 == 0);
+    PLAN_CHECK(!vq::cut_batch(plan, 90000, 3, halves, 2, true).fused_consensus);                 // a crop range would end inside a clip
+    PLAN_CHECK(vq::cut_batch(plan, 90000, 2, halves, 2, true).fused_consensus);
+    PLAN_CHECK(vq::cut_batch(plan, 3 * (cap / 3), 3, halves, 2, true).fused_consensus);          // below the cap: one launch
+    {
+        TsnPlan none = plan;
+        none.consensus_layer = -1;
+        PLAN_CHECK(!vq::cut_batch(none, 96, 3, halves, 2, false).fused_consensus);
+    }
+    // 5. the closest tuned size within 1.6x
+    PLAN_CHECK(vq::nearest_size(V{48, 96, 200}, 96) == 96 && vq::nearest_size(V{48, 72}, 64) == 72 && vq::nearest_size(V{72, 48}, 50) == 48);
+    PLAN_CHECK(vq::nearest_size(V{48, 80}, 64) == 48 && vq::nearest_size(V{80, 48}, 64) == 80);      // the first of equals
+    PLAN_CHECK(vq::nearest_size(V{16}, 10) == 16 && vq::nearest_size(V{10}, 16) == 10);              // exactly 1.6x
+    PLAN_CHECK(vq::nearest_size(V{17}, 10) == 0 && vq::nearest_size(V{10}, 17) == 0 && vq::nearest_size(V{}, 10) == 0);
+    printf("plan: ok (%d checks of validate_plan, %d mutations)\n", distinct, (int)(sizeof kMutations / sizeof kMutations[0]));
+    return 0;
+}
+}  // namespace plan_test
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "single" && argc > 2) return run_single(argv[2]);
@@ -273,6 +574,7 @@ int main(int argc, char** argv) {
     if (mode == "csv") return run_csv();
     if (mode == "corners") return run_corners();
     if (mode == "pool") return run_pool();
-    fprintf(stderr, "usage: san_driver single|batch <dir> | csv\n");
+    if (mode == "plan") return plan_test::run();
+    fprintf(stderr, "usage: san_driver single|batch <dir> | coef <file> | csv | corners | pool | plan\n");
     return 2;
 }

@@ -3,7 +3,8 @@ UndefinedBehaviorSanitizer and under ThreadSanitizer.
 
 vq_jpeg_host.cc parses UNTRUSTED files on worker threads (markers, Huffman tables, restart markers, the host entropy decoder, the
 unstuffing pass of the device decoder); vq_corners.cc selects corners on host threads; vq_block_pool.cc is a process-wide pool
-shared by every extractor handle; vq_csv.cc writes text into caller-sized buffers.  GPU sanitizers are not available on the
+shared by every extractor handle; vq_csv.cc writes text into caller-sized buffers; vq_tsn_plan.cc holds every check that stands
+between a caller's layer plan and the device.  GPU sanitizers are not available on the
 pool, so these units are kept free of HIP and built here by tests/sanitize/Makefile with plain g++; tests/sanitize/san_driver.cc
 drives them the way csrc/vq_jpeg.hip / vq_flow.hip / vq_tsn.hip do, with buffers of EXACTLY the sizes the product reserves.
 The corpus: the committed JPEG fixtures (4:2:0 / 4:2:2 / 4:4:4 / grey, optimised tables, restart intervals, odd sizes) and
@@ -75,7 +76,7 @@ def test_threaded_batch_stages_under_asan_and_tsan(drivers, corpus):
         assert "batches decoded" in out and " 0 batches decoded" not in out, out
 
 
-@pytest.mark.parametrize("mode", ["csv", "corners", "pool"])
+@pytest.mark.parametrize("mode", ["csv", "corners", "pool", "plan"])
 def test_formatter_corner_selection_and_block_pool(drivers, mode):
     for kind in ("asan", "tsan"):
         assert mode + ": ok" in _run(drivers[kind], mode)

@@ -1142,3 +1142,69 @@ def test_a_narrow_winograd_layer_at_a_large_batch_is_cut_into_crop_ranges(tsn, m
     _, ps = big.forward(crops, 1, mean)
     big.close()
     assert (ps[:2] == ps_small[:2]).all() and (ps[-2:] == ps_small[2:]).all() and (ps[2:-2] == ps_small[0]).all()
+
+
+def _launch_item_tables(bi, net, channels, setenv):
+    """item_of_layer and the item count of bn_inception(channels) under the four grouping switches."""
+    g = bi.bn_inception(channels)
+    w = net.synthetic_weights(g, seed=2)
+    tables = {}
+    for group in (1, 0):
+        for pool in (0, 1):
+            setenv("VQ_TSN_GROUP", str(group))
+            setenv("VQ_TSN_GROUP_POOL", str(pool))
+            m = net.TsnNet(g, w, max_crops=2)
+            items, n_items = m.launch_items()
+            m.close()
+            tables["bn_inception(%d) group=%d group_pool=%d" % (channels, group, pool)] = {"n_items": int(n_items), "item_of_layer": items.tolist()}
+    return tables
+
+
+@pytest.mark.parametrize("channels", [3, 10])
+def test_launch_items_are_those_of_the_parent(tsn, monkeypatch, channels):
+    """The launch grouping -- which layers share a kernel launch, and in which order the launches go -- is what the speed rests on and
+    nothing else pins it: tests/golden/tsn_plan/launch_items.json holds what the executor gave before its plan code moved into
+    csrc/host/vq_tsn_plan.cc (recorded with this body), for both networks, grouped and VQ_TSN_GROUP=0, VQ_TSN_GROUP_POOL 0 and 1."""
+    import json
+    bi, net = tsn
+    monkeypatch.setenv("VQ_TUNE_CACHE", "0")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tsn_plan", "launch_items.json")) as f:
+        want = json.load(f)
+    got = _launch_item_tables(bi, net, channels, monkeypatch.setenv)
+    assert len(got) == 4
+    for key, table in got.items():
+        assert table == want[key], key
+
+
+def test_profiled_forward_times_every_launch(tsn, monkeypatch):
+    """A split-K layer is two launches, the K slices and the combine pass, that share one pair of profiling events: the slices carry the start
+    event, the combine pass the stop event.  The 1 024-channel 1x1 convolution on a 7x7 map (2 slices) and a global pool, profiled: both
+    layers get a finite, positive duration and the features are the bits of the un-profiled run; with VQ_TSN_SPLITK=0 the same holds and
+    the values differ from the split ones by rounding only (the bound of test_k_split_is_a_property_of_the_layer_not_of_the_batch)."""
+    bi, net = tsn
+    monkeypatch.setenv("VQ_TUNE_CACHE", "0")
+    monkeypatch.setenv("VQ_TSN_SPLIT", "1")
+    monkeypatch.delenv("VQ_TSN_TILE", raising=False)
+    g = _mini(bi, 1024, 7, 7, 128, 1, 1, 0)
+    w = net.synthetic_weights(g, seed=7)
+    crops = np.random.default_rng(8).integers(0, 256, (4, 7, 7, 1024), dtype=np.uint8)
+    mean = np.full(1024, 120.0, np.float32)
+    outs = {}
+    for sk in ("1", "0"):
+        monkeypatch.setenv("VQ_TSN_SPLITK", sk)
+        m = net.TsnNet(g, w, max_crops=4, feature_blob="gp")
+        assert len(m.plan.ops) == 2
+        f0, p0 = m.forward(crops, 2, mean)
+        b0 = m.read_blob("c_bn", 4)
+        m.set_profile(2)
+        for _ in range(3):
+            f, p = m.forward(crops, 2, mean)
+            assert (f == f0).all() and (p == p0).all() and (m.read_blob("c_bn", 4) == b0).all()
+        _names, kinds, ms, _flops = m.layer_times()
+        assert kinds == ["conv", "gavgpool"]
+        assert ms.shape == (2,) and np.isfinite(ms).all() and (ms > 0).all(), ms
+        m.close()
+        outs[sk] = (b0, p0, f0)
+    for a, b in zip(outs["0"], outs["1"]):
+        assert np.abs(a - b).max() <= 2e-6 * np.abs(a).max()
+    assert not (outs["0"][0] == outs["1"][0]).all()        # the layer really ran split

@@ -12,8 +12,9 @@
 //     matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, 256 FLOP/clk/CU) from LDS-staged,
 //     register-prefetched tiles -- the 1x1, stride-2 and stem layers;
 //   * Winograd F(2x2,3x3) form (vq_wino.hip) -- the 3x3 / stride-1 layers.
-// The executor below validates the plan once, autotunes the tiling per layer and batch size, and runs the
-// layer list on one stream (profiling) or as sub-batches on several (production).
+// The executor below has the plan validated and the launch sequence built once (host/vq_tsn_plan.cc: everything that needs no GPU),
+// autotunes the tiling per layer and batch size, and runs the layer list on one stream (profiling) or as sub-batches on several
+// (production).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -150,11 +151,6 @@ struct ConvArgs {
     FullDiv d_howo, d_wo;          // first pixel of the tile -> (image, row, column) on the scalar unit
     unsigned s_wo, s_ho;           // recip22 constants: the per-lane walk of at most BM pixels from there
 };
-
-constexpr int KPAD = 32;       // weights are packed [Cout][Kp] with Kp a multiple of 32
-// ... except the x-major space-to-depth stem (7x7 / stride 2 over c channels): four kernel rows of 7 x-taps x 2 rows x c floats each,
-// every row padded to whole 16-byte chunks, walked side by side (launch_conv_layer)
-static inline int stem_rows_kp(int c) { return 4 * ((14 * c + 3) / 4 * 4); }
 
 template <int BM, int BN, int BK>
 struct ConvSmem {
@@ -924,7 +920,7 @@ __global__ void gavgpool_kernel(const float* __restrict__ in, float* __restrict_
 // acc += acc[lane ^ s], s = 32, 16, 8, 4, 2, 1 (fp32 addition commutes, so every lane holds the same bits); last + b[n].
 // No accumulator is shared between crops or outputs, rows past M / columns past N recompute the last valid one and store nothing: the
 // bits of y[m][:] do not depend on the batch size, the crop's position, the sub-batch split or the crop range of the launch.
-constexpr int FC_ROWS = 4, FC_COLS = 8;
+constexpr int FC_ROWS = 4;     // x FC_COLS (host/vq_tsn_plan.h)
 __global__ __launch_bounds__(64) void inner_product_kernel(const float* __restrict__ x, int x_stride, const float* __restrict__ W,
                                                            const float* __restrict__ bias, float* __restrict__ y, int y_stride, int M,
                                                            int K, int N) {
@@ -994,7 +990,6 @@ __global__ void splitk_combine_kernel(const float* __restrict__ part, int ksplit
 // like gavgpool_kernel does (sequential fp32 sum over h, w, then / (H*W)) and stored as the per-snippet blob
 // (calcSig_wOF.py:95,112); the T values of a clip meet in LDS and are summed in fp64 in numpy's axis-0 order
 // (calcSig_wOF.py:82) -- the same bits as the two separate kernels.  Clips of up to kMaxFusedT snippets.
-constexpr int kMaxFusedT = 16;
 __global__ void gavgpool_consensus_kernel(const float* __restrict__ in, float* __restrict__ out, double* __restrict__ feat, int T,
                                           int HW, int Cs_in, int coff_in, int C, int Cs_out, int coff_out) {
     // block = 64 channels x T snippets of clip blockIdx.y; thread (c, t) pools snippet t, thread (c, 0) forms the consensus
@@ -1041,22 +1036,14 @@ __global__ void consensus_kernel(const float* __restrict__ per_snippet, double* 
 // ------------------------------------------------------------------------------------------------
 // handle + executor
 // ------------------------------------------------------------------------------------------------
-// k*k*Cin of a convolution in ALGORITHMIC terms: a layer that reads slot 0 counts the un-padded input channels and,
-// in space-to-depth form, the kernel size of the original convolution.
-static inline double first_layer_k2c(const vq_input_desc& in, const vq_layer_desc& L) {
-    if (L.src != 0) return (double)L.k * L.k * L.cin;
-    const int k = (in.s2d_pad >= 0 && in.s2d_kernel > 0) ? in.s2d_kernel : L.k;
-    return (double)k * k * in.c;
-}
-
-static inline bool is_wino(int op) { return op == VQ_OP_CONV_WINOGRAD || op == VQ_OP_CONV_WINOGRAD16; }
-static inline bool is_conv(int op) { return op == VQ_OP_CONV || is_wino(op); }
-
-// One kernel launch of a forward: a single layer, or the Winograd convolutions of one graph level together.
-struct LaunchItem {
-    int kind = 0;              // 0 = one layer, 1 = Winograd group
-    std::vector<int> layers;   // kind 1: longest K loop first (its workgroups are dispatched first; the short ones fill the tail)
-    int max_crops = 0;         // crops one launch may cover: every slot it touches stays below 2^31 bytes (32-bit offsets)
+// What one launch needs beyond the plan: where it goes, what it covers, which events time it.  Handed down the launch path, which
+// reads the handle (const vq_tsn*) and writes nothing into it; a function that changes a field for what it calls makes a copy.
+struct Launch {
+    hipStream_t stream;
+    hipEvent_t ev_start, ev_stop;   // profiling (both may be null)
+    int crop0;                      // first crop the launch works on (sub-batches, 32-bit offset chunks)
+    int T;                          // snippets per clip of the forward in flight
+    bool fused_consensus;           // the global pool launch also forms the consensus (whole clips per launch, T <= kMaxFusedT)
 };
 
 struct vq_tsn {
@@ -1066,12 +1053,7 @@ struct vq_tsn {
     int cus = 256;
     int max_crops = 0;
     int in_channels = 0;
-    vq_input_desc input = {0, 0, 0, -1, 0};
-    std::vector<vq_tensor_desc> tensors;
-    std::vector<vq_layer_desc> layers;
-    std::vector<LaunchItem> items;        // the launch sequence (a topological order of the layer graph by levels)
-    std::vector<int> item_of_layer;
-    int consensus_layer = -1;             // the global-pool layer that writes the feature slot: runs fused with the consensus
+    TsnPlan plan;                         // tensors, layers, launch sequence, K splits: everything decided without the GPU (host/vq_tsn_plan.h)
     std::map<int, std::vector<int>> tuned;   // tile_key(n_crops, paired) -> per-layer index into kTiles / Winograd variant
     std::map<int, int> split_pref;           // batch size -> 0: this size runs faster on ONE stream than as sub-batches (vq_tsn_set_split); absent: split
     std::set<int> tuned_borrowed;            // keys whose table was copied from a neighbouring size by ensure_tuned (not measured: never persisted)
@@ -1087,34 +1069,27 @@ struct vq_tsn {
     float* zeros = nullptr;               // 256 bytes of zeros (load target of masked lanes)
     ConvSeg* seg_table = nullptr;         // destination tables of all conv layers, back to back
     std::vector<int> seg_table_off;       // per layer: first entry
-    std::vector<int> ksplit;              // per layer: K slices of a direct convolution (1 = not split; layer geometry only)
     float* split_scratch = nullptr;       // [slice][max_crops * Ho * Wo][Cout] partial sums of the split layer in flight
-    size_t split_slice_floats = 0;        // floats between slices (= max_crops * split_crop_floats)
-    size_t split_crop_floats = 0;         // scratch floats one crop owns per slice: largest Ho*Wo*Cout of a split layer + one row of slack
+    size_t split_slice_floats = 0;        // floats between slices (= max_crops * plan.split_crop_floats)
     float* zero_bias = nullptr;           // zeros for the slices' epilogues (the bias is added once, by the combine pass)
     float* blob = nullptr;                // weights + biases
     int64_t blob_floats = 0;
-    int feature_slot = -1, D = 0;
+    int feature_slot = -1;
     uint8_t* crops_dev = nullptr;
     size_t crops_cap = 0;
     float* mean_dev = nullptr;
     std::vector<float> mean_cached;       // what mean_dev holds (uploaded only when the caller's mean changes)
     double* feat_dev = nullptr;           // [max_crops][D] (B <= max_crops)
-    double flops_per_crop = 0;
     int last_crops = 0;
-    int cur_T = 1;                        // snippets per clip of the forward in flight
-    bool fused_consensus = false;         // this forward: the global pool launch also forms the consensus (whole clips per launch, T <= kMaxFusedT)
     int profile_depth = 0;                // > 0: HIP events around every launch (bench roofline accounting)
     int profile_count = 0;                // profiled forwards so far (ring of profile_depth event sets)
     int profile_every = 1;                // while profiling: every n-th forward carries the events, all run on one stream
     int profile_tick = 0;                 // forwards since vq_tsn_set_profile
     bool profile_split = false;           // while profiling: the un-sampled forwards run split over the sub-batch streams (vq_tsn_set_profile_split)
     std::vector<hipEvent_t> events;       // profile_depth x n_items x {start, stop}
-    int crop_off = 0;                     // first crop the next launch works on (sub-batches, 32-bit offset chunks)
     int n_split = 1;                      // VQ_TSN_SPLIT: sub-batches of one forward run on separate streams
     std::vector<int> split_parts;         // VQ_TSN_SPLIT=a,b,..: relative sizes of the sub-batches (default equal)
-    hipStream_t ls = nullptr;             // stream the next launch goes to
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // profiling: events of the next launch
+    int parts_sum = 1;                    // ... and their sum
     std::vector<hipStream_t> split_streams;       // [n_split]; entry 0 unused (caller's stream)
     hipEvent_t fork_ev = nullptr;
     std::vector<hipEvent_t> join_ev;              // per extra stream
@@ -1184,7 +1159,7 @@ static bool pixel_walk_ok(const ConvArgs& a) {
 }
 
 template <int BM, int BN, int WM, int WN, int BK, int KERNEL, bool SMALL>
-static int launch_conv_t(vq_tsn* net, ConvArgs& a) {
+static int launch_conv_t(const Launch& ln, ConvArgs& a) {
     a.tiles_m = cdiv(a.M, BM);
     a.tiles_n = cdiv(a.Cout, BN);
     void (*kern)(ConvArgs);
@@ -1207,12 +1182,12 @@ static int launch_conv_t(vq_tsn* net, ConvArgs& a) {
         kern = conv_igemm_kernel<BM, BN, WM, WN, BK, SMALL, KERNEL == kPool>;
     }
     VQ_DYN_LDS(kern, lds_max);            // per instantiation and device
-    VQ_LAUNCH(kern, a.tiles_m * a.tiles_n * a.ksplit, 256, lds, net->ls, net->ev_start, net->ev_stop, a);
+    VQ_LAUNCH(kern, a.tiles_m * a.tiles_n * a.ksplit, 256, lds, ln.stream, ln.ev_start, ln.ev_stop, a);
     VQ_CHECK_LAUNCH();
     return VQ_OK;
 }
 
-typedef int (*ConvLaunch)(vq_tsn*, ConvArgs&);
+typedef int (*ConvLaunch)(const Launch&, ConvArgs&);
 
 struct ConvTile {
     int bm, bn, bk;
@@ -1285,8 +1260,8 @@ static bool tile_candidate(const vq_layer_desc& L, const ConvTile& t, bool timed
 }
 
 static int heuristic_tile(const vq_tsn* net, int li, int n_crops) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& td = net->tensors[L.dst];
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
     const int M = n_crops * td.h * td.w, N = L.cout;
     int best = 0;
     double bs = -1;
@@ -1312,7 +1287,7 @@ static int heuristic_tile(const vq_tsn* net, int li, int n_crops) {
 // substitute gives the same bits.
 static ConvLaunch conv_launch(const vq_tsn* net, int li, const ConvArgs& a, bool stem_rows, int ti) {
     const ConvTile* t = &kTiles[ti];
-    if (net->layers[li].pre_pool_k > 0) {
+    if (net->plan.layers[li].pre_pool_k > 0) {
         // max-pool folded into the loader: any tiling gives the same bits, so an unsupported choice (heuristic, VQ_TSN_TILE)
         // is replaced by the BK = 16 tiling of the same shape
         if (!pooled_ok(*t, a.Cin)) ti = tile_index(std::min(t->bm, 128), std::min(t->bn, 128), 16, 0);
@@ -1326,13 +1301,13 @@ static ConvLaunch conv_launch(const vq_tsn* net, int li, const ConvArgs& a, bool
     return t->piped[small] && pixel_walk_ok(a) ? t->piped[small] : t->conv[small];
 }
 
-static void fill_conv_args(vq_tsn* net, int li, int n_crops, ConvArgs& a) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& ts = net->tensors[L.src];
-    const vq_tensor_desc& td = net->tensors[L.dst];
-    a.in = net->slots[L.src] + (size_t)net->crop_off * ts.h * ts.w * ts.c;
+static void fill_conv_args(const vq_tsn* net, const Launch& ln, int li, int n_crops, ConvArgs& a) {
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& ts = net->plan.tensors[L.src];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
+    a.in = net->slots[L.src] + (size_t)ln.crop0 * ts.h * ts.w * ts.c;
     a.out = net->slots[L.dst];
-    a.out_row0 = net->crop_off * td.h * td.w;
+    a.out_row0 = ln.crop0 * td.h * td.w;
     a.w = net->blob + L.w_off;
     a.bias = net->blob + L.b_off;
     a.zeros = net->zeros;
@@ -1366,16 +1341,16 @@ static void fill_conv_args(vq_tsn* net, int li, int n_crops, ConvArgs& a) {
     a.w_bytes = (unsigned)((size_t)L.cout * a.Kp * sizeof(float));
 }
 
-static int launch_conv_layer(vq_tsn* net, int li, int n_crops, int tile_idx) {
+static int launch_conv_layer(const vq_tsn* net, const Launch& ln, int li, int n_crops, int tile_idx) {
     ConvArgs a;
-    fill_conv_args(net, li, n_crops, a);
-    const vq_layer_desc& L = net->layers[li];
+    fill_conv_args(net, ln, li, n_crops, a);
+    const vq_layer_desc& L = net->plan.layers[li];
     // A convolution without padding that reads ALL channels of its slot finds the kw taps of a kernel row side by side
     // in memory ([kw][Cin] is one contiguous run of the NHWC row, and the packed weights have the same order): fold the
     // row into the channel axis -- k rows of one tap with kw*Cin channels.  The space-to-depth stem (4x4 over 12
     // channels) becomes 4 taps of 48 contiguous floats and, with BK = 16, runs on the aligned path: no per-chunk tap
     // decoding in its K loop.
-    const bool stem_rows = L.src == 0 && net->input.s2d_pad >= 0 && net->input.s2d_order == 1;
+    const bool stem_rows = L.src == 0 && net->plan.input.s2d_pad >= 0 && net->plan.input.s2d_order == 1;
     if (stem_rows) {
         // The x-major space-to-depth stem (vq_input_desc.s2d_order = 1): a kernel row is 7 x-taps x (2 rows x c channels) = 14 c contiguous
         // floats of the slot (RGB: 42, + 2 of the next pixel against zero weights = 44; flow stack: 140), and the weights are packed
@@ -1385,53 +1360,51 @@ static int launch_conv_layer(vq_tsn* net, int li, int n_crops, int tile_idx) {
         // loop, a uniform scalar offset per step).
         a.k = a.kw = 1;
         a.Cin = 4 * L.k * L.cin;                       // never reached: the walk stays inside its one "tap"
-        a.col_off = net->tensors[L.src].w * net->tensors[L.src].c;
+        a.col_off = net->plan.tensors[L.src].w * net->plan.tensors[L.src].c;
         a.c_step = 4;
-        a.Kp = stem_rows_kp(net->input.c);
+        a.Kp = stem_rows_kp(net->plan.input.c);
         a.w_bytes = (unsigned)((size_t)L.cout * a.Kp * sizeof(float));
-    } else if (L.pad == 0 && L.k > 1 && L.cin == net->tensors[L.src].c && L.src_coff == 0) {
+    } else if (L.pad == 0 && L.k > 1 && L.cin == net->plan.tensors[L.src].c && L.src_coff == 0) {
         a.kw = 1;
         a.Cin = L.k * L.cin;
     }
     const ConvLaunch run = conv_launch(net, li, a, stem_rows, tile_idx);
     const ConvTile& t = kTiles[tile_idx];
     if (!run) return fail(VQ_E_INVALID, "layer %d: no kernel for tile %dx%dx%d pipe=%d", li, t.bm, t.bn, t.bk, t.pipe);
-    if (net->ksplit[li] == 1) return run(net, a);
+    if (net->plan.ksplit[li] == 1) return run(ln, a);
     // K slices into the scratch planes (zero bias, no ReLU: the slice tables say so), then the combine pass into the
-    // layer's destination.  The profiling events bracket the pair.
-    const hipEvent_t e0 = net->ev_start, e1 = net->ev_stop;
-    a.ksplit = net->ksplit[li];
+    // layer's destination.  The profiling events bracket the pair: the slices carry the start event, the combine pass the stop event.
+    a.ksplit = net->plan.ksplit[li];
     a.k_per = a.Kp / a.ksplit;
     a.seg_stride = (L.cout + 31) / 32;
     a.bias = net->zero_bias;
     // Sub-batches of one forward run on separate streams and may be at DIFFERENT split layers at the same moment: every
     // crop owns a fixed stretch of each scratch plane (split_crop_floats, room for the largest split layer), and a
     // launch writes its [M][Cout] partial sums at the first whole row inside the stretch of its first crop.
-    a.out_row0 = (int)cdiv((int64_t)net->crop_off * (int64_t)net->split_crop_floats, (int64_t)L.cout);
-    net->ev_stop = nullptr;
-    int rc = run(net, a);
-    net->ev_stop = e1;
+    a.out_row0 = (int)cdiv((int64_t)ln.crop0 * (int64_t)net->plan.split_crop_floats, (int64_t)L.cout);
+    Launch slices = ln, combine = ln;
+    slices.ev_stop = nullptr;
+    combine.ev_start = nullptr;
+    const int rc = run(slices, a);
     if (rc != VQ_OK) return rc;
-    net->ev_start = nullptr;
-    const vq_tensor_desc& td = net->tensors[L.dst];
-    float* out = net->slots[L.dst] + (size_t)net->crop_off * td.h * td.w * td.c + L.dst_coff;
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
+    float* out = net->slots[L.dst] + (size_t)ln.crop0 * td.h * td.w * td.c + L.dst_coff;
     const int64_t work = (int64_t)a.M * (L.cout / 4);
-    VQ_LAUNCH(splitk_combine_kernel, (unsigned)cdiv(work, 256), 256, 0, net->ls, net->ev_start, net->ev_stop,
+    VQ_LAUNCH(splitk_combine_kernel, (unsigned)cdiv(work, 256), 256, 0, combine.stream, combine.ev_start, combine.ev_stop,
               net->split_scratch + (size_t)a.out_row0 * L.cout, a.ksplit, net->split_slice_floats, a.M, L.cout, net->blob + L.b_off, L.relu, out, td.c);
-    net->ev_start = e0;
     VQ_CHECK_LAUNCH();
     return VQ_OK;
 }
 
-static void fill_wino_job(vq_tsn* net, int li, int n_crops, WinoJob& a, int variant) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& ts = net->tensors[L.src];
-    const vq_tensor_desc& td = net->tensors[L.dst];
+static void fill_wino_job(const vq_tsn* net, const Launch& ln, int li, int n_crops, WinoJob& a, int variant) {
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& ts = net->plan.tensors[L.src];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
     memset(&a, 0, sizeof a);
-    a.in = net->slots[L.src] + (size_t)net->crop_off * ts.h * ts.w * ts.c;
+    a.in = net->slots[L.src] + (size_t)ln.crop0 * ts.h * ts.w * ts.c;
     a.u = net->blob + L.w_off;
     a.bias = net->blob + L.b_off;
-    a.out = net->slots[L.dst] + (size_t)net->crop_off * td.h * td.w * td.c;
+    a.out = net->slots[L.dst] + (size_t)ln.crop0 * td.h * td.w * td.c;
     a.H = ts.h;
     a.W = ts.w;
     a.Cs_in = ts.c;
@@ -1452,13 +1425,13 @@ static void fill_wino_job(vq_tsn* net, int li, int n_crops, WinoJob& a, int vari
     a.u_bytes = (unsigned)((size_t)16 * L.cout * L.cin * sizeof(float));
 }
 
-static void fill_pool_args(vq_tsn* net, int li, int n_crops, PoolArgs& a) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& ts = net->tensors[L.src];
-    const vq_tensor_desc& td = net->tensors[L.dst];
+static void fill_pool_args(const vq_tsn* net, const Launch& ln, int li, int n_crops, PoolArgs& a) {
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& ts = net->plan.tensors[L.src];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
     memset(&a, 0, sizeof a);
-    a.in = net->slots[L.src] + (size_t)net->crop_off * ts.h * ts.w * ts.c;
-    a.out = net->slots[L.dst] + (size_t)net->crop_off * td.h * td.w * td.c;
+    a.in = net->slots[L.src] + (size_t)ln.crop0 * ts.h * ts.w * ts.c;
+    a.out = net->slots[L.dst] + (size_t)ln.crop0 * td.h * td.w * td.c;
     a.H = ts.h;
     a.W = ts.w;
     a.Cs_in = ts.c;
@@ -1478,57 +1451,52 @@ static void fill_pool_args(vq_tsn* net, int li, int n_crops, PoolArgs& a) {
 }
 
 // The Winograd layers among `members` (independent of each other) plus the pooling layers among them as one launch.
-static int launch_wino_layers(vq_tsn* net, const std::vector<int>& members, int n_crops, int variant) {
+static int launch_wino_layers(const vq_tsn* net, const Launch& ln, const std::vector<int>& members, int n_crops, int variant) {
     WinoGroup g;
     memset(&g, 0, sizeof g);
     for (int li : members) {
-        if (is_wino(net->layers[li].op)) {
+        if (is_wino(net->plan.layers[li].op)) {
             VQ_REQUIRE(g.n_jobs < kWinoMaxJobs, "a Winograd launch carries at most %d convolutions", kWinoMaxJobs);
-            fill_wino_job(net, li, n_crops, g.job[g.n_jobs++], variant);
+            fill_wino_job(net, ln, li, n_crops, g.job[g.n_jobs++], variant);
         } else {
             VQ_REQUIRE(g.n_pools < kWinoMaxPools, "a Winograd launch carries at most %d pooling layers", kWinoMaxPools);
-            fill_pool_args(net, li, n_crops, g.pool[g.n_pools++]);
+            fill_pool_args(net, ln, li, n_crops, g.pool[g.n_pools++]);
         }
     }
     bool both = true;
     for (int li : members)
-        if (net->layers[li].op == VQ_OP_CONV_WINOGRAD) both = false;
+        if (net->plan.layers[li].op == VQ_OP_CONV_WINOGRAD) both = false;
     if (variant >= 2 && !both) {                         // a table written for another layout: the same channel blocks on 32 tiles (same bits)
         variant -= 2;
         for (int q = 0; q < g.n_jobs; ++q) VQ_REQUIRE(!g.job[q].t16, "internal: mixed Winograd layouts in one launch");
     }
-    return launch_wino_group(g, variant, net->ls, net->ev_start, net->ev_stop);
+    return launch_wino_group(g, variant, ln.stream, ln.ev_start, ln.ev_stop);
 }
 
-static int run_layer(vq_tsn* net, int li, int n_crops, int tune_key);
+static int run_layer(const vq_tsn* net, const Launch& ln, int li, int n_crops, int tune_key);
 
 // Launch one item on crops [crop0, crop0 + n_crops) of the batch; tune_key = the batch size whose tuning table applies.
 // A launch addresses its slots with 32-bit byte offsets, so an item whose slots exceed 2^31 bytes at this batch size
 // runs as several launches over crop ranges (the results do not depend on the cut: every crop is independent).
-static int run_item(vq_tsn* net, const LaunchItem& it, int crop0, int n_crops, int tune_key) {
-    const hipEvent_t e0 = net->ev_start, e1 = net->ev_stop;
+// `whole`: the stream, the events around the item and its first crop (crop0).
+static int run_item(const vq_tsn* net, const Launch& whole, const LaunchItem& it, int n_crops, int tune_key) {
     for (int done = 0; done < n_crops;) {
         const int n = std::min(n_crops - done, it.max_crops);
-        net->crop_off = crop0 + done;
+        Launch ln = whole;
+        ln.crop0 = whole.crop0 + done;
         // profiling: the first chunk carries the start event, the last one the stop event
-        net->ev_start = done == 0 ? e0 : nullptr;
-        net->ev_stop = done + n == n_crops ? e1 : nullptr;
+        if (done != 0) ln.ev_start = nullptr;
+        if (done + n != n_crops) ln.ev_stop = nullptr;
         int rc;
         if (it.kind == 1) {
             auto tn = net->tuned.find(tune_key);
-            rc = launch_wino_layers(net, it.layers, n, tn != net->tuned.end() ? tn->second[it.layers[0]] : 0);
+            rc = launch_wino_layers(net, ln, it.layers, n, tn != net->tuned.end() ? tn->second[it.layers[0]] : 0);
         } else {
-            rc = run_layer(net, it.layers[0], n, tune_key);
+            rc = run_layer(net, ln, it.layers[0], n, tune_key);
         }
-        if (rc != VQ_OK) {
-            net->crop_off = 0;
-            net->ev_start = net->ev_stop = nullptr;
-            return rc;
-        }
+        if (rc != VQ_OK) return rc;
         done += n;
     }
-    net->crop_off = 0;
-    net->ev_start = net->ev_stop = nullptr;
     return VQ_OK;
 }
 
@@ -1557,9 +1525,8 @@ struct EventSet {          // the sweep's events go on every way out
 static int autotune(vq_tsn* net, int n_crops, bool paired) {
     const int key = tile_key(n_crops, paired);
     std::vector<int>& choice = net->tuned[key];
-    choice.assign(net->layers.size(), 0);
+    choice.assign(net->plan.layers.size(), 0);
     net->tuned_borrowed.erase(key);
-    net->ls = net->stream;
     const int ways = paired ? std::max(1, std::min(net->n_split, net->max_crops / n_crops)) : 1;     // streams that run the launch side by side
     EventSet events;
     events.ev.assign(2 + ways, nullptr);
@@ -1567,9 +1534,12 @@ static int autotune(vq_tsn* net, int n_crops, bool paired) {
         if (l != 2) VQ_HIP(hipEventCreate(&events.ev[l]));
     const hipEvent_t e0 = events.ev[0], e1 = events.ev[1];
     hipEvent_t* const f = events.ev.data() + 2;               // f[1 .. ways-1]
+    // way l: the launch on crops [l * n_crops, (l + 1) * n_crops) on its stream (only durations matter: no clips, no consensus)
+    std::vector<Launch> way((size_t)ways);
+    for (int l = 0; l < ways; ++l) way[l] = Launch{l > 0 ? net->split_streams[l] : net->stream, nullptr, nullptr, l * n_crops, 1, false};
     auto timed = [&](const LaunchItem& it, int reps, float* ms) -> int {
         VQ_HIP(hipEventRecord(e0, net->stream));
-        int rc = run_item(net, it, 0, n_crops, key);           // warm
+        int rc = run_item(net, way[0], it, n_crops, key);      // warm
         if (rc != VQ_OK) return rc;
         VQ_HIP(hipEventRecord(e1, net->stream));
         VQ_HIP(hipEventSynchronize(e1));
@@ -1583,9 +1553,7 @@ static int autotune(vq_tsn* net, int n_crops, bool paired) {
         for (int l = 1; l < ways; ++l) VQ_HIP(hipStreamWaitEvent(net->split_streams[l], e0, 0));
         for (int r = 0; r < reps; ++r)
             for (int l = 0; l < ways; ++l) {
-                net->ls = l > 0 ? net->split_streams[l] : net->stream;
-                rc = run_item(net, it, l * n_crops, n_crops, key);
-                net->ls = net->stream;
+                rc = run_item(net, way[l], it, n_crops, key);
                 if (rc != VQ_OK) return rc;
             }
         VQ_HIP(hipEventRecord(e1, net->stream));
@@ -1604,22 +1572,22 @@ static int autotune(vq_tsn* net, int n_crops, bool paired) {
         std::vector<int> saved = choice;
         net->tuned.erase(key);                                // run_layer falls back to the heuristic without a table
         for (int r = 0; r < 10; ++r)
-            for (const LaunchItem& it : net->items) {
-                const int rc = run_item(net, it, 0, n_crops, key);
+            for (const LaunchItem& it : net->plan.items) {
+                const int rc = run_item(net, way[0], it, n_crops, key);
                 if (rc != VQ_OK) return rc;
             }
         VQ_HIP(hipStreamSynchronize(net->stream));
         net->tuned[key] = saved;
     }
     std::vector<int>& pick = net->tuned[key];
-    for (const LaunchItem& it : net->items) {
+    for (const LaunchItem& it : net->plan.items) {
         const int li = it.layers[0];
-        if (!is_conv(net->layers[li].op)) continue;
-        const bool wino = is_wino(net->layers[li].op);
+        if (!is_conv(net->plan.layers[li].op)) continue;
+        const bool wino = is_wino(net->plan.layers[li].op);
         std::vector<std::pair<float, int>> seen;
-        const int n_wino = net->layers[li].op == VQ_OP_CONV_WINOGRAD16 ? 2 * kWinoVariants : kWinoVariants;     // + the 16-tile units
+        const int n_wino = net->plan.layers[li].op == VQ_OP_CONV_WINOGRAD16 ? 2 * kWinoVariants : kWinoVariants;     // + the 16-tile units
         for (int t = 0; t < (wino ? n_wino : kNumTiles); ++t) {
-            if (!wino && !tile_candidate(net->layers[li], kTiles[t], true)) continue;
+            if (!wino && !tile_candidate(net->plan.layers[li], kTiles[t], true)) continue;
             for (int m : it.layers) pick[m] = t;               // a grouped launch runs one variant for all its members
             float ms = 0.f;
             const int rc = timed(it, 3, &ms);
@@ -1644,226 +1612,79 @@ static int autotune(vq_tsn* net, int n_crops, bool paired) {
     return VQ_OK;
 }
 
-// Make sure a tiling table exists for this batch size.  The first size seen is autotuned; a later size within 1.5x of
+// Make sure a tiling table exists for this batch size.  The first size seen is autotuned; a later size within 1.6x of
 // a tuned one borrows that table (the ragged last batch of a video must not cost 2 s of tuning launches -- every
 // tiling gives the same bits, only the speed differs); anything further away is tuned itself.
 static int ensure_tuned(vq_tsn* net, int n_crops, bool paired) {
     const int key = tile_key(n_crops, paired);
     if (net->forced_tile >= 0 || net->tuned.find(key) != net->tuned.end()) return VQ_OK;
     // the nearest size timed the same way (side by side / alone); failing that the nearest one timed the other way
-    int nearest = 0, nearest_key = 0;
-    for (int same = 1; same >= 0 && nearest == 0; --same)
-        for (const auto& kv : net->tuned) {
-            const bool kp = kv.first >= kPairedKey;
-            const int size = kv.first - (kp ? kPairedKey : 0);
-            if ((kp == paired) != (same == 1) || net->tuned_borrowed.count(kv.first)) continue;
-            if (10 * std::max(size, n_crops) > 16 * std::min(size, n_crops)) continue;            // further than 1.6x away
-            if (nearest == 0 || std::abs(size - n_crops) < std::abs(nearest - n_crops)) {
-                nearest = size;
-                nearest_key = kv.first;
-            }
+    for (const bool p : {paired, !paired}) {            // the nearest size timed the same way; failing that the other way
+        std::vector<int> sizes;                                   // measured (not borrowed) tables of that pairing
+        for (const auto& kv : net->tuned)
+            if ((kv.first >= kPairedKey) == p && !net->tuned_borrowed.count(kv.first)) sizes.push_back(kv.first - (p ? kPairedKey : 0));
+        if (const int nearest = nearest_size(sizes, n_crops)) {
+            net->tuned[key] = net->tuned[tile_key(nearest, p)];
+            net->tuned_borrowed.insert(key);
+            return VQ_OK;
         }
-    if (nearest > 0) {
-        net->tuned[key] = net->tuned[nearest_key];
-        net->tuned_borrowed.insert(key);
-        return VQ_OK;
     }
     if (!net->autotune) return VQ_OK;             // VQ_TSN_AUTOTUNE=0: the occupancy heuristic for sizes without a table
     return autotune(net, n_crops, paired);
 }
 
-static int run_layer(vq_tsn* net, int li, int n_crops, int tune_key) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& ts = net->tensors[L.src];
-    const vq_tensor_desc& td = net->tensors[L.dst];
+static int run_layer(const vq_tsn* net, const Launch& ln, int li, int n_crops, int tune_key) {
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& ts = net->plan.tensors[L.src];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
     if (L.op == VQ_OP_CONV) {
         int t = net->forced_tile;   // VQ_TSN_TILE (read at creation): test / tuning aid
         if (t < 0) {
             auto it = net->tuned.find(tune_key);
             t = it != net->tuned.end() ? it->second[li] : heuristic_tile(net, li, n_crops);
         }
-        return launch_conv_layer(net, li, n_crops, t);
+        return launch_conv_layer(net, ln, li, n_crops, t);
     }
     if (is_wino(L.op)) {
         auto it = net->tuned.find(tune_key);
-        return launch_wino_layers(net, std::vector<int>{li}, n_crops, it != net->tuned.end() ? it->second[li] : 0);
+        return launch_wino_layers(net, ln, std::vector<int>{li}, n_crops, it != net->tuned.end() ? it->second[li] : 0);
     }
     if (L.op == VQ_OP_MAXPOOL || L.op == VQ_OP_AVGPOOL) {
         PoolArgs a;
-        fill_pool_args(net, li, n_crops, a);
+        fill_pool_args(net, ln, li, n_crops, a);
         const int64_t blocks = (a.total + 255) / 256;
         if (L.op == VQ_OP_MAXPOOL)
-            VQ_LAUNCH(pool_kernel<true>, (unsigned)blocks, 256, 0, net->ls, net->ev_start, net->ev_stop, a);
+            VQ_LAUNCH(pool_kernel<true>, (unsigned)blocks, 256, 0, ln.stream, ln.ev_start, ln.ev_stop, a);
         else
-            VQ_LAUNCH(pool_kernel<false>, (unsigned)blocks, 256, 0, net->ls, net->ev_start, net->ev_stop, a);
+            VQ_LAUNCH(pool_kernel<false>, (unsigned)blocks, 256, 0, ln.stream, ln.ev_start, ln.ev_stop, a);
         VQ_CHECK_LAUNCH();
         return VQ_OK;
     }
     if (L.op == VQ_OP_GLOBAL_AVGPOOL) {
-        const float* gin = net->slots[L.src] + (size_t)net->crop_off * ts.h * ts.w * ts.c;
-        float* gout = net->slots[L.dst] + (size_t)net->crop_off * td.c;
-        const int T = net->cur_T;
-        if (li == net->consensus_layer && net->fused_consensus) {
+        const float* gin = net->slots[L.src] + (size_t)ln.crop0 * ts.h * ts.w * ts.c;
+        float* gout = net->slots[L.dst] + (size_t)ln.crop0 * td.c;
+        const int T = ln.T;
+        if (li == net->plan.consensus_layer && ln.fused_consensus) {
             // the feature blob: global pool and segment consensus in one pass (the launch covers whole clips)
             const int B = n_crops / T;
-            VQ_LAUNCH(gavgpool_consensus_kernel, dim3(cdiv(L.cin, 64), B), dim3(64, T), 0, net->ls, net->ev_start, net->ev_stop, gin, gout,
-                      net->feat_dev + (size_t)(net->crop_off / T) * net->D, T, ts.h * ts.w, ts.c, L.src_coff, L.cin, td.c, L.dst_coff);
+            VQ_LAUNCH(gavgpool_consensus_kernel, dim3(cdiv(L.cin, 64), B), dim3(64, T), 0, ln.stream, ln.ev_start, ln.ev_stop, gin, gout,
+                      net->feat_dev + (size_t)(ln.crop0 / T) * net->plan.D, T, ts.h * ts.w, ts.c, L.src_coff, L.cin, td.c, L.dst_coff);
         } else {
-            VQ_LAUNCH(gavgpool_kernel, cdiv((int64_t)n_crops * L.cin, 256), 256, 0, net->ls, net->ev_start, net->ev_stop, gin, gout, n_crops,
+            VQ_LAUNCH(gavgpool_kernel, cdiv((int64_t)n_crops * L.cin, 256), 256, 0, ln.stream, ln.ev_start, ln.ev_stop, gin, gout, n_crops,
                       ts.h * ts.w, ts.c, L.src_coff, L.cin, td.c, L.dst_coff);
         }
         VQ_CHECK_LAUNCH();
         return VQ_OK;
     }
     if (L.op == VQ_OP_INNER_PRODUCT) {
-        const float* xin = net->slots[L.src] + (size_t)net->crop_off * ts.c + L.src_coff;
-        float* yout = net->slots[L.dst] + (size_t)net->crop_off * td.c + L.dst_coff;
-        VQ_LAUNCH(inner_product_kernel, dim3(cdiv(n_crops, FC_ROWS), cdiv(L.cout, FC_COLS)), 64, 0, net->ls, net->ev_start, net->ev_stop, xin, ts.c,
+        const float* xin = net->slots[L.src] + (size_t)ln.crop0 * ts.c + L.src_coff;
+        float* yout = net->slots[L.dst] + (size_t)ln.crop0 * td.c + L.dst_coff;
+        VQ_LAUNCH(inner_product_kernel, dim3(cdiv(n_crops, FC_ROWS), cdiv(L.cout, FC_COLS)), 64, 0, ln.stream, ln.ev_start, ln.ev_stop, xin, ts.c,
                   net->blob + L.w_off, net->blob + L.b_off, yout, td.c, n_crops, L.cin, L.cout);
         VQ_CHECK_LAUNCH();
         return VQ_OK;
     }
     return fail(VQ_E_INVALID, "layer %d: unknown op %d", li, L.op);
-}
-
-static int pool_out_size(int size, int k, int s, int p) {
-    int out = (size + 2 * p - k + s - 1) / s + 1;
-    if (p > 0 && (out - 1) * s >= size + p) --out;
-    return out;
-}
-
-// Channel range of one slot that a layer reads or writes.
-struct SlotRange {
-    int slot, c0, c1;
-};
-static bool overlaps(const std::vector<SlotRange>& x, const std::vector<SlotRange>& y) {
-    for (const SlotRange& p : x)
-        for (const SlotRange& q : y)
-            if (p.slot == q.slot && p.c0 < q.c1 && q.c0 < p.c1) return true;
-    return false;
-}
-
-// The launch sequence.  Layer i depends on an earlier layer j when i reads what j wrote, overwrites what j read, or
-// writes the same channels (slots are never recycled, so in a valid plan only the first kind occurs, but all three are
-// honoured).  Layers are levelled (level = 1 + deepest dependency) and launched level by level, which is a topological
-// order; inside a level every layer is independent of every other, so the level's Winograd convolutions -- the 3x3 and
-// the first double-3x3 arm of an inception module -- share ONE launch (vq_wino.hip).
-static void build_items(vq_tsn* net, const vq_conv_segment* segments) {
-    const int n = (int)net->layers.size();
-    std::vector<std::vector<SlotRange>> rd(n), wr(n);
-    for (int i = 0; i < n; ++i) {
-        const vq_layer_desc& L = net->layers[i];
-        const bool whole = L.op == VQ_OP_CONV && L.cin % KPAD != 0;
-        rd[i].push_back(whole ? SlotRange{L.src, 0, net->tensors[L.src].c} : SlotRange{L.src, L.src_coff, L.src_coff + L.cin});
-        if (L.op == VQ_OP_CONV && L.seg_count > 0)
-            for (int q = 0; q < L.seg_count; ++q) {
-                const vq_conv_segment& sg = segments[L.seg_first + q];
-                wr[i].push_back(SlotRange{sg.dst, sg.dst_coff, sg.dst_coff + sg.cout});
-            }
-        else
-            wr[i].push_back(SlotRange{L.dst, L.dst_coff, L.dst_coff + L.cout});
-    }
-    std::vector<int> level(n, 0), floor_level(n, 0);
-    int n_levels = 0;
-    auto levelise = [&]() {
-        n_levels = 0;
-        for (int i = 0; i < n; ++i) {
-            level[i] = floor_level[i];
-            for (int j = 0; j < i; ++j)
-                if (overlaps(wr[j], rd[i]) || overlaps(rd[j], wr[i]) || overlaps(wr[j], wr[i])) level[i] = std::max(level[i], level[j] + 1);
-            n_levels = std::max(n_levels, level[i] + 1);
-        }
-    };
-    levelise();
-    // A pooling layer that reads a module's input is ready one level before the module's Winograd convolutions (it sits
-    // beside the 1x1 reductions).  Nothing needs it that early: hold it back one level so it can ride in their launch.
-    if (net->group_wino && net->group_pool) {
-        for (int i = 0; i < n; ++i) {
-            const int op = net->layers[i].op;
-            if (op != VQ_OP_MAXPOOL && op != VQ_OP_AVGPOOL) continue;
-            bool here = false, next = false;
-            for (int j = 0; j < n; ++j)
-                if (is_wino(net->layers[j].op)) {
-                    here |= level[j] == level[i];
-                    next |= level[j] == level[i] + 1;
-                }
-            if (!here && next) floor_level[i] = level[i] + 1;
-        }
-        levelise();
-    }
-    auto slot_bytes_per_crop = [&](int slot) {
-        const vq_tensor_desc& t = net->tensors[slot];
-        return (size_t)t.h * t.w * t.c * sizeof(float);
-    };
-    auto item_limit = [&](const std::vector<int>& members) {
-        size_t worst = 1;
-        for (int li : members) {
-            const vq_layer_desc& L = net->layers[li];
-            worst = std::max(worst, slot_bytes_per_crop(L.src));
-            if (L.op == VQ_OP_CONV && L.seg_count > 0)
-                for (int q = 0; q < L.seg_count; ++q) worst = std::max(worst, slot_bytes_per_crop(segments[L.seg_first + q].dst));
-            else
-                worst = std::max(worst, slot_bytes_per_crop(L.dst));
-        }
-        size_t limit = std::max<size_t>(1, (size_t)0x7FFFFFF0u / worst);
-        // the Winograd kernel multiplies pixel indices of a slot on 24 bits (vq_wino.hip: launch_t requires crops x H x W < 2^23 for the
-        // source AND the destination): with >= 64 channels per pixel the byte limit above implies it, a narrower slot at a large batch
-        // needs the cap itself (the launch then covers the batch in several crop ranges, like any other item)
-        for (int li : members) {
-            const vq_layer_desc& L = net->layers[li];
-            if (!is_wino(L.op)) continue;
-            for (int slot : {L.src, L.dst}) {
-                const vq_tensor_desc& t = net->tensors[slot];
-                limit = std::min(limit, std::max<size_t>(1, ((size_t)(1u << 23) - 1) / ((size_t)t.h * t.w)));
-            }
-            // ... and decodes a workgroup's first tile with a multiply-high division that is exact while (tiles + 32) x tiles per image < 2^32
-            const vq_tensor_desc& ts = net->tensors[L.src];
-            const size_t tpi = (size_t)((ts.h + 1) / 2) * ((ts.w + 1) / 2);
-            if ((1ull << 32) / tpi > 64) limit = std::min(limit, std::max<size_t>(1, ((size_t)((1ull << 32) / tpi) - 64) / tpi));
-        }
-        return (int)limit;
-    };
-    net->items.clear();
-    net->item_of_layer.assign(n, -1);
-    for (int lv = 0; lv < n_levels; ++lv) {
-        std::vector<int> wino, pools;
-        for (int i = 0; i < n; ++i)
-            if (level[i] == lv && is_wino(net->layers[i].op) && net->group_wino) wino.push_back(i);
-        for (int i = 0; i < n; ++i) {
-            if (level[i] != lv || (is_wino(net->layers[i].op) && net->group_wino)) continue;
-            const int op = net->layers[i].op;
-            // the level's pooling rides in its Winograd launch (few short workgroups that fill the tail)
-            if (!wino.empty() && (op == VQ_OP_MAXPOOL || op == VQ_OP_AVGPOOL) && (int)pools.size() < kWinoMaxPools && net->group_pool) {
-                pools.push_back(i);
-                continue;
-            }
-            LaunchItem it;
-            it.kind = 0;
-            it.layers = {i};
-            it.max_crops = item_limit(it.layers);
-            net->item_of_layer[i] = (int)net->items.size();
-            net->items.push_back(it);
-        }
-        // longest K loop first: the hardware hands out workgroups in index order, so the short ones fill the tail
-        // (a launch carries layers of one filter layout: the 32-tile form first, then the 16-tile form; a level of BN-Inception has one)
-        std::stable_sort(wino.begin(), wino.end(), [&](int x, int y) {
-            if (net->layers[x].op != net->layers[y].op) return net->layers[x].op < net->layers[y].op;
-            return net->layers[x].cin > net->layers[y].cin;
-        });
-        for (size_t q = 0; q < wino.size();) {
-            size_t end = q;
-            while (end < wino.size() && end - q < (size_t)kWinoMaxJobs && net->layers[wino[end]].op == net->layers[wino[q]].op) ++end;
-            LaunchItem it;
-            it.kind = 1;
-            it.layers.assign(wino.begin() + q, wino.begin() + end);
-            const bool first = q == 0;
-            q = end;
-            if (first) it.layers.insert(it.layers.end(), pools.begin(), pools.end());
-            it.max_crops = item_limit(it.layers);
-            for (int m : it.layers) net->item_of_layer[m] = (int)net->items.size();
-            net->items.push_back(it);
-        }
-    }
 }
 
 extern "C" {
@@ -1873,116 +1694,10 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
                   const vq_input_desc* input, int32_t feature_slot, int32_t max_crops, int32_t device, vq_tsn** out) {
     VQ_REQUIRE(out, "out is NULL");
     *out = nullptr;
-    VQ_REQUIRE(tensors && layers && blob_host && input, "NULL argument");
+    TsnPlan plan;
+    const int vrc = validate_plan(tensors, n_tensors, layers, n_layers, segments, n_segments, blob_host, blob_floats, input, feature_slot, max_crops, &plan);
+    if (vrc != VQ_OK) return vrc;
     const int in_channels = input->c;
-    VQ_REQUIRE(n_tensors > 0 && n_layers > 0 && blob_floats > 0 && max_crops > 0, "sizes must be positive");
-    VQ_REQUIRE(n_segments >= 0 && (n_segments == 0 || segments), "bad segment table");
-    VQ_REQUIRE(feature_slot > 0 && feature_slot < n_tensors, "feature_slot out of range");
-    VQ_REQUIRE(tensors[feature_slot].h == 1 && tensors[feature_slot].w == 1, "feature slot must be 1x1xD");
-    VQ_REQUIRE(tensors[0].c % 4 == 0, "input slot channels must be padded to a multiple of 4 (got %d)", tensors[0].c);
-    VQ_REQUIRE(input->h > 0 && input->w > 0 && in_channels > 0, "input crops must be h x w x c with positive sizes");
-    if (input->s2d_pad < 0) {
-        VQ_REQUIRE(tensors[0].h == input->h && tensors[0].w == input->w, "input slot is %dx%d but the crops are %dx%d", tensors[0].h,
-                   tensors[0].w, input->h, input->w);
-        VQ_REQUIRE(in_channels <= tensors[0].c && tensors[0].c - in_channels < 4, "in_channels %d does not fit the %d-channel input slot",
-                   in_channels, tensors[0].c);
-    } else {
-        VQ_REQUIRE(tensors[0].c == 4 * in_channels, "space-to-depth input slot needs 4 x %d channels (got %d)", in_channels, tensors[0].c);
-        VQ_REQUIRE(input->s2d_pad <= 64, "space-to-depth shift out of range");
-        VQ_REQUIRE(input->s2d_order == 0 || input->s2d_order == 1, "s2d_order must be 0 or 1");
-    }
-    // validate every layer against the tensor table BEFORE anything is launched: a mismatch here would be
-    // an out-of-bounds access on the device
-    double macs = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const vq_layer_desc& L = layers[i];
-        const bool multi = L.op == VQ_OP_CONV && L.seg_count > 0;
-        VQ_REQUIRE(L.src >= 0 && L.src < n_tensors && L.dst > 0 && L.dst < n_tensors && L.src != L.dst,
-                   "layer %d: bad tensor slots %d -> %d", i, L.src, L.dst);
-        const vq_tensor_desc& ts = tensors[L.src];
-        const vq_tensor_desc& td = tensors[L.dst];
-        // one crop of any slot must stay addressable with a signed 32-bit byte offset (the kernels' buffer offsets);
-        // larger batches are cut into crop ranges per launch (LaunchItem::max_crops)
-        VQ_REQUIRE((size_t)ts.h * ts.w * ts.c * sizeof(float) <= 0x7FFFFFF0u && (size_t)td.h * td.w * td.c * sizeof(float) <= 0x7FFFFFF0u,
-                   "layer %d: one crop of a tensor slot exceeds 2 GiB", i);
-        VQ_REQUIRE(L.src_coff >= 0 && L.cin > 0 && L.src_coff + L.cin <= ts.c, "layer %d: reads channels [%d,%d) of a %d-channel slot",
-                   i, L.src_coff, L.src_coff + L.cin, ts.c);
-        VQ_REQUIRE(multi || (L.dst_coff >= 0 && L.cout > 0 && L.dst_coff + L.cout <= td.c),
-                   "layer %d: writes channels [%d,%d) of a %d-channel slot", i, L.dst_coff, L.dst_coff + L.cout, td.c);
-        if (multi) {
-            VQ_REQUIRE(L.seg_first >= 0 && L.seg_first + L.seg_count <= n_segments, "layer %d: segments outside the table", i);
-            int sum = 0;
-            for (int q = 0; q < L.seg_count; ++q) {
-                const vq_conv_segment& sg = segments[L.seg_first + q];
-                VQ_REQUIRE(sg.dst > 0 && sg.dst < n_tensors && sg.dst != L.src, "layer %d segment %d: bad slot", i, q);
-                const vq_tensor_desc& t2 = tensors[sg.dst];
-                VQ_REQUIRE(sg.cout > 0 && sg.cout % 32 == 0 && sg.dst_coff >= 0 && sg.dst_coff % 4 == 0 && sg.dst_coff + sg.cout <= t2.c,
-                           "layer %d segment %d: channels [%d,%d) do not fit a %d-channel slot (cout must be a multiple of 32)", i, q,
-                           sg.dst_coff, sg.dst_coff + sg.cout, t2.c);
-                VQ_REQUIRE(t2.h == td.h && t2.w == td.w && t2.c % 4 == 0, "layer %d segment %d: spatial size differs", i, q);
-                sum += sg.cout;
-            }
-            VQ_REQUIRE(sum == L.cout, "layer %d: segments cover %d of %d output channels", i, sum, L.cout);
-        }
-        VQ_REQUIRE(L.k >= 1 && L.stride >= 1 && L.pad >= 0 && L.pad < L.k, "layer %d: bad kernel/stride/pad", i);
-        // (an InnerProduct writes single floats: its destination slot, cout and dst_coff are free -- 101 class scores)
-        const bool fc = L.op == VQ_OP_INNER_PRODUCT;
-        VQ_REQUIRE(ts.c % 4 == 0 && L.src_coff % 4 == 0 && L.cin % 4 == 0 && (fc || (td.c % 4 == 0 && L.dst_coff % 4 == 0 && L.cout % 4 == 0)),
-                   "layer %d: channel counts and offsets must be multiples of 4", i);
-        if (L.op == VQ_OP_CONV) {
-            VQ_REQUIRE(L.k <= 8, "layer %d: conv kernels up to 8x8 (the tap mask is 64 bits)", i);
-            if (L.pre_pool_k > 0) {
-                VQ_REQUIRE(L.pre_pool_k == 3 && L.pre_pool_stride >= 1 && L.pre_pool_stride <= 3,
-                           "layer %d: the pooled-input form takes a 3x3 max window with stride 1..3", i);
-                VQ_REQUIRE(L.k == 1 && L.stride == 1 && L.pad == 0 && L.cin % 32 == 0, "layer %d: the pooled-input form is a 1x1 convolution over a multiple of 32 channels", i);
-                VQ_REQUIRE(td.h == pool_out_size(ts.h, 3, L.pre_pool_stride, 0) && td.w == pool_out_size(ts.w, 3, L.pre_pool_stride, 0),
-                           "layer %d: pooled-input size mismatch (Caffe ceil rule)", i);
-            } else
-            VQ_REQUIRE(td.h == (ts.h + 2 * L.pad - L.k) / L.stride + 1 && td.w == (ts.w + 2 * L.pad - L.k) / L.stride + 1,
-                       "layer %d: conv output size mismatch", i);
-            int64_t kp = (int64_t)(L.k * L.k * L.cin + KPAD - 1) / KPAD * KPAD;
-            if (L.src == 0 && input->s2d_pad >= 0 && input->s2d_order == 1) {      // x-major stem: [Cout][steps][4][4], see launch_conv_layer
-                VQ_REQUIRE(L.k == 4 && L.cin == 4 * in_channels && L.stride == 1 && L.pad == 0 && L.src_coff == 0 && L.pre_pool_k == 0 &&
-                               L.seg_count == 0 && input->s2d_kernel == 7,
-                           "layer %d: the x-major space-to-depth stem is a 7x7 / stride-2 convolution reading the whole input slot", i);
-                kp = stem_rows_kp(in_channels);
-            }
-            VQ_REQUIRE(L.w_off >= 0 && L.w_off % 4 == 0 && L.w_off + (int64_t)L.cout * kp <= blob_floats,
-                       "layer %d: weights outside the blob", i);
-            VQ_REQUIRE(L.b_off >= 0 && L.b_off + L.cout <= blob_floats, "layer %d: bias outside the blob", i);
-            VQ_REQUIRE(L.cin % KPAD == 0 || L.src_coff == 0, "layer %d: small-Cin convolution must read a whole slot", i);
-            VQ_REQUIRE(L.cin % KPAD == 0 || L.cin == ts.c, "layer %d: small-Cin convolution must read a whole slot", i);
-            macs += (double)td.h * td.w * L.cout * first_layer_k2c(*input, L);   // algorithmic, un-padded
-        } else if (is_wino(L.op)) {
-            VQ_REQUIRE(L.k == 3 && L.stride == 1 && L.pad == 1 && L.seg_count == 0, "layer %d: Winograd form is 3x3 / stride 1 / pad 1, one destination", i);
-            VQ_REQUIRE(L.cin % (L.op == VQ_OP_CONV_WINOGRAD16 ? 16 : 8) == 0 && L.cout % 32 == 0,
-                       "layer %d: Winograd form needs Cin %% 8 == 0 (16-tile units: %% 16) and Cout %% 32 == 0", i);
-            VQ_REQUIRE(td.h == ts.h && td.w == ts.w, "layer %d: conv output size mismatch", i);
-            VQ_REQUIRE(L.w_off >= 0 && L.w_off % 4 == 0 &&
-                           L.w_off + (int64_t)(L.op == VQ_OP_CONV_WINOGRAD16 ? 2 : 1) * 16 * L.cout * L.cin <= blob_floats,
-                       "layer %d: transformed filters outside the blob", i);
-            VQ_REQUIRE(L.b_off >= 0 && L.b_off % 4 == 0 && L.b_off + L.cout <= blob_floats, "layer %d: bias outside the blob", i);
-            macs += (double)td.h * td.w * L.cout * L.cin * 9;   // algorithmic (direct-form) count
-        } else if (L.op == VQ_OP_MAXPOOL || L.op == VQ_OP_AVGPOOL) {
-            VQ_REQUIRE(L.cin == L.cout, "layer %d: pooling keeps the channel count", i);
-            VQ_REQUIRE(!(L.op == VQ_OP_AVGPOOL && L.has_bias) || (L.b_off >= 0 && L.b_off % 4 == 0 && L.b_off + L.cout <= blob_floats),
-                       "layer %d: pooling bias outside the blob", i);
-            VQ_REQUIRE(td.h == pool_out_size(ts.h, L.k, L.stride, L.pad) && td.w == pool_out_size(ts.w, L.k, L.stride, L.pad),
-                       "layer %d: pooling output size mismatch (Caffe ceil rule)", i);
-        } else if (L.op == VQ_OP_GLOBAL_AVGPOOL) {
-            VQ_REQUIRE(L.cin == L.cout && td.h == 1 && td.w == 1, "layer %d: global pool must write a 1x1 slot", i);
-        } else if (L.op == VQ_OP_INNER_PRODUCT) {
-            VQ_REQUIRE(ts.h == 1 && ts.w == 1 && td.h == 1 && td.w == 1, "layer %d: InnerProduct reads and writes 1x1 slots", i);
-            VQ_REQUIRE(L.seg_count == 0 && L.pre_pool_k == 0 && L.relu == 0, "layer %d: InnerProduct has one destination, no pooled input, no ReLU", i);
-            VQ_REQUIRE(L.has_bias == 1, "layer %d: InnerProduct always adds its bias: has_bias must be 1 and b_off address it", i);
-            VQ_REQUIRE(L.w_off >= 0 && L.w_off % 4 == 0 && L.w_off + (int64_t)L.cout * L.cin <= blob_floats, "layer %d: weights outside the blob", i);
-            VQ_REQUIRE(L.b_off >= 0 && L.b_off + L.cout <= blob_floats, "layer %d: bias outside the blob", i);
-            VQ_REQUIRE(L.cout <= 65535 * FC_COLS, "layer %d: InnerProduct with more than %d outputs", i, 65535 * FC_COLS);
-            macs += (double)L.cin * L.cout;
-        } else {
-            return fail(VQ_E_INVALID, "layer %d: unknown op %d", i, L.op);
-        }
-    }
     int ndev = 0;
     VQ_HIP(hipGetDeviceCount(&ndev));
     VQ_REQUIRE(device >= 0 && device < ndev, "device %d out of range (%d visible)", device, ndev);
@@ -1991,16 +1706,9 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
     net->device = device;
     net->max_crops = max_crops;
     net->in_channels = in_channels;
-    net->input = *input;
-    net->tensors.assign(tensors, tensors + n_tensors);
-    net->layers.assign(layers, layers + n_layers);
+    net->plan = std::move(plan);
     net->feature_slot = feature_slot;
-    net->D = tensors[feature_slot].c;
     net->blob_floats = blob_floats;
-    net->flops_per_crop = 2.0 * macs;
-    for (int i = 0; i < n_layers; ++i)
-        if (layers[i].op == VQ_OP_GLOBAL_AVGPOOL && layers[i].dst == feature_slot && layers[i].dst_coff == 0 && layers[i].cout == net->D)
-            net->consensus_layer = i;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) net->cus = prop.multiProcessorCount;
     net->slots.assign(n_tensors, nullptr);
@@ -2021,31 +1729,12 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
     if (e != hipSuccess) return bail("hipMalloc(weights)", e);
     e = hipMemcpy(net->blob, blob_host, (size_t)blob_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) return bail("hipMemcpy(weights)", e);
-    {   // Which direct convolutions run split over K: single-destination layers with aligned channels on maps of at most
-        // 7 x 7 (M = 49 x crops: at any usual batch fewer output tiles than the chip has room for, each a long serial K chain
-        // on one wave per SIMD), cut into slices of at least 16 K-steps of 32 -- at most 4 slices.  On the 14 x 14 maps the
-        // same cut LOSES (3c/3x3 0.058 -> 0.076 ms at 96 crops: enough tiles already, the scratch round trip costs more).
-        // A function of the layer alone -- never of the batch actually run -- so a crop's features do not depend on the batch
-        // it travels in.  VQ_TSN_SPLITK=0 turns it off (A/B measurements).
-        net->ksplit.assign(n_layers, 1);
+    {   // the K split of the 7 x 7 layers (choose_ksplit) and its scratch planes; VQ_TSN_SPLITK=0 turns it off (A/B measurements)
         const char* sk = getenv("VQ_TSN_SPLITK");
-        size_t scratch = 0;
-        int max_cout = 4;
-        for (int i = 0; i < n_layers && !(sk && atoi(sk) == 0); ++i) {
-            const vq_layer_desc& L = layers[i];
-            const vq_tensor_desc& td = tensors[L.dst];
-            if (L.op != VQ_OP_CONV || L.seg_count > 0 || L.pre_pool_k > 0 || L.cin % KPAD != 0 || td.h * td.w > 49) continue;
-            const int steps = L.k * L.k * L.cin / KPAD;
-            int ks = std::min(4, steps / 16);
-            while (ks > 1 && steps % ks != 0) --ks;
-            if (ks <= 1) continue;
-            net->ksplit[i] = ks;
-            scratch = std::max(scratch, (size_t)td.h * td.w * L.cout);
-            max_cout = std::max(max_cout, L.cout);
-        }
-        if (scratch > 0) {
-            net->split_crop_floats = scratch + (size_t)max_cout;
-            net->split_slice_floats = (size_t)max_crops * net->split_crop_floats;
+        choose_ksplit(net->plan, !(sk && atoi(sk) == 0));
+        const int max_cout = net->plan.max_cout;
+        if (net->plan.split_crop_floats > 0) {
+            net->split_slice_floats = (size_t)max_crops * net->plan.split_crop_floats;
             e = pool_alloc(device, net->split_slice_floats * 4 * sizeof(float), (void**)&net->split_scratch);      // up to 4 slices
             if (e != hipSuccess) return bail("hipMalloc(split-K scratch)", e);
             e = hipMalloc((void**)&net->zero_bias, (size_t)max_cout * sizeof(float));
@@ -2061,8 +1750,8 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
             const vq_layer_desc& L = layers[i];
             if (L.op != VQ_OP_CONV) continue;
             net->seg_table_off[i] = (int)table.size();
-            if (net->ksplit[i] > 1) {       // slice q of a split layer writes plane q of the scratch, raw
-                for (int q = 0; q < net->ksplit[i]; ++q)
+            if (net->plan.ksplit[i] > 1) {       // slice q of a split layer writes plane q of the scratch, raw
+                for (int q = 0; q < net->plan.ksplit[i]; ++q)
                     for (int b = 0; b < (L.cout + 31) / 32; ++b)
                         table.push_back(ConvSeg{net->split_scratch + (size_t)q * net->split_slice_floats, L.cout, 0});
                 continue;
@@ -2108,7 +1797,8 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
             net->n_split = std::min(std::max(sp ? atoi(sp) : 2, 1), 8);
             net->split_parts.assign(net->n_split, 1);
         }
-        build_items(net, segments);
+        net->parts_sum = parts_sum(net->split_parts);
+        build_items(net->plan, net->group_wino, net->group_pool);
         net->split_streams.assign(net->n_split, nullptr);
         net->join_ev.assign(net->n_split, nullptr);
         for (int l = 1; l < net->n_split; ++l) {
@@ -2126,7 +1816,7 @@ int vq_tsn_create(const vq_tensor_desc* tensors, int32_t n_tensors, const vq_lay
     if (e != hipSuccess) return bail("hipMemset(zero page)", e);
     e = vq::malloc_trim((void**)&net->mean_dev, (size_t)in_channels * sizeof(float));
     if (e != hipSuccess) return bail("vq::malloc_trim(mean)", e);
-    e = vq::malloc_trim((void**)&net->feat_dev, (size_t)max_crops * net->D * sizeof(double));
+    e = vq::malloc_trim((void**)&net->feat_dev, (size_t)max_crops * net->plan.D * sizeof(double));
     if (e != hipSuccess) return bail("vq::malloc_trim(features)", e);
     *out = net;
     return VQ_OK;
@@ -2153,26 +1843,27 @@ int vq_tsn_set_stream(vq_tsn* net, void* s) {
 }
 
 // The launches of one forward, in order, on net->stream (and the sub-batch streams): preprocess, the launch items, the consensus.
-static int forward_launches(vq_tsn* net, const uint8_t* src, int n_crops, int T, int n_split, const std::vector<int>& sub,
-                            const std::vector<int>& sub_off, hipEvent_t* ev) {
-    const vq_tensor_desc& t0 = net->tensors[0];
+static int forward_launches(vq_tsn* net, const uint8_t* src, int n_crops, int T, const BatchCut& cut, hipEvent_t* ev) {
+    const std::vector<int>&sub = cut.sub, &sub_off = cut.sub_off;
+    const int n_split = (int)sub.size();
+    const vq_tensor_desc& t0 = net->plan.tensors[0];
     const int in_c = net->in_channels;
-    const int n_items = (int)net->items.size();
+    const int n_items = (int)net->plan.items.size();
     // uint8 crops [crop0, crop0 + n) -> the fp32 input slot, on stream st
     auto preprocess = [&](int crop0, int n, hipStream_t st) -> int {
-        const uint8_t* from = src + (size_t)crop0 * net->input.h * net->input.w * in_c;
+        const uint8_t* from = src + (size_t)crop0 * net->plan.input.h * net->plan.input.w * in_c;
         float* to = net->slots[0] + (size_t)crop0 * t0.h * t0.w * t0.c;
-        if (net->input.s2d_pad < 0) {
-            const int64_t nchunk = (int64_t)n * net->input.h * net->input.w * (t0.c / 4);
+        if (net->plan.input.s2d_pad < 0) {
+            const int64_t nchunk = (int64_t)n * net->plan.input.h * net->plan.input.w * (t0.c / 4);
             preprocess_kernel<<<cdiv(nchunk, 256), 256, 0, st>>>(from, to, nchunk, in_c, t0.c, net->mean_dev);
         } else {
             const int64_t nchunk = (int64_t)n * t0.h * t0.w * in_c;
             if (in_c == 3 && t0.c == 12)
-                preprocess_s2d3_kernel<<<cdiv(nchunk / 3, 256), 256, 0, st>>>(from, to, nchunk / 3, net->input.h, net->input.w, t0.h, t0.w,
-                                                                               net->input.s2d_pad, net->mean_dev, net->input.s2d_order);
+                preprocess_s2d3_kernel<<<cdiv(nchunk / 3, 256), 256, 0, st>>>(from, to, nchunk / 3, net->plan.input.h, net->plan.input.w, t0.h, t0.w,
+                                                                               net->plan.input.s2d_pad, net->mean_dev, net->plan.input.s2d_order);
             else
-                preprocess_s2d_kernel<<<cdiv(nchunk, 256), 256, 0, st>>>(from, to, nchunk, net->input.h, net->input.w, in_c, t0.h, t0.w,
-                                                                        net->input.s2d_pad, net->mean_dev, net->input.s2d_order);
+                preprocess_s2d_kernel<<<cdiv(nchunk, 256), 256, 0, st>>>(from, to, nchunk, net->plan.input.h, net->plan.input.w, in_c, t0.h, t0.w,
+                                                                        net->plan.input.s2d_pad, net->mean_dev, net->plan.input.s2d_order);
         }
         VQ_CHECK_LAUNCH();
         return VQ_OK;
@@ -2189,13 +1880,14 @@ static int forward_launches(vq_tsn* net, const uint8_t* src, int n_crops, int T,
             const int rc = preprocess(sub_off[sb], sub[sb], sb > 0 ? net->split_streams[sb] : net->stream);
             if (rc != VQ_OK) return rc;
         }
-        for (const LaunchItem& it : net->items)
+        Launch on[8];                                     // n_split <= 8 (VQ_TSN_SPLIT)
+        for (int sb = 0; sb < n_split; ++sb)
+            on[sb] = Launch{sb > 0 ? net->split_streams[sb] : net->stream, nullptr, nullptr, sub_off[sb], T, cut.fused_consensus};
+        for (const LaunchItem& it : net->plan.items)
             for (int sb = 0; sb < n_split; ++sb) {
-                net->ls = sb > 0 ? net->split_streams[sb] : net->stream;
-                const int rc = run_item(net, it, sub_off[sb], sub[sb], tile_key(sub[sb], true));
+                const int rc = run_item(net, on[sb], it, sub[sb], tile_key(sub[sb], true));
                 if (rc != VQ_OK) return rc;
             }
-        net->ls = net->stream;
         for (int l = 1; l < n_split; ++l) {
             VQ_HIP(hipEventRecord(net->join_ev[l], net->split_streams[l]));
             VQ_HIP(hipStreamWaitEvent(net->stream, net->join_ev[l], 0));
@@ -2203,21 +1895,17 @@ static int forward_launches(vq_tsn* net, const uint8_t* src, int n_crops, int T,
     } else {
         const int prc = preprocess(0, n_crops, net->stream);
         if (prc != VQ_OK) return prc;
-        net->ls = net->stream;
         for (int q = 0; q < n_items; ++q) {
-            if (ev) {
-                net->ev_start = ev[2 * q];
-                net->ev_stop = ev[2 * q + 1];
-            }
-            const int rc = run_item(net, net->items[q], 0, n_crops, tile_key(n_crops, false));
+            const Launch ln{net->stream, ev ? ev[2 * q] : nullptr, ev ? ev[2 * q + 1] : nullptr, 0, T, cut.fused_consensus};
+            const int rc = run_item(net, ln, net->plan.items[q], n_crops, tile_key(n_crops, false));
             if (rc != VQ_OK) return rc;
         }
     }
     if (ev) ++net->profile_count;
     const int B = n_crops / T;
-    if (!net->fused_consensus) {                  // consensus not fused into the global-pool launch: separate pass
-        consensus_kernel<<<cdiv((int64_t)B * net->D, 256), 256, 0, net->stream>>>(net->slots[net->feature_slot], net->feat_dev, B, T,
-                                                                                  net->D, net->D);
+    if (!cut.fused_consensus) {                   // consensus not fused into the global-pool launch: separate pass
+        consensus_kernel<<<cdiv((int64_t)B * net->plan.D, 256), 256, 0, net->stream>>>(net->slots[net->feature_slot], net->feat_dev, B, T,
+                                                                                  net->plan.D, net->plan.D);
         VQ_CHECK_LAUNCH();
     }
     return VQ_OK;
@@ -2231,7 +1919,7 @@ int vq_tsn_forward(vq_tsn* net, const uint8_t* crops, int32_t crops_on_device, i
     std::lock_guard<std::mutex> lk(net->mu);
     DeviceGuard g(net->device);
     const int in_c = net->in_channels;
-    const int64_t npix = (int64_t)n_crops * net->input.h * net->input.w;
+    const int64_t npix = (int64_t)n_crops * net->plan.input.h * net->plan.input.w;
     const uint8_t* src = crops;
     if (!crops_on_device) {
         const size_t bytes = (size_t)npix * in_c;
@@ -2252,59 +1940,37 @@ int vq_tsn_forward(vq_tsn* net, const uint8_t* crops, int32_t crops_on_device, i
     }
     if (net->poison)
         for (size_t i = 0; i < net->slots.size(); ++i) {
-            const vq_tensor_desc& t = net->tensors[i];
+            const vq_tensor_desc& t = net->plan.tensors[i];
             VQ_HIP(hipMemsetAsync(net->slots[i], 0xFF, (size_t)net->max_crops * t.h * t.w * t.c * sizeof(float), net->stream));
         }
-    net->cur_T = T;
-    const int n_items = (int)net->items.size();
+    const int n_items = (int)net->plan.items.size();
     hipEvent_t* ev = nullptr;
     const bool profiling = net->profile_depth > 0;
     if (profiling && net->profile_tick++ % net->profile_every == 0)
         ev = net->events.data() + (size_t)(net->profile_count % net->profile_depth) * (2 * n_items);
     // A sampled forward stays on the caller's stream (each duration is then the launch alone); so do the forwards between two
     // sampled ones (they issue exactly the same launches) unless vq_tsn_set_profile_split asked for the product's own mode there.
-    int parts_sum = 0;
-    for (int v : net->split_parts) parts_sum += v;
     bool one_stream = profiling && (ev || !net->profile_split);
     if (!one_stream && !net->split_pref.empty()) {       // a measured preference of the nearest batch size within 1.6x (default: split)
-        int best = 0, pref = 1;
-        for (const auto& kv : net->split_pref)
-            if (10 * std::max(kv.first, n_crops) <= 16 * std::min(kv.first, n_crops) && (best == 0 || std::abs(kv.first - n_crops) < std::abs(best - n_crops))) {
-                best = kv.first;
-                pref = kv.second;
-            }
-        if (pref == 0) one_stream = true;
+        std::vector<int> sizes;
+        for (const auto& kv : net->split_pref) sizes.push_back(kv.first);
+        const int best = nearest_size(sizes, n_crops);
+        if (best > 0 && net->split_pref[best] == 0) one_stream = true;
     }
-    int n_split = (!one_stream && net->n_split > 1 && n_crops % parts_sum == 0) ? net->n_split : 1;
-    std::vector<int> sub(n_split, n_crops), sub_off(n_split, 0);
-    if (n_split > 1) {
-        for (int sb = 0, o = 0; sb < n_split; ++sb) {
-            sub[sb] = n_crops / parts_sum * net->split_parts[sb];
-            sub_off[sb] = o;
-            o += sub[sb];
-        }
-    }
-    {   // the consensus rides in the global-pool launch when every launch of that layer covers whole clips
-        bool whole = net->consensus_layer >= 0 && T <= kMaxFusedT;
-        if (whole) {
-            const int cap = net->items[net->item_of_layer[net->consensus_layer]].max_crops;
-            for (int sb = 0; sb < n_split; ++sb)
-                if (sub[sb] % T != 0 || sub_off[sb] % T != 0 || (sub[sb] > cap && cap % T != 0)) whole = false;
-        }
-        net->fused_consensus = whole;
-    }
+    const BatchCut cut = cut_batch(net->plan, n_crops, T, net->split_parts, net->parts_sum, one_stream);
+    const int n_split = (int)cut.sub.size();
     for (int sb = 0; sb < n_split; ++sb) {      // n_split == 1: sub[0] is the whole batch
-        const int rc = ensure_tuned(net, sub[sb], n_split > 1);
+        const int rc = ensure_tuned(net, cut.sub[sb], n_split > 1);
         if (rc != VQ_OK) return rc;
     }
-    const int frc = forward_launches(net, src, n_crops, T, n_split, sub, sub_off, ev);
+    const int frc = forward_launches(net, src, n_crops, T, cut, ev);
     if (frc != VQ_OK) return frc;
     net->last_crops = n_crops;
     const int B = n_crops / T;
     if (feat_host)
-        VQ_HIP(hipMemcpyAsync(feat_host, net->feat_dev, (size_t)B * net->D * sizeof(double), hipMemcpyDeviceToHost, net->stream));
+        VQ_HIP(hipMemcpyAsync(feat_host, net->feat_dev, (size_t)B * net->plan.D * sizeof(double), hipMemcpyDeviceToHost, net->stream));
     if (per_snippet_host)
-        VQ_HIP(hipMemcpyAsync(per_snippet_host, net->slots[net->feature_slot], (size_t)n_crops * net->D * sizeof(float),
+        VQ_HIP(hipMemcpyAsync(per_snippet_host, net->slots[net->feature_slot], (size_t)n_crops * net->plan.D * sizeof(float),
                               hipMemcpyDeviceToHost, net->stream));
     if (feat_host || per_snippet_host || !crops_on_device) VQ_HIP(hipStreamSynchronize(net->stream));
     return VQ_OK;
@@ -2319,11 +1985,11 @@ int vq_tsn_feat_devptr(vq_tsn* net, void** feat_dev, void** per_snippet_dev) {
 
 int vq_tsn_read_tensor(vq_tsn* net, int32_t slot, int32_t n_crops, float* host) {
     VQ_REQUIRE(net && host, "NULL argument");
-    VQ_REQUIRE(slot >= 0 && slot < (int)net->tensors.size(), "slot out of range");
+    VQ_REQUIRE(slot >= 0 && slot < (int)net->plan.tensors.size(), "slot out of range");
     VQ_REQUIRE(n_crops > 0 && n_crops <= net->max_crops, "n_crops out of range");
     std::lock_guard<std::mutex> lk(net->mu);
     DeviceGuard g(net->device);
-    const vq_tensor_desc& t = net->tensors[slot];
+    const vq_tensor_desc& t = net->plan.tensors[slot];
     VQ_HIP(hipMemcpyAsync(host, net->slots[slot], (size_t)n_crops * t.h * t.w * t.c * sizeof(float), hipMemcpyDeviceToHost,
                           net->stream));
     VQ_HIP(hipStreamSynchronize(net->stream));
@@ -2338,7 +2004,7 @@ int vq_tsn_set_profile(vq_tsn* net, int32_t depth) {
     VQ_HIP(hipStreamSynchronize(net->stream));
     for (hipEvent_t e : net->events) (void)hipEventDestroy(e);
     net->events.clear();
-    net->events.resize((size_t)depth * 2 * net->items.size());
+    net->events.resize((size_t)depth * 2 * net->plan.items.size());
     for (hipEvent_t& e : net->events) VQ_HIP(hipEventCreate(&e));
     net->profile_depth = depth;
     net->profile_count = 0;
@@ -2357,10 +2023,10 @@ int vq_tsn_set_profile_every(vq_tsn* net, int32_t every) {
 // Share of a grouped launch's time attributed to one member, as a rough time estimate: matrix-core work of a
 // convolution (16 multiplies per tile and channel pair) at 100 TFLOP/s, bytes of a pooling layer at 4 TB/s.
 static double wino_weight(const vq_tsn* net, int li) {
-    const vq_layer_desc& L = net->layers[li];
-    const vq_tensor_desc& td = net->tensors[L.dst];
+    const vq_layer_desc& L = net->plan.layers[li];
+    const vq_tensor_desc& td = net->plan.tensors[L.dst];
     if (!is_wino(L.op)) {
-        const vq_tensor_desc& ts = net->tensors[L.src];
+        const vq_tensor_desc& ts = net->plan.tensors[L.src];
         return ((double)ts.h * ts.w + (double)td.h * td.w) * L.cin * 4.0 / 4e12;
     }
     return 2.0 * 16.0 * ((td.h + 1) / 2) * ((td.w + 1) / 2) * (double)L.cin * L.cout / 100e12;
@@ -2375,20 +2041,20 @@ int vq_tsn_set_profile_split(vq_tsn* net, int32_t unsampled_split) {
 
 int vq_tsn_layer_times(vq_tsn* net, float* ms, double* flops, int32_t n_layers) {
     VQ_REQUIRE(net && ms, "NULL argument");
-    VQ_REQUIRE(n_layers == (int)net->layers.size(), "n_layers must be %d", (int)net->layers.size());
+    VQ_REQUIRE(n_layers == (int)net->plan.layers.size(), "n_layers must be %d", (int)net->plan.layers.size());
     std::lock_guard<std::mutex> lk(net->mu);
     if (net->profile_depth == 0 || net->profile_count == 0) return fail(VQ_E_STATE, "no profiled forward has run");
     DeviceGuard g(net->device);
     VQ_HIP(hipStreamSynchronize(net->stream));
     const int sets = std::min(net->profile_count, net->profile_depth);
-    const int n_items = (int)net->items.size();
+    const int n_items = (int)net->plan.items.size();
     for (int i = 0; i < n_layers; ++i) ms[i] = 0.f;
     for (int sidx = 0; sidx < sets; ++sidx) {
         hipEvent_t* ev = net->events.data() + (size_t)sidx * (2 * n_items);
         for (int q = 0; q < n_items; ++q) {
             float t = 0.f;
             VQ_HIP(hipEventElapsedTime(&t, ev[2 * q], ev[2 * q + 1]));
-            const LaunchItem& it = net->items[q];
+            const LaunchItem& it = net->plan.items[q];
             double wsum = 0;
             for (int m : it.layers) wsum += it.kind == 1 ? wino_weight(net, m) : 1.0;
             for (int m : it.layers)                               // a grouped launch: split by matrix-core work
@@ -2397,9 +2063,9 @@ int vq_tsn_layer_times(vq_tsn* net, float* ms, double* flops, int32_t n_layers) 
     }
     if (flops) {
         for (int i = 0; i < n_layers; ++i) {
-            const vq_layer_desc& L = net->layers[i];
-            const vq_tensor_desc& td = net->tensors[L.dst];
-            flops[i] = is_conv(L.op) ? 2.0 * net->last_crops * td.h * td.w * L.cout * first_layer_k2c(net->input, L)
+            const vq_layer_desc& L = net->plan.layers[i];
+            const vq_tensor_desc& td = net->plan.tensors[L.dst];
+            flops[i] = is_conv(L.op) ? 2.0 * net->last_crops * td.h * td.w * L.cout * first_layer_k2c(net->plan.input, L)
                                           : (L.op == VQ_OP_INNER_PRODUCT ? 2.0 * net->last_crops * L.cin * L.cout : 0.0);
         }
     }
@@ -2408,9 +2074,9 @@ int vq_tsn_layer_times(vq_tsn* net, float* ms, double* flops, int32_t n_layers) 
 
 int vq_tsn_launch_items(vq_tsn* net, int32_t* item_of_layer, int32_t n_layers, int32_t* n_items) {
     VQ_REQUIRE(net && item_of_layer && n_items, "NULL argument");
-    VQ_REQUIRE(n_layers == (int)net->layers.size(), "n_layers must be %d", (int)net->layers.size());
-    for (int i = 0; i < n_layers; ++i) item_of_layer[i] = net->item_of_layer[i];
-    *n_items = (int)net->items.size();
+    VQ_REQUIRE(n_layers == (int)net->plan.layers.size(), "n_layers must be %d", (int)net->plan.layers.size());
+    for (int i = 0; i < n_layers; ++i) item_of_layer[i] = net->plan.item_of_layer[i];
+    *n_items = (int)net->plan.items.size();
     return VQ_OK;
 }
 
@@ -2472,13 +2138,13 @@ int vq_tsn_tile_tables(vq_tsn* net, int32_t* sizes, int32_t* flags, int32_t cap,
 
 int vq_tsn_get_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, int32_t* tiles, int32_t n_layers) {
     VQ_REQUIRE(net && tiles, "NULL argument");
-    VQ_REQUIRE(n_layers == (int)net->layers.size(), "n_layers must be %d", (int)net->layers.size());
+    VQ_REQUIRE(n_layers == (int)net->plan.layers.size(), "n_layers must be %d", (int)net->plan.layers.size());
     std::lock_guard<std::mutex> lk(net->mu);
     auto it = net->tuned.find(tile_key(n_crops, paired != 0));
     for (int i = 0; i < n_layers; ++i) {
         tiles[4 * i] = tiles[4 * i + 1] = tiles[4 * i + 2] = tiles[4 * i + 3] = 0;
-        if (is_wino(net->layers[i].op)) {   // 32 tiles (128 pixels) x 32 (v+1) channels, 8 channels per step
-            const int lead = net->items[net->item_of_layer[i]].layers[0];   // a grouped launch runs ONE variant: its first member's
+        if (is_wino(net->plan.layers[i].op)) {   // 32 tiles (128 pixels) x 32 (v+1) channels, 8 channels per step
+            const int lead = net->plan.items[net->plan.item_of_layer[i]].layers[0];   // a grouped launch runs ONE variant: its first member's
             const int v = it != net->tuned.end() ? it->second[lead] : 0;
             tiles[4 * i] = v >= 2 ? 64 : 128;             // pixels per unit: 16 or 32 tiles of 2 x 2
             tiles[4 * i + 1] = 32 * ((v & 1) + 1);
@@ -2486,7 +2152,7 @@ int vq_tsn_get_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, int32_t* tile
             tiles[4 * i + 3] = 2;
             continue;
         }
-        if (net->layers[i].op != VQ_OP_CONV) continue;
+        if (net->plan.layers[i].op != VQ_OP_CONV) continue;
         const int t = it != net->tuned.end() ? it->second[i] : heuristic_tile(net, i, n_crops);
         tiles[4 * i] = kTiles[t].bm;
         tiles[4 * i + 1] = kTiles[t].bn;
@@ -2508,20 +2174,20 @@ int vq_tsn_layer_tiles(vq_tsn* net, int32_t n_crops, int32_t* tiles, int32_t n_l
 
 int vq_tsn_set_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, const int32_t* tiles, int32_t n_layers) {
     VQ_REQUIRE(net && tiles, "NULL argument");
-    VQ_REQUIRE(n_layers == (int)net->layers.size(), "n_layers must be %d", (int)net->layers.size());
+    VQ_REQUIRE(n_layers == (int)net->plan.layers.size(), "n_layers must be %d", (int)net->plan.layers.size());
     VQ_REQUIRE(n_crops > 0 && n_crops <= net->max_crops, "n_crops out of range");
-    std::vector<int> choice(net->layers.size(), 0);
+    std::vector<int> choice(net->plan.layers.size(), 0);
     for (int i = 0; i < n_layers; ++i) {
-        if (is_wino(net->layers[i].op)) {
+        if (is_wino(net->plan.layers[i].op)) {
             const int bn = tiles[4 * i + 1], bk = tiles[4 * i + 2];
             const bool t16 = tiles[4 * i] == 64 && bk == 16;
             VQ_REQUIRE(tiles[4 * i + 3] == 2 && (bn == 32 || bn == 64) && (t16 || (tiles[4 * i] == 128 && bk == 8)) &&
-                           (!t16 || net->layers[i].op == VQ_OP_CONV_WINOGRAD16),
+                           (!t16 || net->plan.layers[i].op == VQ_OP_CONV_WINOGRAD16),
                        "layer %d: no Winograd variant for tile %dx%dx%d", i, tiles[4 * i], bn, bk);
             choice[i] = bn / 32 - 1 + (t16 ? 2 : 0);
             continue;
         }
-        if (net->layers[i].op != VQ_OP_CONV) continue;
+        if (net->plan.layers[i].op != VQ_OP_CONV) continue;
         const int found = tile_index(tiles[4 * i], tiles[4 * i + 1], tiles[4 * i + 2], tiles[4 * i + 3]);
         VQ_REQUIRE(found >= 0, "layer %d: no kernel for tile %dx%dx%d pipe=%d", i, tiles[4 * i], tiles[4 * i + 1], tiles[4 * i + 2],
                    tiles[4 * i + 3]);
@@ -2539,8 +2205,7 @@ int vq_tsn_set_tiles(vq_tsn* net, int32_t n_crops, int32_t paired, const int32_t
 int vq_tsn_set_layer_tiles(vq_tsn* net, int32_t n_crops, const int32_t* tiles, int32_t n_layers) {
     int rc = vq_tsn_set_tiles(net, n_crops, 0, tiles, n_layers);
     if (rc != VQ_OK) return rc;
-    int parts_sum = 0;
-    for (int v : net->split_parts) parts_sum += v;
+    const int parts_sum = net->parts_sum;
     if (net->n_split > 1 && parts_sum > 0 && n_crops % parts_sum == 0)
         for (int v : net->split_parts) {
             rc = vq_tsn_set_tiles(net, n_crops / parts_sum * v, 1, tiles, n_layers);
@@ -2551,7 +2216,7 @@ int vq_tsn_set_layer_tiles(vq_tsn* net, int32_t n_crops, const int32_t* tiles, i
 
 int vq_tsn_flops_per_crop(vq_tsn* net, double* flops) {
     VQ_REQUIRE(net && flops, "NULL argument");
-    *flops = net->flops_per_crop;
+    *flops = net->plan.flops_per_crop;
     return VQ_OK;
 }
 

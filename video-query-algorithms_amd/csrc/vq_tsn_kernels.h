@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "host/vq_tsn_plan.h"   // KPAD, FC_COLS, kMaxFusedT, kWinoMaxJobs, kWinoMaxPools
+
 namespace vq {
 
 // XCD-aware tile order: workgroups b and b+8 share an XCD (and its L2); give each XCD a contiguous run of
@@ -153,10 +155,7 @@ struct WinoJob {
 #endif
 };
 
-constexpr int kWinoMaxJobs = 4;
-// Independent layers of one graph level (the 3x3 and the first double-3x3 arm of an inception module, and the module's
-// pooling arm) as ONE launch: their workgroups fill each other's tail rounds and kernel boundaries disappear.
-constexpr int kWinoMaxPools = 2;
+// kWinoMaxJobs convolutions and kWinoMaxPools pooling layers of one graph level as ONE launch (host/vq_tsn_plan.h)
 struct WinoGroup {
     int n_jobs;
     int n_pools;         // pooling layers of the same graph level: their (few, short) workgroups come last and fill the tail
