@@ -10,6 +10,8 @@
 //   san_driver corners         the corner selection of the warped-flow step, 24 frames over host threads
 //   san_driver pool            the device-block pool's bookkeeping hammered from 8 threads
 //   san_driver plan            the TSN executor's plan checks, launch sequence, K split, batch cut on a hand-built inception level
+//   san_driver flow [<file>]   the flow handle's host arithmetic (csrc/host/vq_flow_host.cc): without a file its own checks, from 4 threads;
+//                              with one, a case per line in and a result per line out (%.17g), for tests/test_sanitizers.py to judge
 #include <dirent.h>
 
 #include <algorithm>
@@ -24,6 +26,7 @@
 
 #include "vq_block_pool.h"
 #include "vq_corners.h"
+#include "vq_flow_host.h"
 #include "vq_jpeg_host.h"
 #include "vq_tsn_plan.h"
 
@@ -566,6 +569,172 @@ static int run() {
 }
 }  // namespace plan_test
 
+// ---- the flow handle's host arithmetic (csrc/host/vq_flow_host.cc) ---------------------------------------------------------------
+namespace flow_test {
+#define FLOW_CHECK(cond)                                             \
+    do {                                                             \
+        if (!(cond)) {                                               \
+            fprintf(stderr, "flow: line %d: %s\n", __LINE__, #cond); \
+            return 30;                                               \
+        }                                                            \
+    } while (0)
+
+static void print9(const char* tag, const double* m) {
+    printf("%s", tag);
+    for (int q = 0; q < 9; ++q) printf(" %.17g", m[q]);
+    printf("\n");
+}
+
+// One case per line (numbers separated by blanks), one result line per case:
+//   pyramid h w nscales scale_step max_pairs | tiles w h pairs slots halo max_cells | chunks iterations block | invert m0..m8 |
+//   guard matches inliers m0..m8 | ransac_scratch n max_points | warp_scratch n max_corners | refit n, then n lines sx sy dx dy mask
+static int run_file(const char* path) {
+    FILE* in = fopen(path, "r");
+    if (!in) return 31;
+    char op[32];
+    int cases = 0;
+    while (fscanf(in, "%31s", op) == 1) {
+        const std::string what = op;
+        ++cases;
+        if (what == "pyramid") {
+            int h, w, ns, mp;
+            float step;
+            if (fscanf(in, "%d %d %d %f %d", &h, &w, &ns, &step, &mp) != 5) return 32;
+            const std::vector<vq::Level> lv = vq::pyramid_levels(h, w, ns, step, mp);
+            printf("pyramid %zu", lv.size());
+            for (const vq::Level& l : lv) printf(" %d %d %zu", l.h, l.w, l.off);
+            printf("\n");
+        } else if (what == "tiles") {
+            int w, h, pairs, slots, halo, cells;
+            if (fscanf(in, "%d %d %d %d %d %d", &w, &h, &pairs, &slots, &halo, &cells) != 6) return 32;
+            const vq::TileCut c = vq::fit_tiles(w, h, pairs, slots, halo, cells);
+            printf("tiles %d %d %d %d %d %d\n", c.nx, c.ny, c.tw, c.th, c.ew, c.eh);
+        } else if (what == "chunks") {
+            int iters, block;
+            if (fscanf(in, "%d %d", &iters, &block) != 2) return 32;
+            const int most = vq::max_launches(iters, block);
+            printf("chunks %d", most);
+            for (int l0 = 0; l0 < most; l0 += vq::launch_chunk(l0, most)) printf(" %d", vq::launch_chunk(l0, most));
+            printf("\n");
+        } else if (what == "invert" || what == "guard") {
+            int matches = 0, inliers = 0;
+            double m[9], o[9];
+            if (what == "guard" && fscanf(in, "%d %d", &matches, &inliers) != 2) return 32;
+            for (double& v : m)
+                if (fscanf(in, "%lf", &v) != 1) return 32;
+            if (what == "guard") {
+                const bool replaced = vq::guard_homography(matches, inliers, m);
+                print9(replaced ? "guard replaced" : "guard kept", m);
+            } else if (vq::invert3x3(m, o)) {
+                print9("invert ok", o);
+            } else {
+                printf("invert singular\n");
+            }
+        } else if (what == "ransac_scratch" || what == "warp_scratch") {
+            int n, most;
+            if (fscanf(in, "%d %d", &n, &most) != 2) return 32;
+            if (what == "ransac_scratch") {
+                const vq::RansacScratch a = vq::ransac_scratch(n, most);
+                printf("ransac_scratch %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", a.h, a.src, a.dst, a.counts, a.best, a.winner, a.mask, a.total, a.points_bytes);
+            } else {
+                const vq::WarpScratch a = vq::warp_scratch(n, most);
+                printf("warp_scratch %zu %zu %zu %zu %zu\n", a.corners, a.moved, a.counts, a.total, a.corners_bytes);
+            }
+        } else if (what == "refit") {
+            int n;
+            if (fscanf(in, "%d", &n) != 1 || n < 0) return 32;
+            std::vector<float> src((size_t)n * 2), dst((size_t)n * 2);          // exactly n points: a read past them is an overflow
+            std::vector<uint8_t> mask((size_t)n);
+            for (int i = 0; i < n; ++i) {
+                int keep;
+                if (fscanf(in, "%f %f %f %f %d", &src[2 * i], &src[2 * i + 1], &dst[2 * i], &dst[2 * i + 1], &keep) != 5) return 32;
+                mask[i] = (uint8_t)keep;
+            }
+            double H[9];
+            if (vq::refit_homography(src.data(), dst.data(), mask.data(), n, H)) print9("refit ok", H);
+            else printf("refit fail\n");
+        } else {
+            return 33;
+        }
+    }
+    fclose(in);
+    return cases ? 0 : 34;
+}
+
+// What needs no oracle: the layouts tile their blocks without overlap, the chunks add up, the guards, the refusals.
+static int self_checks() {
+    for (int n : {1, 3, 64}) {
+        for (int mp : {4, 320, 8192}) {
+            const vq::RansacScratch a = vq::ransac_scratch(n, mp);
+            FLOW_CHECK(a.h == 0 && a.src == (size_t)n * 72 && a.dst == a.src + a.points_bytes && a.counts == a.dst + a.points_bytes);
+            FLOW_CHECK(a.best == a.counts + 4u * n && a.winner == a.best + 4u * n && a.mask == a.winner + 4u * n && a.total == a.mask + (size_t)n * mp + 64);
+            FLOW_CHECK(a.src % 8 == 0 && a.dst % 4 == 0 && a.counts % 4 == 0);
+            const vq::WarpScratch b = vq::warp_scratch(n, mp);
+            FLOW_CHECK(b.corners == 0 && b.moved == b.corners_bytes && b.counts == 2 * b.corners_bytes && b.total == b.counts + 4u * n && b.counts % 4 == 0);
+        }
+    }
+    for (int iters = 1; iters <= 301; ++iters) {
+        const int most = vq::max_launches(iters, 4);
+        int sum = 0, l0 = 0;
+        for (; l0 < most; l0 += vq::launch_chunk(l0, most)) {
+            const int c = vq::launch_chunk(l0, most);
+            FLOW_CHECK(c >= 1 && c <= (l0 < 4 ? 2 : 4) && (c == (l0 < 4 ? 2 : 4) || l0 + c == most));
+            sum += c;
+        }
+        FLOW_CHECK(sum == most && l0 == most && most == (iters + 3) / 4 + 2);
+    }
+    const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, flat[9] = {1, 2, 3, 2, 4, 6, 0, 0, 1};
+    double o[9] = {7, 7, 7, 7, 7, 7, 7, 7, 7};
+    FLOW_CHECK(!vq::invert3x3(flat, o) && o[0] == 7 && o[8] == 7);
+    FLOW_CHECK(vq::invert3x3(eye, o) && memcmp(o, eye, sizeof eye) == 0);
+    for (int matches : {50, 51})
+        for (int inliers : {25, 26}) {
+            double H[9] = {1.01, 0.02, 3.0, -0.015, 0.99, -2.0, 2e-5, -1e-5, 1.0};
+            const bool replaced = vq::guard_homography(matches, inliers, H);
+            FLOW_CHECK(replaced == !(matches == 51 && inliers == 26) && (memcmp(H, eye, sizeof eye) == 0) == replaced);
+        }
+    double S[9] = {1, 2, 3, 2, 4, 6, 0, 0, 1};
+    FLOW_CHECK(vq::guard_homography(1000, 1000, S) && memcmp(S, eye, sizeof eye) == 0);
+    // refit: fewer than 4 counted points, coincident points, and a translation it must recover; the mask decides what counts
+    std::vector<float> src, dst;
+    std::vector<uint8_t> mask;
+    for (int i = 0; i < 40; ++i) {
+        src.insert(src.end(), {(float)(13 * i % 97), (float)(29 * i % 61)});
+        dst.insert(dst.end(), {src[2 * i] + 2.0f, src[2 * i + 1] - 1.0f});
+        mask.push_back(i % 2 == 0);
+        if (i % 2) dst[2 * i] += 500.0f;                                        // masked out: must not count
+    }
+    double H[9];
+    FLOW_CHECK(vq::refit_homography(src.data(), dst.data(), mask.data(), 40, H));
+    const double want[9] = {1, 0, 2, 0, 1, -1, 0, 0, 1};
+    for (int q = 0; q < 9; ++q) FLOW_CHECK(std::fabs(H[q] - want[q]) < 1e-9);
+    std::vector<uint8_t> three(40, 0);
+    three[0] = three[7] = three[39] = 1;
+    FLOW_CHECK(!vq::refit_homography(src.data(), dst.data(), three.data(), 40, H));
+    std::vector<float> same(80, 5.5f);
+    std::vector<uint8_t> all(40, 1);
+    FLOW_CHECK(!vq::refit_homography(same.data(), same.data(), all.data(), 40, H));
+    FLOW_CHECK(!vq::refit_homography(src.data(), dst.data(), mask.data(), 0, H));
+    const std::vector<vq::Level> lv = vq::pyramid_levels(16, 16, 16, 0.95f, 3);
+    FLOW_CHECK(lv.size() == 1 && lv[0].h == 16 && lv[0].w == 16 && lv[0].off == 0);
+    const vq::TileCut c = vq::fit_tiles(340, 256, 64, 512, 4, 2048);
+    FLOW_CHECK(c.nx * c.tw >= 340 && c.ny * c.th >= 256 && c.ew == c.tw + 8 && c.eh == c.th + 8 && c.ew * c.eh <= 2048);
+    return 0;
+}
+
+static int run(const char* path) {
+    if (path) return run_file(path);
+    std::vector<int> rc(4, -1);                       // pure functions: four threads must not meet anywhere
+    std::vector<std::thread> th;
+    for (int t = 0; t < 4; ++t) th.emplace_back([&rc, t] { rc[t] = self_checks(); });
+    for (auto& x : th) x.join();
+    for (int v : rc)
+        if (v) return v;
+    printf("flow: ok\n");
+    return 0;
+}
+}  // namespace flow_test
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "single" && argc > 2) return run_single(argv[2]);
@@ -575,6 +744,7 @@ int main(int argc, char** argv) {
     if (mode == "corners") return run_corners();
     if (mode == "pool") return run_pool();
     if (mode == "plan") return plan_test::run();
-    fprintf(stderr, "usage: san_driver single|batch <dir> | coef <file> | csv | corners | pool | plan\n");
+    if (mode == "flow") return flow_test::run(argc > 2 ? argv[2] : nullptr);
+    fprintf(stderr, "usage: san_driver single|batch <dir> | coef <file> | csv | corners | pool | plan | flow [<file>]\n");
     return 2;
 }

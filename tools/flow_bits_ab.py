@@ -1,4 +1,4 @@
-"""Two builds of the library on the same frame pairs: are the TV-L1 fields and iteration counts the same BITS?
+"""Two builds of the library on the same frame pairs: are the TV-L1 fields, the iteration counts and what the warped call returns the same BITS?
     python tools/flow_bits_ab.py <lib A> <lib B>
 Each library runs in a child process (VQ_AMD_LIB) and leaves its fields in an .npz; the parent compares u1 / u2 as 32-bit patterns."""
 import os
@@ -32,6 +32,13 @@ def child(out):
         r = m.flow(f0, f1, iterations=True)
         res.update({"f%d_u1" % h: r["u1"], "f%d_u2" % h: r["u2"], "f%d_it" % h: r["iters"]})
         m.close()
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _warp_inputs as wi                                            # the warped call: guards, identity fallback, both passes
+    f0, f1 = wi.guard_batch("abcd")
+    m = flow.Tvl1Flow(4, *wi.GUARD_SIZE)
+    r = m.warped(f0, f1, seed=3, images=True, fields=True)
+    res.update({"w_" + k: (v.view(np.uint64) if v.dtype == np.float64 else v) for k, v in r.items()})       # H as bit patterns
+    m.close()
     np.savez(out, **res)
 
 

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "vq_amd.h"
@@ -113,5 +114,68 @@ template <typename T>
 inline hipError_t malloc_trim(T** p, size_t bytes) {
     return malloc_trim(reinterpret_cast<void**>(p), bytes);
 }
+
+// Move-only owners of what a handle keeps on a device: device memory, pinned host memory, an event, a stream.  A handle that holds
+// them as members needs no free function; it must be destroyed with its device current.  Creation reports the HIP error (use VQ_HIP).
+template <typename T, hipError_t (*Release)(T)>
+struct Owned {
+    T v{};
+    Owned() = default;
+    Owned(Owned&& o) noexcept : v(o.v) { o.v = T{}; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            reset();
+            v = o.v;
+            o.v = T{};
+        }
+        return *this;
+    }
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { reset(); }
+    void reset() {
+        if (v) (void)Release(v);
+        v = T{};
+    }
+    operator T() const { return v; }
+    explicit operator bool() const { return v != T{}; }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDefault) { return reset(), hipEventCreateWithFlags(&v, flags); }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags = hipStreamDefault) { return reset(), hipStreamCreateWithFlags(&v, flags); }
+};
+template <typename T>
+struct PinnedMem : Owned<void*, hipHostFree> {
+    hipError_t alloc(size_t count) { return reset(), hipHostMalloc(&v, count * sizeof(T)); }
+    T* get() const { return static_cast<T*>(v); }
+    operator T*() const { return get(); }
+};
+template <typename T>
+struct DeviceMem : Owned<void*, hipFree> {
+    size_t bytes = 0;
+    DeviceMem() = default;
+    DeviceMem(DeviceMem&& o) noexcept : Owned(std::move(o)), bytes(o.bytes) { o.bytes = 0; }
+    DeviceMem& operator=(DeviceMem&& o) noexcept {
+        if (this != &o) {
+            Owned::operator=(std::move(o));
+            bytes = o.bytes;
+            o.bytes = 0;
+        }
+        return *this;
+    }
+    // at least `need` bytes (vq::malloc_trim); never shrinks, and what the block held is gone when it had to grow
+    hipError_t grow(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        reset();
+        bytes = 0;
+        const hipError_t e = malloc_trim(&v, need);
+        if (e == hipSuccess) bytes = need;
+        return e;
+    }
+    T* get() const { return static_cast<T*>(v); }
+    operator T*() const { return get(); }
+};
 
 }  // namespace vq

@@ -19,24 +19,22 @@
 // A pair that has converged (mean squared update <= epsilon^2, or the iteration cap) is switched off on the device and its
 // workgroups exit at once; the host looks at the number of live pairs every few launches only.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
 #include "vq_common.h"
 #include "host/vq_corners.h"
+#include "host/vq_flow_host.h"      // pyramid sizes, tile cuts, launch chunks, the fp64 homography algebra, scratch layouts
 
 using namespace vq;
 
 namespace {
 
 constexpr float kGradIsZero = 1e-10f;
-
-struct Level {
-    int h, w;
-    size_t off;          // float offset of this level inside a per-plane pyramid buffer (per pair: see plane())
-};
 
 // bilinear sample positions of cv::resize INTER_LINEAR (fp64 coordinate, fp32 weights -- oracle.resize_bilinear)
 __global__ void resize_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int ih, int iw, int oh, int ow, float gain) {
@@ -98,30 +96,6 @@ constexpr int kBlkIters = VQ_FLOW_BLOCK_ITERS;      // inner iterations per laun
 constexpr int kTileNC = VQ_FLOW_TILE_NC;          // cells per thread
 constexpr int kTileThreads = VQ_FLOW_TILE_THREADS;  // tvl1_tile_kernel: threads of a workgroup; two workgroups share a compute unit (128 VGPRs, 48 KB of LDS each)
 constexpr int kTileCells = kTileNC * kTileThreads;   // cells of a tile = floats of one of its six LDS planes
-// The cut of a w x h level into nx x ny tiles of ceil(w / nx) x ceil(h / ny) own pixels that costs `pairs` pairs the least on `slots`
-// workgroup slots (two per compute unit): a workgroup's time goes with its cells (halo included) in whole waves, a launch's with its rounds.
-struct TileCut {
-    int nx, ny, tw, th, ew, eh;
-};
-inline TileCut fit_tiles(int w, int h, int pairs, int slots) {
-    TileCut best{0, 0, 0, 0, 0, 0};
-    long long best_cost = -1;
-    for (int nx = 1; nx <= (w + 7) / 8; ++nx) {
-        const int tw = (w + nx - 1) / nx, ew = tw + 2 * kBlkIters;
-        for (int ny = 1; ny <= (h + 7) / 8; ++ny) {
-            const int th = (h + ny - 1) / ny, eh = th + 2 * kBlkIters;
-            if ((long long)ew * eh > kTileCells) continue;
-            const long long waves = ((long long)ew * eh + 63) / 64;
-            const long long rounds = ((long long)nx * ny * pairs + slots - 1) / slots;
-            const long long cost = rounds * waves;
-            if (best_cost < 0 || cost < best_cost) {
-                best_cost = cost;
-                best = TileCut{nx, ny, tw, th, ew, eh};
-            }
-        }
-    }
-    return best;
-}
 struct BlkSched {                 // what a pair does in one launch of the blocked form
     int mode;                     // kBlkRun: a block of n iterations; kBlkReplay: the exact n iterations of a block that ran past the stop; kBlkDone
     int src;                      // the set of planes the launch reads (it writes the other one)
@@ -130,13 +104,13 @@ struct BlkSched {                 // what a pair does in one launch of the block
 };
 constexpr int kBlkRun = 0, kBlkReplay = 1, kBlkDone = 2;
 struct alignas(128) PairState {   // own cache lines per pair: the error sums of different pairs never contend for a line
-    double err[3][kBlkIters];     // sums of squared primal updates; slot L % 3 belongs to launch L (the two-launch form uses err[0][0])
+    double err[3][kBlkIters];     // sums of squared primal updates; slot L % 3 belongs to launch L
     BlkSched blk[3];              // slot L % 3: the schedule of launch L (written by its first thread, read by launch L + 1)
-    int stop_iter;                // two-launch form: iterations >= stop_iter of the current warp do not run
+    int stop_iter;                // unused since round 5 (written by the warp kernel, never read)
     int iters;                    // inner iterations run in the current warp
     int final_set;                // the set of planes that holds the pair's fields when the warp's loop is over
 };
-constexpr int kNoStop = 0x7FFFFFFF;
+constexpr int kNoStop = 0x7FFFFFFF;      // what stop_iter is set to
 
 // Start of a warp: I1 and its gradient sampled at x + u, |grad|^2, the constant part of rho; the pair becomes active.
 __global__ void tvl1_warp_kernel(const float* __restrict__ i0, const float* __restrict__ i1, const float* __restrict__ i1x,
@@ -254,14 +228,14 @@ __device__ __forceinline__ void dual_pair2(f2& pa, f2& pb, f2 ux, f2 uy, float t
 }
 
 // ---- the blocked form: kBlkIters inner iterations per launch, the fields of a tile resident in LDS ----------------------------
-// The two-launch form streams every plane through the caches twice per inner iteration (22 floats per pixel) and needs two
-// dependent launches for it; on the coarse levels a launch is a few microseconds of work.  Here a workgroup loads a tile of
+// The two-launch form of rounds 1-2 (a primal and a dual kernel; git history) streamed every plane through the caches twice per inner
+// iteration (22 floats per pixel) in two dependent launches; on the coarse levels a launch is a few microseconds of work.  Here a workgroup loads a tile of
 // E x E pixels -- T x T of its own plus a halo of K = kBlkIters on every side -- ONCE: u1, u2, p11..p22 into LDS, the four constant
 // planes into registers (a thread owns fixed cells), runs n <= K iterations on it (primal step in place, barrier, dual step in
 // place, barrier: the primal step reads the dual variables of the left / upper neighbour, the dual step the new primal values of
 // the right / lower one, so the region whose values are exact shrinks by one pixel per iteration and side and is the tile itself
 // after K) and writes its T x T pixels to the OTHER set of planes.  Per pixel the operations and their order are those of the
-// kernels above: same bits.  Traffic per pixel and iteration: (10 x (E/T)^2 + 6) / K floats (4.8 at E = 64) instead of 22.  What the
+// two-launch form: same bits.  Traffic per pixel and iteration: (10 x (E/T)^2 + 6) / K floats (4.8 at E = 64) instead of 22.  What the
 // kernel is bound by after that is arithmetic: five correctly rounded divisions and two square roots per pixel and iteration.
 // Shapes measured on 64 pairs of 340 x 256 (two-launch form: 39.2 ms per batch): E = 56 with 256 threads and every field in LDS
 // 41.6 ms; 512 threads 41.5; own cells in registers, LDS for the neighbours' values only 36.5; the same without branches around
@@ -328,16 +302,18 @@ __device__ __forceinline__ BlkSched next_schedule(const PairState& st, int L, in
     return BlkSched{kBlkReplay, prev.src, prev.base, j + 1};
 }
 
-// The product form: tiles FITTED to the level, two workgroups per compute unit.  What round 4 measured about the kernel above: a
+// The product form: tiles FITTED to the level, two workgroups per compute unit.  What round 4 measured about the square-tile kernel of
+// round 3 (E = 64 on 1 024 threads, the last shape in the list above; git history): a
 // workgroup takes 11-12 us whether 41 or 64 of its waves' cells are live (a level cut into fewer, emptier or fuller 4 096-cell tiles
 // costs the same per round of workgroups) -- with ONE workgroup of 16 waves per unit (100 KB of LDS, 118 VGPRs) every barrier, every
 // LDS round trip and every division chain of its 4 iterations is exposed; the vector ALUs issue 45 % of the time.  So: 512 threads and
 // at most 2 048 cells per workgroup (48 KB of LDS, the same 4 cells and <= 128 VGPRs per thread), TWO workgroups per unit whose phases
 // overlap, and the level cut into nx x ny tiles of ceil(w / nx) x ceil(h / ny) own pixels chosen on the host for the fewest rounds x
-// waves (fit_tiles): inner loops 22.1 -> 20.0 ms per batch of 64 pairs (256 threads / 1 024 cells: 22.3, the halo eats it; 1 024 threads
+// waves (fit_tiles, host/vq_flow_host.cc): inner loops 22.1 -> 20.0 ms per batch of 64 pairs (256 threads / 1 024 cells: 22.3, the halo eats it; 1 024 threads
 // with fitted tiles: 22.1).  The tile's cells are dealt to the threads in row-major order (cell tid + NT k of the ew x eh tile, which is
 // also its place in the LDS planes: no padding needed, neighbours in a row are neighbours in a wave), so the cells a tile does NOT have are
-// whole waves of its last quarter.  Per pixel the arithmetic and its order are those of the kernel above: same bits (tested).
+// whole waves of its last quarter.  Per pixel the arithmetic and its order are those of the square-tile kernel: same bits (they were
+// compared until round 5; tests/test_flow_edges_gpu.py now holds every cut to the same bits).
 template <int NT, bool FAST>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VQ_FLOW_TILE_WPE, VQ_FLOW_TILE_WPE))) void tvl1_tile_kernel(BlockArgs a) {
     constexpr int K = kBlkIters, NC = kTileNC;                 // a tile has at most NC x NT cells
@@ -372,8 +348,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VQ_FLOW_TILE
     const int tid = (int)threadIdx.x;
     float cgx[NC], cgy[NC], cgr[NC], crc[NC], ru1[NC], ru2[NC], r11[NC], r12[NC], r21[NC], r22[NC];
     // what the iterations ask about a cell, decided once (lane masks): it exists; its left / upper neighbour is in the tile AND in the image
-    // (a tile-edge cell is outside the exact region, and subtracting the 0 the square kernel reads there gives the same bits as not
-    // subtracting); its right / lower one; it is one of the tile's own pixels
+    // (a tile-edge cell is outside the exact region, and subtracting a 0 there gives the same bits as not subtracting); its right / lower one; it is one of the tile's own pixels
     bool live[NC], hl[NC], hu[NC], rgt[NC], blw[NC], own[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
@@ -839,78 +814,362 @@ __global__ void ransac_homography_kernel(const float* __restrict__ src, const fl
 
 }  // namespace
 
+struct FieldSet {                          // the fields the inner iterations update, one allocation of [pair][h_l][w_l] floats each
+    DeviceMem<float> u1, u2, p11, p12, p21, p22;
+    std::array<DeviceMem<float>*, 6> planes() { return {&u1, &u2, &p11, &p12, &p21, &p22}; }      // in the order of BlockArgs::set
+    std::array<float*, 6> pointers() const { return {u1, u2, p11, p12, p21, p22}; }
+};
+
+// One mutex serialises the exported calls; the *_locked functions below assume it is held.  The helper thread that vq_flow_warped
+// starts while it holds the lock (good_features_locked on side_stream, beside the first flow pass) touches only corner_plane,
+// frame_max, peaks_host and -- reading -- frames_dev[0] and the constants of the first block; the flow pass touches none of those.
 struct vq_flow {
-    std::recursive_mutex mu;               // recursive: vq_flow_warped holds it across the calls it is composed of
+    std::mutex mu;
     int device = 0, max_pairs = 0, h = 0, w = 0;
     vq_tvl1_params prm;
     std::vector<Level> levels;
-    size_t pyr_floats = 0;                 // floats of one pair's pyramid
-    float *pyr0 = nullptr, *pyr1 = nullptr;      // [level][pair][h_l][w_l]
-    float* plane[12] = {nullptr};          // i1x, i1y, i1wx, i1wy, grad, rho_c, u1, u2 / p11, p12, p21, p22 at the current level ...
-    float* alt[6] = {nullptr};             // second set of u1, u2, p11, p12, p21, p22 (the one-launch iteration ping-pongs between the sets)
-    float* tmp[2] = {nullptr, nullptr};    // flow of the coarser level while it is resized
-    uint8_t* frames_dev[2] = {nullptr, nullptr};
-    uint8_t* img_dev[2] = {nullptr, nullptr};
-    PairState* st = nullptr;
-    int* n_active = nullptr;
-    int* iters_log = nullptr;              // [levels][warps][pairs]
-    int* live_host = nullptr;              // pinned: [0], [1] the two most recent polls of n_active (two-launch form); [2] the blocked form's live flag
-    int* live_flag_dev = nullptr;          // live_host + 2 as the device sees it
-    hipEvent_t poll_ev[2] = {nullptr, nullptr};
-    double* hinv_dev = nullptr;
-    unsigned* frame_max = nullptr;         // [max_pairs] bit pattern of the largest corner strength of a frame
-    void* match_dev = nullptr;             // RANSAC scratch (matches, winners, masks), grown on demand
-    size_t match_bytes = 0;
-    float* peaks_host = nullptr;           // pinned: the corner-peak maps of a batch on their way to the host's selection
-    size_t peaks_host_floats = 0;
-    void* warp_dev = nullptr;              // vq_flow_warped: corners, moved corners, counts
-    size_t warp_bytes = 0;
-    float* corner_plane[2] = {nullptr, nullptr};   // corner strength / peak maps: their own memory, so that the corner search of a
-    hipStream_t side_stream = nullptr;             // batch can run (on this stream) beside its first flow pass
-    hipEvent_t side_ev = nullptr;
-    std::vector<hipEvent_t> loop_ev;       // a start / stop pair around the inner loop of every (level, warp) of a call
-    double last_inner_ms = 0.0;            // device time of those loops in the last vq_flow_tvl1 call (sum of the pairs)
-    int last_iter_launches = 0;            // iteration-kernel launches of the last call
     bool exact_math = true;                // VQ_FLOW_FAST=1 at creation switches to hardware reciprocals / roots in the inner iterations (see tv_rcp)
     int n_cus = 256;                       // compute units of the device (tile fitting)
+    DeviceMem<float> pyr0, pyr1;           // [level][pair][h_l][w_l]
+    DeviceMem<float> i1x, i1y, i1wx, i1wy, grad, rho_c;      // at the current level: gradient of I1, the same warped, |grad|^2, the constant part of rho
+    FieldSet set[2];                       // the flow lives in set[0] between the loops; a launch of the iteration reads one set and writes the other
+    DeviceMem<float> tmp[2];               // flow of the coarser level while it is resized
+    DeviceMem<uint8_t> frames_dev[2], img_dev[2];
+    DeviceMem<PairState> st;
+    DeviceMem<int> n_active;
+    DeviceMem<int> iters_log;              // [levels][warps][pairs]
+    PinnedMem<int> live_host;              // 1 while a pair of the current warp is live; the kernels clear it, the host reads it behind poll_ev
+    int* live_flag_dev = nullptr;          // live_host as the device sees it
+    Event poll_ev[2];
+    std::vector<Event> loop_ev;            // a start / stop pair around the inner loop of every (level, warp) of a call
+    DeviceMem<double> hinv_dev;
+    DeviceMem<unsigned> frame_max;         // [max_pairs] bit pattern of the largest corner strength of a frame
+    DeviceMem<char> match_dev;             // RANSAC scratch (ransac_scratch), grown on demand
+    PinnedMem<float> peaks_host;           // the corner-peak maps of a batch on their way to the host's selection; created by the first corner search
+    DeviceMem<char> warp_dev;              // vq_flow_warped: corners, moved corners, counts (warp_scratch), grown on demand
+    DeviceMem<float> corner_plane[2];      // corner strength / peak maps: their own memory, so that the corner search of a batch can run
+    Stream side_stream;                    // (on this stream) beside its first flow pass; created by the first vq_flow_warped
+    Event side_ev;
+    double last_inner_ms = 0.0;            // device time of the inner loops in the last flow pass (sum over loop_ev's pairs)
+    int last_iter_launches = 0;            // iteration-kernel launches of the last flow pass
 };
 
-static void flow_free(vq_flow* f) {
-    for (float* p : f->plane)
-        if (p) (void)hipFree(p);
-    for (float* p : f->tmp)
-        if (p) (void)hipFree(p);
-    for (float* p : f->alt)
-        if (p) (void)hipFree(p);
-    if (f->pyr0) (void)hipFree(f->pyr0);
-    if (f->pyr1) (void)hipFree(f->pyr1);
-    for (int k = 0; k < 2; ++k) {
-        if (f->frames_dev[k]) (void)hipFree(f->frames_dev[k]);
-        if (f->img_dev[k]) (void)hipFree(f->img_dev[k]);
-    }
-    if (f->st) (void)hipFree(f->st);
-    if (f->n_active) (void)hipFree(f->n_active);
-    if (f->iters_log) (void)hipFree(f->iters_log);
-    if (f->live_host) (void)hipHostFree(f->live_host);
-    for (hipEvent_t e : f->poll_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : f->loop_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (f->hinv_dev) (void)hipFree(f->hinv_dev);
-    if (f->frame_max) (void)hipFree(f->frame_max);
-    if (f->match_dev) (void)hipFree(f->match_dev);
-    if (f->warp_dev) (void)hipFree(f->warp_dev);
-    if (f->peaks_host) (void)hipHostFree(f->peaks_host);
-    for (float* p : f->corner_plane)
-        if (p) (void)hipFree(p);
-    if (f->side_stream) (void)hipStreamDestroy(f->side_stream);
-    if (f->side_ev) (void)hipEventDestroy(f->side_ev);
+namespace {
+
+// The cut of level L for a batch of n_pairs pairs: the flow pass runs it, vq_flow_tile_cut reports it.
+TileCut level_cut(const vq_flow& f, const Level& L, int n_pairs) {
+    return fit_tiles(L.w, L.h, n_pairs, std::max(1, VQ_FLOW_TILE_WPE * 256 / kTileThreads) * f.n_cus, kBlkIters, kTileCells);
 }
 
-// The cut of level L for a batch of n_pairs pairs: vq_flow_tvl1 runs it, vq_flow_tile_cut reports it.
-static TileCut level_cut(const vq_flow* f, const Level& L, int n_pairs) {
-    return fit_tiles(L.w, L.h, n_pairs, std::max(1, VQ_FLOW_TILE_WPE * 256 / kTileThreads) * f->n_cus);
+// Level 0 of the pyramids: the frames as floats (0..255); the second frame optionally through a homography first.
+int frames_to_level0(const vq_flow& f, const uint8_t* d0, const uint8_t* d1, int n_pairs, const double* homographies_host, hipStream_t st) {
+    const int64_t full = (int64_t)n_pairs * f.h * f.w;
+    u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d0, f.pyr0, full);
+    if (homographies_host) {
+        std::vector<double> inv((size_t)n_pairs * 9);
+        for (int p = 0; p < n_pairs; ++p)
+            VQ_REQUIRE(invert3x3(homographies_host + (size_t)p * 9, inv.data() + (size_t)p * 9), "homography %d is singular", p);
+        VQ_HIP(hipMemcpyAsync(f.hinv_dev, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        VQ_HIP(hipStreamSynchronize(st));           // `inv` leaves scope
+        u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d1, f.tmp[0], full);
+        homography_warp_kernel<<<cdiv(full, 256), 256, 0, st>>>(f.tmp[0], f.pyr1, f.hinv_dev, n_pairs, f.h, f.w);
+    } else {
+        u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d1, f.pyr1, full);
+    }
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
 }
+
+int build_pyramids(const vq_flow& f, int n_pairs, hipStream_t st) {
+    for (size_t s = 1; s < f.levels.size(); ++s) {
+        const Level &a = f.levels[s - 1], &b = f.levels[s];
+        const int64_t tot = (int64_t)n_pairs * b.h * b.w;
+        resize_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f.pyr0 + a.off, f.pyr0 + b.off, n_pairs, a.h, a.w, b.h, b.w, 1.0f);
+        resize_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f.pyr1 + a.off, f.pyr1 + b.off, n_pairs, a.h, a.w, b.h, b.w, 1.0f);
+    }
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
+}
+
+int gradient_and_zeroed_duals(const vq_flow& f, const Level& L, int n_pairs, hipStream_t st) {
+    const int64_t tot = (int64_t)n_pairs * L.h * L.w;
+    gradient_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f.pyr1 + L.off, f.i1x, f.i1y, n_pairs, L.h, L.w);
+    const FieldSet& s0 = f.set[0];
+    for (float* p : {s0.p11.get(), s0.p12.get(), s0.p21.get(), s0.p22.get()}) VQ_HIP(hipMemsetAsync(p, 0, (size_t)tot * sizeof(float), st));
+    return VQ_OK;
+}
+
+// Everything a launch of the iteration kernel is told about a level, except the launch's number L.
+BlockArgs block_args(const vq_flow& f, const Level& L, const TileCut& cut) {
+    const vq_tvl1_params& P = f.prm;
+    BlockArgs ba;
+    ba.i1wx = f.i1wx;
+    ba.i1wy = f.i1wy;
+    ba.grad = f.grad;
+    ba.rho_c = f.rho_c;
+    for (int k = 0; k < 2; ++k) {
+        const std::array<float*, 6> planes = f.set[k].pointers();
+        std::copy(planes.begin(), planes.end(), ba.set[k]);
+    }
+    ba.st = f.st;
+    ba.n_active = f.n_active;
+    ba.live_flag = f.live_flag_dev;
+    ba.h = L.h;
+    ba.w = L.w;
+    ba.L = 0;
+    ba.max_iters = P.iterations;
+    ba.l_t = (float)((double)P.lambda * (double)P.theta);      // oracle: float32(lam * theta) on the float32 parameters
+    ba.theta = P.theta;
+    ba.taut = (float)((double)P.tau / (double)P.theta);
+    ba.eps2 = (double)P.epsilon * (double)P.epsilon;           // oracle: float(float32(epsilon)) ** 2
+    ba.ew = cut.ew;
+    ba.eh = cut.eh;
+    ba.tw = cut.tw;
+    ba.th = cut.th;
+    ba.inv_ew = 1.0f / (float)cut.ew;
+    return ba;
+}
+
+// The warps of level L (loop_slot: the level's place in coarse-to-fine order): per warp the warp kernel, the inner loop between two
+// events of loop_ev, the settle kernel and, when asked for, the iteration log.
+int warp_loop(vq_flow& f, const Level& L, int loop_slot, int n_pairs, bool log_iters, hipStream_t st, int& iter_launches) {
+    const vq_tvl1_params& P = f.prm;
+    const int64_t tot = (int64_t)n_pairs * L.h * L.w;
+    const TileCut cut = level_cut(f, L, n_pairs);
+    const dim3 tgrid((unsigned)cut.nx, (unsigned)cut.ny, (unsigned)n_pairs);
+    const size_t tlds = (size_t)6 * cut.eh * cut.ew * sizeof(float);
+    BlockArgs ba = block_args(f, L, cut);
+    SettleArgs sa;
+    for (int q = 0; q < 6; ++q) {
+        sa.set0[q] = ba.set[0][q];
+        sa.set1[q] = ba.set[1][q];
+    }
+    const FieldSet& s0 = f.set[0];
+    const int launches = max_launches(P.iterations, kBlkIters);
+    for (int wp = 0; wp < P.warps; ++wp) {
+        tvl1_warp_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f.pyr0 + L.off, f.pyr1 + L.off, f.i1x, f.i1y, s0.u1, s0.u2, f.i1wx, f.i1wy, f.grad, f.rho_c, f.st,
+                                                         f.n_active, f.live_flag_dev, n_pairs, L.h, L.w);
+        // Converged pairs switch themselves off on the device (their workgroups exit at once).  The host polls the live flag
+        // once per chunk of launches, one chunk BEHIND what it has queued: the stream never runs dry while
+        // the host waits, at the price of at most one chunk of empty launches after the last pair has stopped.
+        const size_t ev_i = 2 * ((size_t)loop_slot * P.warps + wp);
+        VQ_HIP(hipEventRecord(f.loop_ev[ev_i], st));
+        int chunk_no = 0;
+        for (int l0 = 0; l0 < launches; ++chunk_no) {
+            const int chunk = launch_chunk(l0, launches);
+            for (int k = 0; k < chunk; ++k) {
+                ba.L = l0 + k;
+                if (f.exact_math) tvl1_tile_kernel<kTileThreads, false><<<tgrid, kTileThreads, tlds, st>>>(ba);
+                else tvl1_tile_kernel<kTileThreads, true><<<tgrid, kTileThreads, tlds, st>>>(ba);
+                ++iter_launches;
+            }
+            VQ_CHECK_LAUNCH();
+            l0 += chunk;
+            VQ_HIP(hipEventRecord(f.poll_ev[chunk_no & 1], st));
+            if (chunk_no > 0) {
+                VQ_HIP(hipEventSynchronize(f.poll_ev[(chunk_no - 1) & 1]));
+                // the kernels clear the flag in host memory when the last pair stops: no copy in the stream
+                if (__atomic_load_n(const_cast<volatile int*>(f.live_host.get()), __ATOMIC_ACQUIRE) == 0) break;
+            }
+        }
+        VQ_HIP(hipEventRecord(f.loop_ev[ev_i + 1], st));
+        tvl1_settle_kernel<<<dim3((unsigned)std::min(cdiv((int64_t)L.h * L.w, 256), 32), (unsigned)n_pairs), 256, 0, st>>>(f.st, sa, L.h * L.w);
+        VQ_CHECK_LAUNCH();
+        if (log_iters) log_iters_kernel<<<cdiv(n_pairs, 256), 256, 0, st>>>(f.st, f.iters_log + ((size_t)loop_slot * P.warps + wp) * n_pairs, n_pairs);
+    }
+    return VQ_OK;
+}
+
+// From level L to the next finer level F: bilinear resize, flow values divided by the scale step.
+int upsample_flow(const vq_flow& f, const Level& L, const Level& F, int n_pairs, hipStream_t st) {
+    const int64_t tot = (int64_t)n_pairs * L.h * L.w, ftot = (int64_t)n_pairs * F.h * F.w;
+    const float inv = (float)(1.0 / (double)f.prm.scale_step);
+    const FieldSet& s0 = f.set[0];
+    VQ_HIP(hipMemcpyAsync(f.tmp[0], s0.u1, (size_t)tot * sizeof(float), hipMemcpyDeviceToDevice, st));
+    VQ_HIP(hipMemcpyAsync(f.tmp[1], s0.u2, (size_t)tot * sizeof(float), hipMemcpyDeviceToDevice, st));
+    resize_kernel<<<cdiv(ftot, 256), 256, 0, st>>>(f.tmp[0], s0.u1, n_pairs, L.h, L.w, F.h, F.w, inv);
+    resize_kernel<<<cdiv(ftot, 256), 256, 0, st>>>(f.tmp[1], s0.u2, n_pairs, L.h, L.w, F.h, F.w, inv);
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
+}
+
+// What the caller asked for goes to the host; then the call's device time of the inner loops is summed from loop_ev.
+int read_back(vq_flow& f, int n_pairs, float* u1_host, float* u2_host, uint8_t* flow_x_host, uint8_t* flow_y_host, int32_t* iters_host, hipStream_t st) {
+    const int64_t full = (int64_t)n_pairs * f.h * f.w;
+    const FieldSet& s0 = f.set[0];
+    if (iters_host)
+        VQ_HIP(hipMemcpyAsync(iters_host, f.iters_log, f.levels.size() * f.prm.warps * n_pairs * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (u1_host) VQ_HIP(hipMemcpyAsync(u1_host, s0.u1, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (u2_host) VQ_HIP(hipMemcpyAsync(u2_host, s0.u2, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (flow_x_host || flow_y_host) {
+        flow_to_image_kernel<<<cdiv(full, 256), 256, 0, st>>>(s0.u1, f.img_dev[0], full, f.prm.bound);
+        flow_to_image_kernel<<<cdiv(full, 256), 256, 0, st>>>(s0.u2, f.img_dev[1], full, f.prm.bound);
+        VQ_CHECK_LAUNCH();
+        if (flow_x_host) VQ_HIP(hipMemcpyAsync(flow_x_host, f.img_dev[0], (size_t)full, hipMemcpyDeviceToHost, st));
+        if (flow_y_host) VQ_HIP(hipMemcpyAsync(flow_y_host, f.img_dev[1], (size_t)full, hipMemcpyDeviceToHost, st));
+    }
+    VQ_HIP(hipStreamSynchronize(st));
+    f.last_inner_ms = 0.0;
+    for (size_t q = 0; q + 1 < f.loop_ev.size(); q += 2) {
+        float ms = 0.f;
+        VQ_HIP(hipEventElapsedTime(&ms, f.loop_ev[q], f.loop_ev[q + 1]));
+        f.last_inner_ms += ms;
+    }
+    return VQ_OK;
+}
+
+// One flow pass over n_pairs pairs: coarse to fine, per level the gradient, the warps and the way up.
+int tvl1_locked(vq_flow& f, const uint8_t* frames0, const uint8_t* frames1, bool frames_on_device, int n_pairs, const double* homographies_host,
+                float* u1_host, float* u2_host, uint8_t* flow_x_host, uint8_t* flow_y_host, int32_t* iters_host, hipStream_t st) {
+    const size_t full = (size_t)n_pairs * f.h * f.w;
+    if (!frames_on_device) {
+        VQ_HIP(hipMemcpyAsync(f.frames_dev[0], frames0, full, hipMemcpyHostToDevice, st));
+        VQ_HIP(hipMemcpyAsync(f.frames_dev[1], frames1, full, hipMemcpyHostToDevice, st));
+        frames0 = f.frames_dev[0];
+        frames1 = f.frames_dev[1];
+    }
+    int rc = frames_to_level0(f, frames0, frames1, n_pairs, homographies_host, st);
+    if (rc == VQ_OK) rc = build_pyramids(f, n_pairs, st);
+    if (rc != VQ_OK) return rc;
+    const int nl = (int)f.levels.size();
+    const size_t coarsest = (size_t)n_pairs * f.levels[nl - 1].h * f.levels[nl - 1].w;
+    VQ_HIP(hipMemsetAsync(f.set[0].u1, 0, coarsest * sizeof(float), st));
+    VQ_HIP(hipMemsetAsync(f.set[0].u2, 0, coarsest * sizeof(float), st));
+    int iter_launches = 0;
+    for (int s = nl - 1; s >= 0; --s) {
+        const Level& L = f.levels[s];
+        rc = gradient_and_zeroed_duals(f, L, n_pairs, st);
+        if (rc == VQ_OK) rc = warp_loop(f, L, nl - 1 - s, n_pairs, iters_host != nullptr, st, iter_launches);
+        if (rc == VQ_OK && s > 0) rc = upsample_flow(f, L, f.levels[s - 1], n_pairs, st);
+        if (rc != VQ_OK) return rc;
+    }
+    rc = read_back(f, n_pairs, u1_host, u2_host, flow_x_host, flow_y_host, iters_host, st);
+    if (rc != VQ_OK) return rc;
+    f.last_iter_launches = iter_launches;
+    return VQ_OK;
+}
+
+// The corner search of n frames already in device memory, on `st`.  Touches only the corner planes, frame_max and the pinned peak
+// buffer (see vq_flow): vq_flow_warped runs it on a thread of its own beside the first flow pass.
+int good_features_locked(vq_flow& f, const uint8_t* d, int n, int max_corners, float quality, float min_distance, float* corners_host,
+                         int32_t* counts_host, hipStream_t st) {
+    const int h = f.h, w = f.w;
+    const int64_t full = (int64_t)n * h * w;
+    const size_t batch_floats = (size_t)f.max_pairs * h * w;
+    for (DeviceMem<float>& corner_plane : f.corner_plane) VQ_HIP(corner_plane.grow(batch_floats * sizeof(float)));
+    float *strength = f.corner_plane[0], *peaks = f.corner_plane[1];
+    VQ_HIP(hipMemsetAsync(f.frame_max, 0, (size_t)n * sizeof(unsigned), st));
+    corner_strength_kernel<<<dim3((unsigned)cdiv((int64_t)h * w, 256), (unsigned)n), 256, 0, st>>>(d, strength, f.frame_max, n, h, w);
+    corner_peaks_kernel<<<cdiv(full, 256), 256, 0, st>>>(strength, peaks, n, h, w);
+    VQ_CHECK_LAUNCH();
+    if (!f.peaks_host) VQ_HIP(f.peaks_host.alloc(batch_floats));          // pinned, once: 22 MB per batch of 64 frames come back through it
+    std::vector<unsigned> top((size_t)n);
+    VQ_HIP(hipMemcpyAsync(f.peaks_host, peaks, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipMemcpyAsync(top.data(), f.frame_max, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipStreamSynchronize(st));
+    // the selection is per frame and sequential inside a frame: frames are spread over host threads (csrc/host/vq_corners.cc)
+    vq::select_corners_batch(f.peaks_host, top.data(), n, h, w, max_corners, quality, min_distance, corners_host, counts_host);
+    return VQ_OK;
+}
+
+int ransac_homography_locked(vq_flow& f, const float* src_host, const float* dst_host, const int32_t* counts_host, int n, int max_points,
+                             float threshold, int hypotheses, uint32_t seed, bool refit, double* h_host, int32_t* inliers_host, int32_t* winner_host,
+                             uint8_t* mask_host, hipStream_t st) {
+    const RansacScratch at = ransac_scratch(n, max_points);
+    VQ_HIP(f.match_dev.grow(at.total));
+    char* base = f.match_dev;
+    double* h_dev = (double*)(base + at.h);
+    float *src_dev = (float*)(base + at.src), *dst_dev = (float*)(base + at.dst);
+    int *cnt_dev = (int*)(base + at.counts), *best_dev = (int*)(base + at.best), *win_dev = (int*)(base + at.winner);
+    uint8_t* mask_dev = (uint8_t*)(base + at.mask);
+    VQ_HIP(hipMemcpyAsync(src_dev, src_host, at.points_bytes, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(dst_dev, dst_host, at.points_bytes, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(cnt_dev, counts_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    const size_t lds = (size_t)max_points * 4 * sizeof(float);
+    VQ_DYN_LDS(ransac_homography_kernel, 8192 * 16);
+    ransac_homography_kernel<<<n, 256, lds, st>>>(src_dev, dst_dev, cnt_dev, max_points, hypotheses, seed, (double)threshold * (double)threshold,
+                                                  h_dev, best_dev, win_dev, mask_dev);
+    VQ_CHECK_LAUNCH();
+    std::vector<uint8_t> mask((size_t)n * max_points);
+    std::vector<int> win((size_t)n);
+    VQ_HIP(hipMemcpyAsync(h_host, h_dev, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipMemcpyAsync(inliers_host, best_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipMemcpyAsync(win.data(), win_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipMemcpyAsync(mask.data(), mask_dev, mask.size(), hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipStreamSynchronize(st));
+    if (refit)
+        for (int p = 0; p < n; ++p)
+            if (inliers_host[p] >= 4) {
+                double H[9];
+                if (refit_homography(src_host + (size_t)p * max_points * 2, dst_host + (size_t)p * max_points * 2, mask.data() + (size_t)p * max_points,
+                                     counts_host[p], H))
+                    memcpy(h_host + (size_t)p * 9, H, sizeof H);
+            }
+    if (winner_host) memcpy(winner_host, win.data(), (size_t)n * sizeof(int));
+    if (mask_host) memcpy(mask_host, mask.data(), mask.size());
+    return VQ_OK;
+}
+
+// The warped flow of extract_warp_gpu (flow-match branch), the frames uploaded once and the first-pass fields never leaving the
+// device: TV-L1 -> Shi-Tomasi corners of the first frame (selection on host threads) -> the corners moved by the flow (device) -> RANSAC
+// homography (device kernel + host refit) with dense_flow's guards (guard_homography) -> the second frame warped back by it -> TV-L1 again.
+// tsn/flow.py:Tvl1Flow.warped_steps is the same sequence call by call (tests compare the two).
+int warped_locked(vq_flow& f, const uint8_t* frames0, const uint8_t* frames1, int n, uint32_t seed, int hypotheses, float* u1_host, float* u2_host,
+                  uint8_t* flow_x_host, uint8_t* flow_y_host, double* h_host, int32_t* matches_host, int32_t* inliers_host, hipStream_t st) {
+    constexpr int kMaxCorners = 1000;
+    const int h = f.h, w = f.w;
+    std::vector<float> corners((size_t)n * kMaxCorners * 2), moved((size_t)n * kMaxCorners * 2);
+    std::vector<int32_t> counts((size_t)n), inl((size_t)n);
+    // The corners depend on the first frames alone: their search (two small kernels, 22 MB of peak maps to the host, the selection on
+    // host threads) runs on a stream and a thread of its own beside the first flow pass instead of between the two passes.
+    if (!f.side_stream) VQ_HIP(f.side_stream.create(hipStreamNonBlocking));
+    if (!f.side_ev) VQ_HIP(f.side_ev.create(hipEventDisableTiming));
+    const size_t full = (size_t)n * h * w;
+    VQ_HIP(hipMemcpyAsync(f.frames_dev[0], frames0, full, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipEventRecord(f.side_ev, st));
+    VQ_HIP(hipMemcpyAsync(f.frames_dev[1], frames1, full, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipStreamWaitEvent(f.side_stream, f.side_ev, 0));
+    int rc_corners = VQ_OK;
+    std::string err_corners;
+    std::thread side([&] {
+        DeviceGuard gs(f.device);
+        rc_corners = good_features_locked(f, f.frames_dev[0], n, kMaxCorners, 0.001f, 3.0f, corners.data(), counts.data(), f.side_stream);
+        if (rc_corners != VQ_OK) err_corners = last_error_ref();        // the message lives in the helper thread's slot
+    });
+    int rc = tvl1_locked(f, f.frames_dev[0], f.frames_dev[1], true, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+    side.join();
+    if (rc != VQ_OK) return rc;
+    if (rc_corners != VQ_OK) return fail(rc_corners, "%s", err_corners.c_str());
+    const WarpScratch at = warp_scratch(n, kMaxCorners);
+    VQ_HIP(f.warp_dev.grow(at.total));
+    float *c_dev = (float*)(f.warp_dev + at.corners), *m_dev = (float*)(f.warp_dev + at.moved);
+    int* n_dev = (int*)(f.warp_dev + at.counts);
+    VQ_HIP(hipMemcpyAsync(c_dev, corners.data(), at.corners_bytes, hipMemcpyHostToDevice, st));
+    VQ_HIP(hipMemcpyAsync(n_dev, counts.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    move_corners_kernel<<<cdiv((int64_t)n * kMaxCorners, 256), 256, 0, st>>>(c_dev, n_dev, f.set[0].u1, f.set[0].u2, m_dev, n, kMaxCorners, h, w);
+    VQ_CHECK_LAUNCH();
+    VQ_HIP(hipMemcpyAsync(moved.data(), m_dev, at.corners_bytes, hipMemcpyDeviceToHost, st));
+    VQ_HIP(hipStreamSynchronize(st));
+    std::vector<double> H((size_t)n * 9), Hinv((size_t)n * 9);
+    // vq_flow_ransac_homography's own check, made where the RANSAC step begins: the first pass has run and left its timing by then
+    // (the number of matches and the threshold are fixed here, so `hypotheses` is all it can refuse)
+    VQ_REQUIRE(hypotheses > 0 && hypotheses <= (1 << 20), "RANSAC parameters out of range (at most 8192 matches per pair)");
+    rc = ransac_homography_locked(f, corners.data(), moved.data(), counts.data(), n, kMaxCorners, 1.0f, hypotheses, seed, true, H.data(), inl.data(), nullptr,
+                                  nullptr, st);
+    if (rc != VQ_OK) return rc;
+    // the flow pass with homographies G shows the second frame as out(x) = frame1(G^-1 x); the compensated frame is frame1(H x): G = H^-1,
+    // which the pass inverts again -- as Tvl1Flow.warped_steps does through numpy.linalg.inv (handing it H itself would change bits)
+    for (int p = 0; p < n; ++p) {
+        guard_homography(counts[p], inl[p], H.data() + (size_t)p * 9);
+        invert3x3(H.data() + (size_t)p * 9, Hinv.data() + (size_t)p * 9);          // cannot fail behind the guard
+    }
+    if (h_host) memcpy(h_host, H.data(), H.size() * sizeof(double));
+    if (matches_host) memcpy(matches_host, counts.data(), (size_t)n * sizeof(int32_t));
+    if (inliers_host) memcpy(inliers_host, inl.data(), (size_t)n * sizeof(int32_t));
+    return tvl1_locked(f, f.frames_dev[0], f.frames_dev[1], true, n, Hinv.data(), u1_host, u2_host, flow_x_host, flow_y_host, nullptr, st);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -942,80 +1201,53 @@ int vq_flow_create(int32_t max_pairs, int32_t h, int32_t w, const vq_tvl1_params
     VQ_HIP(hipGetDeviceCount(&ndev));
     VQ_REQUIRE(device >= 0 && device < ndev, "device %d out of range (%d visible)", device, ndev);
     DeviceGuard g(device);
-    auto* f = new vq_flow;
+    auto f = std::make_unique<vq_flow>();          // an early return below destroys it, and what it owns, with `device` still current
     f->device = device;
     f->max_pairs = max_pairs;
     f->h = h;
     f->w = w;
     f->prm = prm;
-    {
-        const char* e3 = getenv("VQ_FLOW_FAST");
-        f->exact_math = !(e3 && *e3 == '1');
-        hipDeviceProp_t prop;
-        VQ_HIP(hipGetDeviceProperties(&prop, device));
-        f->n_cus = std::max(1, prop.multiProcessorCount);
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tvl1_tile_kernel<kTileThreads, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   6 * kTileCells * (int)sizeof(float)));
-        VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tvl1_tile_kernel<kTileThreads, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   6 * kTileCells * (int)sizeof(float)));
-    }
-    // level sizes, finest first: round(previous * scale_step), stop before 16 pixels (oracle.pyramid_sizes)
-    size_t off = 0;
-    int lh = h, lw = w;
-    for (int s = 0; s < prm.nscales; ++s) {
-        if (s > 0) {
-            const int nh = (int)std::nearbyint((double)lh * (double)prm.scale_step), nw = (int)std::nearbyint((double)lw * (double)prm.scale_step);
-            if (nh < 16 || nw < 16) break;
-            lh = nh;
-            lw = nw;
-        }
-        f->levels.push_back(Level{lh, lw, off});
-        off += (size_t)max_pairs * lh * lw;
-    }
-    f->pyr_floats = off;
-    auto bail = [&](const char* what, hipError_t e) {
-        flow_free(f);
-        delete f;
-        return fail(e == hipErrorOutOfMemory ? VQ_E_NOMEM : VQ_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    };
-    const size_t full = (size_t)max_pairs * h * w;
-    hipError_t e;
-    if ((e = vq::malloc_trim((void**)&f->pyr0, off * sizeof(float))) != hipSuccess) return bail("vq::malloc_trim(pyramid)", e);
-    if ((e = vq::malloc_trim((void**)&f->pyr1, off * sizeof(float))) != hipSuccess) return bail("vq::malloc_trim(pyramid)", e);
-    for (float*& p : f->plane)
-        if ((e = vq::malloc_trim((void**)&p, full * sizeof(float))) != hipSuccess) return bail("vq::malloc_trim(plane)", e);
-    for (float*& p : f->tmp)
-        if ((e = vq::malloc_trim((void**)&p, full * sizeof(float))) != hipSuccess) return bail("vq::malloc_trim(plane)", e);
-    for (float*& p : f->alt)
-        if ((e = vq::malloc_trim((void**)&p, full * sizeof(float))) != hipSuccess) return bail("vq::malloc_trim(plane)", e);
+    const char* fast = getenv("VQ_FLOW_FAST");
+    f->exact_math = !(fast && *fast == '1');
+    hipDeviceProp_t prop;
+    VQ_HIP(hipGetDeviceProperties(&prop, device));
+    f->n_cus = std::max(1, prop.multiProcessorCount);
+    VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tvl1_tile_kernel<kTileThreads, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               6 * kTileCells * (int)sizeof(float)));
+    VQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tvl1_tile_kernel<kTileThreads, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               6 * kTileCells * (int)sizeof(float)));
+    f->levels = pyramid_levels(h, w, prm.nscales, prm.scale_step, max_pairs);
+    const Level& coarsest = f->levels.back();
+    const size_t pyramid = (coarsest.off + (size_t)max_pairs * coarsest.h * coarsest.w) * sizeof(float);
+    const size_t full = (size_t)max_pairs * h * w, plane = full * sizeof(float);
+    VQ_HIP(f->pyr0.grow(pyramid));
+    VQ_HIP(f->pyr1.grow(pyramid));
+    for (DeviceMem<float>* image_plane : {&f->i1x, &f->i1y, &f->i1wx, &f->i1wy, &f->grad, &f->rho_c}) VQ_HIP(image_plane->grow(plane));
+    for (DeviceMem<float>* set0_plane : f->set[0].planes()) VQ_HIP(set0_plane->grow(plane));
+    for (DeviceMem<float>& tmp_plane : f->tmp) VQ_HIP(tmp_plane.grow(plane));
+    for (DeviceMem<float>* set1_plane : f->set[1].planes()) VQ_HIP(set1_plane->grow(plane));
     for (int k = 0; k < 2; ++k) {
-        if ((e = vq::malloc_trim((void**)&f->frames_dev[k], full)) != hipSuccess) return bail("vq::malloc_trim(frames)", e);
-        if ((e = vq::malloc_trim((void**)&f->img_dev[k], full)) != hipSuccess) return bail("vq::malloc_trim(images)", e);
+        VQ_HIP(f->frames_dev[k].grow(full));
+        VQ_HIP(f->img_dev[k].grow(full));
     }
-    if ((e = vq::malloc_trim((void**)&f->st, (size_t)max_pairs * sizeof(PairState))) != hipSuccess) return bail("vq::malloc_trim(state)", e);
-    if ((e = vq::malloc_trim((void**)&f->n_active, sizeof(int))) != hipSuccess) return bail("vq::malloc_trim(state)", e);
-    if ((e = vq::malloc_trim((void**)&f->iters_log, (size_t)f->levels.size() * prm.warps * max_pairs * sizeof(int))) != hipSuccess)
-        return bail("vq::malloc_trim(log)", e);
-    if ((e = hipHostMalloc((void**)&f->live_host, 4 * sizeof(int))) != hipSuccess) return bail("hipHostMalloc(poll)", e);
-    if ((e = hipHostGetDevicePointer((void**)&f->live_flag_dev, f->live_host + 2, 0)) != hipSuccess) return bail("hipHostGetDevicePointer(poll)", e);
-    for (hipEvent_t& ev : f->poll_ev)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    f->loop_ev.assign((size_t)2 * f->levels.size() * prm.warps, nullptr);
-    for (hipEvent_t& ev : f->loop_ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = vq::malloc_trim((void**)&f->hinv_dev, (size_t)max_pairs * 9 * sizeof(double))) != hipSuccess) return bail("vq::malloc_trim(homographies)", e);
-    if ((e = vq::malloc_trim((void**)&f->frame_max, (size_t)max_pairs * sizeof(unsigned))) != hipSuccess) return bail("vq::malloc_trim(state)", e);
-    *out = f;
+    VQ_HIP(f->st.grow((size_t)max_pairs * sizeof(PairState)));
+    VQ_HIP(f->n_active.grow(sizeof(int)));
+    VQ_HIP(f->iters_log.grow(f->levels.size() * prm.warps * max_pairs * sizeof(int)));
+    VQ_HIP(f->live_host.alloc(1));
+    VQ_HIP(hipHostGetDevicePointer((void**)&f->live_flag_dev, f->live_host, 0));
+    for (Event& ev : f->poll_ev) VQ_HIP(ev.create(hipEventDisableTiming));
+    f->loop_ev.resize((size_t)2 * f->levels.size() * prm.warps);
+    for (Event& ev : f->loop_ev) VQ_HIP(ev.create());
+    VQ_HIP(f->hinv_dev.grow((size_t)max_pairs * 9 * sizeof(double)));
+    VQ_HIP(f->frame_max.grow((size_t)max_pairs * sizeof(unsigned)));
+    *out = f.release();
     return VQ_OK;
 }
 
 int vq_flow_destroy(vq_flow* f) {
     if (!f) return VQ_OK;
-    {
-        DeviceGuard g(f->device);
-        (void)hipDeviceSynchronize();
-        flow_free(f);
-    }
+    DeviceGuard g(f->device);
+    (void)hipDeviceSynchronize();
     delete f;
     return VQ_OK;
 }
@@ -1034,7 +1266,7 @@ int vq_flow_tile_cut(vq_flow* f, int32_t level, int32_t n_pairs, int32_t out[6])
     VQ_REQUIRE(f && out, "NULL argument");
     VQ_REQUIRE(level >= 0 && level < (int)f->levels.size(), "level %d outside [0,%d)", level, (int)f->levels.size());
     VQ_REQUIRE(n_pairs > 0 && n_pairs <= f->max_pairs, "n_pairs %d outside (0,%d]", n_pairs, f->max_pairs);
-    const TileCut cut = level_cut(f, f->levels[level], n_pairs);
+    const TileCut cut = level_cut(*f, f->levels[level], n_pairs);
     out[0] = cut.nx;
     out[1] = cut.ny;
     out[2] = cut.tw;
@@ -1044,316 +1276,40 @@ int vq_flow_tile_cut(vq_flow* f, int32_t level, int32_t n_pairs, int32_t out[6])
     return VQ_OK;
 }
 
+// The calls that use the device: argument checks, the handle's lock, its device made current, one *_locked function.
+
 int vq_flow_tvl1(vq_flow* f, const uint8_t* frames0, const uint8_t* frames1, int32_t frames_on_device, int32_t n_pairs,
                  const double* homographies_host, float* u1_host, float* u2_host, uint8_t* flow_x_host, uint8_t* flow_y_host,
                  int32_t* iters_host, void* hip_stream) {
     VQ_REQUIRE(f && frames0 && frames1, "NULL argument");
     VQ_REQUIRE(n_pairs > 0 && n_pairs <= f->max_pairs, "n_pairs %d outside (0,%d]", n_pairs, f->max_pairs);
-    std::lock_guard<std::recursive_mutex> lk(f->mu);
+    std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    const vq_tvl1_params& P = f->prm;
-    const int h = f->h, w = f->w;
-    const int64_t full = (int64_t)n_pairs * h * w;
-    const uint8_t *d0 = frames0, *d1 = frames1;
-    if (!frames_on_device) {
-        VQ_HIP(hipMemcpyAsync(f->frames_dev[0], frames0, (size_t)full, hipMemcpyHostToDevice, st));
-        VQ_HIP(hipMemcpyAsync(f->frames_dev[1], frames1, (size_t)full, hipMemcpyHostToDevice, st));
-        d0 = f->frames_dev[0];
-        d1 = f->frames_dev[1];
-    }
-    float *i1x = f->plane[0], *i1y = f->plane[1], *i1wx = f->plane[2], *i1wy = f->plane[3], *grad = f->plane[4], *rho_c = f->plane[5];
-    float *u1 = f->plane[6], *u2 = f->plane[7], *p11 = f->plane[8], *p12 = f->plane[9], *p21 = f->plane[10], *p22 = f->plane[11];
-    const int nl = (int)f->levels.size();
-    // level 0 of the pyramids: the frames as floats (0..255); the second frame optionally through a homography first
-    u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d0, f->pyr0, full);
-    if (homographies_host) {
-        std::vector<double> inv((size_t)n_pairs * 9);
-        for (int p = 0; p < n_pairs; ++p) {          // 3x3 inverse by cofactors (fp64), as numpy.linalg.inv does to rounding
-            const double* m = homographies_host + (size_t)p * 9;
-            const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-            VQ_REQUIRE(std::fabs(det) > 1e-300, "homography %d is singular", p);
-            double* o = inv.data() + (size_t)p * 9;
-            o[0] = (m[4] * m[8] - m[5] * m[7]) / det;
-            o[1] = (m[2] * m[7] - m[1] * m[8]) / det;
-            o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-            o[3] = (m[5] * m[6] - m[3] * m[8]) / det;
-            o[4] = (m[0] * m[8] - m[2] * m[6]) / det;
-            o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-            o[6] = (m[3] * m[7] - m[4] * m[6]) / det;
-            o[7] = (m[1] * m[6] - m[0] * m[7]) / det;
-            o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-        }
-        VQ_HIP(hipMemcpyAsync(f->hinv_dev, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        VQ_HIP(hipStreamSynchronize(st));           // `inv` leaves scope
-        u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d1, f->tmp[0], full);
-        homography_warp_kernel<<<cdiv(full, 256), 256, 0, st>>>(f->tmp[0], f->pyr1, f->hinv_dev, n_pairs, h, w);
-    } else {
-        u8_to_float_kernel<<<cdiv(full, 256), 256, 0, st>>>(d1, f->pyr1, full);
-    }
-    VQ_CHECK_LAUNCH();
-    for (int s = 1; s < nl; ++s) {
-        const Level &a = f->levels[s - 1], &b = f->levels[s];
-        const int64_t tot = (int64_t)n_pairs * b.h * b.w;
-        resize_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f->pyr0 + a.off, f->pyr0 + b.off, n_pairs, a.h, a.w, b.h, b.w, 1.0f);
-        resize_kernel<<<cdiv(tot, 256), 256, 0, st>>>(f->pyr1 + a.off, f->pyr1 + b.off, n_pairs, a.h, a.w, b.h, b.w, 1.0f);
-    }
-    VQ_CHECK_LAUNCH();
-    {
-        const Level& c = f->levels[nl - 1];
-        VQ_HIP(hipMemsetAsync(u1, 0, (size_t)n_pairs * c.h * c.w * sizeof(float), st));
-        VQ_HIP(hipMemsetAsync(u2, 0, (size_t)n_pairs * c.h * c.w * sizeof(float), st));
-    }
-    const double eps2 = (double)P.epsilon * (double)P.epsilon;      // oracle: float(float32(epsilon)) ** 2
-    int iter_launches = 0;
-    for (int s = nl - 1; s >= 0; --s) {
-        const Level& L = f->levels[s];
-        const int64_t tot = (int64_t)n_pairs * L.h * L.w;
-        const float *i0 = f->pyr0 + L.off, *i1 = f->pyr1 + L.off;
-        gradient_kernel<<<cdiv(tot, 256), 256, 0, st>>>(i1, i1x, i1y, n_pairs, L.h, L.w);
-        for (float* p : {p11, p12, p21, p22}) VQ_HIP(hipMemsetAsync(p, 0, (size_t)tot * sizeof(float), st));
-        const float l_t = (float)((double)P.lambda * (double)P.theta);      // oracle: float32(lam * theta) on the float32 parameters
-        const float taut = (float)((double)P.tau / (double)P.theta);
-        const TileCut cut = level_cut(f, L, n_pairs);
-        const dim3 tgrid((unsigned)cut.nx, (unsigned)cut.ny, (unsigned)n_pairs);
-        const size_t tlds = (size_t)6 * cut.eh * cut.ew * sizeof(float);
-        BlockArgs ba;
-        ba.ew = cut.ew;
-        ba.eh = cut.eh;
-        ba.tw = cut.tw;
-        ba.th = cut.th;
-        ba.inv_ew = 1.0f / (float)cut.ew;
-        ba.i1wx = i1wx;
-        ba.i1wy = i1wy;
-        ba.grad = grad;
-        ba.rho_c = rho_c;
-        ba.st = f->st;
-        ba.n_active = f->n_active;
-        ba.live_flag = f->live_flag_dev;
-        ba.h = L.h;
-        ba.w = L.w;
-        ba.max_iters = P.iterations;
-        ba.l_t = l_t;
-        ba.theta = P.theta;
-        ba.taut = taut;
-        ba.eps2 = eps2;
-        float* set[2][6] = {{u1, u2, p11, p12, p21, p22}, {f->alt[0], f->alt[1], f->alt[2], f->alt[3], f->alt[4], f->alt[5]}};
-        SettleArgs sa;
-        for (int q = 0; q < 6; ++q) {
-            sa.set0[q] = ba.set[0][q] = set[0][q];
-            sa.set1[q] = ba.set[1][q] = set[1][q];
-        }
-        for (int wp = 0; wp < P.warps; ++wp) {
-            tvl1_warp_kernel<<<cdiv(tot, 256), 256, 0, st>>>(i0, i1, i1x, i1y, u1, u2, i1wx, i1wy, grad, rho_c, f->st, f->n_active, f->live_flag_dev, n_pairs, L.h, L.w);
-            // Converged pairs switch themselves off on the device (their workgroups exit at once).  The host polls the number
-            // of live pairs once per chunk of iterations, one chunk BEHIND what it has queued: the stream never runs dry while
-            // the host waits, at the price of at most one chunk of empty launches after the last pair has stopped.
-            int chunk_no = 0;
-            const size_t ev_i = 2 * ((size_t)(nl - 1 - s) * P.warps + wp);
-            VQ_HIP(hipEventRecord(f->loop_ev[ev_i], st));
-            {
-                // blocks of kBlkIters iterations; a pair needs at most ceil(iterations / K) blocks, one replay and one closing launch
-                const int max_launches = cdiv(P.iterations, kBlkIters) + 2;
-                for (int l0 = 0; l0 < max_launches; ++chunk_no) {
-                    const int chunk = std::min(max_launches - l0, l0 < 4 ? 2 : 4);
-                    for (int k = 0; k < chunk; ++k) {
-                        ba.L = l0 + k;
-                        if (f->exact_math) tvl1_tile_kernel<kTileThreads, false><<<tgrid, kTileThreads, tlds, st>>>(ba);
-                        else tvl1_tile_kernel<kTileThreads, true><<<tgrid, kTileThreads, tlds, st>>>(ba);
-                        ++iter_launches;
-                    }
-                    VQ_CHECK_LAUNCH();
-                    l0 += chunk;
-                    VQ_HIP(hipEventRecord(f->poll_ev[chunk_no & 1], st));
-                    if (chunk_no > 0) {
-                        VQ_HIP(hipEventSynchronize(f->poll_ev[(chunk_no - 1) & 1]));
-                        // the kernels clear the flag in host memory when the last pair stops: no copy in the stream
-                        if (__atomic_load_n(const_cast<volatile int*>(f->live_host + 2), __ATOMIC_ACQUIRE) == 0) break;
-                    }
-                }
-            }
-            VQ_HIP(hipEventRecord(f->loop_ev[ev_i + 1], st));
-            tvl1_settle_kernel<<<dim3((unsigned)std::min(cdiv((int64_t)L.h * L.w, 256), 32), (unsigned)n_pairs), 256, 0, st>>>(f->st, sa, L.h * L.w);
-            VQ_CHECK_LAUNCH();
-            if (iters_host)
-                log_iters_kernel<<<cdiv(n_pairs, 256), 256, 0, st>>>(f->st, f->iters_log + ((size_t)(nl - 1 - s) * P.warps + wp) * n_pairs, n_pairs);
-        }
-        if (s > 0) {          // to the next finer level: bilinear resize, flow values divided by the scale step
-            const Level& F = f->levels[s - 1];
-            const int64_t ftot = (int64_t)n_pairs * F.h * F.w;
-            const float inv = (float)(1.0 / (double)P.scale_step);
-            VQ_HIP(hipMemcpyAsync(f->tmp[0], u1, (size_t)tot * sizeof(float), hipMemcpyDeviceToDevice, st));
-            VQ_HIP(hipMemcpyAsync(f->tmp[1], u2, (size_t)tot * sizeof(float), hipMemcpyDeviceToDevice, st));
-            resize_kernel<<<cdiv(ftot, 256), 256, 0, st>>>(f->tmp[0], u1, n_pairs, L.h, L.w, F.h, F.w, inv);
-            resize_kernel<<<cdiv(ftot, 256), 256, 0, st>>>(f->tmp[1], u2, n_pairs, L.h, L.w, F.h, F.w, inv);
-            VQ_CHECK_LAUNCH();
-        }
-    }
-    if (iters_host)
-        VQ_HIP(hipMemcpyAsync(iters_host, f->iters_log, (size_t)nl * P.warps * n_pairs * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (u1_host) VQ_HIP(hipMemcpyAsync(u1_host, u1, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (u2_host) VQ_HIP(hipMemcpyAsync(u2_host, u2, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (flow_x_host || flow_y_host) {
-        flow_to_image_kernel<<<cdiv(full, 256), 256, 0, st>>>(u1, f->img_dev[0], full, P.bound);
-        flow_to_image_kernel<<<cdiv(full, 256), 256, 0, st>>>(u2, f->img_dev[1], full, P.bound);
-        VQ_CHECK_LAUNCH();
-        if (flow_x_host) VQ_HIP(hipMemcpyAsync(flow_x_host, f->img_dev[0], (size_t)full, hipMemcpyDeviceToHost, st));
-        if (flow_y_host) VQ_HIP(hipMemcpyAsync(flow_y_host, f->img_dev[1], (size_t)full, hipMemcpyDeviceToHost, st));
-    }
-    VQ_HIP(hipStreamSynchronize(st));
-    f->last_iter_launches = iter_launches;
-    f->last_inner_ms = 0.0;
-    for (size_t q = 0; q + 1 < f->loop_ev.size(); q += 2) {
-        float ms = 0.f;
-        VQ_HIP(hipEventElapsedTime(&ms, f->loop_ev[q], f->loop_ev[q + 1]));
-        f->last_inner_ms += ms;
-    }
-    return VQ_OK;
+    return tvl1_locked(*f, frames0, frames1, frames_on_device != 0, n_pairs, homographies_host, u1_host, u2_host, flow_x_host, flow_y_host, iters_host,
+                       (hipStream_t)hip_stream);
 }
 
 int vq_flow_last_timing(vq_flow* f, double* inner_loops_ms, int32_t* iteration_launches) {
     VQ_REQUIRE(f, "NULL argument");
-    std::lock_guard<std::recursive_mutex> lk(f->mu);
+    std::lock_guard<std::mutex> lk(f->mu);
     if (inner_loops_ms) *inner_loops_ms = f->last_inner_ms;
     if (iteration_launches) *iteration_launches = f->last_iter_launches;
     return VQ_OK;
 }
-
-}  // extern "C"
-
-// ---- camera-motion estimation -------------------------------------------------------------------------------------------
-
-namespace {
-
-bool solve_dense(std::vector<double>& A, std::vector<double>& b, int n) {   // Gaussian elimination, partial pivoting; b <- solution
-    for (int c = 0; c < n; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < n; ++r)
-            if (std::fabs(A[(size_t)r * n + c]) > std::fabs(A[(size_t)piv * n + c])) piv = r;
-        if (std::fabs(A[(size_t)piv * n + c]) < 1e-300) return false;
-        if (piv != c) {
-            for (int q = 0; q < n; ++q) std::swap(A[(size_t)c * n + q], A[(size_t)piv * n + q]);
-            std::swap(b[c], b[piv]);
-        }
-        for (int r = c + 1; r < n; ++r) {
-            const double f = A[(size_t)r * n + c] / A[(size_t)c * n + c];
-            for (int q = c; q < n; ++q) A[(size_t)r * n + q] -= f * A[(size_t)c * n + q];
-            b[r] -= f * b[c];
-        }
-    }
-    for (int c = n - 1; c >= 0; --c) {
-        double v = b[c];
-        for (int q = c + 1; q < n; ++q) v -= A[(size_t)c * n + q] * b[q];
-        b[c] = v / A[(size_t)c * n + c];
-    }
-    return true;
-}
-
-// Least-squares homography (h33 = 1 in normalised coordinates) over the inliers: Hartley normalisation of both point sets,
-// normal equations of the 2k x 8 system in fp64, de-normalised and scaled to H[8] = 1.
-bool refit_homography(const float* src, const float* dst, const uint8_t* mask, int n, double* H) {
-    int k = 0;
-    double cs[2] = {0, 0}, cd[2] = {0, 0};
-    for (int i = 0; i < n; ++i)
-        if (mask[i]) {
-            cs[0] += src[2 * i];
-            cs[1] += src[2 * i + 1];
-            cd[0] += dst[2 * i];
-            cd[1] += dst[2 * i + 1];
-            ++k;
-        }
-    if (k < 4) return false;
-    for (int q = 0; q < 2; ++q) {
-        cs[q] /= k;
-        cd[q] /= k;
-    }
-    double ms = 0, md = 0;
-    for (int i = 0; i < n; ++i)
-        if (mask[i]) {
-            ms += std::sqrt((src[2 * i] - cs[0]) * (src[2 * i] - cs[0]) + (src[2 * i + 1] - cs[1]) * (src[2 * i + 1] - cs[1]));
-            md += std::sqrt((dst[2 * i] - cd[0]) * (dst[2 * i] - cd[0]) + (dst[2 * i + 1] - cd[1]) * (dst[2 * i + 1] - cd[1]));
-        }
-    if (ms <= 0 || md <= 0) return false;
-    const double ss = std::sqrt(2.0) * k / ms, sd = std::sqrt(2.0) * k / md;
-    std::vector<double> N(64, 0.0), r(8, 0.0);
-    for (int i = 0; i < n; ++i) {
-        if (!mask[i]) continue;
-        const double x = (src[2 * i] - cs[0]) * ss, y = (src[2 * i + 1] - cs[1]) * ss;
-        const double u = (dst[2 * i] - cd[0]) * sd, v = (dst[2 * i + 1] - cd[1]) * sd;
-        const double r0[8] = {x, y, 1, 0, 0, 0, -u * x, -u * y}, r1[8] = {0, 0, 0, x, y, 1, -v * x, -v * y};
-        for (int a = 0; a < 8; ++a) {
-            for (int b = 0; b < 8; ++b) N[a * 8 + b] += r0[a] * r0[b] + r1[a] * r1[b];
-            r[a] += r0[a] * u + r1[a] * v;
-        }
-    }
-    if (!solve_dense(N, r, 8)) return false;
-    const double Hn[9] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], 1.0};
-    // H = Td^-1 Hn Ts with Ts = [ss 0 -ss cs0; 0 ss -ss cs1; 0 0 1], Td^-1 = [1/sd 0 cd0; 0 1/sd cd1; 0 0 1]
-    double M[9];
-    for (int a = 0; a < 3; ++a) {
-        M[a * 3] = Hn[a * 3] * ss;
-        M[a * 3 + 1] = Hn[a * 3 + 1] * ss;
-        M[a * 3 + 2] = -Hn[a * 3] * ss * cs[0] - Hn[a * 3 + 1] * ss * cs[1] + Hn[a * 3 + 2];
-    }
-    double G[9];
-    for (int q = 0; q < 3; ++q) {
-        G[q] = M[q] / sd + cd[0] * M[6 + q];
-        G[3 + q] = M[3 + q] / sd + cd[1] * M[6 + q];
-        G[6 + q] = M[6 + q];
-    }
-    if (std::fabs(G[8]) < 1e-300) return false;
-    for (int q = 0; q < 9; ++q) H[q] = G[q] / G[8];
-    return true;
-}
-
-}  // namespace
-
-// The corner search of n frames already in device memory, on `st`; the caller holds the handle's lock (or is the helper thread
-// vq_flow_warped starts while it holds it).  Touches only the corner planes, frame_max and the pinned peak buffer.
-static int good_features_core(vq_flow* f, const uint8_t* d, int n, int max_corners, float quality, float min_distance, float* corners_host,
-                              int32_t* counts_host, hipStream_t st) {
-    const int h = f->h, w = f->w;
-    const int64_t full = (int64_t)n * h * w;
-    for (float*& p : f->corner_plane)
-        if (!p) VQ_HIP(vq::malloc_trim((void**)&p, (size_t)f->max_pairs * h * w * sizeof(float)));
-    float *strength = f->corner_plane[0], *peaks = f->corner_plane[1];
-    VQ_HIP(hipMemsetAsync(f->frame_max, 0, (size_t)n * sizeof(unsigned), st));
-    corner_strength_kernel<<<dim3((unsigned)cdiv((int64_t)h * w, 256), (unsigned)n), 256, 0, st>>>(d, strength, f->frame_max, n, h, w);
-    corner_peaks_kernel<<<cdiv(full, 256), 256, 0, st>>>(strength, peaks, n, h, w);
-    VQ_CHECK_LAUNCH();
-    if (f->peaks_host_floats < (size_t)f->max_pairs * h * w) {          // pinned, once: 22 MB per batch of 64 frames come back through it
-        if (f->peaks_host) (void)hipHostFree(f->peaks_host);
-        f->peaks_host = nullptr;
-        f->peaks_host_floats = 0;
-        VQ_HIP(hipHostMalloc((void**)&f->peaks_host, (size_t)f->max_pairs * h * w * sizeof(float)));
-        f->peaks_host_floats = (size_t)f->max_pairs * h * w;
-    }
-    float* host_peaks = f->peaks_host;
-    std::vector<unsigned> top((size_t)n);
-    VQ_HIP(hipMemcpyAsync(host_peaks, peaks, (size_t)full * sizeof(float), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipMemcpyAsync(top.data(), f->frame_max, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipStreamSynchronize(st));
-    // the selection is per frame and sequential inside a frame: frames are spread over host threads (csrc/host/vq_corners.cc)
-    vq::select_corners_batch(host_peaks, top.data(), n, h, w, max_corners, quality, min_distance, corners_host, counts_host);
-    return VQ_OK;
-}
-
-extern "C" {
 
 int vq_flow_good_features(vq_flow* f, const uint8_t* frames, int32_t frames_on_device, int32_t n, int32_t max_corners, float quality,
                           float min_distance, float* corners_host, int32_t* counts_host, void* hip_stream) {
     VQ_REQUIRE(f && frames && corners_host && counts_host, "NULL argument");
     VQ_REQUIRE(n > 0 && n <= f->max_pairs, "n %d outside (0,%d]", n, f->max_pairs);
     VQ_REQUIRE(max_corners > 0 && quality > 0.f && quality < 1.f && min_distance >= 0.f, "corner parameters out of range");
-    std::lock_guard<std::recursive_mutex> lk(f->mu);
+    std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
     hipStream_t st = (hipStream_t)hip_stream;
-    const uint8_t* d = frames;
     if (!frames_on_device) {
         VQ_HIP(hipMemcpyAsync(f->frames_dev[0], frames, (size_t)n * f->h * f->w, hipMemcpyHostToDevice, st));
-        d = f->frames_dev[0];
+        frames = f->frames_dev[0];
     }
-    return good_features_core(f, d, n, max_corners, quality, min_distance, corners_host, counts_host, st);
+    return good_features_locked(*f, frames, n, max_corners, quality, min_distance, corners_host, counts_host, st);
 }
 
 int vq_flow_ransac_homography(vq_flow* f, const float* src_host, const float* dst_host, const int32_t* counts_host, int32_t n,
@@ -1363,136 +1319,21 @@ int vq_flow_ransac_homography(vq_flow* f, const float* src_host, const float* ds
     VQ_REQUIRE(n > 0 && max_points >= 4 && max_points <= 8192 && hypotheses > 0 && hypotheses <= (1 << 20) && threshold > 0.f,
                "RANSAC parameters out of range (at most 8192 matches per pair)");
     for (int p = 0; p < n; ++p) VQ_REQUIRE(counts_host[p] >= 0 && counts_host[p] <= max_points, "pair %d: %d matches of at most %d", p, counts_host[p], max_points);
-    std::lock_guard<std::recursive_mutex> lk(f->mu);
+    std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    const size_t pts_b = (size_t)n * max_points * 2 * sizeof(float);
-    const size_t need = 2 * pts_b + (size_t)n * (3 * sizeof(int) + 9 * sizeof(double)) + (size_t)n * max_points + 64;
-    if (need > f->match_bytes) {
-        if (f->match_dev) (void)hipFree(f->match_dev);
-        f->match_dev = nullptr;
-        f->match_bytes = 0;
-        VQ_HIP(vq::malloc_trim(&f->match_dev, need));
-        f->match_bytes = need;
-    }
-    char* base = (char*)f->match_dev;
-    double* h_dev = (double*)base;                                   // 8-byte aligned things first
-    float* src_dev = (float*)(base + (size_t)n * 9 * sizeof(double));
-    float* dst_dev = (float*)((char*)src_dev + pts_b);
-    int* cnt_dev = (int*)((char*)dst_dev + pts_b);
-    int* best_dev = cnt_dev + n;
-    int* win_dev = best_dev + n;
-    uint8_t* mask_dev = (uint8_t*)(win_dev + n);
-    VQ_HIP(hipMemcpyAsync(src_dev, src_host, pts_b, hipMemcpyHostToDevice, st));
-    VQ_HIP(hipMemcpyAsync(dst_dev, dst_host, pts_b, hipMemcpyHostToDevice, st));
-    VQ_HIP(hipMemcpyAsync(cnt_dev, counts_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    const size_t lds = (size_t)max_points * 4 * sizeof(float);
-    VQ_DYN_LDS(ransac_homography_kernel, 8192 * 16);
-    ransac_homography_kernel<<<n, 256, lds, st>>>(src_dev, dst_dev, cnt_dev, max_points, hypotheses, seed, (double)threshold * (double)threshold,
-                                                  h_dev, best_dev, win_dev, mask_dev);
-    VQ_CHECK_LAUNCH();
-    std::vector<uint8_t> mask((size_t)n * max_points);
-    std::vector<int> win((size_t)n);
-    VQ_HIP(hipMemcpyAsync(h_host, h_dev, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipMemcpyAsync(inliers_host, best_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipMemcpyAsync(win.data(), win_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipMemcpyAsync(mask.data(), mask_dev, mask.size(), hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipStreamSynchronize(st));
-    if (refit)
-        for (int p = 0; p < n; ++p)
-            if (inliers_host[p] >= 4) {
-                double H[9];
-                if (refit_homography(src_host + (size_t)p * max_points * 2, dst_host + (size_t)p * max_points * 2, mask.data() + (size_t)p * max_points,
-                                     counts_host[p], H))
-                    memcpy(h_host + (size_t)p * 9, H, sizeof H);
-            }
-    if (winner_host) memcpy(winner_host, win.data(), (size_t)n * sizeof(int));
-    if (mask_host) memcpy(mask_host, mask.data(), mask.size());
-    return VQ_OK;
+    return ransac_homography_locked(*f, src_host, dst_host, counts_host, n, max_points, threshold, hypotheses, seed, refit != 0, h_host, inliers_host,
+                                    winner_host, mask_host, (hipStream_t)hip_stream);
 }
 
-// The warped flow of extract_warp_gpu (flow-match branch) in one call, the frames uploaded once and the first-pass fields never leaving the
-// device: TV-L1 -> Shi-Tomasi corners of the first frame (selection on host threads) -> the corners moved by the flow (device) -> RANSAC
-// homography (device kernel + host refit) with dense_flow's guards (> 50 matches, > 25 inliers, else identity) -> the second frame warped
-// back by it -> TV-L1 again.  tsn/flow.py:Tvl1Flow.warped_steps is the same sequence call by call (tests compare the two).
 int vq_flow_warped(vq_flow* f, const uint8_t* frames0, const uint8_t* frames1, int32_t n_pairs, uint32_t seed, int32_t hypotheses, float* u1_host,
                    float* u2_host, uint8_t* flow_x_host, uint8_t* flow_y_host, double* h_host, int32_t* matches_host, int32_t* inliers_host,
                    void* hip_stream) {
     VQ_REQUIRE(f && frames0 && frames1, "NULL argument");
     VQ_REQUIRE(n_pairs > 0 && n_pairs <= f->max_pairs, "n_pairs %d outside (0,%d]", n_pairs, f->max_pairs);
-    std::lock_guard<std::recursive_mutex> lk(f->mu);
+    std::lock_guard<std::mutex> lk(f->mu);
     DeviceGuard g(f->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    constexpr int kMaxCorners = 1000, kMinMatches = 50, kMinInliers = 25;
-    const int n = n_pairs, h = f->h, w = f->w;
-    std::vector<float> corners((size_t)n * kMaxCorners * 2), moved((size_t)n * kMaxCorners * 2);
-    std::vector<int32_t> counts((size_t)n), inl((size_t)n);
-    // The corners depend on the first frames alone: their search (two small kernels, 22 MB of peak maps to the host, the selection on
-    // host threads) runs on a stream and a thread of its own beside the first flow pass instead of between the two passes.
-    if (!f->side_stream) VQ_HIP(hipStreamCreateWithFlags(&f->side_stream, hipStreamNonBlocking));
-    if (!f->side_ev) VQ_HIP(hipEventCreateWithFlags(&f->side_ev, hipEventDisableTiming));
-    const size_t full = (size_t)n * h * w;
-    VQ_HIP(hipMemcpyAsync(f->frames_dev[0], frames0, full, hipMemcpyHostToDevice, st));
-    VQ_HIP(hipEventRecord(f->side_ev, st));
-    VQ_HIP(hipMemcpyAsync(f->frames_dev[1], frames1, full, hipMemcpyHostToDevice, st));
-    VQ_HIP(hipStreamWaitEvent(f->side_stream, f->side_ev, 0));
-    int rc_corners = VQ_OK;
-    std::string err_corners;
-    std::thread side([&] {
-        DeviceGuard gs(f->device);
-        rc_corners = good_features_core(f, f->frames_dev[0], n, kMaxCorners, 0.001f, 3.0f, corners.data(), counts.data(), f->side_stream);
-        if (rc_corners != VQ_OK) err_corners = last_error_ref();        // the message lives in the helper thread's slot
-    });
-    int rc = vq_flow_tvl1(f, f->frames_dev[0], f->frames_dev[1], 1, n_pairs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hip_stream);
-    side.join();
-    if (rc != VQ_OK) return rc;
-    if (rc_corners != VQ_OK) return fail(rc_corners, "%s", err_corners.c_str());
-    const size_t cb = corners.size() * sizeof(float);
-    const size_t need = 2 * cb + (size_t)n * sizeof(int);
-    if (need > f->warp_bytes) {
-        if (f->warp_dev) (void)hipFree(f->warp_dev);
-        f->warp_dev = nullptr;
-        f->warp_bytes = 0;
-        VQ_HIP(vq::malloc_trim(&f->warp_dev, need));
-        f->warp_bytes = need;
-    }
-    float* c_dev = (float*)f->warp_dev;
-    float* m_dev = (float*)((char*)f->warp_dev + cb);
-    int* n_dev = (int*)((char*)f->warp_dev + 2 * cb);
-    VQ_HIP(hipMemcpyAsync(c_dev, corners.data(), cb, hipMemcpyHostToDevice, st));
-    VQ_HIP(hipMemcpyAsync(n_dev, counts.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    move_corners_kernel<<<cdiv((int64_t)n * kMaxCorners, 256), 256, 0, st>>>(c_dev, n_dev, f->plane[6], f->plane[7], m_dev, n, kMaxCorners, h, w);
-    VQ_CHECK_LAUNCH();
-    VQ_HIP(hipMemcpyAsync(moved.data(), m_dev, cb, hipMemcpyDeviceToHost, st));
-    VQ_HIP(hipStreamSynchronize(st));
-    std::vector<double> H((size_t)n * 9), Hinv((size_t)n * 9);
-    rc = vq_flow_ransac_homography(f, corners.data(), moved.data(), counts.data(), n, kMaxCorners, 1.0f, hypotheses, seed, 1, H.data(), inl.data(), nullptr,
-                                   nullptr, hip_stream);
-    if (rc != VQ_OK) return rc;
-    for (int p = 0; p < n; ++p) {
-        double* m = H.data() + (size_t)p * 9;
-        double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        if (counts[p] <= kMinMatches || inl[p] <= kMinInliers || !(std::fabs(det) > 1e-300)) {
-            const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            memcpy(m, eye, sizeof eye);
-            det = 1.0;
-        }
-        // vq_flow_tvl1(homographies = G) shows the second frame as out(x) = frame1(G^-1 x); the compensated frame is frame1(H x): G = H^-1
-        double* o = Hinv.data() + (size_t)p * 9;
-        o[0] = (m[4] * m[8] - m[5] * m[7]) / det;
-        o[1] = (m[2] * m[7] - m[1] * m[8]) / det;
-        o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-        o[3] = (m[5] * m[6] - m[3] * m[8]) / det;
-        o[4] = (m[0] * m[8] - m[2] * m[6]) / det;
-        o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-        o[6] = (m[3] * m[7] - m[4] * m[6]) / det;
-        o[7] = (m[1] * m[6] - m[0] * m[7]) / det;
-        o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-    }
-    if (h_host) memcpy(h_host, H.data(), H.size() * sizeof(double));
-    if (matches_host) memcpy(matches_host, counts.data(), (size_t)n * sizeof(int32_t));
-    if (inliers_host) memcpy(inliers_host, inl.data(), (size_t)n * sizeof(int32_t));
-    return vq_flow_tvl1(f, f->frames_dev[0], f->frames_dev[1], 1, n, Hinv.data(), u1_host, u2_host, flow_x_host, flow_y_host, nullptr, hip_stream);
+    return warped_locked(*f, frames0, frames1, n_pairs, seed, hypotheses, u1_host, u2_host, flow_x_host, flow_y_host, h_host, matches_host, inliers_host,
+                         (hipStream_t)hip_stream);
 }
 
 }  // extern "C"
