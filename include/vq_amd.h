@@ -82,7 +82,10 @@ enum {
     VQ_E_UNSUPPORTED = -5   /* shape outside what the kernels were built for */
 };
 
-enum { VQ_F32 = 0, VQ_F64 = 1 };
+/* How a feature database stores its values.  VQ_F16 = IEEE binary16, opt-in (half the bytes of VQ_F32 per query and per clip): values are
+ * rounded once, when they are stored; every computation widens them exactly and runs in fp64 like the other two, so an fp16 database
+ * scores like an fp32 / fp64 database holding the rounded values.  A library that predates VQ_F16 refuses it in vq_db_create. */
+enum { VQ_F32 = 0, VQ_F64 = 1, VQ_F16 = 2 };
 enum { VQ_LAYOUT_ROWS = 0, VQ_LAYOUT_TILED = 1 };
 
 const char* vq_last_error(void);
@@ -110,7 +113,9 @@ typedef struct vq_db vq_db;
 /* A resident, row-major [N][S][E][D] feature block (N clips, S streams, E ensemble members
  * ("splits"), D = feature length).  Replaces the nested dict the reference builds from one JSON
  * GET per query in Ticket._get_candidate_features (src/models/ticket.py:358-382).
- * dtype VQ_F32 (BASELINE configs) or VQ_F64 (exact values of the shipped CSVs). */
+ * dtype VQ_F32 (BASELINE configs), VQ_F64 (exact values of the shipped CSVs) or VQ_F16 (binary16 rows: vq_db_upload, vq_db_read_rows,
+ * vq_db_adopt_device and vq_db_feats_devptr then speak halves; the caller rounds, vq_db_generate rounds to nearest even).  Every vq_db_*
+ * entry point works on all three; only the tiled layout (vq_db_set_layout: fp32) and the host rows of vq_bootstrap_targets (fp32 / fp64) do not take it. */
 int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int32_t device, vq_db** out);
 int vq_db_destroy(vq_db* db);
 int vq_db_set_stream(vq_db* db, void* hip_stream);
@@ -126,7 +131,7 @@ int vq_db_adopt_device(vq_db* db, void* feats_dev);
  * every load instruction of a wave (one-query scan AND 16-query pass) takes 1 KB of contiguous memory.  The conversion is IN PLACE
  * (a tile's rows and its tiled form cover the same bytes; no second copy of the database, 256 MB of scratch while it runs) and
  * costs one sweep of the block: call it once after loading, off the query path.  Tiled needs fp32, D = 1024, S <= 2, E <= 5
- * (VQ_E_UNSUPPORTED otherwise) and a block that is the library's alone (VQ_E_STATE after vq_db_adopt_device / vq_db_feats_devptr).
+ * (VQ_E_UNSUPPORTED otherwise -- also for VQ_F16 and VQ_F64 databases, which stay row-major and keep working) and a block that is the library's alone (VQ_E_STATE after vq_db_adopt_device / vq_db_feats_devptr).
  * Every other entry point works on either layout; results of the two layouts agree to rounding (<= 1e-12: the k order of a
  * dot differs), each is bit-reproducible in itself.  vq_db_upload into a tiled database deals the rows into their tiles. */
 int vq_db_set_layout(vq_db* db, int32_t layout);

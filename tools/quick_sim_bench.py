@@ -38,12 +38,14 @@ if __name__ == "__main__" and len(sys.argv) == 1:
     bench(10_000, 2, 3)
     bench(100_000, 2, 5, dtype=np.float64)
     bench(1_000_000, 2, 5)
+    bench(10_000, 2, 3, dtype=np.float16)
+    bench(1_000_000, 2, 5, dtype=np.float16)
 
 
-def bench_batched(n=1_000_000, s=2, e=5, d=1024, q=16, reps=6):
+def bench_batched(n=1_000_000, s=2, e=5, d=1024, q=16, reps=6, dtype=np.float32):
     """vq_db_scan_batch at cfg 4 (the fused single launch), three timed repeats."""
     import time
-    db = vqa.FeatureDB.synthetic(n, s, e, d, seed=17, scales=(4.0, 1.0)[:s])
+    db = vqa.FeatureDB.synthetic(n, s, e, d, seed=17, scales=(4.0, 1.0)[:s], dtype=dtype)
     rng = np.random.default_rng(0)
     t = rng.standard_normal((q, s, e, d)) / d
     w = 0.5 + rng.random((q, s))
@@ -61,11 +63,12 @@ def bench_batched(n=1_000_000, s=2, e=5, d=1024, q=16, reps=6):
             call("vq_timer_elapsed_ms", tm, C.byref(ms))
             times.append(ms.value)
         med = sorted(times)[len(times) // 2]
-        dbb = n * s * e * d * 4
-        print("batched Q=%d %s: %.3f ms median (%.3f best) -> %.0f queries/s, DB bytes %.2f TB/s (%.3f of 8 TB/s)"
-              % (q, "two-kernel" if form == "1" else "fused", med, min(times), q / med * 1e3, dbb / med / 1e9, dbb / med / 1e9 / 8), flush=True)
+        dbb = n * s * e * d * np.dtype(dtype).itemsize
+        print("batched Q=%d %s %s: %.3f ms median (%.3f best) -> %.0f queries/s, DB bytes %.2f TB/s (%.3f of 8 TB/s)"
+              % (q, np.dtype(dtype).name, "two-kernel" if form == "1" else "fused", med, min(times), q / med * 1e3, dbb / med / 1e9, dbb / med / 1e9 / 8), flush=True)
     db.close()
 
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "batched":
     bench_batched()
+    bench_batched(dtype=np.float16)

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
         const T* xi = base + off[i];
         const T* xj = base + off[j];
         double s = 0.0;
-        for (int d = lane; d < D; d += 64) s += (double)xi[d] * (double)xj[d];
+        for (int d = lane; d < D; d += 64) s += widen(xi[d]) * widen(xj[d]);
         for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
         if (lane == 0) {
             G[(size_t)i * r + j] = s;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
     if (!ok) return;
     for (int d = tid; d < D; d += 256) {
         double s = 0.0;
-        for (int k = 0; k < r; ++k) s += coef[k] * (double)base[off[k] + d];
+        for (int k = 0; k < r; ++k) s += coef[k] * widen(base[off[k] + d]);
         a.out[(size_t)p * D + d] = s;
     }
 }
@@ -233,7 +233,9 @@ int run_bootstrap(const void* base_dev, int dtype, const std::vector<int64_t>& r
     a.ws_stride = ws_stride;
     a.out = d_out;
     a.status = d_cnt + 2 * P;
-    if (dtype == VQ_F32)
+    if (dtype == VQ_F16)                       // resident rows only (vq_db_bootstrap_target); widened exactly: the targets of an fp32 copy
+        bootstrap_kernel<__half><<<P, 256, 0, stream>>>(a);
+    else if (dtype == VQ_F32)
         bootstrap_kernel<float><<<P, 256, 0, stream>>>(a);
     else
         bootstrap_kernel<double><<<P, 256, 0, stream>>>(a);

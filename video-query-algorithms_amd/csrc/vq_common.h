@@ -1,5 +1,6 @@
 // Shared host-side helpers of libvqamd (error plumbing, HIP call checking).
 #pragma once
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -83,6 +84,12 @@ struct PerDeviceOnce {
         }                                                                                                                        \
     } while (0)
 
+
+// A stored feature value as the fp64 the arithmetic runs in.  binary16 -> binary32 -> binary64 is exact, so an fp16 database (VQ_F16)
+// computes what an fp32 or fp64 database holding the same values computes.
+__device__ __forceinline__ double widen(double x) { return x; }
+__device__ __forceinline__ double widen(float x) { return (double)x; }
+__device__ __forceinline__ double widen(__half x) { return (double)__half2float(x); }
 
 // csrc/vq_boot.hip: closed-form target bootstrapping on rows that already live on the device.  row_off [P][stride]
 // element offsets into base_dev (the n_valid[p] validated matches first, then the n_invalid[p] non-matches).

@@ -66,8 +66,28 @@ __device__ __forceinline__ float4 stream_load4(const float* p) {
     return make_float4(r.x, r.y, r.z, r.w);
 }
 
+// The same image for a lane that holds 8 consecutive elements of a 512-element chunk (fp16 rows: 16 bytes per lane, 1 KB per wave
+// instruction): four lane-linear planes of 128 doubles per chunk, plane q / 2 holds elements q = 2 (q / 2), 2 (q / 2) + 1 of every lane.
+__device__ __forceinline__ int t_lds_index8(int D, int v, int k) {
+    const int j = k >> 9, r = k & 511, lane = r >> 3, q = r & 7;
+    return v * D + (j << 9) + ((q >> 1) << 7) + (lane << 1) + (q & 1);
+}
+
+// binary16 -> binary64 is exact (through binary32, subnormals included): an fp16 database scores like the fp64 arithmetic on its values
+__device__ __forceinline__ double half_to_double(_Float16 h) { return (double)(float)h; }
+
 template <typename T>
 struct Quad;
+template <>
+struct Quad<__half> {                  // scan_generic_kernel: 8-byte loads
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    h4 v;
+    __device__ __forceinline__ void load(const __half* p) { v = __builtin_nontemporal_load(reinterpret_cast<const h4*>(p)); }
+    __device__ __forceinline__ double x0() const { return half_to_double(v.x); }
+    __device__ __forceinline__ double x1() const { return half_to_double(v.y); }
+    __device__ __forceinline__ double x2() const { return half_to_double(v.z); }
+    __device__ __forceinline__ double x3() const { return half_to_double(v.w); }
+};
 template <>
 struct Quad<float> {
     float4 v;
@@ -90,6 +110,40 @@ struct Quad<double> {
     __device__ __forceinline__ double x1() const { return a.y; }
     __device__ __forceinline__ double x2() const { return b.x; }
     __device__ __forceinline__ double x3() const { return b.y; }
+};
+
+// What a lane of scan_kernel holds of one wave instruction (1 KB of contiguous memory) and its share of the dot: N consecutive elements of
+// a chunk of 64 N, against the planes of the LDS image of that chunk (tc = the chunk's image + 2 lane: every read is 64 x 16 contiguous bytes).
+template <typename T>
+struct LaneVec : Quad<T> {             // fp32: one 16-byte load, fp64: two; 4 elements of a 256-chunk
+    static constexpr int N = 4;
+    static __device__ __forceinline__ int lds_index(int D, int v, int k) { return t_lds_index(D, v, k); }
+    __device__ __forceinline__ double dot(const double* tc, double p) const {
+        const double2 ta = *reinterpret_cast<const double2*>(tc);
+        const double2 tb = *reinterpret_cast<const double2*>(tc + 128);
+        p = fma(this->x0(), ta.x, p);
+        p = fma(this->x1(), ta.y, p);
+        p = fma(this->x2(), tb.x, p);
+        p = fma(this->x3(), tb.y, p);
+        return p;
+    }
+};
+template <>
+struct LaneVec<__half> {               // fp16: one 16-byte load = 8 elements of a 512-chunk; per element cvt f16->f32, cvt f32->f64, fp64 FMA
+    static constexpr int N = 8;
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    h8 v;
+    static __device__ __forceinline__ int lds_index(int D, int v, int k) { return t_lds_index8(D, v, k); }
+    __device__ __forceinline__ void load(const __half* p) { v = __builtin_nontemporal_load(reinterpret_cast<const h8*>(p)); }
+    __device__ __forceinline__ double dot(const double* tc, double p) const {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const double2 tg = *reinterpret_cast<const double2*>(tc + 128 * g);
+            p = fma(half_to_double(v[2 * g]), tg.x, p);
+            p = fma(half_to_double(v[2 * g + 1]), tg.y, p);
+        }
+        return p;
+    }
 };
 
 struct ScanArgs {
@@ -135,8 +189,8 @@ __device__ __forceinline__ double clip_close_stream(const ScanArgs& a, ClipAcc& 
     return m;
 }
 
-// One wavefront per clip, grid-strided.  S streams x E splits per clip and CH = D/256 chunks per
-// vector are compile-time, so every index is static and everything stays in registers.  The next
+// One wavefront per clip, grid-strided.  S streams x E splits per clip and CH = D/256 (fp16 rows: D/512 wave instructions per
+// vector, LaneVec) are compile-time, so every index is static and everything stays in registers.  The next
 // vector (possibly of the wave's next clip) is in flight while the current one is multiplied, so
 // every wave keeps 2 x CH x 1 KiB of HBM reads outstanding.
 // LEAN (round 6): left alone, the compiler keeps the WHOLE query slice of a lane in registers across clips (the LDS reads do not depend on
@@ -148,7 +202,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 
     extern __shared__ __attribute__((aligned(16))) double t_lds[];
     constexpr int NV = S * E;
     constexpr int D = CH * 256;
-    for (int i = threadIdx.x; i < NV * D; i += blockDim.x) t_lds[t_lds_index(D, i / D, i % D)] = a.t[i];
+    using V = LaneVec<T>;
+    constexpr int CW = 64 * V::N, NCH = D / CW;                        // elements of a wave instruction, instructions per vector
+    for (int i = threadIdx.x; i < NV * D; i += blockDim.x) t_lds[V::lds_index(D, i / D, i % D)] = a.t[i];
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -162,11 +218,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 
         for (int s = 0; s < S; ++s) w[s] = a.w[s];
     }
 
-    Quad<T> cur[CH], nxt[CH];
+    V cur[NCH], nxt[NCH];
     int64_t c = wave;
     if (c < a.n) {
 #pragma unroll
-        for (int j = 0; j < CH; ++j) cur[j].load(feats + c * clip_elems + j * 256 + lane * 4);
+        for (int j = 0; j < NCH; ++j) cur[j].load(feats + c * clip_elems + j * CW + lane * V::N);
     }
     while (c < a.n) {
         if constexpr (LEAN) asm volatile("" ::: "memory");             // the query fragments are read again, not carried over
@@ -178,22 +234,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 
                                        : (cn < a.n ? feats + cn * clip_elems : nullptr);
             if (nb) {
 #pragma unroll
-                for (int j = 0; j < CH; ++j) nxt[j].load(nb + j * 256 + lane * 4);
+                for (int j = 0; j < NCH; ++j) nxt[j].load(nb + j * CW + lane * V::N);
             }
             double p = 0.0;
 #pragma unroll
-            for (int j = 0; j < CH; ++j) {
-                const double2 ta = *reinterpret_cast<const double2*>(&t_lds[v * D + j * 256 + lane * 2]);
-                const double2 tb = *reinterpret_cast<const double2*>(&t_lds[v * D + j * 256 + 128 + lane * 2]);
-                p = fma(cur[j].x0(), ta.x, p);
-                p = fma(cur[j].x1(), ta.y, p);
-                p = fma(cur[j].x2(), tb.x, p);
-                p = fma(cur[j].x3(), tb.y, p);
-            }
+            for (int j = 0; j < NCH; ++j) p = cur[j].dot(&t_lds[v * D + j * CW + lane * 2], p);
             clip_add(a, st, c, v / E, v % E, wave_sum(p), lane);
             if (v % E == E - 1) st.av[v / E] = clip_close_stream(a, st, c, v / E, lane);
 #pragma unroll
-            for (int j = 0; j < CH; ++j) cur[j] = nxt[j];
+            for (int j = 0; j < NCH; ++j) cur[j] = nxt[j];
         }
         if (a.w && lane == 0) a.scores[c] = score_from_avg(st.av, w, S);
         c = cn;
@@ -415,6 +464,30 @@ struct ChunkP<double, P> {
     __device__ __forceinline__ double at(int m, int e) const { return (e & 1) ? v[m][e >> 1].y : v[m][e >> 1].x; }
 };
 
+// fp16 rows: a lane's 16-byte load is 8 consecutive halves, so across the four k-lanes a load instruction still covers 64 contiguous bytes of
+// each clip -- 32 elements, two 16-element pieces: piece m holds elements 32 (m / 2) + 8 kk + 4 (m % 2) + e of the chunk.  The query rows
+// in LDS are stored in that order (batch_query_pos), so the MFMA loop reads them exactly as it does for fp32.  Rows only.
+template <int P>
+struct ChunkP<__half, P> {
+    static_assert(P % 2 == 0, "a 16-byte load of halves is two pieces");
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    h8 v[P / 2];
+    __device__ __forceinline__ void load(const __half* p) {     // p = chunk start + 8 kk; plain loads, as for fp32
+#pragma unroll
+        for (int m = 0; m < P / 2; ++m) v[m] = *reinterpret_cast<const h8*>(p + 32 * m);
+    }
+    __device__ __forceinline__ void load_tiled(const __half* p) { load(p); }   // never used: the tiled layout is fp32 only
+    __device__ __forceinline__ double at(int m, int e) const { return half_to_double(v[m >> 1][4 * (m & 1) + e]); }
+};
+
+// Where element k of a query row sits inside the row in LDS.  The MFMA loop reads position 16 m + 4 kk + e for piece m, k-lane kk, step e;
+// for fp32 / fp64 rows that IS element k.  For fp16 rows the lane holds element 32 (m / 2) + 8 kk + 4 (m % 2) + e there.
+template <typename T>
+__device__ __forceinline__ int batch_query_pos(int k) {
+    if constexpr (sizeof(T) == 2) return (k & ~31) + ((k & 4) << 2) + ((k & 24) >> 1) + (k & 3);
+    return k;
+}
+
 // Where query slot q starts in LDS (in doubles): rows of D doubles plus a swizzle that makes the 32 lanes of a
 // ds_read_b64 group (16 queries x 2 k quarters, 4 doubles apart) hit 32 distinct 8-byte bank slots: D is a multiple
 // of 32, so slot = (q % 4) + 8 (q / 4) + 4 kk + const is a bijection onto 0..31.
@@ -498,7 +571,9 @@ template <typename T, int CH, int TW, bool PRES, int P, bool TILED = false>
 __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) double tq[];      // 16 swizzled rows of D doubles (+ 32 of slack)
     constexpr int D = CH * 256, CE = 16 * P, NCHUNK = D / CE;       // a chunk = P pieces of 16 elements
-    constexpr int NBUF = (sizeof(T) == 4 ? 16 : 8) / P;              // the ring holds 64 VGPRs of features per lane
+    // the ring holds 64 VGPRs of features per lane (fp16 rows: 64 where the vector divides into four 128-element buffers, else 32)
+    constexpr int NBUF = sizeof(T) == 2 ? (NCHUNK % (32 / P) == 0 ? 32 / P : 16 / P) : (sizeof(T) == 4 ? 16 : 8) / P;
+    constexpr int KL = sizeof(T) == 2 ? 8 : 4;                       // consecutive elements a k-lane holds per load
     static_assert(NCHUNK % NBUF == 0, "chunk ring must divide the vector");
     const int lane = threadIdx.x & 63, col = lane & 15, kk = lane >> 4;
     // everything that indexes tiles is wave-uniform: kept on the scalar unit (the register budget of 4 waves per SIMD is
@@ -534,7 +609,7 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
     auto lane_off = [&](int64_t tile) -> uint32_t {
         if (TILED) return (uint32_t)(kk * 64 + col * 4);
         const int last = (int)min((int64_t)15, a.n - 1 - tile * 16);
-        return (uint32_t)(min(col, last) * (int)clip_elems + 4 * kk);
+        return (uint32_t)(min(col, last) * (int)clip_elems + KL * kk);
     };
     ChunkP<T, P> buf[NBUF];
     if (valid_in(0) > 0) {
@@ -565,7 +640,7 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
                 __syncthreads();                                      // every wave is done with the previous slice's rows
                 for (int i = threadIdx.x; i < a.Q * D; i += blockDim.x) {
                     const int q = i / D, k = i - q * D;
-                    tq[query_row(q, D) + k] = a.t[((size_t)q * NV + v) * D + k];
+                    tq[query_row(q, D) + batch_query_pos<T>(k)] = a.t[((size_t)q * NV + v) * D + k];
                 }
                 __syncthreads();
 #pragma unroll
@@ -710,14 +785,14 @@ __global__ __launch_bounds__(256) void scale_query_kernel(const T* feats, int64_
     const int v = blockIdx.x;
     double p = 0.0;
     for (int k = threadIdx.x; k < D; k += blockDim.x) {
-        const double x = (double)feats[feat_index(tiled, row, v, k, NV, D)];
+        const double x = widen(feats[feat_index(tiled, row, v, k, NV, D)]);
         p = fma(x, x, p);
     }
     p = wave_sum(p);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = p;
     __syncthreads();
     const double rr = ((part[0] + part[1]) + part[2]) + part[3];
-    for (int k = threadIdx.x; k < D; k += blockDim.x) t[(int64_t)v * D + k] = (double)feats[feat_index(tiled, row, v, k, NV, D)] / rr;
+    for (int k = threadIdx.x; k < D; k += blockDim.x) t[(int64_t)v * D + k] = widen(feats[feat_index(tiled, row, v, k, NV, D)]) / rr;
 }
 
 // counter-based synthetic rows (shared with oracle/sim_oracle.py::synth_features)
@@ -740,7 +815,15 @@ __global__ void generate_kernel(T* feats, int64_t total, uint64_t seed_mul, uint
         if (k >= total) break;
         const int s = (int)((k / per_stream) % S);
         const float u = (float)synth_u24(seed_mul, idx0 + (uint64_t)k) * 5.9604644775390625e-08f;  // 2^-24
-        feats[k] = (T)(u * scales[s]);
+        if constexpr (sizeof(T) == 2) {
+            // the fp32 value of the other storage types, THEN rounded to nearest even (subnormal halves are kept).  The product is made
+            // opaque: left alone the compiler folds multiply and conversion into one v_fma_mixlo_f16, which rounds the exact product once
+            float x = u * scales[s];
+            asm volatile("" : "+v"(x));
+            feats[k] = __float2half_rn(x);
+        } else {
+            feats[k] = (T)(u * scales[s]);
+        }
     }
 }
 
@@ -1181,7 +1264,8 @@ __global__ __launch_bounds__(kTopkSmallThreads) void topk_small_kernel(const dou
 
 // rows of the database -> a dense [cnt][row_elems] block (vq_db_read_rows: the few validated clips a sharded round sends to the
 // rank that solves the bootstrapping problems).  16 bytes per thread.
-__global__ void gather_rows_kernel(const uint4* feats, const int64_t* rows, int64_t cnt, int64_t row_vec16, uint4* out, int tiled_nv, int tiled_d4) {
+template <typename U>       // U = uint4: rows of whole 16-byte units; uint2: fp16 rows whose D is no multiple of 8 (8-byte units, rows layout)
+__global__ void gather_rows_kernel(const U* feats, const int64_t* rows, int64_t cnt, int64_t row_vec16, U* out, int tiled_nv, int tiled_d4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cnt * row_vec16) return;
     const int64_t r = i / row_vec16, k = i - r * row_vec16;
@@ -1262,7 +1346,7 @@ struct vq_db {
     int batch_q = 0;                 // queries of the last batched scan
     double* grid_buf = nullptr;      // scratch for grid / gathers
     int64_t grid_cap = 0;
-    size_t elem() const { return dtype == VQ_F64 ? 8 : 4; }
+    size_t elem() const { return dtype == VQ_F64 ? 8 : dtype == VQ_F16 ? 2 : 4; }
 };
 
 static int db_free(vq_db* db) {
@@ -1278,16 +1362,21 @@ static int ensure_grid_buf(vq_db* db, int64_t bytes);
 
 // rows (by number) -> a dense row-major [L][S][E][D] block in the handle's scratch, whatever the layout; caller holds the lock
 static int gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense) {
-    const int64_t row_bytes = (int64_t)db->S * db->E * db->D * (int64_t)db->elem();      // D % 4 == 0: whole 16-byte pieces
+    const int64_t row_bytes = (int64_t)db->S * db->E * db->D * (int64_t)db->elem();      // D % 4 == 0: whole 16-byte pieces (fp16: 8-byte)
     const int64_t rb = ((int64_t)L * 8 + 15) / 16 * 16;
     const int rc = ensure_grid_buf(db, rb + (int64_t)L * row_bytes);
     if (rc != VQ_OK) return rc;
     char* base = (char*)db->grid_buf;
     VQ_HIP(hipMemcpyAsync(base, rows_host, (size_t)L * 8, hipMemcpyHostToDevice, db->stream));
-    const int64_t vec = row_bytes / 16;
     const bool tiled = db->layout == VQ_LAYOUT_TILED;
-    gather_rows_kernel<<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint4*)db->feats, (const int64_t*)base, L, vec, (uint4*)(base + rb),
-                                                                            tiled ? db->S * db->E : 0, db->D / 4);
+    if (row_bytes % 16) {
+        const int64_t vec = row_bytes / 8;
+        gather_rows_kernel<uint2><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint2*)db->feats, (const int64_t*)base, L, vec, (uint2*)(base + rb), 0, 0);
+    } else {
+        const int64_t vec = row_bytes / 16;
+        gather_rows_kernel<uint4><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint4*)db->feats, (const int64_t*)base, L, vec, (uint4*)(base + rb),
+                                                                                      tiled ? db->S * db->E : 0, db->D / 4);
+    }
     VQ_CHECK_LAUNCH();
     *dense = base + rb;
     return VQ_OK;
@@ -1415,7 +1504,7 @@ int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int3
     VQ_REQUIRE(S <= 8, "at most 8 streams are supported (got %d)", S);
     VQ_REQUIRE(S * E <= 64, "S*E must be <= 64 (got %d)", S * E);
     VQ_REQUIRE(D % 4 == 0, "D must be a multiple of 4 (got %d)", D);
-    VQ_REQUIRE(dtype == VQ_F32 || dtype == VQ_F64, "dtype must be VQ_F32 or VQ_F64");
+    VQ_REQUIRE(dtype == VQ_F32 || dtype == VQ_F64 || dtype == VQ_F16, "dtype must be VQ_F32, VQ_F64 or VQ_F16");
     VQ_REQUIRE(n < (1ll << 31) * (long long)SEL_CHUNK, "n too large");
     int ndev = 0;
     VQ_HIP(hipGetDeviceCount(&ndev));
@@ -1577,7 +1666,11 @@ int vq_db_generate(vq_db* db, uint64_t seed, int64_t global_row0, const float* s
     const int64_t threads = (total + 3) / 4;
     const int64_t blocks = (threads + 255) / 256;
     VQ_REQUIRE(blocks < (1ll << 31), "DB too large for one generate launch");
-    if (db->dtype == VQ_F32)
+    if (db->dtype == VQ_F16)
+        generate_kernel<__half><<<(unsigned)blocks, 256, 0, db->stream>>>((__half*)db->feats, total, seed_mul,
+                                                                           (uint64_t)(global_row0 * per_row),
+                                                                           db->E * db->D, db->S, scales_dev);
+    else if (db->dtype == VQ_F32)
         generate_kernel<float><<<(unsigned)blocks, 256, 0, db->stream>>>((float*)db->feats, total, seed_mul,
                                                                           (uint64_t)(global_row0 * per_row),
                                                                           db->E * db->D, db->S, scales_dev);
@@ -1653,7 +1746,9 @@ int vq_db_set_query_from_row(vq_db* db, int64_t row, double* t_out_host) {
     std::lock_guard<std::mutex> lk(db->mu);
     DeviceGuard g(db->device);
     const int NV = db->S * db->E;
-    if (db->dtype == VQ_F32)
+    if (db->dtype == VQ_F16)
+        scale_query_kernel<__half><<<NV, 256, 0, db->stream>>>((const __half*)db->feats, row, NV, db->D, db->t, false);
+    else if (db->dtype == VQ_F32)
         scale_query_kernel<float><<<NV, 256, 0, db->stream>>>((const float*)db->feats, row, NV, db->D, db->t, db->layout == VQ_LAYOUT_TILED);
     else
         scale_query_kernel<double><<<NV, 256, 0, db->stream>>>((const double*)db->feats, row, NV, db->D, db->t, false);
@@ -1690,7 +1785,11 @@ static int launch_scan_t(vq_db* db, const ScanArgs& a) {
     static const int force_lean = getenv("VQ_SCAN_LEAN") ? atoi(getenv("VQ_SCAN_LEAN")) : -1;
     // (measured, MI355X, fp32 rows, lean against not: 10 000 clips x 2 x 3: 49 against 59 us; 50 000: 0.77 against 0.72 of the HBM peak; 1 M x 2 x 3:
     // 0.81 against 0.76; 1 M x 2 x 5: 0.81 against 0.82; fp64 rows 200 000 x 2 x 3: 0.75 against 0.76)
-    const bool lean = force_lean >= 0 ? force_lean != 0 : (a.n < (int64_t)db->cus * per_cu * 4 * 16 || (sizeof(T) == 4 && S * E <= 6));
+    // fp16 rows: always lean.  The streaming instantiation holds the same 256-380 VGPRs of query (one wave per SIMD) but has half the bytes per
+    // vector in flight and three instructions per element to hide: 1 M x 2 x 5: 3.54 against 5.67 ms (0.72 against 0.45 of the HBM peak);
+    // 1 M x 2 x 3: 1.95 against 2.57 ms; 50 000 x 2 x 5: 0.18 against 0.30 ms; 10 000 x 2 x 3: 31 against 43 us
+    const bool lean = force_lean >= 0 ? force_lean != 0
+                                      : (sizeof(T) == 2 || a.n < (int64_t)db->cus * per_cu * 4 * 16 || (sizeof(T) == 4 && S * E <= 6));
     if (lean) {
         auto kern = scan_kernel<T, S, E, CH, true>;
         VQ_DYN_LDS(kern, lds);
@@ -1730,6 +1829,16 @@ static int launch_scan(vq_db* db, const ScanArgs& a) {
     scan_generic_kernel<T><<<grid, 256, 0, db->stream>>>(a);
     VQ_CHECK_LAUNCH();
     return VQ_OK;
+}
+
+// the one dispatch on the storage type (vq_db_scan and vq_db_query_round: the same kernels, the same bits)
+static int launch_scan_dtype(vq_db* db, const ScanArgs& a) {
+    switch (db->dtype) {
+        case VQ_F16: return launch_scan<__half>(db, a);
+        case VQ_F32: return launch_scan<float>(db, a);
+        case VQ_F64: return launch_scan<double>(db, a);
+    }
+    return fail(VQ_E_STATE, "internal: database of unknown dtype %d", db->dtype);
 }
 
 static int run_select(vq_db* db, const SelPred& pred, int64_t limit1, int64_t host_result[3], bool with_prefix = false) {
@@ -1779,13 +1888,26 @@ int vq_db_scan(vq_db* db, const double* w_host, int32_t keep_sims) {
     a.S = db->S;
     a.E = db->E;
     a.D = db->D;
-    const int rc = db->dtype == VQ_F32 ? launch_scan<float>(db, a) : launch_scan<double>(db, a);
+    const int rc = launch_scan_dtype(db, a);
     if (rc != VQ_OK) return rc;
     db->have_avg = true;
     db->have_sims = keep_sims != 0;
     db->have_scores = w_host != nullptr;
     return VQ_OK;
 }
+
+}  // extern "C"
+
+// the instantiation of the 16-query pass for a database (the tiled branch does not exist for fp16 rows)
+template <typename T, int CH, int TW>
+static auto fused_kernel_for(bool pres, bool tiled) -> void (*)(BatchFusedArgs) {
+    if constexpr (sizeof(T) != 2) {
+        if (tiled) return pres ? batch_fused_kernel<T, CH, TW, true, 8, true> : batch_fused_kernel<T, CH, TW, false, 8, true>;
+    }
+    return pres ? batch_fused_kernel<T, CH, TW, true, 8> : batch_fused_kernel<T, CH, TW, false, 8>;
+}
+
+extern "C" {
 
 int vq_db_scan_batch(vq_db* db, int32_t n_queries, const double* t_host, const double* w_host, double* scores_host) {
     VQ_REQUIRE(db && t_host && w_host, "NULL argument");
@@ -1832,12 +1954,13 @@ int vq_db_scan_batch(vq_db* db, int32_t n_queries, const double* t_host, const d
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
 #define VQ_FUSED_LAUNCH(T, CH)                                                                                             \
     {                                                                                                                      \
-        auto kern = db->present ? batch_fused_kernel<T, CH, TW, true, 8> : batch_fused_kernel<T, CH, TW, false, 8>;       \
-        if (tiled) kern = db->present ? batch_fused_kernel<T, CH, TW, true, 8, true> : batch_fused_kernel<T, CH, TW, false, 8, true>; \
+        auto kern = fused_kernel_for<T, CH, TW>(db->present != nullptr, tiled);                                            \
         VQ_DYN_LDS(kern, (kBatchSlots * CH * 256 + 32) * 8);                                                                \
         kern<<<blocks, 1024, lds, db->stream>>>(f);                                                                        \
     }
-        if (db->dtype == VQ_F32) {
+        if (db->dtype == VQ_F16) {
+            if (ch == 4) VQ_FUSED_LAUNCH(__half, 4) else if (ch == 3) VQ_FUSED_LAUNCH(__half, 3) else if (ch == 2) VQ_FUSED_LAUNCH(__half, 2) else VQ_FUSED_LAUNCH(__half, 1)
+        } else if (db->dtype == VQ_F32) {
             if (ch == 4) VQ_FUSED_LAUNCH(float, 4) else if (ch == 3) VQ_FUSED_LAUNCH(float, 3) else if (ch == 2) VQ_FUSED_LAUNCH(float, 2) else VQ_FUSED_LAUNCH(float, 1)
         } else {
             if (ch == 4) VQ_FUSED_LAUNCH(double, 4) else if (ch == 3) VQ_FUSED_LAUNCH(double, 3) else if (ch == 2) VQ_FUSED_LAUNCH(double, 2) else VQ_FUSED_LAUNCH(double, 1)
@@ -1968,7 +2091,7 @@ int vq_db_set_layout(vq_db* db, int32_t layout) {
     if (layout == db->layout) return VQ_OK;
     if (layout == VQ_LAYOUT_TILED) {
         if (db->dtype != VQ_F32 || !fast_scan_shape(db))
-            return fail(VQ_E_UNSUPPORTED, "the tiled layout exists for fp32 databases with D = 1024, S <= 2, E <= 5 (got dtype %d, D %d, S %d, E %d)", db->dtype,
+            return fail(VQ_E_UNSUPPORTED, "the tiled layout exists for fp32 databases (not fp16 / fp64) with D = 1024, S <= 2, E <= 5 (got dtype %d, D %d, S %d, E %d)", db->dtype,
                         db->D, db->S, db->E);
         if (!db->owns_feats || db->feats_exposed)
             return fail(VQ_E_STATE, "the feature block is not the library's alone (adopted, or its address was handed out): it stays row-major");
@@ -2161,7 +2284,7 @@ int vq_db_query_round(vq_db* db, void* block, int64_t block_bytes, int32_t flags
         a.S = db->S;
         a.E = db->E;
         a.D = db->D;
-        const int rc = db->dtype == VQ_F32 ? launch_scan<float>(db, a) : launch_scan<double>(db, a);
+        const int rc = launch_scan_dtype(db, a);
         if (rc != VQ_OK) return rc;
         db->have_avg = true;
         db->have_scores = do_scores;

@@ -16,7 +16,9 @@ from typing import Iterable, Mapping, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import VQ_F32, VQ_F64, call
+from ._lib import VQ_F16, VQ_F32, VQ_F64, call
+
+_VQ_DTYPE = {np.dtype(np.float16): VQ_F16, np.dtype(np.float32): VQ_F32, np.dtype(np.float64): VQ_F64}
 
 
 def _np_ptr(a: np.ndarray):
@@ -51,18 +53,19 @@ class RoundResult:
 
 
 class FeatureDB:
-    """N clips x S streams x E ensemble slots x D floats, resident on ``device``."""
+    """N clips x S streams x E ensemble slots x D floats, resident on ``device``.  ``dtype`` is how the block is STORED: float32, float64
+    or (opt-in) float16 -- half the bytes per query and per clip; values are rounded once on the way in and every result is what the
+    fp64 arithmetic gives on the rounded values."""
 
     def __init__(self, n: int, n_streams: int, n_splits: int, dim: int = 1024, dtype=np.float32, device: int = 0,
                  clip_ids: Sequence[int] | None = None):
         self.n, self.S, self.E, self.D = int(n), int(n_streams), int(n_splits), int(dim)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("FeatureDB dtype must be float32 or float64")
+        if self.dtype not in _VQ_DTYPE:
+            raise TypeError("FeatureDB dtype must be float32, float64 or float16")
         self.device = int(device)
         self._h = C.c_void_p()
-        call("vq_db_create", self.n, self.S, self.E, self.D, VQ_F64 if self.dtype == np.float64 else VQ_F32,
-             self.device, C.byref(self._h))
+        call("vq_db_create", self.n, self.S, self.E, self.D, _VQ_DTYPE[self.dtype], self.device, C.byref(self._h))
         self.clip_ids = (np.arange(1, self.n + 1, dtype=np.int64) if clip_ids is None
                          else np.asarray(clip_ids, dtype=np.int64).copy())
         if self.clip_ids.shape != (self.n,):
@@ -80,14 +83,16 @@ class FeatureDB:
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_arrays(cls, feats: np.ndarray, clip_ids=None, present=None, device: int = 0) -> "FeatureDB":
+    def from_arrays(cls, feats: np.ndarray, clip_ids=None, present=None, device: int = 0, dtype=None) -> "FeatureDB":
+        """Without ``dtype`` the block is stored as it comes if it is float32 / float64 and as float32 otherwise (float16 input
+        included); ``dtype`` says how to store it -- ``np.float16`` keeps halves as they are and rounds anything else (upload)."""
         feats = np.asarray(feats)
         if feats.ndim != 4:
             raise ValueError("feats must be [N,S,E,D]")
-        if feats.dtype not in (np.float32, np.float64):
+        if dtype is None and feats.dtype not in (np.float32, np.float64):
             feats = feats.astype(np.float32)
         n, s, e, d = feats.shape
-        db = cls(n, s, e, d, feats.dtype, device, clip_ids)
+        db = cls(n, s, e, d, feats.dtype if dtype is None else dtype, device, clip_ids)
         db.upload(0, feats)
         if present is not None:
             db.set_present(present)
@@ -128,7 +133,9 @@ class FeatureDB:
                 for vec in cand[st][sp].values():
                     dim = len(vec)
                     break
-        feats = np.zeros((n, len(stream_list), n_slots, dim), dtype=dtype)
+        # a float16 database is the float64 block rounded once (upload), never a double rounding through another type
+        host_dtype = np.float64 if np.dtype(dtype) == np.float16 else dtype
+        feats = np.zeros((n, len(stream_list), n_slots, dim), dtype=host_dtype)
         present = np.zeros((n, len(stream_list), n_slots), dtype=np.uint8)
         for si, (st, sps) in enumerate(zip(stream_list, slot_splits)):
             for ei, sp in enumerate(sps):
@@ -136,7 +143,7 @@ class FeatureDB:
                 if not d:
                     continue
                 rows = np.fromiter((order[c] for c in d), dtype=np.int64, count=len(d))
-                feats[rows, si, ei] = np.asarray(list(d.values()), dtype=dtype)
+                feats[rows, si, ei] = np.asarray(list(d.values()), dtype=host_dtype)
                 present[rows, si, ei] = 1
         db = cls(n, len(stream_list), n_slots, dim, dtype, device,
                  np.fromiter(order.keys(), dtype=np.int64, count=n))
@@ -182,6 +189,11 @@ class FeatureDB:
 
     # ------------------------------------------------------------------ data movement
     def upload(self, row0: int, feats: np.ndarray):
+        """Rows [row0, row0 + len(feats)) from the host, converted to the database's dtype.  Into a float16 database: round to nearest
+        even; a finite value no half can hold raises ``ValueError`` (feature_store.to_float16)."""
+        if self.dtype == np.float16:
+            from .feature_store import to_float16
+            feats = to_float16(feats)
         a = np.ascontiguousarray(feats, dtype=self.dtype)
         if a.shape[1:] != (self.S, self.E, self.D):
             raise ValueError("rows must be [n,%d,%d,%d]" % (self.S, self.E, self.D))
@@ -189,7 +201,7 @@ class FeatureDB:
 
     def set_layout(self, layout: str):
         """"rows" ([N][S][E][D]) or "tiled" ([tile of 16 clips][S*E][D/4][clip][4]: the order in which every load of the scans
-        takes whole lines; fp32, D = 1024, S <= 2, E <= 5).  In place, one sweep of the block: call once after loading."""
+        takes whole lines; fp32 only, D = 1024, S <= 2, E <= 5).  In place, one sweep of the block: call once after loading."""
         call("vq_db_set_layout", self._h, {"rows": _lib.VQ_LAYOUT_ROWS, "tiled": _lib.VQ_LAYOUT_TILED}[layout])
 
     @property

@@ -5,7 +5,7 @@ src/models/ticket.py:358-382: ``{dnn_stream_id, dnn_stream_split, name, video_cl
 (clip, stream, split)) after ``load_db`` parsed the CSV tree (src/api/api_load_records.py:41-61).  At the 1M-clip
 scale of BASELINE configs[3] that is 10 G floats of JSON.  The store keeps the same information as
 
-    <dir>/features.npy   [N][S][E][D] float32 (or float64), C order -- the FeatureDB block, memory-mappable
+    <dir>/features.npy   [N][S][E][D] float32 (or float64, or float16), C order -- the FeatureDB block, memory-mappable
     <dir>/clip_ids.npy   [N] int64, row order = the order the reference would first meet the clips
     <dir>/present.npy    [N][S][E] uint8 (only when some (clip, stream, split) is missing)
     <dir>/meta.json      {"streams": [...], "splits": [...], "feature_name": "global_pool", "dim": D}
@@ -24,11 +24,27 @@ import numpy as np
 from .tsn import feature_csv
 
 
+def to_float16(a) -> np.ndarray:
+    """``a`` as binary16: numpy's ``astype`` (round to nearest even) plus the check it lacks -- a finite value that no half can hold
+    (it would become +-inf: |x| >= 65520) raises ``ValueError`` naming the first such index.  The one host-side conversion of every
+    fp16 route (FeatureDB, the store)."""
+    a = np.asarray(a)
+    if a.dtype == np.float16:
+        return a
+    with np.errstate(over="ignore"):
+        h = a.astype(np.float16)
+    bad = np.isinf(h) & np.isfinite(a)
+    if bad.any():
+        idx = tuple(int(i) for i in np.argwhere(bad)[0])
+        raise ValueError("value %r at index %r does not fit float16 (largest finite value 65504)" % (float(a[idx]), idx))
+    return h
+
+
 def save_store(path: str, feats: np.ndarray, clip_ids: Sequence[int], streams: Sequence[str], splits: Sequence[int],
                feature_name: str = "global_pool", present: np.ndarray | None = None) -> str:
     feats = np.asarray(feats)
-    if feats.ndim != 4 or feats.dtype not in (np.float32, np.float64):
-        raise ValueError("feats must be [N,S,E,D] float32/float64")
+    if feats.ndim != 4 or feats.dtype not in (np.float16, np.float32, np.float64):
+        raise ValueError("feats must be [N,S,E,D] float16/float32/float64")
     n, s, e, d = feats.shape
     clip_ids = np.asarray(clip_ids, dtype=np.int64)
     if clip_ids.shape != (n,) or len(streams) != s or len(splits) != e:
@@ -70,7 +86,7 @@ def store_from_csv_tree(features_dir: str, out: str, streams: Sequence[str] = fe
     """``<features_dir>/<video>/<name ending in the split digit>/<stream>_<blob>_features.csv`` (the layout
     ``load_db`` walks, src/api/load_db.py:10-28 + api_load_records.py:41-61) -> a store.  Clips of successive videos
     (sorted by name) get ids ``clip_id_base + running index + 1`` in (video, clip number) order; a (clip, stream, split)
-    without a row is marked absent."""
+    without a row is marked absent.  ``dtype=np.float16`` rounds to nearest even and refuses values no half can hold (to_float16)."""
     per_video = []
     all_splits = set()
     for video in sorted(d for d in os.listdir(features_dir) if os.path.isdir(os.path.join(features_dir, d))):
@@ -106,7 +122,7 @@ def store_from_csv_tree(features_dir: str, out: str, streams: Sequence[str] = fe
                 if sp in by_split and st in by_split[sp]:
                     cl, f, _m = by_split[sp][st]
                     rows = np.array([local[int(c)] for c in cl], dtype=np.int64)
-                    feats[rows, si, ei] = f.astype(dtype)
+                    feats[rows, si, ei] = to_float16(f) if feats.dtype == np.float16 else f.astype(dtype)
                     present[rows, si, ei] = 1
         row0 += len(clips)
     save_store(out, feats, ids, streams, splits, present=present)

@@ -257,7 +257,10 @@ class ShardedFeatureDB:
 
     def _sum(self, arr: np.ndarray) -> np.ndarray:
         """All-reduce SUM of an array in which every element is non-zero on at most one rank (x + 0 is exact)."""
-        t = self._torch.from_numpy(np.ascontiguousarray(arr)).to(self._cdev)
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype == np.float16:                       # rows of a float16 database travel widened (exact; every half, subnormal ones
+            return self._sum(arr.astype(np.float32)).astype(np.float16)     # included, is a normal float32) and come back as they were
+        t = self._torch.from_numpy(arr).to(self._cdev)
         self._coll(lambda: self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self.group))
         return self._host(t)
 
