@@ -173,6 +173,9 @@ int vq_db_bootstrap_target(vq_db* db, const int64_t* valid_rows, int32_t n_valid
  * if w != NULL also score[c] = 1 - sqrt(sum_s (w_s (1 - avg))^2 / sum_s w_s^2).
  * Replaces Ticket.compute_similarities (ticket.py:120-163) + compute_scores (ticket.py:165-180).
  * keep_sims != 0 additionally keeps the per-split dot products for vq_db_read_similarities. */
+/* SEARCH SETS (vq_amd_rows.h, included below): with a row view in use (vq_db_rows_define / vq_db_rows_use) this scan and every
+ * entry point behind it down to vq_db_min_score run over the view's M rows only -- compact [M] results, rows given and returned
+ * as positions in the view; vq_db_scan_batch then returns VQ_E_UNSUPPORTED.  With no view in use nothing changes. */
 int vq_db_scan(vq_db* db, const double* w_host, int32_t keep_sims);
 /* score[c] from the cached avg[N][S] (no DB read): Ticket.compute_scores, ticket.py:165-180. */
 /* Batched scan: n_queries (<= 16) queries in ONE pass over the database -- the all-pairs form of the scan for a broker
@@ -598,4 +601,5 @@ int vq_broadcast_query(vq_comm* comm, void* buf_dev, int64_t bytes, int32_t root
 #ifdef __cplusplus
 }
 #endif
+#include "vq_amd_rows.h"      /* row views: search sets on one resident database (additive to ABI 12) */
 #endif /* VQ_AMD_H */

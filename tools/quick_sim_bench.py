@@ -72,3 +72,56 @@ def bench_batched(n=1_000_000, s=2, e=5, d=1024, q=16, reps=6, dtype=np.float32)
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "batched":
     bench_batched()
     bench_batched(dtype=np.float16)
+
+
+def _timed_scan(db, w, tm):
+    call("vq_timer_start", tm, None)
+    db.scan(weights=w)
+    call("vq_timer_stop", tm, None)
+    ms = C.c_float()
+    call("vq_timer_elapsed_ms", tm, C.byref(ms))
+    return ms.value
+
+
+def bench_view(n=1_000_000, s=2, e=5, d=1024, frac=10, run=100, reps=40, dtype=np.float32):
+    """The scan over a search set of M = N / frac rows of an N-row database, against the scan of a plain M-row database on the same
+    box (what a database per search set costs): one contiguous run; runs of `run` rows (a video) spread evenly; the same runs on the
+    tiled layout.  The two handles are timed in turn, `reps` times; medians.  GB/s counts the bytes the M clips NEED (their rows and
+    their scores), not what a tiled scan reads of the tiles it touches."""
+    m = n // frac
+    w = [1.0, 1.5][:s]
+    big = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=dtype)
+    small = vqa.FeatureDB.synthetic(m, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=dtype)
+    for db in (big, small):
+        db.set_query_from_row(7, want=False)
+    starts = (np.arange(m // run) * (n // (m // run))).astype(np.int64)
+    runs = (starts[:, None] + np.arange(run)[None, :]).reshape(-1)
+    big.define_search_rows("contiguous", np.arange(n // 3, n // 3 + m))
+    big.define_search_rows("runs", runs)
+    need = m * s * e * d * np.dtype(dtype).itemsize + m * 8
+    tm = C.c_void_p()
+    call("vq_timer_create", C.byref(tm))
+    print("view scan, N=%d M=%d S=%d E=%d %s (%d timed scans each, in turn with the plain M-row database)" % (n, m, s, e, np.dtype(dtype).name, reps), flush=True)
+    for layout, name in (("rows", "contiguous"), ("rows", "runs"), ("tiled", "runs")):
+        big.use_search_set(None)
+        big.set_layout(layout)
+        big.use_search_set(name)
+        for db in (big, small):
+            for _ in range(3):
+                db.scan(weights=w)
+        tv, tp = [], []
+        for _ in range(reps):
+            tp.append(_timed_scan(small, w, tm))
+            tv.append(_timed_scan(big, w, tm))
+        mv, mp = sorted(tv)[reps // 2], sorted(tp)[reps // 2]
+        touched = np.unique(big.use_search_set(name).rows >> 4).size * 16 if layout == "tiled" else m
+        print("  %-5s %-10s: view %.3f ms (best %.3f), plain M-row database %.3f ms (best %.3f): ratio %.3f; %.0f GB/s of needed bytes (%.2f of 8 TB/s), "
+              "reads %.2f x the rows needed" % (layout, name if name == "contiguous" else "runs of %d" % run, mv, min(tv), mp, min(tp), mv / mp,
+                                                need / mv / 1e6, need / mv / 1e6 / 8000, touched / m), flush=True)
+    big.close()
+    small.close()
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "view":
+    bench_view(s=2, e=5)
+    bench_view(s=2, e=3)

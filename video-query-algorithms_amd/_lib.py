@@ -117,6 +117,11 @@ SIGNATURES = {
     "vq_allgather_features": [_P, _P, _I64, _P, _P], "vq_allgather_scores": [_P, _P, _I64, _P, _P],
     "vq_broadcast_query": [_P, _P, _I64, _I32, _P],
 }
+# include/vq_amd_rows.h: row views (search sets on one resident database) -- additive to ABI 12, bound like the table above
+ROW_VIEW_SIGNATURES = {
+    "vq_db_rows_define": [_P, _P, _I64, _pI32], "vq_db_rows_use": [_P, _I32], "vq_db_rows_drop": [_P, _I32],
+    "vq_db_rows_active": [_P, _pI32, _pI64],
+}
 _SPECIAL = {"vq_last_error": ([], C.c_char_p), "vq_abi_version": ([], C.c_int)}
 
 _lib = None
@@ -169,7 +174,7 @@ def load(path: str | None = None):
         for name, (args, res) in _SPECIAL.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, res
-        for name, args in SIGNATURES.items():
+        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = ABI mismatch; fail loudly
             fn.argtypes, fn.restype = args, C.c_int
         if lib.vq_abi_version() != ABI_VERSION:

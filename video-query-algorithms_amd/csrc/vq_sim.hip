@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "vq_common.h"
@@ -159,6 +160,18 @@ struct ScanArgs {
     int32_t S, E, D;
 };
 
+// A row view (vq_db_rows_define / vq_db_rows_use): the one-query scan over M chosen rows of the database, in database order, as if it
+// held only those.  Work item i of the row-major kernels reads clip items[i] and writes avg / ne / sims / scores at POSITION i (n = M: the
+// result arrays are compact); the presence mask stays indexed by database row.  A tiled database cannot gather rows (a clip is 16-byte
+// pieces of its tile): there work item i is the touched tile items[i], read whole as ever, and lane (clip j of the tile) stores only if
+// pos[16 i + j] >= 0 -- its clip's position in the view (n stays the database's N there, n_items = touched tiles).  The arithmetic per clip
+// is the full scan's, operation for operation: a clip scores the same bits under a view.
+struct ScanViewArgs : ScanArgs {
+    const int64_t* items;     // [M] rows, strictly ascending | tiled: [n_items] touched tiles, ascending
+    const int64_t* pos;       // tiled: [n_items][16] position in the view, or -1
+    int64_t n_items;          // M | touched tiles
+};
+
 // Per-clip bookkeeping, carried by every lane (wave-uniform values): ensemble mean
 // (ticket.py:155-160: sequential sum over the splits present, divided by their count) and the
 // weighted score (ticket.py:172-180).
@@ -176,6 +189,16 @@ __device__ __forceinline__ void clip_add(const ScanArgs& a, ClipAcc& st, int64_t
         ++st.cnt;
     }
     if (a.sims && lane == 0) a.sims[idx] = sim;
+}
+
+// the same under a row view: the presence bits are the database row's, the result goes to the position in the view
+__device__ __forceinline__ void clip_add_view(const ScanArgs& a, ClipAcc& st, int64_t pos, int64_t row, int s, int e, double sim, int lane) {
+    const bool p = a.present ? a.present[(row * a.S + s) * a.E + e] != 0 : true;
+    if (p) {
+        st.acc = st.acc + sim;
+        ++st.cnt;
+    }
+    if (a.sims && lane == 0) a.sims[(pos * a.S + s) * a.E + e] = sim;
 }
 
 __device__ __forceinline__ double clip_close_stream(const ScanArgs& a, ClipAcc& st, int64_t c, int s, int lane) {
@@ -197,8 +220,14 @@ __device__ __forceinline__ double clip_close_stream(const ScanArgs& a, ClipAcc& 
 // the clip: 192-320 VGPRs, one wave per SIMD) -- right for a database of a million clips, where every wave streams for milliseconds, and wrong
 // for one of ten thousand (configs[0]: three clips per wave), whose scan then runs at 4.3 TB/s with 4 waves per compute unit in flight.  The
 // LEAN instantiation re-reads the query from LDS for every clip and fits three waves per SIMD (what the 48 KB LDS image allows per unit).
-template <typename T, int S, int E, int CH, bool LEAN = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 1, LEAN ? 3 : 8))) void scan_kernel(ScanArgs a) {
+// VIEW: c walks the positions of a row view and r is the database row read (ScanViewArgs).  The position is kept wave-uniform on the
+// scalar unit, so the row list is read with scalar loads: they do not enter the in-order vector-memory queue, whose waits stay those of the
+// plain scan (a vector index load between the feature loads made the compiler drain the queue once per clip: 4-5 % of the scan).  The
+// row of the item after the next is fetched a whole clip before its address is needed (index clamped, no branch), so the prefetch of
+// the next clip never waits on an index load.
+template <typename T, int S, int E, int CH, bool LEAN = false, bool VIEW = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 1, LEAN ? 3 : 8))) void scan_kernel(
+    std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double t_lds[];
     constexpr int NV = S * E;
     constexpr int D = CH * 256;
@@ -220,18 +249,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 
 
     V cur[NCH], nxt[NCH];
     int64_t c = wave;
+    int64_t r = 0, rn = 0;                                             // VIEW: the rows of item c and of item c + nwaves
+    if constexpr (VIEW) {
+        c = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (c < a.n) {
+            r = a.items[c];
+            rn = a.items[min(c + nwaves, a.n - 1)];
+        }
+    }
     if (c < a.n) {
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) cur[j].load(feats + c * clip_elems + j * CW + lane * V::N);
+        for (int j = 0; j < NCH; ++j) cur[j].load(feats + (VIEW ? r : c) * clip_elems + j * CW + lane * V::N);
     }
     while (c < a.n) {
         if constexpr (LEAN) asm volatile("" ::: "memory");             // the query fragments are read again, not carried over
         const int64_t cn = c + nwaves;
+        int64_t rnn = 0;
+        if constexpr (VIEW) rnn = a.items[min(cn + nwaves, a.n - 1)];  // needed one clip from now
         ClipAcc st;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            const T* nb = (v + 1 < NV) ? feats + c * clip_elems + (int64_t)(v + 1) * D
-                                       : (cn < a.n ? feats + cn * clip_elems : nullptr);
+            const T* nb = (v + 1 < NV) ? feats + (VIEW ? r : c) * clip_elems + (int64_t)(v + 1) * D
+                                       : (cn < a.n ? feats + (VIEW ? rn : cn) * clip_elems : nullptr);
             if (nb) {
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) nxt[j].load(nb + j * CW + lane * V::N);
@@ -239,19 +278,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEAN ? 3 : 
             double p = 0.0;
 #pragma unroll
             for (int j = 0; j < NCH; ++j) p = cur[j].dot(&t_lds[v * D + j * CW + lane * 2], p);
-            clip_add(a, st, c, v / E, v % E, wave_sum(p), lane);
+            if constexpr (VIEW) clip_add_view(a, st, c, r, v / E, v % E, wave_sum(p), lane);
+            else clip_add(a, st, c, v / E, v % E, wave_sum(p), lane);
             if (v % E == E - 1) st.av[v / E] = clip_close_stream(a, st, c, v / E, lane);
 #pragma unroll
             for (int j = 0; j < NCH; ++j) cur[j] = nxt[j];
         }
         if (a.w && lane == 0) a.scores[c] = score_from_avg(st.av, w, S);
         c = cn;
+        if constexpr (VIEW) {
+            r = rn;
+            rn = rnn;
+        }
     }
 }
 
 // Any shape with D % 4 == 0: runtime loops, query read from global memory (L2-resident).
-template <typename T>
-__global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a) {
+template <typename T, bool VIEW = false>
+__global__ __launch_bounds__(256) void scan_generic_kernel(std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -260,12 +304,16 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a) {
     double w[8];
     if (a.w)
         for (int s = 0; s < a.S; ++s) w[s] = a.w[s];
-    for (int64_t c = wave; c < a.n; c += nwaves) {
+    int64_t c0 = wave;
+    if constexpr (VIEW) c0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int64_t c = c0; c < a.n; c += nwaves) {
+        int64_t r = c;                                                 // the row read; c stays where the results go
+        if constexpr (VIEW) r = a.items[c];
         ClipAcc st;
         for (int s = 0; s < a.S; ++s) {
             for (int e = 0; e < a.E; ++e) {
                 const int v = s * a.E + e;
-                const T* x = feats + (c * NV + v) * (int64_t)D;
+                const T* x = feats + (r * NV + v) * (int64_t)D;
                 const double* t = a.t + (int64_t)v * D;
                 double p = 0.0;
                 for (int k = lane * 4; k < D; k += 256) {
@@ -276,7 +324,8 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a) {
                     p = fma(q.x2(), t[k + 2], p);
                     p = fma(q.x3(), t[k + 3], p);
                 }
-                clip_add(a, st, c, s, e, wave_sum(p), lane);
+                if constexpr (VIEW) clip_add_view(a, st, c, r, s, e, wave_sum(p), lane);
+                else clip_add(a, st, c, s, e, wave_sum(p), lane);
             }
             const double m = clip_close_stream(a, st, c, s, lane);
             // runtime-indexed store into a small per-lane array; the generic path is not the fast path
@@ -294,8 +343,11 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a) {
 // over its four lanes: two butterfly steps per 16 clips and slice where the row-major kernel pays six per clip.  G loads of 1 KB
 // per wave are in flight behind the G being multiplied.  Same bookkeeping per clip as scan_kernel (ensemble mean over the splits
 // present, weighted score); the k order of a dot differs, so the two layouts agree to rounding (<= 1e-12, tested), not bit for bit.
-template <int S, int E, int CH, int G>
-__global__ __launch_bounds__(256) void scan_tiled_kernel(ScanArgs a) {
+// VIEW: the wave walks the TOUCHED tiles of a row view (item it -> tile items[it]: wave-uniform, scalar loads, the index two items on
+// fetched a tile ahead) and a lane stores its clip's results at pos[16 it + col] when that is not -1 (ScanViewArgs; the entry of the
+// wave's next tile is fetched while this one is multiplied); loads and arithmetic are the full scan's.
+template <int S, int E, int CH, int G, bool VIEW = false>
+__global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double t_lds[];    // [NV][D], natural order
     constexpr int NV = S * E;
     constexpr int D = CH * 256;
@@ -308,7 +360,8 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(ScanArgs a) {
     const int lane = threadIdx.x & 63, col = lane & 15, kk = lane >> 4;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const int64_t ntiles = (a.n + 15) / 16;
+    int64_t ntiles = (a.n + 15) / 16;
+    if constexpr (VIEW) ntiles = a.n_items;                          // work items: the touched tiles
     constexpr int64_t tile_elems = (int64_t)NV * 16 * D;
     const float* feats = static_cast<const float*>(a.feats) + lane * 4;
     double w[S];
@@ -318,17 +371,32 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(ScanArgs a) {
     }
     float4 cur[G], nxt[G];
     int64_t tile = wave;
+    int64_t tr = 0, trn = 0, on = -1;                                  // VIEW: the tiles of item `tile` and of the wave's next item; this lane's position
+    if constexpr (VIEW) {
+        tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (tile < ntiles) {
+            tr = a.items[tile];
+            trn = a.items[min(tile + nwaves, ntiles - 1)];
+            on = a.pos[tile * 16 + col];
+        }
+    }
     if (tile < ntiles) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) cur[j] = stream_load4(feats + tile * tile_elems + j * 256);
+        for (int j = 0; j < G; ++j) cur[j] = stream_load4(feats + (VIEW ? tr : tile) * tile_elems + j * 256);
     }
     while (tile < ntiles) {
         const int64_t tn = tile + nwaves;
-        const float* x = feats + tile * tile_elems;
+        int64_t trnn = 0, onn = -1;
+        if constexpr (VIEW) {
+            trnn = a.items[min(tn + nwaves, ntiles - 1)];
+            onn = a.pos[min(tn, ntiles - 1) * 16 + col];
+        }
+        const float* x = feats + (VIEW ? tr : tile) * tile_elems;
         // after the wave's last tile the ring is refilled from the tile just read: the refill stays unconditional
-        const float* xn = tn < ntiles ? feats + tn * tile_elems : x;
-        const int64_t c = tile * 16 + col;
-        const bool mine = kk == 0 && c < a.n;
+        const float* xn = tn < ntiles ? feats + (VIEW ? trn : tn) * tile_elems : x;
+        const int64_t c = (VIEW ? tr : tile) * 16 + col;
+        const int64_t o = VIEW ? on : c;                               // where this lane's clip reports
+        const bool mine = kk == 0 && (VIEW ? o >= 0 : c < a.n);
         const int64_t cc = min(c, a.n - 1);                            // the clip whose presence bits this lane follows
         double acc = 0.0, av[S];
         int cnt = 0;
@@ -362,20 +430,25 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(ScanArgs a) {
                 acc = acc + p;
                 ++cnt;
             }
-            if (a.sims && mine) a.sims[idx] = p;
+            if (a.sims && mine) a.sims[VIEW ? (o * S + s) * E + e : idx] = p;
             if (e == E - 1) {
                 const double m = acc / (double)cnt;
                 if (mine) {
-                    a.avg[c * S + s] = m;
-                    a.ne[c * S + s] = cnt;
+                    a.avg[o * S + s] = m;
+                    a.ne[o * S + s] = cnt;
                 }
                 av[s] = m;
                 acc = 0.0;
                 cnt = 0;
             }
         }
-        if (a.w && mine) a.scores[c] = score_from_avg(av, w, S);
+        if (a.w && mine) a.scores[o] = score_from_avg(av, w, S);
         tile = tn;
+        if constexpr (VIEW) {
+            tr = trn;
+            trn = trnn;
+            on = onn;
+        }
     }
 }
 
@@ -1346,6 +1419,19 @@ struct vq_db {
     int batch_q = 0;                 // queries of the last batched scan
     double* grid_buf = nullptr;      // scratch for grid / gathers
     int64_t grid_cap = 0;
+    // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over
+    // (-1: the whole database) and `na` the number of clips it then covers -- M, or N: what every result-side entry point counts with.
+    struct RowView {
+        bool defined = false;
+        int64_t m = 0;               // rows in the view
+        int64_t ntiles = 0;          // tiles of 16 clips it touches (fp32 databases of a tiled-capable shape; else no tile tables)
+        int64_t* rows = nullptr;     // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
+        int64_t* tiles = nullptr;
+        int64_t* pos = nullptr;
+    };
+    std::vector<RowView> views;
+    int active = -1;
+    int64_t na = 0;
     size_t elem() const { return dtype == VQ_F64 ? 8 : dtype == VQ_F16 ? 2 : 4; }
 };
 
@@ -1355,6 +1441,8 @@ static int db_free(vq_db* db) {
                     db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (auto& v : db->views)
+        if (v.rows) (void)hipFree(v.rows);
     return VQ_OK;
 }
 
@@ -1436,6 +1524,7 @@ int db_copy_scores_ordered(vq_db* db, double* dst_dev, int64_t* n_out, hipStream
     VQ_REQUIRE(db && dst_dev, "NULL argument");
     std::lock_guard<std::mutex> lk(db->mu);
     if (!db->have_scores) return fail(VQ_E_STATE, "no scores: scan (or rescore) first");
+    if (db->active >= 0) return fail(VQ_E_UNSUPPORTED, "a row view is in use: the scores cover its %lld positions, not the shard's rows (vq_db_rows_use(db, -1) first)", (long long)db->na);
     DeviceGuard g(db->device);
     if (n_out) *n_out = db->n;
     if (!db->n) return VQ_OK;
@@ -1513,6 +1602,7 @@ int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int3
     auto* db = new vq_db;
     db->device = device;
     db->n = n;
+    db->na = n;
     db->S = S;
     db->E = E;
     db->D = D;
@@ -1764,16 +1854,19 @@ int vq_db_set_query_from_row(vq_db* db, int64_t row, double* t_out_host) {
 
 }  // extern "C"
 
-template <typename T, int S, int E, int CH>
-static int launch_scan_t(vq_db* db, const ScanArgs& a) {
+// A = ScanArgs, or ScanViewArgs: the VIEW instantiations of the same kernels, under the same launch rules with the view's M for n
+template <typename T, int S, int E, int CH, typename A>
+static int launch_scan_t(vq_db* db, const A& a) {
+    constexpr bool VIEW = std::is_same_v<A, ScanViewArgs>;
     const size_t lds = (size_t)S * E * CH * 256 * 8;
     int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
     if (per_cu < 1) per_cu = 1;
     if (db->layout == VQ_LAYOUT_TILED) {
         if constexpr (sizeof(T) == 4) {
-            auto kern = scan_tiled_kernel<S, E, CH, kTiledGroup>;
+            auto kern = scan_tiled_kernel<S, E, CH, kTiledGroup, VIEW>;
             VQ_DYN_LDS(kern, lds);
-            const int64_t want = ((a.n + 15) / 16 + 3) / 4;   // 4 waves (tiles in flight) per block
+            int64_t want = ((a.n + 15) / 16 + 3) / 4;   // 4 waves (tiles in flight) per block
+            if constexpr (VIEW) want = (a.n_items + 3) / 4;
             const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * per_cu));
             kern<<<grid, 256, lds, db->stream>>>(a);
             VQ_CHECK_LAUNCH();
@@ -1791,7 +1884,7 @@ static int launch_scan_t(vq_db* db, const ScanArgs& a) {
     const bool lean = force_lean >= 0 ? force_lean != 0
                                       : (sizeof(T) == 2 || a.n < (int64_t)db->cus * per_cu * 4 * 16 || (sizeof(T) == 4 && S * E <= 6));
     if (lean) {
-        auto kern = scan_kernel<T, S, E, CH, true>;
+        auto kern = scan_kernel<T, S, E, CH, true, VIEW>;
         VQ_DYN_LDS(kern, lds);
         const int64_t want = (a.n + 3) / 4;
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * per_cu));
@@ -1799,7 +1892,7 @@ static int launch_scan_t(vq_db* db, const ScanArgs& a) {
         VQ_CHECK_LAUNCH();
         return VQ_OK;
     }
-    auto kern = scan_kernel<T, S, E, CH>;
+    auto kern = scan_kernel<T, S, E, CH, false, VIEW>;
     VQ_DYN_LDS(kern, lds);
     // (as many waves as fit the chip.  Fewer waves that each walk the same number of clips -- 2 500 waves of exactly four clips for a
     // 10 000-clip database instead of 3 072 of three or four -- were measured in round 6: 62.9 against 56.8 us per scan; the streams in
@@ -1814,11 +1907,11 @@ static int launch_scan_t(vq_db* db, const ScanArgs& a) {
 // shapes the fast one-query kernels (and with them the tiled layout) exist for
 static bool fast_scan_shape(const vq_db* db) { return db->D == 1024 && db->S >= 1 && db->S <= 2 && db->E >= 1 && db->E <= 5; }
 
-template <typename T>
-static int launch_scan(vq_db* db, const ScanArgs& a) {
+template <typename T, typename A>
+static int launch_scan(vq_db* db, const A& a) {
     if (db->D == 1024) {
 #define C_(s_, e_) \
-    if (db->S == s_ && db->E == e_) return launch_scan_t<T, s_, e_, 4>(db, a);
+    if (db->S == s_ && db->E == e_) return launch_scan_t<T, s_, e_, 4, A>(db, a);
         C_(1, 1) C_(1, 2) C_(1, 3) C_(1, 4) C_(1, 5)
         C_(2, 1) C_(2, 2) C_(2, 3) C_(2, 4) C_(2, 5)
 #undef C_
@@ -1826,24 +1919,53 @@ static int launch_scan(vq_db* db, const ScanArgs& a) {
     if (db->layout != VQ_LAYOUT_ROWS) return fail(VQ_E_STATE, "internal: tiled layout on a shape without a tiled scan kernel");
     const int64_t want = (a.n + 3) / 4;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * 8));
-    scan_generic_kernel<T><<<grid, 256, 0, db->stream>>>(a);
+    scan_generic_kernel<T, std::is_same_v<A, ScanViewArgs>><<<grid, 256, 0, db->stream>>>(a);
     VQ_CHECK_LAUNCH();
     return VQ_OK;
 }
 
 // the one dispatch on the storage type (vq_db_scan and vq_db_query_round: the same kernels, the same bits)
-static int launch_scan_dtype(vq_db* db, const ScanArgs& a) {
+template <typename A>
+static int launch_scan_args(vq_db* db, const A& a) {
     switch (db->dtype) {
-        case VQ_F16: return launch_scan<__half>(db, a);
-        case VQ_F32: return launch_scan<float>(db, a);
-        case VQ_F64: return launch_scan<double>(db, a);
+        case VQ_F16: return launch_scan<__half, A>(db, a);
+        case VQ_F32: return launch_scan<float, A>(db, a);
+        case VQ_F64: return launch_scan<double, A>(db, a);
     }
     return fail(VQ_E_STATE, "internal: database of unknown dtype %d", db->dtype);
 }
 
+// ... and on the row view in use: none -> the kernels, the arguments and the launch of ever; M = 0 -> nothing to launch
+static int launch_scan_dtype(vq_db* db, const ScanArgs& a) {
+    if (db->active < 0) return launch_scan_args<ScanArgs>(db, a);
+    const vq_db::RowView& v = db->views[db->active];
+    if (v.m == 0) return VQ_OK;
+    ScanViewArgs va;
+    static_cast<ScanArgs&>(va) = a;
+    va.pos = nullptr;
+    if (db->layout == VQ_LAYOUT_TILED) {
+        if (!v.tiles) return fail(VQ_E_STATE, "internal: a row view without tile tables on a tiled database");
+        va.items = v.tiles;
+        va.pos = v.pos;
+        va.n_items = v.ntiles;            // va.n stays N: the ragged last tile's bound
+    } else {
+        va.items = v.rows;
+        va.n_items = va.n = v.m;
+    }
+    return launch_scan_args<ScanViewArgs>(db, va);
+}
+
 static int run_select(vq_db* db, const SelPred& pred, int64_t limit1, int64_t host_result[3], bool with_prefix = false) {
-    if (db->n <= kSelSmallN && limit1 < 0) {             // a small database: one launch
-        select_small_kernel<<<1, kSelSmallThreads, 0, db->stream>>>(db->scores, (int)db->n, pred, db->sel_result, db->rows0, db->rows1, db->matchp,
+    const int64_t n = db->na;                            // the clips the scores cover: N, or the M of the row view in use
+    const int nblk = (int)cdiv(n, SEL_CHUNK);
+    if (n == 0) {                                        // an empty view: empty lists, no near-band maximum
+        static const int64_t kEmpty[4] = {0, 0, -1, 0};
+        VQ_HIP(hipMemcpyAsync(db->sel_result, kEmpty, 3 * 8, hipMemcpyHostToDevice, db->stream));
+        if (host_result) memcpy(host_result, kEmpty, 3 * 8);
+        return VQ_OK;
+    }
+    if (n <= kSelSmallN && limit1 < 0) {             // a small database: one launch
+        select_small_kernel<<<1, kSelSmallThreads, 0, db->stream>>>(db->scores, (int)n, pred, db->sel_result, db->rows0, db->rows1, db->matchp,
                                                                     db->nearp, with_prefix ? (int)kRoundPrefix : 0);
         VQ_CHECK_LAUNCH();
         if (!host_result) return VQ_OK;
@@ -1851,13 +1973,13 @@ static int run_select(vq_db* db, const SelPred& pred, int64_t limit1, int64_t ho
         VQ_HIP(hipStreamSynchronize(db->stream));
         return VQ_OK;
     }
-    select_count_kernel<<<db->nblk, SEL_BLOCK, 0, db->stream>>>(db->scores, db->n, pred, db->blk_cnt, db->blk_max,
+    select_count_kernel<<<nblk, SEL_BLOCK, 0, db->stream>>>(db->scores, n, pred, db->blk_cnt, db->blk_max,
                                                                  db->blk_arg);
     VQ_CHECK_LAUNCH();
-    select_scan_kernel<<<1, SEL_BLOCK, 0, db->stream>>>(db->blk_cnt, db->blk_max, db->blk_arg, db->nblk, db->sel_result,
+    select_scan_kernel<<<1, SEL_BLOCK, 0, db->stream>>>(db->blk_cnt, db->blk_max, db->blk_arg, nblk, db->sel_result,
                                                          limit1);
     VQ_CHECK_LAUNCH();
-    select_scatter_kernel<<<db->nblk, SEL_BLOCK, 0, db->stream>>>(db->scores, db->n, pred, db->blk_cnt, db->rows0,
+    select_scatter_kernel<<<nblk, SEL_BLOCK, 0, db->stream>>>(db->scores, n, pred, db->blk_cnt, db->rows0,
                                                                    db->rows1, limit1, db->matchp, db->nearp, with_prefix ? kRoundPrefix : 0);
     VQ_CHECK_LAUNCH();
     if (!host_result) return VQ_OK;                  // vq_db_query_round: the counts travel with the round's block
@@ -1888,7 +2010,7 @@ int vq_db_scan(vq_db* db, const double* w_host, int32_t keep_sims) {
     a.S = db->S;
     a.E = db->E;
     a.D = db->D;
-    const int rc = launch_scan_dtype(db, a);
+    const int rc = launch_scan_dtype(db, a);          // over the row view in use, if any
     if (rc != VQ_OK) return rc;
     db->have_avg = true;
     db->have_sims = keep_sims != 0;
@@ -1915,6 +2037,7 @@ int vq_db_scan_batch(vq_db* db, int32_t n_queries, const double* t_host, const d
     VQ_REQUIRE(db->D % 256 == 0 && db->D <= 1024, "batched scan needs D in {256,512,768,1024} (got %d)", db->D);
     VQ_REQUIRE(db->S <= 8, "at most 8 streams");
     std::lock_guard<std::mutex> lk(db->mu);
+    if (db->active >= 0) return fail(VQ_E_UNSUPPORTED, "vq_db_scan_batch runs over the whole database: row view %d is in use (vq_db_rows_use(db, -1) first)", db->active);
     DeviceGuard g(db->device);
     const int Q = n_queries, NV = db->S * db->E;
     const int64_t n_t = (int64_t)Q * NV * db->D, n_w = (int64_t)Q * db->S, n_sc = (int64_t)Q * db->n;
@@ -1994,7 +2117,7 @@ int vq_db_rescore(vq_db* db, const double* w_host) {
     if (!db->have_avg) return fail(VQ_E_STATE, "vq_db_rescore: no similarities cached (call vq_db_scan first)");
     DeviceGuard g(db->device);
     VQ_HIP(hipMemcpyAsync(db->w, w_host, db->S * 8, hipMemcpyHostToDevice, db->stream));
-    rescore_kernel<<<cdiv(db->n, 256), 256, 0, db->stream>>>(db->avg, db->w, db->scores, db->n, db->S);
+    if (db->na) rescore_kernel<<<cdiv(db->na, 256), 256, 0, db->stream>>>(db->avg, db->w, db->scores, db->na, db->S);
     VQ_CHECK_LAUNCH();
     db->have_scores = true;
     return VQ_OK;
@@ -2006,10 +2129,11 @@ int vq_db_read_similarities(vq_db* db, double* avg_host, int32_t* ne_host, doubl
     if (!db->have_avg) return fail(VQ_E_STATE, "no similarities cached (call vq_db_scan first)");
     if (sims_host && !db->have_sims) return fail(VQ_E_STATE, "per-split similarities were not kept (scan with keep_sims=1)");
     DeviceGuard g(db->device);
-    if (avg_host) VQ_HIP(hipMemcpyAsync(avg_host, db->avg, (size_t)db->n * db->S * 8, hipMemcpyDeviceToHost, db->stream));
-    if (ne_host) VQ_HIP(hipMemcpyAsync(ne_host, db->ne, (size_t)db->n * db->S * 4, hipMemcpyDeviceToHost, db->stream));
+    if (!db->na) return VQ_OK;                        // an empty row view
+    if (avg_host) VQ_HIP(hipMemcpyAsync(avg_host, db->avg, (size_t)db->na * db->S * 8, hipMemcpyDeviceToHost, db->stream));
+    if (ne_host) VQ_HIP(hipMemcpyAsync(ne_host, db->ne, (size_t)db->na * db->S * 4, hipMemcpyDeviceToHost, db->stream));
     if (sims_host)
-        VQ_HIP(hipMemcpyAsync(sims_host, db->sims, (size_t)db->n * db->S * db->E * 8, hipMemcpyDeviceToHost, db->stream));
+        VQ_HIP(hipMemcpyAsync(sims_host, db->sims, (size_t)db->na * db->S * db->E * 8, hipMemcpyDeviceToHost, db->stream));
     VQ_HIP(hipStreamSynchronize(db->stream));
     return VQ_OK;
 }
@@ -2019,7 +2143,8 @@ int vq_db_read_scores(vq_db* db, double* scores_host) {
     std::lock_guard<std::mutex> lk(db->mu);
     if (!db->have_scores) return fail(VQ_E_STATE, "no scores computed (scan with weights, or rescore)");
     DeviceGuard g(db->device);
-    VQ_HIP(hipMemcpyAsync(scores_host, db->scores, (size_t)db->n * 8, hipMemcpyDeviceToHost, db->stream));
+    if (!db->na) return VQ_OK;
+    VQ_HIP(hipMemcpyAsync(scores_host, db->scores, (size_t)db->na * 8, hipMemcpyDeviceToHost, db->stream));
     VQ_HIP(hipStreamSynchronize(db->stream));
     return VQ_OK;
 }
@@ -2043,10 +2168,10 @@ int vq_db_ne_devptr(vq_db* db, void** p) {
 int vq_db_read_scores_at(vq_db* db, const int64_t* rows_host, int32_t L, double* out_host) {
     VQ_REQUIRE(db && out_host, "NULL argument");
     VQ_REQUIRE(L >= 0 && (L == 0 || rows_host), "bad rows");
+    std::lock_guard<std::mutex> lk(db->mu);              // the bound is the view in use: read under the lock
     for (int l = 0; l < L; ++l)
-        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->n, "rows[%d] = %lld outside [0,%lld)", l, (long long)rows_host[l], (long long)db->n);
+        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->na, "rows[%d] = %lld outside [0,%lld)", l, (long long)rows_host[l], (long long)db->na);
     if (L == 0) return VQ_OK;
-    std::lock_guard<std::mutex> lk(db->mu);
     if (!db->have_scores) return fail(VQ_E_STATE, "no scores computed (scan with weights, or rescore)");
     DeviceGuard g(db->device);
     int rc = ensure_grid_buf(db, (int64_t)L * 16);
@@ -2104,9 +2229,11 @@ int vq_db_write_avg(vq_db* db, const double* avg_host, const int32_t* ne_host) {
     VQ_REQUIRE(db && avg_host, "NULL argument");
     std::lock_guard<std::mutex> lk(db->mu);
     DeviceGuard g(db->device);
-    VQ_HIP(hipMemcpyAsync(db->avg, avg_host, (size_t)db->n * db->S * 8, hipMemcpyHostToDevice, db->stream));
-    if (ne_host) VQ_HIP(hipMemcpyAsync(db->ne, ne_host, (size_t)db->n * db->S * 4, hipMemcpyHostToDevice, db->stream));
-    VQ_HIP(hipStreamSynchronize(db->stream));
+    if (db->na) {
+        VQ_HIP(hipMemcpyAsync(db->avg, avg_host, (size_t)db->na * db->S * 8, hipMemcpyHostToDevice, db->stream));
+        if (ne_host) VQ_HIP(hipMemcpyAsync(db->ne, ne_host, (size_t)db->na * db->S * 4, hipMemcpyHostToDevice, db->stream));
+        VQ_HIP(hipStreamSynchronize(db->stream));
+    }
     db->have_avg = true;
     db->have_scores = false;
     return VQ_OK;
@@ -2128,10 +2255,10 @@ int vq_db_scores_grid(vq_db* db, const double* w_grid_host, int32_t G, const int
                       double* out_host) {
     VQ_REQUIRE(db && w_grid_host && rows_host && out_host, "NULL argument");
     VQ_REQUIRE(G > 0 && L > 0, "G and L must be positive");
-    for (int l = 0; l < L; ++l)
-        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->n, "rows[%d] = %lld outside [0,%lld)", l,
-                   (long long)rows_host[l], (long long)db->n);
     std::lock_guard<std::mutex> lk(db->mu);
+    for (int l = 0; l < L; ++l)
+        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->na, "rows[%d] = %lld outside [0,%lld)", l,
+                   (long long)rows_host[l], (long long)db->na);
     if (!db->have_avg) return fail(VQ_E_STATE, "no similarities cached (call vq_db_scan first)");
     DeviceGuard g(db->device);
     const int64_t wb = (int64_t)G * db->S * 8, rb = (int64_t)L * 8, ob = (int64_t)G * L * 8;
@@ -2152,9 +2279,9 @@ int vq_db_loss_surface(vq_db* db, const double* w_grid_host, int32_t G, const in
                        const double* th_grid_host, int32_t T, double ballast, double* out_host) {
     VQ_REQUIRE(db && w_grid_host && rows_host && labels_host && th_grid_host && out_host, "NULL argument");
     VQ_REQUIRE(G > 0 && L > 0 && T > 0 && L <= 4096, "G, L, T must be positive (L <= 4096 labelled clips)");
-    for (int l = 0; l < L; ++l)
-        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->n, "rows[%d] = %lld outside [0,%lld)", l, (long long)rows_host[l], (long long)db->n);
     std::lock_guard<std::mutex> lk(db->mu);
+    for (int l = 0; l < L; ++l)
+        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->na, "rows[%d] = %lld outside [0,%lld)", l, (long long)rows_host[l], (long long)db->na);
     if (!db->have_avg) return fail(VQ_E_STATE, "no similarities cached (call vq_db_scan first)");
     DeviceGuard g(db->device);
     // one staging block: weights | rows | labels | thresholds in, the surface out
@@ -2289,7 +2416,7 @@ int vq_db_query_round(vq_db* db, void* block, int64_t block_bytes, int32_t flags
         db->have_avg = true;
         db->have_scores = do_scores;
     } else if (do_scores) {
-        rescore_kernel<<<cdiv(db->n, 256), 256, 0, db->stream>>>(db->avg, db->w, db->scores, db->n, db->S);
+        if (db->na) rescore_kernel<<<cdiv(db->na, 256), 256, 0, db->stream>>>(db->avg, db->w, db->scores, db->na, db->S);
         VQ_CHECK_LAUNCH();
         db->have_scores = true;
     }
@@ -2305,8 +2432,19 @@ int vq_db_query_round(vq_db* db, void* block, int64_t block_bytes, int32_t flags
     // one copy back: from the similarities (a scan) or from the scores (a re-weighting) to the end of what was computed
     const int first = do_scan ? 0 : 2;
     const int64_t end = do_select ? db->round_off[6] : (do_scores ? db->round_off[3] : db->round_off[2]);
-    VQ_HIP(hipMemcpyAsync(host + off[2] + db->round_off[first], db->round_dev + db->round_off[first], (size_t)(end - db->round_off[first]),
-                          hipMemcpyDeviceToHost, db->stream));
+    if (db->active < 0) {
+        VQ_HIP(hipMemcpyAsync(host + off[2] + db->round_off[first], db->round_dev + db->round_off[first], (size_t)(end - db->round_off[first]),
+                              hipMemcpyDeviceToHost, db->stream));
+    } else {
+        // a row view: the block keeps the layout for N, every array holds its first M entries and only those travel
+        const int64_t m = db->na;
+        const int64_t len[3] = {m * db->S * 8, m * db->S * 4, m * 8};
+        for (int i = first; i < 3 && db->round_off[i] < end; ++i)
+            if (len[i]) VQ_HIP(hipMemcpyAsync(host + off[2] + db->round_off[i], db->round_dev + db->round_off[i], (size_t)len[i], hipMemcpyDeviceToHost, db->stream));
+        if (do_select)
+            VQ_HIP(hipMemcpyAsync(host + off[2] + db->round_off[3], db->round_dev + db->round_off[3], (size_t)(db->round_off[6] - db->round_off[3]),
+                                  hipMemcpyDeviceToHost, db->stream));
+    }
     VQ_HIP(hipStreamSynchronize(db->stream));
     if (do_select) {
         const int64_t* res = (const int64_t*)(host + off[5]);
@@ -2338,16 +2476,21 @@ int vq_db_topk(vq_db* db, int64_t k, int64_t* rows_host, double* vals_host, int6
     std::lock_guard<std::mutex> lk(db->mu);
     if (!db->have_scores) return fail(VQ_E_STATE, "no scores computed (scan with weights, or rescore)");
     DeviceGuard g(db->device);
-    if (k > db->n) k = db->n;
-    if (db->n <= kTopkSmallN && k <= kTopkSmallK) {                  // a small resident database: one launch, one copy back
+    const int64_t n = db->na;                                        // the clips the scores cover (a row view: its M positions)
+    if (n == 0) {
+        *k_out = 0;
+        return VQ_OK;
+    }
+    if (k > n) k = n;
+    if (n <= kTopkSmallN && k <= kTopkSmallK) {                  // a small resident database: one launch, one copy back
         const int64_t bytes = 64 + k * 16;
         int rc = ensure_grid_buf(db, bytes);
         if (rc != VQ_OK) return rc;
         char* base = (char*)db->grid_buf;
         auto kern = topk_small_kernel;
-        const size_t lds = (size_t)db->n * 8;
+        const size_t lds = (size_t)n * 8;
         VQ_DYN_LDS(kern, (size_t)kTopkSmallN * 8);
-        kern<<<1, kTopkSmallThreads, lds, db->stream>>>(db->scores, (int)db->n, (int)k, (int64_t*)(base + 64), (double*)(base + 64 + k * 8), (int64_t*)base);
+        kern<<<1, kTopkSmallThreads, lds, db->stream>>>(db->scores, (int)n, (int)k, (int64_t*)(base + 64), (double*)(base + 64 + k * 8), (int64_t*)base);
         VQ_CHECK_LAUNCH();
         std::vector<char> host((size_t)bytes);
         VQ_HIP(hipMemcpyAsync(host.data(), base, (size_t)bytes, hipMemcpyDeviceToHost, db->stream));
@@ -2373,9 +2516,9 @@ int vq_db_topk(vq_db* db, int64_t k, int64_t* rows_host, double* vals_host, int6
     uint64_t st[2] = {0ull, (uint64_t)k};
     VQ_HIP(hipMemcpyAsync(db->tk_state, st, 16, hipMemcpyHostToDevice, db->stream));
     VQ_HIP(hipMemsetAsync(db->tk_hist, 0, 256 * 4, db->stream));
-    const unsigned hgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((db->n + 255) / 256, (int64_t)db->cus * 8));
+    const unsigned hgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)db->cus * 8));
     for (int pass = 0; pass < 8; ++pass) {
-        topk_hist_kernel<<<hgrid, 256, 0, db->stream>>>(db->scores, db->n, pass, db->tk_state, db->tk_hist);
+        topk_hist_kernel<<<hgrid, 256, 0, db->stream>>>(db->scores, n, pass, db->tk_state, db->tk_hist);
         VQ_CHECK_LAUNCH();
         topk_pick_kernel<<<1, 64, 0, db->stream>>>(pass, db->tk_state, db->tk_hist);
         VQ_CHECK_LAUNCH();
@@ -2430,9 +2573,9 @@ int vq_db_topk(vq_db* db, int64_t k, int64_t* rows_host, double* vals_host, int6
 int vq_db_min_score(vq_db* db, const int64_t* rows_host, int32_t L, double* min_out) {
     VQ_REQUIRE(db && min_out, "NULL argument");
     VQ_REQUIRE(L >= 0 && (L == 0 || rows_host), "bad rows");
-    for (int l = 0; l < L; ++l)
-        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->n, "rows[%d] outside the DB", l);
     std::lock_guard<std::mutex> lk(db->mu);
+    for (int l = 0; l < L; ++l)
+        VQ_REQUIRE(rows_host[l] >= 0 && rows_host[l] < db->na, "rows[%d] outside the DB", l);
     if (!db->have_scores) return fail(VQ_E_STATE, "no scores computed");
     DeviceGuard g(db->device);
     double m = 1.0;   // ticket.py:302 min_score = 1
@@ -2450,6 +2593,101 @@ int vq_db_min_score(vq_db* db, const int64_t* rows_host, int32_t L, double* min_
         for (int l = 0; l < L; ++l) m = std::min(m, v[l]);   // Python min(a, b): b if b < a else a
     }
     *min_out = m;
+    return VQ_OK;
+}
+
+// ---- row views -------------------------------------------------------------------------------------------------------------------
+int vq_db_rows_define(vq_db* db, const int64_t* rows_host, int64_t m, int32_t* view_out) {
+    VQ_REQUIRE(db && view_out, "NULL argument");
+    VQ_REQUIRE(m >= 0 && m <= db->n && (m == 0 || rows_host), "a row view has 0 <= m <= %lld rows (got %lld)", (long long)db->n, (long long)m);
+    for (int64_t i = 0; i < m; ++i) {
+        VQ_REQUIRE(rows_host[i] >= 0 && rows_host[i] < db->n, "rows[%lld] = %lld outside [0,%lld)", (long long)i, (long long)rows_host[i], (long long)db->n);
+        if (i) {
+            VQ_REQUIRE(rows_host[i] != rows_host[i - 1], "rows[%lld] = %lld is a duplicate: a row view lists every row once", (long long)i, (long long)rows_host[i]);
+            VQ_REQUIRE(rows_host[i] > rows_host[i - 1], "rows[%lld] = %lld after %lld: a row view is strictly ascending (database order)", (long long)i,
+                       (long long)rows_host[i], (long long)rows_host[i - 1]);
+        }
+    }
+    std::lock_guard<std::mutex> lk(db->mu);
+    DeviceGuard g(db->device);
+    // the tiled form of the same view, built whenever the database could be tiled: a view defined on rows survives vq_db_set_layout
+    std::vector<int64_t> host(rows_host, rows_host + m);
+    int64_t ntiles = 0;
+    if (db->dtype == VQ_F32 && fast_scan_shape(db)) {
+        for (int64_t i = 0; i < m; ++i) ntiles += (i == 0 || (rows_host[i] >> 4) != (rows_host[i - 1] >> 4)) ? 1 : 0;
+        host.resize((size_t)(m + ntiles + ntiles * 16), -1);
+        int64_t* tiles = host.data() + m;
+        int64_t* pos = tiles + ntiles;
+        int64_t t = -1;
+        for (int64_t i = 0; i < m; ++i) {
+            if (i == 0 || (rows_host[i] >> 4) != (rows_host[i - 1] >> 4)) tiles[++t] = rows_host[i] >> 4;
+            pos[t * 16 + (rows_host[i] & 15)] = i;
+        }
+    }
+    vq_db::RowView v;
+    v.defined = true;
+    v.m = m;
+    v.ntiles = ntiles;
+    VQ_HIP(vq::malloc_trim((void**)&v.rows, std::max<size_t>(64, host.size() * 8)));
+    if (ntiles) {
+        v.tiles = v.rows + m;
+        v.pos = v.tiles + ntiles;
+    }
+    if (!host.empty()) {
+        hipError_t e = hipMemcpyAsync(v.rows, host.data(), host.size() * 8, hipMemcpyHostToDevice, db->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(v.rows);
+            return fail(VQ_E_HIP, "uploading the row view failed: %s", hipGetErrorString(e));
+        }
+    }
+    size_t slot = 0;
+    while (slot < db->views.size() && db->views[slot].defined) ++slot;
+    if (slot == db->views.size()) db->views.emplace_back();
+    db->views[slot] = v;
+    *view_out = (int32_t)slot;
+    return VQ_OK;
+}
+
+static int check_view(vq_db* db, int32_t view) {
+    if (view < 0 || (size_t)view >= db->views.size() || !db->views[view].defined) return fail(VQ_E_INVALID, "no row view %d on this handle", view);
+    return VQ_OK;
+}
+
+int vq_db_rows_use(vq_db* db, int32_t view) {
+    VQ_REQUIRE(db, "db is NULL");
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (view != -1) {
+        const int rc = check_view(db, view);
+        if (rc != VQ_OK) return rc;
+    }
+    if (view == db->active) return VQ_OK;
+    db->active = view;
+    db->na = view < 0 ? db->n : db->views[view].m;
+    // what the handle holds was computed over another population
+    db->have_avg = db->have_scores = db->have_sims = false;
+    db->last_n0 = db->last_n1 = 0;
+    return VQ_OK;
+}
+
+int vq_db_rows_drop(vq_db* db, int32_t view) {
+    VQ_REQUIRE(db, "db is NULL");
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int rc = check_view(db, view);
+    if (rc != VQ_OK) return rc;
+    if (view == db->active) return fail(VQ_E_STATE, "row view %d is in use (vq_db_rows_use another one, or -1, first)", view);
+    DeviceGuard g(db->device);
+    VQ_HIP(hipStreamSynchronize(db->stream));            // a scan over it may still be running
+    (void)hipFree(db->views[view].rows);
+    db->views[view] = vq_db::RowView();
+    return VQ_OK;
+}
+
+int vq_db_rows_active(vq_db* db, int32_t* view, int64_t* m) {
+    VQ_REQUIRE(db, "db is NULL");
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (view) *view = db->active;
+    if (m) *m = db->na;
     return VQ_OK;
 }
 

@@ -52,6 +52,53 @@ class RoundResult:
     __slots__ = ("avg", "n_e", "scores", "match_rows", "near_rows", "near_argmax")
 
 
+class SearchSetView:
+    """What a ticket sees of a database for one round: the clips of its search set, in database order.  Immutable -- a ticket binds
+    to this object, not to the (shared, mutable) state of the handle.  ``clip_ids`` [M] and ``rows`` [M] (the database rows, strictly
+    ascending); a clip's POSITION in the view is what the database's result arrays and row arguments are indexed by while the
+    view is in use.  The trivial view (``set_id`` None) is the whole database: positions are rows."""
+    __slots__ = ("set_id", "clip_ids", "rows", "n", "token", "_pos", "_whole")
+
+    def __init__(self, set_id, clip_ids: np.ndarray, rows: np.ndarray, token: int = -1, whole=None):
+        ids, r = np.asarray(clip_ids, dtype=np.int64), np.asarray(rows, dtype=np.int64)
+        if whole is None:                                     # the trivial view shares the database's own arrays and index
+            ids, r = ids.copy(), r.copy()
+            ids.setflags(write=False)
+            r.setflags(write=False)
+        for name, value in (("set_id", set_id), ("clip_ids", ids), ("rows", r), ("n", int(ids.shape[0])), ("token", int(token)),
+                            ("_pos", None), ("_whole", whole)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a search-set view is immutable")
+
+    def row_of(self, clip_id) -> int:
+        """The clip's position in the view; ``KeyError`` for a clip outside the search set."""
+        if self._whole is not None:
+            return self._whole.row_of(clip_id)
+        if self._pos is None:
+            object.__setattr__(self, "_pos", {int(c): i for i, c in enumerate(self.clip_ids.tolist())})      # a cache, not state
+        return self._pos[int(clip_id)]
+
+    def has_clip(self, clip_id) -> bool:
+        try:
+            self.row_of(clip_id)
+            return True
+        except (KeyError, TypeError, ValueError):
+            return False
+
+
+def whole_view(db) -> SearchSetView:
+    """The trivial view of a database object (FeatureDB, ShardedFeatureDB, or a look-alike with ``clip_ids`` and ``row_of``)."""
+    n = len(db.clip_ids)
+    return SearchSetView(None, db.clip_ids, np.arange(n, dtype=np.int64), whole=db)
+
+
+def search_set_rows(db, clip_ids) -> np.ndarray:
+    """Clip ids -> the strictly ascending database rows of a search set (duplicates collapse; an unknown id is a KeyError)."""
+    return np.unique(np.fromiter((db.row_of(c) for c in clip_ids), dtype=np.int64))
+
+
 class FeatureDB:
     """N clips x S streams x E ensemble slots x D floats, resident on ``device``.  ``dtype`` is how the block is STORED: float32, float64
     or (opt-in) float16 -- half the bytes per query and per clip; values are rounded once on the way in and every result is what the
@@ -80,6 +127,66 @@ class FeatureDB:
         self.lock = threading.RLock()
         self.sims_owner = None
         self.scores_owner = None
+        # search sets (define_search_set): id -> view; the one the handle runs over now (None: the whole database) and how many
+        # clips the result arrays then cover
+        self._sets = {}
+        self._set_in_use = None
+        self._whole = None
+        self._na = self.n
+
+    # ------------------------------------------------------------------ search sets
+    def define_search_set(self, set_id, clip_ids):
+        """Make the clips ``clip_ids`` (any order; duplicates collapse; an id the database does not hold is a ``KeyError``) a search
+        set of this database: its ascending rows go to the device once (vq_db_rows_define) and stay there until
+        :meth:`drop_search_set`.  Returns the view object."""
+        return self.define_search_rows(set_id, search_set_rows(self, clip_ids))
+
+    def define_search_rows(self, set_id, rows):
+        """The same from database rows (strictly ascending)."""
+        if set_id is None:
+            raise ValueError("None names the whole database")
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        with self.lock:
+            if set_id in self._sets:
+                raise ValueError("search set %r is already defined (drop_search_set first)" % (set_id,))
+            vid = C.c_int32(-1)
+            call("vq_db_rows_define", self._h, _np_ptr(r) if r.size else None, int(r.size), C.byref(vid))
+            view = SearchSetView(set_id, self.clip_ids[r], r, token=vid.value)
+            self._sets[set_id] = view
+            return view
+
+    def has_search_set(self, set_id) -> bool:
+        try:
+            return set_id is not None and set_id in self._sets
+        except TypeError:                                     # an unhashable id names no set
+            return False
+
+    def use_search_set(self, set_id) -> SearchSetView:
+        """Run the one-query path over search set ``set_id`` from now on (``None``: the whole database) and return its view.  While a
+        set is in use every result array is compact ([M]...) and every row argument and result is a position in the view
+        (include/vq_amd_rows.h).  No library call when the set in use does not change; a change invalidates the similarities and
+        scores the handle holds."""
+        with self.lock:
+            if set_id is None:
+                if self._whole is None:
+                    self._whole = whole_view(self)
+                view = self._whole
+            else:
+                view = self._sets[set_id]
+            if set_id != self._set_in_use:
+                call("vq_db_rows_use", self._h, view.token)
+                self._set_in_use, self._na = set_id, view.n
+            return view
+
+    def drop_search_set(self, set_id):
+        with self.lock:
+            view = self._sets[set_id]
+            call("vq_db_rows_drop", self._h, view.token)         # the set in use: VqError (VQ_E_STATE)
+            del self._sets[set_id]
+
+    @property
+    def search_set_in_use(self):
+        return self._set_in_use
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -273,8 +380,9 @@ class FeatureDB:
         behind the scan (same stream as ``set_stream``)."""
         _lib.require_torch_runtime("FeatureDB.device_tensor")
         import torch
-        name, shape, typestr = {"avg": ("vq_db_avg_devptr", (self.n, self.S), "<f8"), "ne": ("vq_db_ne_devptr", (self.n, self.S), "<i4"),
-                                "scores": ("vq_db_scores_devptr", (self.n,), "<f8")}[kind]
+        n = self._na                                          # a search set in use: its M positions
+        name, shape, typestr = {"avg": ("vq_db_avg_devptr", (n, self.S), "<f8"), "ne": ("vq_db_ne_devptr", (n, self.S), "<i4"),
+                                "scores": ("vq_db_scores_devptr", (n,), "<f8")}[kind]
         p = C.c_void_p()
         call(name, self._h, C.byref(p))
 
@@ -362,7 +470,7 @@ class FeatureDB:
         blk = self._round_block()
         off = self._round_off
         raw = blk.bytes()
-        n, S = self.n, self.S
+        n, S = self._na, self.S                               # the block is laid out for N; a search set fills the first M of each array
 
         def view(piece, dtype, count, shape):
             return raw[off[piece]:off[piece] + count * dtype().itemsize].view(dtype).reshape(shape)
@@ -403,19 +511,21 @@ class FeatureDB:
         call("vq_db_rescore", self._h, _np_ptr(w))
 
     def similarities(self, sims: bool = False):
-        avg = np.empty((self.n, self.S), dtype=np.float64)
-        ne = np.empty((self.n, self.S), dtype=np.int32)
-        sm = np.empty((self.n, self.S, self.E), dtype=np.float64) if sims else None
+        avg = np.empty((self._na, self.S), dtype=np.float64)
+        ne = np.empty((self._na, self.S), dtype=np.int32)
+        sm = np.empty((self._na, self.S, self.E), dtype=np.float64) if sims else None
         call("vq_db_read_similarities", self._h, _np_ptr(avg), _np_ptr(ne), _np_ptr(sm) if sims else None)
         return (avg, ne, sm) if sims else (avg, ne)
 
     def write_avg(self, avg: np.ndarray, n_e: np.ndarray | None = None):
         a = np.ascontiguousarray(avg, dtype=np.float64)
         ne = None if n_e is None else np.ascontiguousarray(n_e, dtype=np.int32)
+        if a.size != self._na * self.S or (ne is not None and ne.size != a.size):
+            raise ValueError("avg / n_e must be [%d,%d]: what the database (or the search set in use) covers" % (self._na, self.S))
         call("vq_db_write_avg", self._h, _np_ptr(a), _np_ptr(ne) if ne is not None else None)
 
     def scores(self) -> np.ndarray:
-        out = np.empty(self.n, dtype=np.float64)
+        out = np.empty(self._na, dtype=np.float64)
         call("vq_db_read_scores", self._h, _np_ptr(out))
         return out
 
@@ -445,14 +555,16 @@ class FeatureDB:
         """Order-preserving partition (ticket.py:325-340): (match_rows, near_rows, near_argmax).  Partition and
         copy-out are one locked call of the library, so handles shared between broker threads stay consistent."""
         nm, nn, am = C.c_int64(), C.c_int64(), C.c_int64()
-        m = np.empty(self.n, dtype=np.int64)
-        r = np.empty(self.n, dtype=np.int64)
+        m = np.empty(max(self._na, 1), dtype=np.int64)
+        r = np.empty(max(self._na, 1), dtype=np.int64)
         call("vq_db_select_rows", self._h, float(threshold), float(lower), _np_ptr(m), m.size, _np_ptr(r), r.size,
              C.byref(nm), C.byref(nn), C.byref(am))
         return m[:nm.value].copy(), r[:nn.value].copy(), am.value
 
     def topk(self, k: int):
-        k = int(min(k, self.n))
+        k = int(min(k, self._na))
+        if k <= 0 and self._na == 0:                          # an empty search set has no best clips
+            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
         rows = np.empty(k, dtype=np.int64)
         vals = np.empty(k, dtype=np.float64)
         kk = C.c_int64()

@@ -86,12 +86,14 @@ class Hyperparameter:
     def _labelled_rows(ticket):
         """(DB rows, labels) of the clips of the previous round: the user's verdict where there is one, the engine's own
         call otherwise (hyperparameter.py:45-50).  A clip listed twice keeps its first position and last label, like
-        the dict of the reference; an unknown clip is a KeyError, like ``ticket.scores[clip]`` there."""
+        the dict of the reference; an unknown clip is a KeyError, like ``ticket.scores[clip]`` there.  The rows are positions in the
+        view the ticket's round is bound to (its search set, ticket.py), which is what the database's score arrays are indexed by."""
         label = {}
         for m in ticket.matches:
             verdict = m["user_match"]
             label[m["video_clip"]] = m["is_match"] if verdict is None else verdict
-        return [ticket.feature_db.row_of(clip) for clip in label], list(label.values())
+        index = getattr(ticket, "_view", None) or ticket.feature_db
+        return [index.row_of(clip) for clip in label], list(label.values())
 
     def _refine(self, surface, iw, it):
         """Minimum of the separable parabola through the best cell and its four neighbours, clamped to the

@@ -50,6 +50,30 @@ def all_gather_rows(local, n_total: int, group=None):
     return torch.cat(parts, dim=0)
 
 
+def all_gather_counts(local, counts: Sequence[int], group=None):
+    """The same for row blocks whose lengths every rank already knows (``counts[r]`` rows on rank r -- a search set's share of each
+    shard, derived from the set's row list, so no sizes are exchanged): ``[sum(counts), ...]`` in rank-major order."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    counts = [int(c) for c in counts]
+    if world == 1:
+        return local
+    if local.is_cuda and dist.get_backend(group) == "gloo":
+        return all_gather_counts(local.cpu(), counts, group).to(local.device)
+    max_rows = max(max(counts), 1)
+    tail = tuple(local.shape[1:])
+    padded = local
+    if local.shape[0] != max_rows:
+        padded = torch.zeros((max_rows,) + tail, dtype=local.dtype, device=local.device)
+        padded[:local.shape[0]].copy_(local)
+    out = torch.empty((world * max_rows,) + tail, dtype=local.dtype, device=local.device)
+    dist.all_gather_into_tensor(out, padded.contiguous(), group=group)
+    if all(c == max_rows for c in counts):
+        return out
+    return torch.cat([out[r * max_rows:r * max_rows + counts[r]] for r in range(world)], dim=0)
+
+
 def merge_topk(rows_per_rank: Sequence[np.ndarray], vals_per_rank: Sequence[np.ndarray], row0_per_rank: Sequence[int],
                k: int):
     """Merge per-shard top-k lists (local row indices) into the global top-k: descending score, ties by ascending

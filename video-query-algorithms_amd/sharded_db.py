@@ -17,6 +17,10 @@ broker code scores on every GPU of the node (half B):
   the row lists are concatenated rank-major = order-preserving; ``random.sample`` then draws on ONE rank, in the
   broker's process, so a seeded broker picks the clips CPython would (ticket.py:333,341);
 * top-k: per-rank top-k lists merged with the global stable tie-break (``shard.merge_topk``);
+* search sets (``define_search_set`` / ``use_search_set``): the root announces a set once as its ascending GLOBAL rows, every rank
+  defines the sub-list that falls into its range on its own GPU, and ``use`` is one announcement carrying the set's number; while a
+  set is in use every result is indexed by position in it, the gathers take per-rank counts that every rank derives from the list
+  (nothing is exchanged per query) and global view order is rank-major because the list is ascending;
 * target bootstrapping: the handful of user-validated rows are fetched from their owners (``vq_db_read_rows``) and the
   closed forms run on the root's GPU (``csrc/vq_boot.hip``, the same kernel the resident route uses).
 
@@ -38,10 +42,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .shard import all_gather_rows, merge_topk, shard_range
+from .shard import all_gather_counts, all_gather_rows, merge_topk, shard_range
 
 OP_CLOSE, OP_RESTRICT, OP_SET_QUERY, OP_QUERY_FROM_ROW, OP_SCAN, OP_RESCORE, OP_SIMS, OP_SCORES, OP_GRID, OP_SELECT, OP_TOPK, \
-    OP_MIN, OP_FETCH, OP_SCAN_BATCH, OP_LAYOUT, OP_WRITE_AVG, OP_ROUND = range(17)
+    OP_MIN, OP_FETCH, OP_SCAN_BATCH, OP_LAYOUT, OP_WRITE_AVG, OP_ROUND, OP_DEFINE_SET, OP_USE_SET, OP_DROP_SET = range(20)
 
 
 def _atomic(method):
@@ -89,6 +93,11 @@ class ShardedFeatureDB:
         self.lock = threading.RLock()
         self.sims_owner = None
         self.scores_owner = None
+        # search sets: id -> view (workers of a served database know a set by its number only), number -> per-rank counts, and the
+        # window of the global result arrays this rank fills: [_pos0, _pos0 + _nloc) of _ntot (no set in use: its rows of N)
+        self._sets, self._set_counts, self._next_token = {}, {}, 0
+        self._set_in_use, self._counts, self._whole = None, None, None
+        self._pos0, self._nloc, self._ntot = self.row0, int(local.n), self.n
         backend = dist.get_backend(group)
         # collectives move tensors on the backend's device: RCCL = this rank's GPU (result arrays are viewed in place, never
         # staged through the host), gloo = host memory (CPU tests; rehearsals of N ranks on one card)
@@ -253,7 +262,13 @@ class ShardedFeatureDB:
 
     def _gather(self, kinds):
         parts = self._local_step(lambda: self._result_tensors(kinds))
-        return [self._host(self._coll(lambda p=p: all_gather_rows(p, self.n, self.group))) for p in parts]
+        return [self._host(self._coll(lambda p=p: self._all_rows(p))) for p in parts]
+
+    def _all_rows(self, part):
+        """This rank's rows of a per-clip result -> all of them in global order (of the search set in use, if any)."""
+        if self._counts is None:
+            return all_gather_rows(part, self.n, self.group)
+        return all_gather_counts(part, self._counts, self.group)
 
     def _sum(self, arr: np.ndarray) -> np.ndarray:
         """All-reduce SUM of an array in which every element is non-zero on at most one rank (x + 0 is exact)."""
@@ -271,6 +286,82 @@ class ShardedFeatureDB:
             raise ValueError("row outside [0,%d)" % self.n)
         pos = np.flatnonzero((rows_global >= self.row0) & (rows_global < self.row0 + self.local.n))
         return pos, rows_global[pos] - self.row0
+
+    def _mine_pos(self, where: np.ndarray):
+        """The same for rows of the RESULT arrays: database rows, or positions in the search set in use."""
+        where = np.asarray(where, dtype=np.int64).reshape(-1)
+        if where.size and (where.min() < 0 or where.max() >= self._ntot):
+            raise ValueError("row outside [0,%d)" % self._ntot)
+        pos = np.flatnonzero((where >= self._pos0) & (where < self._pos0 + self._nloc))
+        return pos, where[pos] - self._pos0
+
+    # ------------------------------------------------------------------ search sets
+    @_atomic
+    def define_search_set(self, set_id, clip_ids):
+        """As :meth:`FeatureDB.define_search_set`, on every rank: the set travels ONCE, as its ascending global rows, and each rank
+        keeps the rows of its own range resident.  SPMD: every rank passes the same arguments."""
+        from .feature_db import search_set_rows
+        if set_id is None:
+            raise ValueError("None names the whole database")
+        if set_id in self._sets:
+            raise ValueError("search set %r is already defined (drop_search_set first)" % (set_id,))
+        rows = search_set_rows(self, clip_ids)                     # KeyError for an unknown clip: before anything is announced
+        token = self._next_token
+        self._announce(OP_DEFINE_SET, ints=np.concatenate([[token], rows]))
+        return self._define_rows(set_id, token, rows)
+
+    def _define_rows(self, set_id, token, rows):
+        from .feature_db import SearchSetView
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        self._next_token = max(self._next_token, int(token) + 1)
+        lo, hi = self.row0, self.row0 + self.local.n
+        self._local_step(lambda: self.local.define_search_rows(int(token), rows[(rows >= lo) & (rows < hi)] - lo))
+        bounds = [shard_range(self.n, self.world, g) for g in range(self.world)]
+        self._set_counts[int(token)] = [int(np.count_nonzero((rows >= r0) & (rows < r0 + k))) for r0, k in bounds]
+        view = SearchSetView(set_id, self.clip_ids[rows], rows, token=int(token))
+        self._sets[set_id] = view
+        return view
+
+    def has_search_set(self, set_id) -> bool:
+        try:
+            return set_id is not None and set_id in self._sets
+        except TypeError:
+            return False
+
+    @_atomic
+    def use_search_set(self, set_id):
+        """As :meth:`FeatureDB.use_search_set`: one announcement carrying the set's number -- none when the set in use does not
+        change.  Returns the (global) view."""
+        from .feature_db import whole_view
+        if set_id is None:
+            if self._whole is None:
+                self._whole = whole_view(self)
+            view = self._whole
+        else:
+            view = self._sets[set_id]
+        if set_id != self._set_in_use:
+            self._announce(OP_USE_SET, ints=[view.token])
+            self._local_step(lambda: self.local.use_search_set(None if set_id is None else view.token))
+            self._set_in_use = set_id
+            self._counts = None if set_id is None else self._set_counts[view.token]
+            if self._counts is None:
+                self._pos0, self._nloc, self._ntot = self.row0, int(self.local.n), self.n
+            else:
+                self._pos0, self._nloc, self._ntot = int(sum(self._counts[:self.rank])), self._counts[self.rank], int(sum(self._counts))
+        return view
+
+    @_atomic
+    def drop_search_set(self, set_id):
+        view = self._sets[set_id]
+        if set_id == self._set_in_use:
+            raise ValueError("search set %r is in use (use_search_set another one, or None, first)" % (set_id,))
+        self._announce(OP_DROP_SET, ints=[view.token])
+        self._local_step(lambda: self.local.drop_search_set(view.token))
+        del self._sets[set_id], self._set_counts[view.token]
+
+    @property
+    def search_set_in_use(self):
+        return self._set_in_use
 
     # ------------------------------------------------------------------ query
     @_atomic
@@ -357,10 +448,10 @@ class ShardedFeatureDB:
         similarities were displaced by another ticket's round on the same database restores them before it scores (ticket.py)."""
         a = np.ascontiguousarray(avg, dtype=np.float64)
         ne = None if n_e is None else np.ascontiguousarray(n_e, dtype=np.int64)
-        if a.shape != (self.n, self.S) or (ne is not None and ne.shape != (self.n, self.S)):
-            raise ValueError("avg / n_e must be [%d,%d]" % (self.n, self.S))
+        if a.shape != (self._ntot, self.S) or (ne is not None and ne.shape != (self._ntot, self.S)):
+            raise ValueError("avg / n_e must be [%d,%d]" % (self._ntot, self.S))
         self._announce(OP_WRITE_AVG, ints=[] if ne is None else ne.reshape(-1), floats=a.reshape(-1))
-        lo, hi = self.row0, self.row0 + self.local.n
+        lo, hi = self._pos0, self._pos0 + self._nloc
         self._local_step(lambda: self.local.write_avg(a[lo:hi], None if ne is None else ne[lo:hi].astype(np.int32)))
 
     @_atomic
@@ -387,7 +478,7 @@ class ShardedFeatureDB:
         if not sims:
             return avg, ne
         part = self._local_step(lambda: self._torch.from_numpy(np.ascontiguousarray(self.local.similarities(sims=True)[2])).to(self._cdev))
-        full = self._coll(lambda: all_gather_rows(part, self.n, self.group))
+        full = self._coll(lambda: self._all_rows(part))
         return avg, ne, self._host(full)
 
     @_atomic
@@ -400,7 +491,7 @@ class ShardedFeatureDB:
         caller that keeps working on the GPU, or a throughput measurement, wants)."""
         self._announce(OP_SCORES)
         part = self._local_step(lambda: self._result_tensors(["scores"]))[0]
-        return self._coll(lambda: all_gather_rows(part, self.n, self.group))
+        return self._coll(lambda: self._all_rows(part))
 
     @property
     def stream(self):
@@ -416,7 +507,7 @@ class ShardedFeatureDB:
         self._announce(OP_GRID, ints=np.concatenate([[wg.shape[0]], r]), floats=wg)
 
         def part():
-            pos, mine = self._mine(r)
+            pos, mine = self._mine_pos(r)
             out = np.zeros((wg.shape[0], r.size), dtype=np.float64)
             if pos.size:
                 out[:, pos] = self.local.scores_grid(wg, mine)
@@ -433,7 +524,7 @@ class ShardedFeatureDB:
         def part():
             m, r, am = self.local.select(float(threshold), float(lower))
             best = float(self.local.scores_at([am])[0]) if am >= 0 else 0.0
-            return m + self.row0, r + self.row0, (am + self.row0 if am >= 0 else -1), best
+            return m + self._pos0, r + self._pos0, (am + self._pos0 if am >= 0 else -1), best
         return self._merge_selection(*self._local_step(part))
 
     def _merge_selection(self, m, r, am, best):
@@ -504,7 +595,7 @@ class ShardedFeatureDB:
             best = float(r.scores[r.near_argmax]) if band is not None and r.near_argmax >= 0 else 0.0
             return r, np.ascontiguousarray(np.concatenate(cols, axis=1)), best
         r, packed, best = self._local_step(part)
-        full = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(packed).to(self._cdev), self.n, self.group)))
+        full = self._host(self._coll(lambda: self._all_rows(torch.from_numpy(packed).to(self._cdev))))
         out = RoundResult()
         out.avg = out.n_e = out.scores = out.match_rows = out.near_rows = None
         out.near_argmax = -1
@@ -518,18 +609,18 @@ class ShardedFeatureDB:
         if band is not None:
             am = int(r.near_argmax)
             out.match_rows, out.near_rows, out.near_argmax = self._merge_selection(
-                np.asarray(r.match_rows, dtype=np.int64) + self.row0, np.asarray(r.near_rows, dtype=np.int64) + self.row0,
-                am + self.row0 if am >= 0 else -1, best)
+                np.asarray(r.match_rows, dtype=np.int64) + self._pos0, np.asarray(r.near_rows, dtype=np.int64) + self._pos0,
+                am + self._pos0 if am >= 0 else -1, best)
         return out
 
     @_atomic
     def topk(self, k: int):
         torch = self._torch
-        k = int(min(k, self.n))
+        k = int(min(k, self._ntot))
         self._announce(OP_TOPK, ints=[k])
 
         def part():
-            rows, vals = self.local.topk(min(k, self.local.n)) if self.local.n else (np.zeros(0, np.int64), np.zeros(0))
+            rows, vals = self.local.topk(min(k, self._nloc)) if self._nloc and k else (np.zeros(0, np.int64), np.zeros(0))
             buf = np.zeros((1, 1 + 2 * k), dtype=np.int64)
             buf[0, 0] = rows.size
             buf[0, 1:1 + rows.size] = rows
@@ -539,7 +630,8 @@ class ShardedFeatureDB:
         allb = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(buf).to(self._cdev), self.world, self.group)))
         rows = [allb[g, 1:1 + allb[g, 0]] for g in range(self.world)]
         vals = [allb[g, 1 + k:1 + k + allb[g, 0]].view(np.float64) for g in range(self.world)]
-        row0s = [shard_range(self.n, self.world, g)[0] for g in range(self.world)]
+        row0s = [shard_range(self.n, self.world, g)[0] for g in range(self.world)] if self._counts is None else \
+            np.concatenate([[0], np.cumsum(self._counts)[:-1]]).tolist()
         return merge_topk(rows, vals, row0s, k)
 
     @_atomic
@@ -548,7 +640,7 @@ class ShardedFeatureDB:
         self._announce(OP_MIN, ints=r)
 
         def part():
-            _pos, mine = self._mine(r)
+            _pos, mine = self._mine_pos(r)
             return self.local.min_score(mine)              # 1 when the rank holds none of the rows (ticket.py:302)
         m = self._local_step(part)
         t = self._torch.tensor([1.0 if m is None else m], dtype=self._torch.float64, device=self._cdev)
@@ -671,7 +763,13 @@ class ShardedFeatureDB:
         elif op == OP_LAYOUT:
             self.set_layout("tiled" if ints[0] else "rows")
         elif op == OP_WRITE_AVG:
-            self.write_avg(floats.reshape(self.n, S), ints.reshape(self.n, S) if ints.size else None)
+            self.write_avg(floats.reshape(self._ntot, S), ints.reshape(self._ntot, S) if ints.size else None)
+        elif op == OP_DEFINE_SET:
+            self._define_rows(int(ints[0]), int(ints[0]), ints[1:])      # a worker knows a set by its number
+        elif op == OP_USE_SET:
+            self.use_search_set(None if ints[0] < 0 else int(ints[0]))
+        elif op == OP_DROP_SET:
+            self.drop_search_set(int(ints[0]))
         else:
             raise RuntimeError("unknown operation %d announced" % op)
 

@@ -17,7 +17,7 @@ from collections.abc import Mapping
 
 import numpy as np
 
-from .feature_db import FeatureDB
+from .feature_db import FeatureDB, whole_view
 
 
 class ScoreMap(Mapping):
@@ -100,6 +100,7 @@ class TicketScoring:
     _stream_gap = None                       # per stream: does any clip lack it (compute_scores' KeyError of ticket.py:177)
     _round = None                            # token of this ticket's latest compute_similarities (see _own_similarities)
     _score_weights = None
+    _view = None                             # the search-set view this round is bound to (feature_db.SearchSetView)
     feature_db_dtype = np.float64            # dtype used when the DB is built from API records
     device = 0
 
@@ -138,6 +139,10 @@ class TicketScoring:
                 pass                                          # a target object that takes no attributes
         self._ahead = None
         with _db_lock(db):                    # one resident database may serve several tickets: these calls are one step
+            # The clips of THIS ticket's search set (ticket.py:363-365), when the resident database has it defined: the round runs
+            # over that view and everything below is indexed by position in it.  The ticket keeps the view OBJECT -- the set the
+            # handle has in use is shared state that the next ticket changes.
+            view = self._bind_view(db)
             db.restrict_slots(slot_used)      # per query; the database's own mask is never modified (no device call unless it changes)
             self._round = object()            # whose similarities the database holds now (see _own_similarities)
             ahead = self._look_ahead(hyperparameters, stream_names) if hasattr(db, "query_round") else None
@@ -161,7 +166,16 @@ class TicketScoring:
         self._stream_names = stream_names
         self._avg, self._n_e = avg, n_e
         self._stream_gap = None
-        self.similarities = SimilarityMap(db.clip_ids, stream_names, avg, n_e, db.row_of)
+        self._view = view
+        self.similarities = SimilarityMap(view.clip_ids, stream_names, avg, n_e, view.row_of)
+
+    def _bind_view(self, db):
+        """Select this ticket's search set on the database (no call when it is the one in use) and return its view; a database
+        without that set defined -- or without search sets at all -- is scanned whole, as ever.  Call with the lock held."""
+        if not hasattr(db, "use_search_set"):
+            return whole_view(db)
+        set_id = getattr(self, "search_set", None)
+        return db.use_search_set(set_id if db.has_search_set(set_id) else None)
 
     @staticmethod
     def _review_band(hyperparameters):
@@ -207,7 +221,7 @@ class TicketScoring:
             # (whose scores may meanwhile be another ticket's: select_clips_to_review / _own_scores look after that)
             self._score_values = ahead["scores"]
             self._score_weights = w
-            self.scores = ScoreMap(db.clip_ids, self._score_values, db.row_of)
+            self.scores = ScoreMap(self._view.clip_ids, self._score_values, self._view.row_of)
             return
         with _db_lock(db):
             self._own_similarities()
@@ -223,7 +237,7 @@ class TicketScoring:
                 self._ahead = None
             self._score_weights = w
             db.scores_owner = (self._round, w.tobytes())
-        self.scores = ScoreMap(db.clip_ids, self._score_values, db.row_of)
+        self.scores = ScoreMap(self._view.clip_ids, self._score_values, self._view.row_of)
 
     # -- a resident database shared between tickets -------------------------------------------------
     def _own_similarities(self):
@@ -231,9 +245,12 @@ class TicketScoring:
         (compute_similarities, optimize_weights, compute_scores, select_clips_to_review -- compute_matches.py:58-89).  When another
         ticket used the same resident database in between, this ticket's averaged similarities (kept on the host since
         compute_similarities) go back to the device before anything is computed from them: N x S x 12 bytes, only ever on a
-        collision.  Call with the database's lock held."""
+        collision -- after this ticket's search set has been selected again (the other ticket's round ran over its own).  Call with
+        the database's lock held."""
         db = self.feature_db
         if getattr(db, "sims_owner", self._round) is not self._round:
+            if hasattr(db, "use_search_set"):
+                db.use_search_set(self._view.set_id)
             db.write_avg(self._avg, self._n_e)
             db.sims_owner, db.scores_owner = self._round, None
 
@@ -249,19 +266,19 @@ class TicketScoring:
 
     # -- ticket.py:301-309 ------------------------------------------------------------------
     def lowest_scoring_user_match(self):
-        db = self.feature_db
-        rows = sorted(db.row_of(int(c)) for c, v in self.user_matches.items()
-                      if v is True and db.has_clip(c) and str(int(c)) == c)
+        view = self._view                            # positions in the ticket's search set
+        rows = sorted(view.row_of(int(c)) for c, v in self.user_matches.items()
+                      if v is True and view.has_clip(c) and str(int(c)) == c)
         min_score, min_clip = 1, None
         for r in rows:                               # same order as the walk over self.scores
             min_score = min(min_score, self._score_values[r])
-            min_clip = int(db.clip_ids[r])
+            min_clip = int(view.clip_ids[r])
         return min_score, min_clip
 
     # -- ticket.py:311-356 ------------------------------------------------------------------
     def select_clips_to_review(self, threshold=0.8, max_number_matches=20, near_miss=0.5):
         db = self.feature_db
-        vals, ids = self._score_values, db.clip_ids
+        vals, ids = self._score_values, self._view.clip_ids
         lower_limit = threshold - near_miss * (1 - threshold)
         ahead = getattr(self, "_ahead", None)
         if ahead is not None and ahead["select"] == (threshold, lower_limit) and ahead["w"] == self._score_weights.tobytes():
@@ -407,10 +424,10 @@ def install(ticket_cls, hyperparameter_cls=None, target_clip_cls=None):
             self._ticket = ticket                          # lets the round use rows of a resident ticket.feature_db
         target_clip_cls.__init__ = remember_ticket
     for name in ("compute_similarities", "compute_scores", "lowest_scoring_user_match", "select_clips_to_review",
-                 "_own_similarities", "_own_scores", "_look_ahead"):
+                 "_own_similarities", "_own_scores", "_look_ahead", "_bind_view"):
         setattr(ticket_cls, name, getattr(TicketScoring, name))
     ticket_cls._review_band = staticmethod(TicketScoring._review_band)
-    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap"):
+    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap", "_view"):
         if not hasattr(ticket_cls, name):
             setattr(ticket_cls, name, getattr(TicketScoring, name))
     if hyperparameter_cls is not None:
