@@ -75,6 +75,42 @@ def extract(args, device, rank, world, timings):
     return first, count, out
 
 
+def csv_device_shares(out_dir, device_index):
+    """Where the device loader's time goes, measured apart from the timed load: reading the files, the host's index pass
+    (feature_csv.index_features), the upload of the same number of bytes from pageable memory (HIP events of vq_timer_* around one
+    vq_db_upload), and FeatureDB.load_csv itself; what load_csv takes beyond index + upload is the kernels, the read-back of the
+    host's list and the launches (csv_load_rest_s, derived)."""
+    import ctypes as C
+    from video_query_algorithms_amd._lib import call
+    files = sorted(os.path.join(d, f) for d, _s, fs in os.walk(out_dir) for f in fs if f.endswith(".csv"))
+    t0 = time.perf_counter()
+    blobs = [open(f, "rb").read() for f in files]
+    t_file = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    counts = [feature_csv.index_features(b)[3] for b in blobs]
+    t_index = time.perf_counter() - t0
+    total = sum(len(b) for b in blobs)
+    rows = max(1, total // 4096)
+    scratch = vqa.FeatureDB(rows, 1, 1, 1024, np.float32, device_index)
+    block = np.ones((rows, 1, 1, 1024), dtype=np.float32)
+    timer, ms = C.c_void_p(), C.c_float()
+    call("vq_timer_create", C.byref(timer))
+    call("vq_timer_start", timer, None)
+    scratch.upload(0, block)
+    call("vq_timer_stop", timer, None)
+    call("vq_timer_elapsed_ms", timer, C.byref(ms))
+    call("vq_timer_destroy", timer)
+    scratch.close()
+    db = vqa.FeatureDB(max(counts), 1, 1, 1024, np.float64, device_index)
+    t0 = time.perf_counter()
+    for b, n in zip(blobs, counts):
+        db.load_csv(b, 0, 0, np.arange(n))
+    t_load = time.perf_counter() - t0
+    db.close()
+    return {"csv_text_bytes": total, "csv_file_read_s": t_file, "csv_index_s": t_index, "csv_upload_s": ms.value / 1e3, "csv_load_s": t_load,
+            "csv_load_rest_s": t_load - t_index - ms.value / 1e3}
+
+
 def main(argv=None, observer=None):
     """``observer`` (tests): an object whose ``start(feats, clip_ids, ticket, hp)`` is called once before the rounds and
     ``round(r, ticket, hp, prev_weights, prev_threshold, labels, rng_state_before_select)`` after each one."""
@@ -86,6 +122,9 @@ def main(argv=None, observer=None):
     ap.add_argument("--labels", type=int, default=20)
     ap.add_argument("--csv-clips", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--csv-loader", choices=("python", "device"), default="python",
+                    help="how the CSV sample is read back: the load_db parser rules in Python (feature_csv.read_features), or "
+                         "FeatureDB.from_csv_tree (the text parsed on the device); csv_read_s is the time of the one chosen")
     ap.add_argument("--gather-features", action="store_true", help="N > 1: all-gather the feature blocks and run the rounds on rank 0 only")
     args = ap.parse_args(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -135,15 +174,25 @@ def main(argv=None, observer=None):
                                        {"rgb": "synthetic:%d" % (100 + split), "warped_optical_flow": "synthetic:%d" % (100 + split)})
         timings["csv_write_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
-        back = np.zeros_like(host)
-        for ei, split in enumerate(SPLITS):
-            nsplit, per_stream = feature_csv.read_split_dir(os.path.join(out_dir, "synthetic_video", "UCF101_split%d" % split))
-            assert nsplit == split
-            for si, st in enumerate(STREAMS):
-                clips, vals, _meta = per_stream[st]
-                assert (clips == clip_ids[:n_csv]).all()
-                back[:, si, ei] = vals
-        timings["csv_read_s"] = time.perf_counter() - t0
+        if args.csv_loader == "device":
+            csv_db = vqa.FeatureDB.from_csv_tree(out_dir, streams=STREAMS, dtype=np.float64, device=device.index)
+            back = csv_db.read_rows(np.arange(n_csv))
+            timings["csv_read_s"] = time.perf_counter() - t0
+            assert csv_db.clips == [("synthetic_video", int(c)) for c in clip_ids[:n_csv]] and csv_db.slot_splits[0] == list(SPLITS)
+            timings["csv_host_fields"] = csv_db.csv_host_fields
+            csv_db.close()
+            timings.update(csv_device_shares(out_dir, device.index))
+        else:
+            back = np.zeros_like(host)
+            for ei, split in enumerate(SPLITS):
+                nsplit, per_stream = feature_csv.read_split_dir(os.path.join(out_dir, "synthetic_video", "UCF101_split%d" % split))
+                assert nsplit == split
+                for si, st in enumerate(STREAMS):
+                    clips, vals, _meta = per_stream[st]
+                    assert (clips == clip_ids[:n_csv]).all()
+                    back[:, si, ei] = vals
+            timings["csv_read_s"] = time.perf_counter() - t0
+        timings["csv_loader"] = args.csv_loader
         assert (back == host).all(), "CSV round trip changed a value"       # repr(float64) is shortest round-trip
         timings["csv_clips"] = n_csv
 

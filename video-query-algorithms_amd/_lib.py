@@ -122,6 +122,11 @@ ROW_VIEW_SIGNATURES = {
     "vq_db_rows_define": [_P, _P, _I64, _pI32], "vq_db_rows_use": [_P, _I32], "vq_db_rows_drop": [_P, _I32],
     "vq_db_rows_active": [_P, _pI32, _pI64],
 }
+# include/vq_amd_csv.h: feature CSV files indexed on the host and parsed on the device -- additive to ABI 12, bound like the tables above
+CSV_SIGNATURES = {
+    "vq_csv_index": [C.c_char_p, _I64, _I64, _pI64, _pI64, _pI32, _P, _P],
+    "vq_db_load_csv": [_P, C.c_char_p, _I64, _I32, _I32, _P, _I64, _I64, _pI64],
+}
 _SPECIAL = {"vq_last_error": ([], C.c_char_p), "vq_abi_version": ([], C.c_int)}
 
 _lib = None
@@ -174,7 +179,7 @@ def load(path: str | None = None):
         for name, (args, res) in _SPECIAL.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, res
-        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()):
+        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()) + list(CSV_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = ABI mismatch; fail loudly
             fn.argtypes, fn.restype = args, C.c_int
         if lib.vq_abi_version() != ABI_VERSION:

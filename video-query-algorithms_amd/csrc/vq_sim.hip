@@ -1375,65 +1375,7 @@ static void round_layout(int64_t n, int S, int64_t off[8]) {
     off[7] = 0;
 }
 
-struct vq_db {
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t n = 0;
-    int S = 0, E = 0, D = 0, dtype = VQ_F32;
-    int cus = 256;
-    void* feats = nullptr;
-    bool owns_feats = true;
-    // VQ_LAYOUT_ROWS: [N][S][E][D].  VQ_LAYOUT_TILED (fp32, own memory): [tile of 16 clips][S*E][D/4][clip][4] in the SAME block (a
-    // tile's 16 rows and its tiled form cover the same bytes; the block is allocated for whole tiles) -- vq_db_set_layout
-    int layout = VQ_LAYOUT_ROWS;
-    bool feats_exposed = false;      // adopted memory, or the raw pointer was handed out: the library no longer controls the layout
-    uint8_t* present = nullptr;
-    double* t = nullptr;        // [S*E*D]
-    bool have_query = false, have_avg = false, have_scores = false, have_sims = false;
-    double* w = nullptr;        // [8]
-    double* sims = nullptr;     // lazily [N][S][E]
-    double* avg = nullptr;      // [N][S]
-    int32_t* ne = nullptr;      // [N][S]
-    double* scores = nullptr;   // [N]
-    // avg | ne | scores | sel_result | match prefix | near prefix are ONE device allocation (round_dev), in the order of the host
-    // block of vq_db_query_round: a round's results go back in one copy
-    char* round_dev = nullptr;
-    int64_t round_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // byte offsets of avg, ne, scores, result, matchp, nearp; [6] = total
-    int64_t* matchp = nullptr;       // first kRoundPrefix rows of the last selection's match list
-    int64_t* nearp = nullptr;
-    // selection scratch
-    int nblk = 0;
-    int2* blk_cnt = nullptr;
-    double* blk_max = nullptr;
-    int64_t* blk_arg = nullptr;
-    int64_t* sel_result = nullptr;   // [3] device
-    int64_t* rows0 = nullptr;        // [N]
-    int64_t* rows1 = nullptr;        // [N]
-    int64_t last_n0 = 0, last_n1 = 0;
-    uint64_t* tk_state = nullptr;    // [2]
-    unsigned int* tk_hist = nullptr; // [256]
-    double* batch_buf = nullptr;     // batched scan: queries [Q][NV][D] | weights [Q][S] | (two-kernel form: sims [NV][Q][N]) | scores [Q][N]
-    double* batch_scores = nullptr;  // where the scores of the last batched scan start inside batch_buf
-    int64_t batch_cap = 0;           // doubles
-    int batch_q = 0;                 // queries of the last batched scan
-    double* grid_buf = nullptr;      // scratch for grid / gathers
-    int64_t grid_cap = 0;
-    // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over
-    // (-1: the whole database) and `na` the number of clips it then covers -- M, or N: what every result-side entry point counts with.
-    struct RowView {
-        bool defined = false;
-        int64_t m = 0;               // rows in the view
-        int64_t ntiles = 0;          // tiles of 16 clips it touches (fp32 databases of a tiled-capable shape; else no tile tables)
-        int64_t* rows = nullptr;     // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
-        int64_t* tiles = nullptr;
-        int64_t* pos = nullptr;
-    };
-    std::vector<RowView> views;
-    int active = -1;
-    int64_t na = 0;
-    size_t elem() const { return dtype == VQ_F64 ? 8 : dtype == VQ_F16 ? 2 : 4; }
-};
+#include "vq_db.h"      // struct vq_db
 
 static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);

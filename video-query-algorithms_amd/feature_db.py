@@ -283,6 +283,86 @@ class FeatureDB:
         return db
 
     @classmethod
+    def from_csv_tree(cls, features_dir: str, streams: Sequence[str] | None = None, clip_id_base: int = 0, dtype=np.float32, device: int = 0,
+                      layout: str = "rows") -> "FeatureDB":
+        """The reference's ``data/features`` tree (``<video>/<name ending in the split digit>/<stream>_<blob>_features.csv``) -> a
+        resident database, the decimal text parsed ON THE DEVICE (:meth:`load_csv`): the rows, ids, presence mask, ``stream_names`` and
+        ``slot_splits`` that ``feature_store.store_from_csv_tree`` + :meth:`from_store` give, bit for bit, without the interpreter
+        converting a value (src/api/api_load_records.py:45-58) and without a store on disk.  Same walk: videos sorted by name, a
+        video's clips in clip-number order, ids ``clip_id_base + row + 1``; a (clip, stream, split) without a row is absent and reads
+        back as zeros.  Pass one indexes the files and keeps only their clip numbers; pass two loads them.  ``clips`` is the
+        ``(video, clip)`` of every row; ``csv_host_fields`` counts the fields the host had to resolve.  ``layout="tiled"`` (fp32) tiles the
+        block first, so the values land in their tiles.  A value that the database's type cannot hold (float16: |x| >= 65520) or that
+        is no number raises ``ValueError`` naming file, line and field."""
+        import os
+        from .tsn import feature_csv
+        streams = list(feature_csv.STREAM_MODES if streams is None else streams)
+        per_video, all_splits, dim = [], set(), None
+        for video in sorted(d for d in os.listdir(features_dir) if os.path.isdir(os.path.join(features_dir, d))):
+            vdir = os.path.join(features_dir, video)
+            by_split = {}
+            for sd in sorted(d for d in os.listdir(vdir) if os.path.isdir(os.path.join(vdir, d))):
+                split_path = os.path.join(vdir, sd)
+                nsplit = int(split_path.rstrip("/")[-1])                      # feature_csv.read_split_dir
+                per_stream = {}
+                for entry in sorted(os.scandir(split_path), key=lambda e: e.name):
+                    if entry.is_file() and entry.name.endswith('.csv') and not entry.name.startswith('.'):
+                        meta, cl, d, _n = feature_csv.index_features(entry.path)
+                        per_stream[meta["dnn_stream"]] = (cl, entry.path, d)
+                by_split[nsplit] = per_stream
+                all_splits.add(nsplit)
+            clips = sorted({int(c) for ps in by_split.values() for (cl, _p, _d) in ps.values() for c in cl})
+            per_video.append((video, clips, by_split))
+            for ps in by_split.values():
+                for (_cl, _p, d) in ps.values():
+                    dim = d
+        splits = sorted(all_splits)
+        n = sum(len(c) for _v, c, _b in per_video)
+        if n == 0:
+            raise ValueError("no feature files under %s" % features_dir)
+        present = np.zeros((n, len(streams), len(splits)), dtype=np.uint8)
+        names, jobs = [], []
+        row0 = 0
+        for video, clips, by_split in per_video:
+            local = {c: row0 + i for i, c in enumerate(clips)}
+            names.extend((video, c) for c in clips)
+            for ei, sp in enumerate(splits):
+                for si, st in enumerate(streams):
+                    if sp in by_split and st in by_split[sp]:
+                        cl, path, _d = by_split[sp][st]
+                        rows = np.array([local[int(c)] for c in cl], dtype=np.int64)
+                        present[rows, si, ei] = 1
+                        last = {r: i for i, r in enumerate(rows.tolist())}      # a clip number met twice in a file: its last row stays
+                        if len(last) != rows.size:
+                            rows[[i for i, r in enumerate(rows.tolist()) if last[r] != i]] = -1
+                        jobs.append((path, si, ei, rows))
+            row0 += len(clips)
+        db = cls(n, len(streams), len(splits), dim, dtype, device, clip_id_base + np.arange(1, n + 1, dtype=np.int64))
+        if layout != "rows":
+            db.set_layout(layout)
+        db.clips, db.csv_host_fields = names, 0
+        if not present.all():
+            # a new handle's block is not cleared and an absent slot reads back as zeros: clear the rows that lack one, then load
+            lacking = np.flatnonzero(~present.reshape(n, -1).all(axis=1))
+            for run in np.split(lacking, np.flatnonzero(np.diff(lacking) != 1) + 1):
+                for r in range(int(run[0]), int(run[-1]) + 1, 4096):
+                    db.upload(r, np.zeros((min(4096, int(run[-1]) + 1 - r), db.S, db.E, db.D), dtype=db.dtype))
+        for path, si, ei, rows in jobs:
+            with open(path, 'rb') as f:
+                data = f.read()
+            try:
+                db.csv_host_fields += db.load_csv(data, si, ei, rows)
+            except _lib.VqError as e:
+                if e.code != -1:                                  # only VQ_E_INVALID is about the file's contents
+                    raise
+                raise ValueError("%s: %s" % (path, e)) from e
+        if not present.all():
+            db.set_present(present)
+        db.stream_names = streams
+        db.slot_splits = [list(splits)] * len(streams)
+        return db
+
+    @classmethod
     def synthetic(cls, n: int, n_streams: int, n_splits: int, dim: int = 1024, seed: int = 0,
                   scales: Sequence[float] = (4.0, 1.0), row0: int = 0, dtype=np.float32, device: int = 0,
                   clip_ids=None) -> "FeatureDB":
@@ -305,6 +385,19 @@ class FeatureDB:
         if a.shape[1:] != (self.S, self.E, self.D):
             raise ValueError("rows must be [n,%d,%d,%d]" % (self.S, self.E, self.D))
         call("vq_db_upload", self._h, int(row0), a.shape[0], _np_ptr(a))
+
+    def load_csv(self, data, stream: int, split: int, rows, chunk_bytes: int = 0) -> int:
+        """The values of one feature file (``data``: its bytes, header line included) into slot (``stream``, ``split``): data row i goes
+        to DATABASE row ``rows[i]``, -1 skips it.  The text is parsed on the device (vq_db_load_csv, include/vq_amd_csv.h) into the
+        database's dtype and layout; returns how many fields the host had to resolve.  ``VqError`` (VQ_E_INVALID) names line and field
+        of a malformed value or of one a float16 database cannot hold; nothing is stored when ``rows`` names a row twice or outside the
+        database, or its length or the file's dim do not match."""
+        data = bytes(data)
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        host = C.c_int64()
+        call("vq_db_load_csv", self._h, data, len(data), int(stream), int(split), _np_ptr(r) if r.size else None, int(r.size), int(chunk_bytes),
+             C.byref(host))
+        return int(host.value)
 
     def set_layout(self, layout: str):
         """"rows" ([N][S][E][D]) or "tiled" ([tile of 16 clips][S*E][D/4][clip][4]: the order in which every load of the scans

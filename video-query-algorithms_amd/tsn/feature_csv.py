@@ -106,6 +106,28 @@ def read_features(csv_path: str) -> Tuple[dict, np.ndarray, np.ndarray]:
     return meta, np.asarray(clips, dtype=np.int64), np.asarray(rows, dtype=np.float64)
 
 
+def index_features(path_or_bytes):
+    """What ``read_features`` learns about a file without converting a value: (header dict, clip numbers [n] int64, dim, n).  One pass
+    of the library over the bytes (``vq_csv_index``, include/vq_amd_csv.h: its rules are the reference reader's on the files the
+    writer produces -- quoted CSV and what only Python's ``int()`` / ``float()`` accept are refused, ``VqError``); the header line is
+    split here, as ``read_features`` does.  ``path_or_bytes``: a path, or the file's bytes."""
+    import ctypes as C
+    from .._lib import call
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, 'rb') as f:
+            data = f.read()
+    cap = data.count(b"\n") + 1
+    clips = np.empty(cap, dtype=np.int64)
+    hb, n, dim = C.c_int64(), C.c_int64(), C.c_int32()
+    call("vq_csv_index", data, len(data), cap, C.byref(hb), C.byref(n), C.byref(dim), None, clips.ctypes.data_as(C.c_void_p))
+    header = next(csv.reader([data[:hb.value].decode()]))
+    meta = {"video": header[0].split('=')[-1], "dnn_stream": header[2].split('=')[-1],
+            "feature_name": header[3].split('=')[-1], "dnn_weights_file_uri": header[4].split('=')[-1]}
+    return meta, clips[:n.value].copy(), int(dim.value), int(n.value)
+
+
 def read_split_dir(split_path: str):
     """One ``<video>/<split>`` directory -> (split number, {stream: (clips, features)}); the split number is the
     LAST CHARACTER of the directory name (api_load_records.py:43)."""
