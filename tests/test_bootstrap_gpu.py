@@ -1,4 +1,10 @@
-"""GPU: target bootstrapping (csrc/vq_boot.hip through the C ABI) against
+"""What this module's 1e-8 is: the bound for the REFERENCE'S RECORDED FIXTURES, whose targets went through explicit 1024 x 1024
+inverses of matrices with condition numbers of 1e3 .. 1e6.  It says that the product reproduces the reference; it does not pin the
+kernel's own arithmetic (an error of 1e-9 in the Gram sum, the elimination or the combination passes here).  That is done in
+tests/test_bootstrap_edges_gpu.py: 8 x the spread of exact / fp64 CPU references (1e-16 .. 3e-14), forced row swaps, every tail of
+the strided loops, the 256-row limit, refusals, bit-exact launch independence and scaling.
+
+GPU: target bootstrapping (csrc/vq_boot.hip through the C ABI) against
   * the CPU oracle's explicit-inverse restatement of target_clip.py:192-197 / :245-260, and
   * the targets and downstream scores the REFERENCE ITSELF produced (tests/golden/bootstrap*, oracle/gen_golden_bootstrap.py).
 

@@ -34,13 +34,29 @@ struct BootArgs {
     double* ws;                // [P][ws_stride] scratch
     int64_t ws_stride;
     double* out;               // [P][D]
-    int32_t* status;           // [P]: 0 ok, 1 singular system
+    int32_t* status;           // [P]: 0 ok, 1 singular system (to working precision: gauss_jordan)
 };
 
+// A pivot counts only above the rounding noise of its column: dim * kPivotTol * the largest entry the column had before
+// elimination.  Linearly dependent rows (a clip validated twice, a multiple of another row) leave a column of residues of a
+// few ulps of that size; an exact zero is the exception there, not the rule (dozens of percent of such inputs used to come
+// back as a finite "target").  The floor scales with the data, sits 2^-40 (256 rows) .. 2^-48 (1 row) below the column and
+// never changes which pivot is taken, so every accepted system is solved to the same bits as without it.
+constexpr double kPivotTol = 16.0 * 2.220446049250313e-16;     // per row of the system, in units of the column's largest entry
+
 // Solve A Z = R in place on the augmented matrix aug[dim][dim + nrhs] (row stride ld): Gauss-Jordan with partial
-// pivoting, whole workgroup.  Returns false on a zero / non-finite pivot.
-__device__ bool gauss_jordan(double* aug, int dim, int nrhs, int ld, int* piv_shared) {
+// pivoting, whole workgroup.  Returns false on a negligible (see above) / non-finite pivot.  piv_floor: dim doubles of LDS.
+__device__ bool gauss_jordan(double* aug, int dim, int nrhs, int ld, int* piv_shared, double* piv_floor) {
     const int tid = threadIdx.x, nt = blockDim.x, width = dim + nrhs;
+    for (int c = tid; c < dim; c += nt) {
+        double cm = 0.0;
+        for (int r = 0; r < dim; ++r) {
+            const double v = fabs(aug[(size_t)r * ld + c]);
+            if (v > cm) cm = v;
+        }
+        piv_floor[c] = (kPivotTol * dim) * cm;
+    }
+    __syncthreads();
     for (int k = 0; k < dim; ++k) {
         if (tid == 0) {
             int best = k;
@@ -52,7 +68,7 @@ __device__ bool gauss_jordan(double* aug, int dim, int nrhs, int ld, int* piv_sh
                     best = r;
                 }
             }
-            *piv_shared = (bv > 0.0 && bv < 1.0e300) ? best : -1;
+            *piv_shared = (bv > piv_floor[k] && bv < 1.0e300) ? best : -1;
         }
         __syncthreads();
         const int p = *piv_shared;
@@ -85,6 +101,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
     __shared__ int piv;
     __shared__ double sh_scale;
+    __shared__ double piv_floor[BOOT_MAX_ROWS];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m = a.n_valid[p], n = a.n_invalid[p], r = m + n, D = a.D;
     const T* base = static_cast<const T*>(a.base);
@@ -112,7 +129,9 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
     if (tid == 0) {
         double tr = 0.0;
         for (int j = 0; j < n; ++j) tr += G[(size_t)(m + j) * r + (m + j)];
-        sh_scale = (n > 0 && a.mu != 0.0) ? a.mu / tr : 0.0;     // target_clip.py:248-249
+        // target_clip.py:248-249.  An inf among the non-matches makes tr = inf and mu / tr = 0, which below means "no non-matches":
+        // a non-finite trace becomes a NaN scale instead, and the first pivot test refuses the problem (mu / 0 = inf ends there too)
+        sh_scale = (n > 0 && a.mu != 0.0) ? (tr < 1.0e300 ? a.mu / tr : __builtin_nan("")) : 0.0;
     }
     __syncthreads();
     const double scale = sh_scale;
@@ -132,7 +151,7 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
             A1[idx] = v;
         }
         __syncthreads();
-        ok = gauss_jordan(A1, n, m + 1, w1, &piv);      // columns n..n+m-1: K' Gyx, column n+m: K' 1
+        ok = gauss_jordan(A1, n, m + 1, w1, &piv, piv_floor);      // columns n..n+m-1: K' Gyx, column n+m: K' 1
         if (ok) {
             // B = Gxx - Gxy C,  C = s K' Gyx;  right-hand sides 1 and Gxy gamma, gamma = s K' 1
             for (int idx = tid; idx < m * (m + 2); idx += 256) {
@@ -152,7 +171,7 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
                 Bm[idx] = v;
             }
             __syncthreads();
-            ok = gauss_jordan(Bm, m, 2, m + 2, &piv);
+            ok = gauss_jordan(Bm, m, 2, m + 2, &piv, piv_floor);
         }
         if (ok) {
             for (int i = tid; i < m; i += 256) coef[i] = Bm[(size_t)i * (m + 2) + m] - Bm[(size_t)i * (m + 2) + m + 1];   // a = beta - delta
@@ -169,7 +188,7 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(BootArgs a) {
             Bm[idx] = c < m ? G[(size_t)i * r + c] : (c == m ? 1.0 : 0.0);
         }
         __syncthreads();
-        ok = gauss_jordan(Bm, m, 2, m + 2, &piv);
+        ok = gauss_jordan(Bm, m, 2, m + 2, &piv, piv_floor);
         if (ok) {
             for (int i = tid; i < m; i += 256) coef[i] = Bm[(size_t)i * (m + 2) + m];
             for (int j = tid; j < n; j += 256) coef[m + j] = 0.0;
