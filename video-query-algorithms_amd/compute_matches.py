@@ -42,19 +42,25 @@ def _review_budget(kind, tk, hp):
     return float("inf"), reach
 
 
-def _one_update(kind, update, url, hp, ticket_factory, target_factory):
+def _begin_update(kind, update, url, hp, ticket_factory, target_factory):
+    """Phase 1 of a round: the ticket, process state 3, the consistency checks (:47-52) and the target's features (:55-56).  Returns
+    the ticket, or None when the round ended with a fatal error."""
     tk = ticket_factory(update, url)
     tk.change_process_state(_IN_PROGRESS)
     fatal, warning = tk.catch_errors(kind)                                  # :47-52
     if fatal:
         tk.change_process_state(_ERROR, message=fatal)
-        return
+        return None
     if warning:
         tk.add_note(warning)
 
     tk.target = target_factory(tk, hp)                                      # :55-58
     tk.target.get_target_features()
-    tk.compute_similarities(hp)
+    return tk
+
+
+def _finish_update(kind, update, tk, hp):
+    """The round behind compute_similarities: weights, the query result, scores, the review set and its side effects (:60-107)."""
     _choose_weights(kind, update, tk, hp)
 
     round_no = 1 if kind == 'new' else tk.latest_query_result["round"] + 1  # :70-74
@@ -74,7 +80,22 @@ def _one_update(kind, update, url, hp, ticket_factory, target_factory):
         tk.change_process_state(_PROCESSED)
 
 
-def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip):
+def _one_update(kind, update, url, hp, ticket_factory, target_factory):
+    tk = _begin_update(kind, update, url, hp, ticket_factory, target_factory)
+    if tk is None:
+        return
+    tk.compute_similarities(hp)
+    _finish_update(kind, update, tk, hp)
+
+
+def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False):
+    """One broker pass.  ``batch=True`` runs it in three phases so that the pending tickets share passes over their resident database
+    (``ticket.compute_similarities_batch``): (1) every pending update gets its ticket, process state 3, its checks and its target
+    features; (2) ONE ``compute_similarities_batch`` over the tickets that survived; (3) every ticket is finished in the original
+    order.  Per ticket the calls -- and with them the ledger -- are the same sequence as without ``batch``; ACROSS tickets they
+    interleave differently (all the phase-1 entries come before any ticket's phase-3 entries), and a ticket's weights / threshold
+    look-ahead is taken from the hyperparameters object as it stands before phase 3 changes it (a ticket whose weights come out
+    different re-weights its own similarities, as ever).  Values agree with the default path to rounding (<= 1e-12)."""
     pending = query_updates.get_status()                                    # :34
     if ticket_factory is None:
         from .ticket import Ticket as _Ticket
@@ -83,9 +104,21 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
             # offline: the update object itself carries the search set (API feature records and/or a resident
             # FeatureDB); the REST side effects of the round are kept in the ticket's ledger
             return _Ticket(update_object, records=update_object.get("records"), feature_db=update_object.get("feature_db"))
-    for kind, update in pending.items():                                    # :37
+    if not batch:
+        for kind, update in pending.items():                                # :37
+            if update is not None:
+                _one_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
+        return
+    from .ticket import compute_similarities_batch
+    started = []
+    for kind, update in pending.items():
         if update is not None:
-            _one_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
+            tk = _begin_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
+            if tk is not None:
+                started.append((kind, update, tk))
+    compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters)
+    for kind, update, tk in started:
+        _finish_update(kind, update, tk, hyperparameters)
 
 
 def catch_no_matches_error(ticket):

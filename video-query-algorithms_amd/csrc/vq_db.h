@@ -48,6 +48,16 @@ struct vq_db {
     double* batch_scores = nullptr;  // where the scores of the last batched scan start inside batch_buf
     int64_t batch_cap = 0;           // doubles
     int batch_q = 0;                 // queries of the last batched scan
+    // Batched rounds (vq_db_query_round_batch, include/vq_amd_rounds.h): ONE lazy allocation that starts with the image of the host
+    // block (queries | weights | bands | n_e | avg | scores | results | prefixes: what comes and goes in one copy each way) followed by
+    // the full match / near lists [Q][N] each and the per-block scratch of the three-pass selection.
+    char* bround_dev = nullptr;
+    int64_t bround_cap = 0;          // bytes
+    int bround_q = 0;                // queries of the last batched round (0: none, or its lists are gone)
+    int64_t bround_rows0 = 0, bround_rows1 = 0;      // byte offsets of the full lists of the last round
+    int64_t bround_n0[16] = {0}, bround_n1[16] = {0};  // its counts per query (-1: that round did not partition)
+    hipEvent_t bround_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // flag 8: start | pass done | selection done | copies done
+    bool bround_timed = false;
     double* grid_buf = nullptr;      // scratch for grid / gathers
     int64_t grid_cap = 0;
     // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over

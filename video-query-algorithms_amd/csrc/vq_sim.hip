@@ -638,9 +638,13 @@ struct BatchFusedArgs {
     double* scores;           // [Q][n]
     int64_t n;
     int32_t Q, S, E, D;
+    double* avg;              // ROUND only: [Q][n][S]
 };
 
-template <typename T, int CH, int TW, bool PRES, int P, bool TILED = false>
+// ROUND (vq_db_query_round_batch, include/vq_amd_rounds.h): the weights come as the round block holds them ([Q][8]) and every stream's
+// mean also goes to avg[q][clip][s] where the stream closes.  Stores only: a score is the same operands in the same order, so the
+// same bits as the plain pass.
+template <typename T, int CH, int TW, bool PRES, int P, bool TILED = false, bool ROUND = false>
 __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) double tq[];      // 16 swizzled rows of D doubles (+ 32 of slack)
     constexpr int D = CH * 256, CE = 16 * P, NCHUNK = D / CE;       // a chunk = P pieces of 16 elements
@@ -766,13 +770,21 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
                 }
             }
             // the stream closes: avg = sum / count, then the terms of ticket.py:172-180 in stream order
-            const double ws = col < a.Q ? a.w[col * a.S + s] : 0.0;
+            const double ws = col < a.Q ? a.w[col * (ROUND ? 8 : a.S) + s] : 0.0;
             denom = denom + ws * ws;
+            // ROUND: the addresses of the avg stores do not depend on the stream, so the compiler would compute them once per round and keep
+            // them (16 VGPRs) alive through the MFMA loop; an opaque lane offset makes it compute them here, where the stream closes
+            [[maybe_unused]] int kko = kk;
+            if constexpr (ROUND) asm volatile("" : "+v"(kko));
 #pragma unroll
             for (int j = 0; j < TW; ++j)
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const double av = ssum[j][rr] / (double)(PRES ? cnt[j][rr] : a.E);
+                    if (ROUND) {                                      // the tile exists (wave-uniform), the query is in use, the row is inside n
+                        const int64_t cc = tile_of(r, j) * 16 + kko + 4 * rr;
+                        if (j < nval && col < a.Q && cc < a.n) a.avg[((int64_t)col * a.n + cc) * a.S + s] = av;
+                    }
                     const double term = ws * (1.0 - av);
                     miss[j][rr] = miss[j][rr] + term * term;
                 }
@@ -957,8 +969,8 @@ __device__ __forceinline__ int2 block_scan_excl2(int2 v, int2* total) {
 }
 
 // pass 1: per-block counts of both classes + block-local first-argmax of class 1 (near band)
-__global__ __launch_bounds__(SEL_BLOCK) void select_count_kernel(const double* scores, int64_t n, SelPred pred,
-                                                                  int2* blk_cnt, double* blk_max, int64_t* blk_arg) {
+__device__ __forceinline__ void select_count_block(const double* scores, int64_t n, SelPred pred, int2* blk_cnt, double* blk_max,
+                                                   int64_t* blk_arg) {
     const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + (int64_t)threadIdx.x * SEL_ITEMS;
     int2 cnt = make_int2(0, 0);
     double bmax = -INFINITY;
@@ -1004,11 +1016,15 @@ __global__ __launch_bounds__(SEL_BLOCK) void select_count_kernel(const double* s
     }
 }
 
+__global__ __launch_bounds__(SEL_BLOCK) void select_count_kernel(const double* scores, int64_t n, SelPred pred,
+                                                                  int2* blk_cnt, double* blk_max, int64_t* blk_arg) {
+    select_count_block(scores, n, pred, blk_cnt, blk_max, blk_arg);
+}
+
 // pass 2 (one block): exclusive scan of the block counts, totals and global first-argmax
 // result[0] = n_class0, result[1] = n_class1, result[2] = argmax row (-1 if none)
-__global__ __launch_bounds__(SEL_BLOCK) void select_scan_kernel(int2* blk_cnt, const double* blk_max,
-                                                                 const int64_t* blk_arg, int nblk, int64_t* result,
-                                                                 int64_t limit1 /* cap on class-1 picks, <0 = none */) {
+__device__ __forceinline__ void select_scan_block(int2* blk_cnt, const double* blk_max, const int64_t* blk_arg, int nblk, int64_t* result,
+                                                  int64_t limit1 /* cap on class-1 picks, <0 = none */) {
     __shared__ int2 carry;
     __shared__ double gmax;
     __shared__ int64_t garg;
@@ -1044,10 +1060,15 @@ __global__ __launch_bounds__(SEL_BLOCK) void select_scan_kernel(int2* blk_cnt, c
     }
 }
 
+__global__ __launch_bounds__(SEL_BLOCK) void select_scan_kernel(int2* blk_cnt, const double* blk_max,
+                                                                 const int64_t* blk_arg, int nblk, int64_t* result,
+                                                                 int64_t limit1 /* cap on class-1 picks, <0 = none */) {
+    select_scan_block(blk_cnt, blk_max, blk_arg, nblk, result, limit1);
+}
+
 // pass 3: scatter rows in original order.  class-1 rows beyond `limit1` (in order) are dropped.
-__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_kernel(const double* scores, int64_t n, SelPred pred,
-                                                                    const int2* blk_off, int64_t* out0, int64_t* out1,
-                                                                    int64_t limit1, int64_t* pre0, int64_t* pre1, int64_t prefix) {
+__device__ __forceinline__ void select_scatter_block(const double* scores, int64_t n, SelPred pred, const int2* blk_off, int64_t* out0,
+                                                     int64_t* out1, int64_t limit1, int64_t* pre0, int64_t* pre1, int64_t prefix) {
     const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + (int64_t)threadIdx.x * SEL_ITEMS;
     int flags[SEL_ITEMS];
     int2 cnt = make_int2(0, 0);
@@ -1078,11 +1099,17 @@ __global__ __launch_bounds__(SEL_BLOCK) void select_scatter_kernel(const double*
     }
 }
 
+__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_kernel(const double* scores, int64_t n, SelPred pred,
+                                                                    const int2* blk_off, int64_t* out0, int64_t* out1,
+                                                                    int64_t limit1, int64_t* pre0, int64_t* pre1, int64_t prefix) {
+    select_scatter_block(scores, n, pred, blk_off, out0, out1, limit1, pre0, pre1, prefix);
+}
+
 // The three passes above as ONE launch of one workgroup for a small database (n <= kSelSmallN): a thread owns a run of consecutive
 // rows, counts / first-arg-max / offsets meet in LDS.  Same lists, same counts, same arg-max as the three-kernel form (tested).
 constexpr int kSelSmallN = 16384, kSelSmallThreads = 1024;
-__global__ __launch_bounds__(kSelSmallThreads) void select_small_kernel(const double* scores, int n, SelPred pred, int64_t* result, int64_t* out0,
-                                                                        int64_t* out1, int64_t* pre0, int64_t* pre1, int prefix) {
+__device__ __forceinline__ void select_small_block(const double* scores, int n, SelPred pred, int64_t* result, int64_t* out0, int64_t* out1,
+                                                   int64_t* pre0, int64_t* pre1, int prefix) {
     __shared__ int2 s_wave[kSelSmallThreads / 64];
     __shared__ double s_max[kSelSmallThreads / 64];
     __shared__ int s_arg[kSelSmallThreads / 64];
@@ -1162,6 +1189,74 @@ __global__ __launch_bounds__(kSelSmallThreads) void select_small_kernel(const do
         result[1] = tot.y;
         result[2] = garg;
     }
+}
+
+__global__ __launch_bounds__(kSelSmallThreads) void select_small_kernel(const double* scores, int n, SelPred pred, int64_t* result, int64_t* out0,
+                                                                        int64_t* out1, int64_t* pre0, int64_t* pre1, int prefix) {
+    select_small_block(scores, n, pred, result, out0, out1, pre0, pre1, prefix);
+}
+
+// ---- the same partition for the Q score rows of a batched round (vq_db_query_round_batch): query q = blockIdx.y partitions scores[q][n]
+// under its own band[q] = (threshold, lower) into its own rows of every output.  The blocks above, unchanged: per query the lists,
+// counts and arg-max are those of the one-query launches on that row of scores.
+struct SelBatchArgs {
+    const double* scores;     // [Q][n]
+    const double* band;       // [Q][2]: threshold, lower
+    int64_t n;
+    int nblk;                 // blocks of SEL_CHUNK rows per query (three-pass form)
+    int2* blk_cnt;            // [Q][nblk]
+    double* blk_max;          // [Q][nblk]
+    int64_t* blk_arg;         // [Q][nblk]
+    int64_t* result;          // [Q][4]: n_match, n_near, near_argmax, 0 (cleared by the host)
+    int64_t* out0;            // [Q][n] match rows
+    int64_t* out1;            // [Q][n] near rows
+    int64_t* pre0;            // [Q][prefix]
+    int64_t* pre1;            // [Q][prefix]
+    int64_t prefix;
+};
+
+__device__ __forceinline__ SelPred batch_pred(const SelBatchArgs& a, int q) {
+    SelPred pred;
+    pred.mode = 0;
+    pred.th = a.band[2 * q];
+    pred.lower = a.band[2 * q + 1];
+    pred.pivot = 0;
+    return pred;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_count_batch_kernel(SelBatchArgs a) {
+    const int q = blockIdx.y;
+    select_count_block(a.scores + (int64_t)q * a.n, a.n, batch_pred(a, q), a.blk_cnt + (int64_t)q * a.nblk, a.blk_max + (int64_t)q * a.nblk,
+                       a.blk_arg + (int64_t)q * a.nblk);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_scan_batch_kernel(SelBatchArgs a) {
+    const int q = blockIdx.x;                                               // one workgroup per query
+    select_scan_block(a.blk_cnt + (int64_t)q * a.nblk, a.blk_max + (int64_t)q * a.nblk, a.blk_arg + (int64_t)q * a.nblk, a.nblk, a.result + 4 * q, -1);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_batch_kernel(SelBatchArgs a) {
+    const int q = blockIdx.y;
+    select_scatter_block(a.scores + (int64_t)q * a.n, a.n, batch_pred(a, q), a.blk_cnt + (int64_t)q * a.nblk, a.out0 + (int64_t)q * a.n,
+                         a.out1 + (int64_t)q * a.n, -1, a.pre0 + q * a.prefix, a.pre1 + q * a.prefix, a.prefix);
+}
+
+__global__ __launch_bounds__(kSelSmallThreads) void select_small_batch_kernel(SelBatchArgs a) {
+    const int q = blockIdx.x;                                               // one workgroup per query, n <= kSelSmallN
+    select_small_block(a.scores + (int64_t)q * a.n, (int)a.n, batch_pred(a, q), a.result + 4 * q, a.out0 + (int64_t)q * a.n, a.out1 + (int64_t)q * a.n,
+                       a.pre0 + q * a.prefix, a.pre1 + q * a.prefix, (int)a.prefix);
+}
+
+// n_e of a batched round: the splits present per (clip, stream) under the handle's mask -- the same for every query of the pass
+__global__ __launch_bounds__(256) void batch_ne_kernel(const uint8_t* present, int32_t* ne, int64_t total /* n * S */, int E) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    int c = E;
+    if (present) {
+        c = 0;
+        for (int e = 0; e < E; ++e) c += present[i * E + e] != 0 ? 1 : 0;
+    }
+    ne[i] = c;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1380,9 +1475,11 @@ static void round_layout(int64_t n, int S, int64_t off[8]) {
 static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);
     void* ptrs[] = {db->present, db->t,       db->sims,  db->round_dev, db->blk_cnt,
-                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf};
+                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (hipEvent_t ev : db->bround_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& v : db->views)
         if (v.rows) (void)hipFree(v.rows);
     return VQ_OK;
@@ -1963,12 +2060,54 @@ int vq_db_scan(vq_db* db, const double* w_host, int32_t keep_sims) {
 }  // extern "C"
 
 // the instantiation of the 16-query pass for a database (the tiled branch does not exist for fp16 rows)
-template <typename T, int CH, int TW>
+template <typename T, int CH, int TW, bool ROUND = false>
 static auto fused_kernel_for(bool pres, bool tiled) -> void (*)(BatchFusedArgs) {
     if constexpr (sizeof(T) != 2) {
-        if (tiled) return pres ? batch_fused_kernel<T, CH, TW, true, 8, true> : batch_fused_kernel<T, CH, TW, false, 8, true>;
+        if (tiled) return pres ? batch_fused_kernel<T, CH, TW, true, 8, true, ROUND> : batch_fused_kernel<T, CH, TW, false, 8, true, ROUND>;
     }
-    return pres ? batch_fused_kernel<T, CH, TW, true, 8> : batch_fused_kernel<T, CH, TW, false, 8>;
+    return pres ? batch_fused_kernel<T, CH, TW, true, 8, false, ROUND> : batch_fused_kernel<T, CH, TW, false, 8, false, ROUND>;
+}
+
+// One 16-query pass over the whole database on the handle's stream: d_t [Q][NV][D], d_w [Q][S] -> d_scores [Q][n].  ROUND: d_w is
+// [Q][8] and the stream means also go to d_avg [Q][n][S] (vq_db_query_round_batch).  Caller holds the lock and has checked the shape.
+template <bool ROUND>
+static int launch_fused_pass(vq_db* db, int Q, const double* d_t, const double* d_w, double* d_scores, double* d_avg) {
+    const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;   // sixteen swizzled query rows
+    const int ch = db->D / 256;
+    const bool tiled = db->layout == VQ_LAYOUT_TILED;      // whole 128-byte lines per load instruction, non-temporal: 0.75 of the HBM peak against 0.71
+    BatchFusedArgs f;
+    f.feats = db->feats;
+    f.t = d_t;
+    f.w = d_w;
+    f.present = db->present;
+    f.scores = d_scores;
+    f.n = db->n;
+    f.Q = Q;
+    f.S = db->S;
+    f.E = db->E;
+    f.D = db->D;
+    f.avg = d_avg;
+    constexpr int TW = 2;                                     // tiles of 16 clips per wave and round
+    // chunks of 8 pieces = 128 elements: a refill reads 512 contiguous bytes of each of the 16 clips (two ring buffers).  With 64-
+    // element chunks and four buffers the pass took 7.60 ms instead of 7.45 at cfg 4 (65 k slow streams of 256-byte reads)
+    const int64_t ntiles = (db->n + 15) / 16;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
+#define VQ_FUSED_LAUNCH(T, CH)                                                                                             \
+    {                                                                                                                      \
+        auto kern = fused_kernel_for<T, CH, TW, ROUND>(db->present != nullptr, tiled);                                     \
+        VQ_DYN_LDS(kern, (kBatchSlots * CH * 256 + 32) * 8);                                                                \
+        kern<<<blocks, 1024, lds, db->stream>>>(f);                                                                        \
+    }
+    if (db->dtype == VQ_F16) {
+        if (ch == 4) VQ_FUSED_LAUNCH(__half, 4) else if (ch == 3) VQ_FUSED_LAUNCH(__half, 3) else if (ch == 2) VQ_FUSED_LAUNCH(__half, 2) else VQ_FUSED_LAUNCH(__half, 1)
+    } else if (db->dtype == VQ_F32) {
+        if (ch == 4) VQ_FUSED_LAUNCH(float, 4) else if (ch == 3) VQ_FUSED_LAUNCH(float, 3) else if (ch == 2) VQ_FUSED_LAUNCH(float, 2) else VQ_FUSED_LAUNCH(float, 1)
+    } else {
+        if (ch == 4) VQ_FUSED_LAUNCH(double, 4) else if (ch == 3) VQ_FUSED_LAUNCH(double, 3) else if (ch == 2) VQ_FUSED_LAUNCH(double, 2) else VQ_FUSED_LAUNCH(double, 1)
+    }
+#undef VQ_FUSED_LAUNCH
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
 }
 
 extern "C" {
@@ -1997,42 +2136,9 @@ int vq_db_scan_batch(vq_db* db, int32_t n_queries, const double* t_host, const d
     db->batch_scores = d_scores;
     VQ_HIP(hipMemcpyAsync(d_t, t_host, (size_t)n_t * 8, hipMemcpyHostToDevice, db->stream));
     VQ_HIP(hipMemcpyAsync(d_w, w_host, (size_t)n_w * 8, hipMemcpyHostToDevice, db->stream));
-    const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;   // sixteen swizzled query rows
-    const int ch = db->D / 256;
     {
-        const bool tiled = db->layout == VQ_LAYOUT_TILED;      // whole 128-byte lines per load instruction, non-temporal: 0.75 of the HBM peak against 0.71
-        BatchFusedArgs f;
-        f.feats = db->feats;
-        f.t = d_t;
-        f.w = d_w;
-        f.present = db->present;
-        f.scores = d_scores;
-        f.n = db->n;
-        f.Q = Q;
-        f.S = db->S;
-        f.E = db->E;
-        f.D = db->D;
-        constexpr int TW = 2;                                     // tiles of 16 clips per wave and round
-        // chunks of 8 pieces = 128 elements: a refill reads 512 contiguous bytes of each of the 16 clips (two ring buffers).  With 64-
-        // element chunks and four buffers the pass took 7.60 ms instead of 7.45 at cfg 4 (65 k slow streams of 256-byte reads)
-        const int64_t ntiles = (db->n + 15) / 16;
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
-#define VQ_FUSED_LAUNCH(T, CH)                                                                                             \
-    {                                                                                                                      \
-        auto kern = fused_kernel_for<T, CH, TW>(db->present != nullptr, tiled);                                            \
-        VQ_DYN_LDS(kern, (kBatchSlots * CH * 256 + 32) * 8);                                                                \
-        kern<<<blocks, 1024, lds, db->stream>>>(f);                                                                        \
-    }
-        if (db->dtype == VQ_F16) {
-            if (ch == 4) VQ_FUSED_LAUNCH(__half, 4) else if (ch == 3) VQ_FUSED_LAUNCH(__half, 3) else if (ch == 2) VQ_FUSED_LAUNCH(__half, 2) else VQ_FUSED_LAUNCH(__half, 1)
-        } else if (db->dtype == VQ_F32) {
-            if (ch == 4) VQ_FUSED_LAUNCH(float, 4) else if (ch == 3) VQ_FUSED_LAUNCH(float, 3) else if (ch == 2) VQ_FUSED_LAUNCH(float, 2) else VQ_FUSED_LAUNCH(float, 1)
-        } else {
-            if (ch == 4) VQ_FUSED_LAUNCH(double, 4) else if (ch == 3) VQ_FUSED_LAUNCH(double, 3) else if (ch == 2) VQ_FUSED_LAUNCH(double, 2) else VQ_FUSED_LAUNCH(double, 1)
-        }
-#undef VQ_FUSED_LAUNCH
-        VQ_CHECK_LAUNCH();
-
+        const int rc = launch_fused_pass<false>(db, Q, d_t, d_w, d_scores, nullptr);
+        if (rc != VQ_OK) return rc;
     }
     db->batch_q = Q;
     if (scores_host) {
@@ -2409,6 +2515,166 @@ static int fetch_selected(vq_db* db, int64_t* match_rows_host, int64_t cap_match
         if (db->last_n1) VQ_HIP(hipMemcpyAsync(near_rows_host, db->rows1, db->last_n1 * 8, hipMemcpyDeviceToHost, db->stream));
     }
     VQ_HIP(hipStreamSynchronize(db->stream));
+    return VQ_OK;
+}
+
+// ---- batched rounds (include/vq_amd_rounds.h) ----------------------------------------------------------------------------------------
+// off[0..8]: the pieces of the host block (and of the head of the device block), off[9] = their bytes, off[10] = prefix length
+static void batch_round_layout(const vq_db* db, int Q, int64_t off[12]) {
+    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
+    const int64_t n = db->n;
+    off[0] = 0;
+    off[1] = off[0] + up((int64_t)Q * db->S * db->E * db->D * 8);
+    off[2] = off[1] + up((int64_t)Q * 8 * 8);
+    off[3] = off[2] + up((int64_t)Q * 2 * 8);
+    off[4] = off[3] + up(n * db->S * 4);
+    off[5] = off[4] + up((int64_t)Q * n * db->S * 8);
+    off[6] = off[5] + up((int64_t)Q * n * 8);
+    off[7] = off[6] + up((int64_t)Q * 4 * 8);
+    off[8] = off[7] + up((int64_t)Q * kRoundPrefix * 8);
+    off[9] = off[8] + up((int64_t)Q * kRoundPrefix * 8);
+    off[10] = kRoundPrefix;
+    off[11] = 0;
+}
+
+int vq_db_batch_round_layout(vq_db* db, int32_t n_queries, int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
+    batch_round_layout(db, n_queries, off);
+    return VQ_OK;
+}
+
+int vq_db_query_round_batch(vq_db* db, int32_t n_queries, void* block, int64_t block_bytes, int32_t flags) {
+    VQ_REQUIRE(db && block, "NULL argument");
+    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
+    VQ_REQUIRE(db->D % 256 == 0 && db->D <= 1024, "a batched round needs D in {256,512,768,1024} (got %d)", db->D);
+    VQ_REQUIRE(db->S <= 8, "at most 8 streams");
+    VQ_REQUIRE((flags & ~15) == 0, "flags: 1 = avg and n_e back, 2 = scores back, 4 = partition, 8 = timed (got %d)", flags);
+    const int Q = n_queries;
+    int64_t off[12];
+    batch_round_layout(db, Q, off);
+    VQ_REQUIRE(block_bytes >= off[9], "the block of a batched round of %d queries needs %lld bytes (vq_db_batch_round_layout), got %lld", Q,
+               (long long)off[9], (long long)block_bytes);
+    const bool want_avg = flags & 1, want_scores = flags & 2, do_select = flags & 4, timed = flags & 8;
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->active >= 0)
+        return fail(VQ_E_UNSUPPORTED, "vq_db_query_round_batch runs over the whole database: row view %d is in use (vq_db_rows_use(db, -1) first)", db->active);
+    DeviceGuard g(db->device);
+    const int64_t n = db->n;
+    const int nblk = cdiv(n, SEL_CHUNK);
+    // behind the image of the host block: the full lists and the scratch of the three-pass selection
+    const int64_t o_rows0 = off[9], o_rows1 = o_rows0 + (int64_t)Q * n * 8, o_cnt = o_rows1 + (int64_t)Q * n * 8;
+    const int64_t o_max = o_cnt + (int64_t)Q * nblk * 8, o_arg = o_max + (int64_t)Q * nblk * 8, need = o_arg + (int64_t)Q * nblk * 8;
+    db->bround_q = 0;                                 // the lists of the round before are gone from here on
+    if (db->bround_cap < need) {
+        if (db->bround_dev && (char*)db->batch_scores >= db->bround_dev && (char*)db->batch_scores < db->bround_dev + db->bround_cap) {
+            db->batch_scores = nullptr;               // the scores of the round before lived in the block that goes
+            db->batch_q = 0;
+        }
+        if (db->bround_dev) VQ_HIP(hipFree(db->bround_dev));
+        db->bround_dev = nullptr;
+        db->bround_cap = 0;
+        VQ_HIP(vq::malloc_trim((void**)&db->bround_dev, (size_t)need));
+        db->bround_cap = need;
+    }
+    if (timed && !db->bround_ev[0])
+        for (auto& ev : db->bround_ev) VQ_HIP(hipEventCreate(&ev));
+    db->bround_timed = false;
+    char* host = (char*)block;
+    char* dev = db->bround_dev;
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[0], db->stream));
+    VQ_HIP(hipMemcpyAsync(dev, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));       // queries | weights | bands: adjacent
+    double* d_scores = (double*)(dev + off[5]);
+    {
+        const int rc = launch_fused_pass<true>(db, Q, (const double*)(dev + off[0]), (const double*)(dev + off[1]), d_scores, (double*)(dev + off[4]));
+        if (rc != VQ_OK) return rc;
+    }
+    db->batch_scores = d_scores;                      // vq_db_batch_scores_devptr: the scores of the last batched pass
+    db->batch_q = Q;
+    batch_ne_kernel<<<cdiv(n * db->S, 256), 256, 0, db->stream>>>(db->present, (int32_t*)(dev + off[3]), n * db->S, db->E);
+    VQ_CHECK_LAUNCH();
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[1], db->stream));
+    if (do_select) {
+        SelBatchArgs a;
+        a.scores = d_scores;
+        a.band = (const double*)(dev + off[2]);
+        a.n = n;
+        a.nblk = nblk;
+        a.blk_cnt = (int2*)(dev + o_cnt);
+        a.blk_max = (double*)(dev + o_max);
+        a.blk_arg = (int64_t*)(dev + o_arg);
+        a.result = (int64_t*)(dev + off[6]);
+        a.out0 = (int64_t*)(dev + o_rows0);
+        a.out1 = (int64_t*)(dev + o_rows1);
+        a.pre0 = (int64_t*)(dev + off[7]);
+        a.pre1 = (int64_t*)(dev + off[8]);
+        a.prefix = kRoundPrefix;
+        VQ_HIP(hipMemsetAsync(dev + off[6], 0, (size_t)Q * 4 * 8, db->stream));
+        if (n <= kSelSmallN) {                        // one workgroup per query
+            select_small_batch_kernel<<<Q, kSelSmallThreads, 0, db->stream>>>(a);
+            VQ_CHECK_LAUNCH();
+        } else {                                      // count / scan / scatter, the query on blockIdx.y
+            select_count_batch_kernel<<<dim3(nblk, Q), SEL_BLOCK, 0, db->stream>>>(a);
+            VQ_CHECK_LAUNCH();
+            select_scan_batch_kernel<<<Q, SEL_BLOCK, 0, db->stream>>>(a);
+            VQ_CHECK_LAUNCH();
+            select_scatter_batch_kernel<<<dim3(nblk, Q), SEL_BLOCK, 0, db->stream>>>(a);
+            VQ_CHECK_LAUNCH();
+        }
+    }
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[2], db->stream));
+    // back: n_e | avg, scores, results | prefixes -- the pieces asked for, adjacent ones in one copy
+    const int64_t piece[3][2] = {{off[3], off[5]}, {off[5], off[6]}, {off[6], off[9]}};
+    const bool want[3] = {want_avg, want_scores, do_select};
+    for (int i = 0; i < 3;) {
+        if (!want[i]) {
+            ++i;
+            continue;
+        }
+        int j = i;
+        while (j + 1 < 3 && want[j + 1]) ++j;
+        VQ_HIP(hipMemcpyAsync(host + piece[i][0], dev + piece[i][0], (size_t)(piece[j][1] - piece[i][0]), hipMemcpyDeviceToHost, db->stream));
+        i = j + 1;
+    }
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[3], db->stream));
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    db->bround_timed = timed;
+    db->bround_rows0 = o_rows0;
+    db->bround_rows1 = o_rows1;
+    const int64_t* res = (const int64_t*)(host + off[6]);
+    for (int q = 0; q < kBatchSlots; ++q) {
+        db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
+        db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
+    }
+    db->bround_q = Q;
+    return VQ_OK;
+}
+
+int vq_db_batch_round_fetch(vq_db* db, int32_t query, int64_t* match_rows_host, int64_t cap_match, int64_t* near_rows_host, int64_t cap_near) {
+    VQ_REQUIRE(db, "db is NULL");
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    if (query < 0 || query >= db->bround_q) return fail(VQ_E_STATE, "the last batched round had %d queries (asked for query %d)", db->bround_q, query);
+    const int64_t n0 = db->bround_n0[query], n1 = db->bround_n1[query];
+    if (n0 < 0 || n1 < 0) return fail(VQ_E_STATE, "the last batched round did not partition (flag 4)");
+    DeviceGuard g(db->device);
+    if (match_rows_host) {
+        VQ_REQUIRE(cap_match >= n0, "match buffer too small (%lld < %lld)", (long long)cap_match, (long long)n0);
+        if (n0) VQ_HIP(hipMemcpyAsync(match_rows_host, db->bround_dev + db->bround_rows0 + (int64_t)query * db->n * 8, (size_t)n0 * 8, hipMemcpyDeviceToHost, db->stream));
+    }
+    if (near_rows_host) {
+        VQ_REQUIRE(cap_near >= n1, "near buffer too small (%lld < %lld)", (long long)cap_near, (long long)n1);
+        if (n1) VQ_HIP(hipMemcpyAsync(near_rows_host, db->bround_dev + db->bround_rows1 + (int64_t)query * db->n * 8, (size_t)n1 * 8, hipMemcpyDeviceToHost, db->stream));
+    }
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    return VQ_OK;
+}
+
+int vq_db_batch_round_times(vq_db* db, float* ms) {
+    VQ_REQUIRE(db && ms, "NULL argument");
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (!db->bround_timed) return fail(VQ_E_STATE, "the last batched round was not timed (flag 8)");
+    for (int i = 0; i < 3; ++i) VQ_HIP(hipEventElapsedTime(&ms[i], db->bround_ev[i], db->bround_ev[i + 1]));
     return VQ_OK;
 }
 

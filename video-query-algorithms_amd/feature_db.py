@@ -597,6 +597,98 @@ class FeatureDB:
                 r.match_rows, r.near_rows = m, q
         return r
 
+    # ------------------------------------------------------------------ up to 16 query rounds in one pass
+    def batch_round_supported(self) -> bool:
+        """Does this database meet the preconditions of the 16-query pass (include/vq_amd_rounds.h)?  The whole database only: the
+        caller selects it first (``use_search_set(None)``)."""
+        return self.D in (256, 512, 768, 1024) and self.S <= 8
+
+    def _batch_round_block(self, q: int):
+        """(block, offsets) for a batched round of ``q`` queries: a page-locked block from the pool of its size (_RoundBlock's pooling,
+        one pool per number of queries -- the layout depends on it)."""
+        pools = self.__dict__.setdefault("_batch_round_pools", {})
+        if q not in pools:
+            off = (C.c_int64 * 12)()
+            call("vq_db_batch_round_layout", self._h, q, off)
+            pools[q] = ([int(v) for v in off], {"free": [], "closed": False})
+        off, pool = pools[q]
+        if pool["free"]:
+            ptr, nbytes = pool["free"].pop()
+        else:
+            p = C.c_void_p()
+            nbytes = off[9]
+            call("vq_host_alloc", C.byref(p), nbytes)
+            ptr = p.value
+        return _RoundBlock(ptr, nbytes, pool), off
+
+    def query_round_batch(self, targets: np.ndarray, weights: np.ndarray, selects=None, want_avg: bool = True, timed: bool = False) -> list:
+        """Up to 16 query rounds in ONE read of the database (vq_db_query_round_batch): ``targets`` [Q,S,E,D] fp64, ``weights`` [Q,S],
+        ``selects`` [Q,2] = (threshold, lower) per query or None.  One :class:`RoundResult` per query with the fields
+        :meth:`query_round` fills: ``avg`` [N,S] (None without ``want_avg``), ``n_e`` [N,S] (ONE array shared by all results: it does not
+        depend on the query), ``scores`` [N], ``match_rows`` / ``near_rows`` / ``near_argmax`` (with ``selects``).  The scores are
+        :meth:`scan_batch`'s bit for bit, scores and avg the one-query round's to rounding (<= 1e-12); the partition is exact on the
+        returned scores.  The arrays are views of one pooled page-locked block that lives as long as they do; a list longer than
+        the prefix is fetched.  The whole database only (a search set in use: ``VqError``); the one-query state of the handle is left
+        alone.  ``timed``: :meth:`batch_round_times` then gives the split of the call."""
+        t = np.asarray(targets, dtype=np.float64)
+        w = np.asarray(weights, dtype=np.float64)
+        if t.ndim != 4 or t.shape[1:] != (self.S, self.E, self.D) or w.shape != (t.shape[0], self.S):
+            raise ValueError("targets must be [Q,%d,%d,%d] and weights [Q,%d]" % (self.S, self.E, self.D, self.S))
+        Q = int(t.shape[0])
+        bands = None if selects is None else np.asarray(selects, dtype=np.float64)
+        if bands is not None and bands.shape != (Q, 2):
+            raise ValueError("selects must be [Q,2]: (threshold, lower) per query")
+        if not 1 <= Q <= 16:
+            call("vq_db_batch_round_layout", self._h, Q, (C.c_int64 * 12)())      # the library's own refusal (VqError)
+        with self.lock:
+            blk, off = self._batch_round_block(Q)
+            raw = blk.bytes()
+            n, S = self.n, self.S
+
+            def view(piece, dtype, shape):
+                count = int(np.prod(shape))
+                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            view(0, np.float64, (Q, S, self.E, self.D))[...] = t
+            wv = view(1, np.float64, (Q, 8))
+            wv[...] = 0.0
+            wv[:, :S] = w
+            flags = _lib.VQ_BROUND_SCORES | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
+            if bands is not None:
+                view(2, np.float64, (Q, 2))[...] = bands
+                flags |= _lib.VQ_BROUND_SELECT
+            call("vq_db_query_round_batch", self._h, Q, C.c_void_p(blk.ptr), blk.nbytes, flags)
+            n_e = view(3, np.int32, (n, S)) if want_avg else None
+            avg = view(4, np.float64, (Q, n, S)) if want_avg else None
+            scores = view(5, np.float64, (Q, n))
+            res = view(6, np.int64, (Q, 4))
+            prefix = off[10]
+            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            out = []
+            for q in range(Q):
+                r = RoundResult()
+                r.avg = avg[q] if want_avg else None
+                r.n_e = n_e
+                r.scores = scores[q]
+                r.match_rows = r.near_rows = None
+                r.near_argmax = -1
+                if bands is not None:
+                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
+                    if nm <= prefix and nn <= prefix:
+                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
+                    else:                                     # a list longer than its prefix: the full lists are still on the device
+                        m = np.empty(nm, dtype=np.int64)
+                        k = np.empty(nn, dtype=np.int64)
+                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(m) if nm else None, nm, _np_ptr(k) if nn else None, nn)
+                        r.match_rows, r.near_rows = m, k
+                out.append(r)
+            return out
+
+    def batch_round_times(self):
+        """(pass, selection, copy-back) in ms of the last ``query_round_batch(..., timed=True)``: device time between HIP events."""
+        ms = (C.c_float * 3)()
+        call("vq_db_batch_round_times", self._h, ms)
+        return tuple(float(v) for v in ms)
+
     def rescore(self, weights: Sequence[float]):
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (self.S,):
@@ -686,8 +778,10 @@ class FeatureDB:
 
     def close(self):
         if self._h:
-            pool = getattr(self, "_round_pool", None)
-            if pool is not None:
+            pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()]
+            for pool in pools:
+                if pool is None:
+                    continue
                 pool["closed"] = True                         # blocks still referenced by result arrays free themselves
                 while pool["free"]:
                     _lib.load().vq_host_free(C.c_void_p(pool["free"].pop()[0]))

@@ -89,6 +89,35 @@ def _db_lock(db):
     return getattr(db, "lock", None) or contextlib.nullcontext()
 
 
+def _query_arrays(ticket, db):
+    """(stream names, query array [S,E,D] fp64, slots in use [S,E]) of a ticket's target on database ``db``."""
+    target_features = ticket.target.target_features
+    stream_names = getattr(db, "stream_names", None) or list(target_features.keys())
+    slot_splits = getattr(db, "slot_splits", None) or [list(target_features[st].keys()) for st in stream_names]
+    # The target's vectors are Python lists (JSON-serialisable, ticket.py:296): turning 6 x 1 024 floats into an array is ~0.15 ms
+    # of interpreter time, more than the whole device side of a 10k-clip round.  The array is kept on the target object and
+    # reused while every vector IS the list object it was made from (TargetClip replaces a vector by a new list whenever it
+    # changes it -- target_clip.py never assigns into one).
+    refs = tuple(target_features[st][sp] for s, st in enumerate(stream_names) for sp in slot_splits[s]
+                 if st in target_features and sp in target_features[st])
+    cached = getattr(ticket.target, "_vq_query_array", None)
+    if cached is not None and cached[0] == (db.S, db.E, db.D) and len(cached[1]) == len(refs) and all(a is b for a, b in zip(cached[1], refs)):
+        t, slot_used = cached[2], cached[3]
+    else:
+        t = np.zeros((db.S, db.E, db.D), dtype=np.float64)
+        slot_used = np.zeros((db.S, db.E), dtype=bool)
+        for s, st in enumerate(stream_names):
+            for e, sp in enumerate(slot_splits[s]):
+                if st in target_features and sp in target_features[st]:
+                    t[s, e] = np.asarray(target_features[st][sp], dtype=np.float64)
+                    slot_used[s, e] = True
+        try:
+            ticket.target._vq_query_array = ((db.S, db.E, db.D), refs, t, slot_used)
+        except AttributeError:
+            pass                                          # a target object that takes no attributes
+    return stream_names, t, slot_used
+
+
 class TicketScoring:
     """Hot-path methods of the reference's Ticket, on the GPU.  Attributes read: ``target``
     (``target_features``, ``splits``), ``search_set``, ``ref_clip_id``, ``user_matches``; attributes
@@ -114,29 +143,7 @@ class TicketScoring:
                                         hyperparameters.feature_name, dtype=self.feature_db_dtype,
                                         device=self.device)
             self.feature_db = db
-        stream_names = getattr(db, "stream_names", None) or list(target_features.keys())
-        slot_splits = getattr(db, "slot_splits", None) or [list(target_features[st].keys()) for st in stream_names]
-        # The target's vectors are Python lists (JSON-serialisable, ticket.py:296): turning 6 x 1 024 floats into an array is ~0.15 ms
-        # of interpreter time, more than the whole device side of a 10k-clip round.  The array is kept on the target object and
-        # reused while every vector IS the list object it was made from (TargetClip replaces a vector by a new list whenever it
-        # changes it -- target_clip.py never assigns into one).
-        refs = tuple(target_features[st][sp] for s, st in enumerate(stream_names) for sp in slot_splits[s]
-                     if st in target_features and sp in target_features[st])
-        cached = getattr(self.target, "_vq_query_array", None)
-        if cached is not None and cached[0] == (db.S, db.E, db.D) and len(cached[1]) == len(refs) and all(a is b for a, b in zip(cached[1], refs)):
-            t, slot_used = cached[2], cached[3]
-        else:
-            t = np.zeros((db.S, db.E, db.D), dtype=np.float64)
-            slot_used = np.zeros((db.S, db.E), dtype=bool)
-            for s, st in enumerate(stream_names):
-                for e, sp in enumerate(slot_splits[s]):
-                    if st in target_features and sp in target_features[st]:
-                        t[s, e] = np.asarray(target_features[st][sp], dtype=np.float64)
-                        slot_used[s, e] = True
-            try:
-                self.target._vq_query_array = ((db.S, db.E, db.D), refs, t, slot_used)
-            except AttributeError:
-                pass                                          # a target object that takes no attributes
+        stream_names, t, slot_used = _query_arrays(self, db)
         self._ahead = None
         with _db_lock(db):                    # one resident database may serve several tickets: these calls are one step
             # The clips of THIS ticket's search set (ticket.py:363-365), when the resident database has it defined: the round runs
@@ -310,6 +317,93 @@ class TicketScoring:
         for clip in forced:
             matches[clip] = self.scores[clip]
         self.matches = matches
+
+
+# -- several tickets in one pass over a resident database -----------------------------------------------------------------------------
+BATCH_PASS = 16       # queries per pass of the batched round (include/vq_amd_rounds.h)
+
+
+def _batchable(ticket, hyperparameters):
+    """(database, stream names, query, slots in use, look-ahead) when the ticket's round can share a 16-query pass, else None: it has
+    a resident database with ``query_round_batch`` that meets the pass's preconditions, runs over the WHOLE database (no search set
+    defined for it) and its hyperparameters say which weights and band come next."""
+    db = ticket.feature_db
+    if db is None or not hasattr(db, "query_round_batch"):
+        return None
+    if hasattr(db, "has_search_set") and db.has_search_set(getattr(ticket, "search_set", None)):
+        return None
+    supported = getattr(db, "batch_round_supported", None)
+    if supported is not None and not supported():
+        return None
+    stream_names, t, slot_used = _query_arrays(ticket, db)
+    ahead = ticket._look_ahead(hyperparameters, stream_names)
+    if ahead is None:
+        return None
+    return db, stream_names, t, slot_used, ahead
+
+
+def _batched_pass(group):
+    """One pass for up to BATCH_PASS tickets that share a database object and a slot mask: what compute_similarities does for each,
+    the look-ahead scores and partition included."""
+    db, slot_used = group[0][2][0], group[0][2][3]
+    targets = np.stack([g[2][2] for g in group])
+    weights = np.stack([g[2][4][0] for g in group])
+    bands = np.array([[g[2][4][1], g[2][4][2]] for g in group], dtype=np.float64)
+    for tk, _hp, _prep in group:
+        tk._ahead = None
+    with _db_lock(db):
+        views = [tk._bind_view(db) for tk, _hp, _prep in group]       # the whole database: no set is defined for any of them
+        db.restrict_slots(slot_used)                                  # once per group
+        results = db.query_round_batch(targets, weights, bands, want_avg=True)
+        # the handle's one-query state is nobody's round now: a later device-side step of any of these tickets puts its
+        # similarities back first (_own_similarities / _own_scores)
+        db.sims_owner = db.scores_owner = None
+    for (tk, hp, prep), view, r in zip(group, views, results):
+        _db, stream_names, _t, _used, (w, th, lower) = prep
+        tk._round = object()
+        tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": (th, lower), "match_rows": r.match_rows,
+                     "near_rows": r.near_rows, "near_argmax": r.near_argmax}
+        tk._hp = hp
+        tk._stream_names = stream_names
+        tk._avg, tk._n_e = r.avg, r.n_e
+        tk._stream_gap = None
+        tk._view = view
+        tk.similarities = SimilarityMap(view.clip_ids, stream_names, r.avg, r.n_e, view.row_of)
+
+
+def compute_similarities_batch(tickets, hyperparameters):
+    """``compute_similarities`` for a list of tickets, those that can sharing passes over their resident database: a broker with
+    several pending tickets pays one read of the database per 16 of them instead of one each.  ``hyperparameters`` is one object or
+    one per ticket.  Every ticket ends with exactly the attributes its own ``compute_similarities`` sets (``similarities``, ``_avg``,
+    ``_n_e``, ``_view``, ``_round``, ``_hp``, ``_stream_names``, ``_stream_gap``, ``_ahead`` -- look-ahead scores and partition included,
+    so the ``compute_scores`` / ``select_clips_to_review`` that follow ask the device for nothing when called with the looked-ahead
+    arguments); values agree with the one-ticket round to rounding (<= 1e-12: the pass runs on the matrix cores).
+
+    Tickets share a pass when they have the same database OBJECT with ``query_round_batch`` that meets the pass's preconditions, no
+    search set defined for them, the same slot mask and a look-ahead; at most 16 per pass, in list order.  Every other ticket -- on
+    a ShardedFeatureDB or another database without the method, with a search set, without a resident database (``from_records``)
+    -- runs its own ``compute_similarities``, in list order; so does, at the end, a ticket left alone in its group (a pass of one
+    gains nothing)."""
+    tickets = list(tickets)
+    hps = list(hyperparameters) if isinstance(hyperparameters, (list, tuple)) else [hyperparameters] * len(tickets)
+    if len(hps) != len(tickets):
+        raise ValueError("one hyperparameters object, or one per ticket")
+    pending = {}                                          # (database object, slot mask) -> the tickets waiting for a pass, in list order
+    for tk, hp in zip(tickets, hps):
+        prep = _batchable(tk, hp)
+        if prep is None:
+            tk.compute_similarities(hp)
+            continue
+        key = (id(prep[0]), prep[3].tobytes())
+        group = pending.setdefault(key, [])
+        group.append((tk, hp, prep))
+        if len(group) == BATCH_PASS:
+            _batched_pass(pending.pop(key))
+    for group in pending.values():
+        if len(group) == 1:                               # nobody to share a pass with: the ticket's own round, bit for bit
+            group[0][0].compute_similarities(group[0][1])
+        else:
+            _batched_pass(group)
 
 
 class Ticket(TicketScoring):
