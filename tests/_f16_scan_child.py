@@ -25,15 +25,11 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
 
 import sim_oracle as so
 import video_query_algorithms_amd as vqa
+from _scan_matrix_cases import one_hot_rows
 
 
 def one_hot():
-    n, s, e, d = 2048, 2, 3, 1024
-    x = np.zeros((n, s, e, d), dtype=np.float16)
-    c = np.arange(n)
-    for v in range(s * e):
-        x[c, v // e, v % e, (7 * c + 131 * v) % d] = 1.0 + 0.25 * (c % 7)            # exact halves
-    t = ((1.0 + np.arange(s * e * d)) * 2.0 ** -16).reshape(s, e, d)                   # distinct per (v, k); products are exact
+    x, t = one_hot_rows(2048, 2, 3, np.float16)                                        # exact halves; distinct per (v, k); products are exact
     db = vqa.FeatureDB.from_arrays(x, dtype=np.float16)
     db.set_query(t)
     db.scan(keep_sims=True)

@@ -1949,6 +1949,7 @@ static bool fast_scan_shape(const vq_db* db) { return db->D == 1024 && db->S >= 
 template <typename T, typename A>
 static int launch_scan(vq_db* db, const A& a) {
     if (db->D == 1024) {
+        // every entry is launched by tests/test_scan_matrix_gpu.py (SHAPES in tests/_scan_matrix_cases.py): a new entry gets a new row there
 #define C_(s_, e_) \
     if (db->S == s_ && db->E == e_) return launch_scan_t<T, s_, e_, 4, A>(db, a);
         C_(1, 1) C_(1, 2) C_(1, 3) C_(1, 4) C_(1, 5)
@@ -2092,6 +2093,7 @@ static int launch_fused_pass(vq_db* db, int Q, const double* d_t, const double* 
     // element chunks and four buffers the pass took 7.60 ms instead of 7.45 at cfg 4 (65 k slow streams of 256-byte reads)
     const int64_t ntiles = (db->n + 15) / 16;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
+    // every (T, CH, mask) is launched by CASES of tests/test_batch_round_gpu.py (the table above it): a new one gets a new case there
 #define VQ_FUSED_LAUNCH(T, CH)                                                                                             \
     {                                                                                                                      \
         auto kern = fused_kernel_for<T, CH, TW, ROUND>(db->present != nullptr, tiled);                                     \
