@@ -20,8 +20,8 @@
  * These stay in DATABASE rows, view or no view: vq_db_set_query_from_row, vq_db_bootstrap_target, vq_db_read_rows,
  * vq_db_upload, vq_db_set_present (the presence mask is [N][S][E] and is read by database row).
  *
- * Not under a view: vq_db_scan_batch and vq_allgather_scores return VQ_E_UNSUPPORTED while one is in use (a view per query of the
- * 16-query pass is out of scope; select the whole database first).
+ * Not under a view: vq_db_scan_batch and vq_allgather_scores return VQ_E_UNSUPPORTED while one is in use (select the whole database
+ * first; a view per query of the 16-query pass is vq_db_query_round_views, vq_amd_round_views.h, which does not consult the view in use).
  *
  * M = 0 is legal: scans launch nothing, the selection returns empty lists and near_argmax = -1, vq_db_topk returns *k_out = 0 and
  * vq_db_min_score 1.

@@ -88,14 +88,16 @@ def _one_update(kind, update, url, hp, ticket_factory, target_factory):
     _finish_update(kind, update, tk, hp)
 
 
-def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False):
+def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False, share_search_sets=False):
     """One broker pass.  ``batch=True`` runs it in three phases so that the pending tickets share passes over their resident database
     (``ticket.compute_similarities_batch``): (1) every pending update gets its ticket, process state 3, its checks and its target
     features; (2) ONE ``compute_similarities_batch`` over the tickets that survived; (3) every ticket is finished in the original
     order.  Per ticket the calls -- and with them the ledger -- are the same sequence as without ``batch``; ACROSS tickets they
     interleave differently (all the phase-1 entries come before any ticket's phase-3 entries), and a ticket's weights / threshold
     look-ahead is taken from the hyperparameters object as it stands before phase 3 changes it (a ticket whose weights come out
-    different re-weights its own similarities, as ever).  Values agree with the default path to rounding (<= 1e-12)."""
+    different re-weights its own similarities, as ever).  Values agree with the default path to rounding (<= 1e-12).
+    ``share_search_sets=True`` (with ``batch``): tickets whose search sets are defined on their database share passes too
+    (``compute_similarities_batch(..., share_search_sets=True)``)."""
     pending = query_updates.get_status()                                    # :34
     if ticket_factory is None:
         from .ticket import Ticket as _Ticket
@@ -116,7 +118,7 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
             tk = _begin_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
             if tk is not None:
                 started.append((kind, update, tk))
-    compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters)
+    compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets)
     for kind, update, tk in started:
         _finish_update(kind, update, tk, hyperparameters)
 

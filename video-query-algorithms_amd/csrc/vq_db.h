@@ -58,6 +58,13 @@ struct vq_db {
     int64_t bround_n0[16] = {0}, bround_n1[16] = {0};  // its counts per query (-1: that round did not partition)
     hipEvent_t bround_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // flag 8: start | pass done | selection done | copies done
     bool bround_timed = false;
+    int64_t bround_qoff[16] = {0};   // where query q's full lists start inside the two list arrays (entries): q N, or a view round's start[q]
+    // View rounds (vq_db_query_round_views, include/vq_amd_round_views.h): the plan's device block, allocated on the first one --
+    // inv [16][stride] i32 | union rows [stride + 16] i32 | touched tiles [stride / 16] i32 | counts [2] i64 | start [17] i64 | the
+    // per-block counts of the compaction [tiles / 256] int2 -- and what the last one covered
+    char* vround_plan = nullptr;
+    bool vround_have = false;
+    int64_t vround_union = 0, vround_tiles = 0;
     double* grid_buf = nullptr;      // scratch for grid / gathers
     int64_t grid_cap = 0;
     // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over

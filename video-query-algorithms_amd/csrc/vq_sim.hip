@@ -641,6 +641,103 @@ struct BatchFusedArgs {
     double* avg;              // ROUND only: [Q][n][S]
 };
 
+// A round over the UNION of up to 16 row views (vq_db_query_round_views, include/vq_amd_round_views.h): n stays the database's N, the
+// tiles the pass walks are those of `items`, and query q's avg / scores are compact pieces that start at entry start[q].
+struct BatchViewArgs : BatchFusedArgs {
+    const int32_t* items;     // rows: the union's database rows, ascending, padded to a multiple of 16 with its last row | tiled: the tiles
+                              // the union touches, ascending | null: the whole database (a view of the round is -1)
+    const int64_t* counts;    // device, written by the plan: [0] rows of the union, [1] tiles it touches (read only with items)
+    const int32_t* inv;       // [16][inv_stride]: the position of a database row in query q's view, -1 = not a member (unused for a whole query)
+    int64_t inv_stride;
+    const int64_t* start;     // device [17]: the first entry of query q's piece
+    uint32_t whole;           // bit q: query q covers the whole database (position = row)
+    uint32_t members;         // bit q: query q's row list is in inv; a query with neither bit (an empty view) stores nothing
+};
+
+// Loads whose address is wave-uniform and whose memory no launch in flight writes (the plan of a view round): through the constant
+// address space they are scalar loads for certain, so they never enter the in-order vector-memory queue between the feature loads
+// (the trap of scan_kernel's VIEW form, see the comment above it).
+typedef int vq_i16 __attribute__((ext_vector_type(16)));
+template <typename U>
+__device__ __forceinline__ U uniform_load(const U* p) {
+    return *(const __attribute__((address_space(4))) U*)(p);
+}
+// element i (per lane) of 16 wave-uniform values: selects, no memory
+__device__ __forceinline__ int pick16(const vq_i16& r, int i) {
+    int v = r[0];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) v = i == k ? r[k] : v;
+    return v;
+}
+struct ViewTile {                // a work item of the VIEW form: its 16 database rows (row-major) or the tile behind it (tiled)
+    vq_i16 rows;
+    int64_t tile, pt;
+};
+
+// What batch_view_kernel asks of the plan, per lane (col = its clip of a tile and its query slot, kk = its k quarter):
+// the work items, this lane's pointer into a (work item, slice) and where a (query, clip) reports.  Every index comes from wave-uniform
+// scalar loads.
+template <typename T, bool TILED, int KL>
+struct ViewWalk {
+    const BatchViewArgs& a;
+    const T* feats;
+    int64_t clip_elems, ntiles, n_union;
+    int NV, D, col, kk;
+    __device__ __forceinline__ ViewWalk(const BatchViewArgs& a_, const T* feats_, int NV_, int D_, int col_, int kk_)
+        : a(a_), feats(feats_), clip_elems((int64_t)NV_ * D_), ntiles((a_.n + 15) / 16), n_union(a_.n), NV(NV_), D(D_), col(col_), kk(kk_) {
+        if (a.items) {                                             // else the whole database: its tiles, addressed as ever
+            if (TILED) ntiles = uniform_load(a.counts + 1);
+            else {
+                n_union = uniform_load(a.counts);
+                ntiles = (n_union + 15) / 16;
+            }
+        }
+    }
+    // the database rows of the 16 clips of virtual tile `tile`: rows past the union repeat its last row and are never stored
+    __device__ __forceinline__ vq_i16 rows_of(int64_t tile) const {
+        if (a.items) return uniform_load(reinterpret_cast<const vq_i16*>(a.items + tile * 16));
+        vq_i16 rw = {};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rw[i] = (int)min(tile * 16 + i, a.n - 1);
+        return rw;
+    }
+    // the tile of the tiled layout behind work item `tile`
+    __device__ __forceinline__ int64_t phys_tile(int64_t tile) const { return a.items ? (int64_t)uniform_load(a.items + tile) : tile; }
+    // this lane's pointer into slice v of work item `tile`: 64-bit, sixteen arbitrary rows can lie more than 2^32 elements apart
+    __device__ __forceinline__ const T* ptr(int64_t tile, int v) const {
+        if constexpr (TILED) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 4);
+        else return feats + (int64_t)pick16(rows_of(tile), col) * clip_elems + ((int64_t)v * D + KL * kk);
+    }
+    __device__ __forceinline__ ViewTile tile(int64_t tile) const {
+        ViewTile vt = {};
+        vt.tile = tile;
+        if constexpr (TILED) vt.pt = phys_tile(tile);
+        else vt.rows = rows_of(tile);
+        return vt;
+    }
+    // the database row of clip idx of a work item, clamped to one that exists (the presence mask is read by database row)
+    __device__ __forceinline__ int64_t mask_row(const ViewTile& vt, int idx) const {
+        if constexpr (TILED) return min(vt.pt * 16 + idx, a.n - 1);
+        else return pick16(vt.rows, idx);
+    }
+    // where (this lane's query, clip idx of the work item) reports in the compact outputs: start[q] + the clip's position in the query's
+    // view, or -1 -- a row past the union, an unused query slot, a clip outside the query's view
+    __device__ __forceinline__ int64_t entry(const ViewTile& vt, int idx) const {
+        int64_t row;
+        bool ok;
+        if constexpr (TILED) {
+            row = vt.pt * 16 + idx;
+            ok = row < a.n;
+        } else {
+            row = pick16(vt.rows, idx);
+            ok = vt.tile * 16 + idx < n_union;
+        }
+        if (!ok || !(((a.whole | a.members) >> col) & 1u)) return -1;         // also the slots past Q
+        const int64_t pos = ((a.whole >> col) & 1u) ? row : (int64_t)a.inv[(int64_t)col * a.inv_stride + row];
+        return pos < 0 ? -1 : a.start[col] + pos;
+    }
+};
+
 // ROUND (vq_db_query_round_batch, include/vq_amd_rounds.h): the weights come as the round block holds them ([Q][8]) and every stream's
 // mean also goes to avg[q][clip][s] where the stream closes.  Stores only: a score is the same operands in the same order, so the
 // same bits as the plain pass.
@@ -798,6 +895,152 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
                 for (int rr = 0; rr < 4; ++rr) {
                     const int64_t cc = tile * 16 + kk + 4 * rr;
                     if (cc < a.n) a.scores[(int64_t)col * a.n + cc] = 1.0 - sqrt(miss[j][rr] / denom);
+                }
+            }
+        }
+    }
+}
+
+// batch_fused_kernel<..., ROUND = true> over the UNION of the round's row views (BatchViewArgs).  It is a kernel of its own, the walk of
+// batch_fused_kernel restated line for line, so that every existing instantiation keeps its code unchanged (the register allocation of
+// those kernels, which spill at 4 waves per SIMD, moves with any edit of their source); what differs is marked VIEW below.
+// The tiles are VIRTUAL -- 16 consecutive rows of the union, gathered (a lane's address is 64-bit: sixteen arbitrary rows can lie more
+// than 2^32 elements apart) -- or, TILED, the touched tiles read whole.  The rows of a tile come in with ONE scalar load (the list is
+// padded to whole tiles) and a lane picks its own with selects; the lane's pointer for the wave's NEXT (tile, slice) is made while the
+// current one is multiplied and carried over, so no index load ever waits between feature loads.  The mask is read by database row; a
+// store for (query, clip) goes to start[q] + the clip's position in that query's view and is skipped for a clip outside it.  The MFMA
+// sequence per (clip, query) is batch_fused_kernel's: which tile, or which row of a tile, a clip occupies does not enter an output element
+// of v_mfma_f64_16x16x4, so avg and scores have the bits of vq_db_query_round_batch.
+template <typename T, int CH, int TW, bool PRES, int P, bool TILED = false>
+__global__ __launch_bounds__(1024) void batch_view_kernel(BatchViewArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double tq[];      // 16 swizzled rows of D doubles (+ 32 of slack)
+    constexpr int D = CH * 256, CE = 16 * P, NCHUNK = D / CE;
+    constexpr int NBUF = sizeof(T) == 2 ? (NCHUNK % (32 / P) == 0 ? 32 / P : 16 / P) : (sizeof(T) == 4 ? 16 : 8) / P;
+    constexpr int KL = sizeof(T) == 2 ? 8 : 4;
+    static_assert(NCHUNK % NBUF == 0, "chunk ring must divide the vector");
+    const int lane = threadIdx.x & 63, col = lane & 15, kk = lane >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int NV = a.S * a.E;
+    const ViewWalk<T, TILED, KL> vw(a, static_cast<const T*>(a.feats), NV, D, col, kk);       // VIEW
+    const int64_t ntiles = vw.ntiles;                                 // VIEW: the work items of the plan
+    const int64_t per_round = (int64_t)gridDim.x * 16 * TW;
+    const int rounds = (int)((ntiles + per_round - 1) / per_round);
+    const double* tb = tq + query_row(col, D) + 4 * kk;
+    for (int i = threadIdx.x; i < kBatchSlots * D; i += blockDim.x) {
+        const int q = i / D, k = i - q * D;
+        if (q >= a.Q) tq[query_row(q, D) + k] = 0.0;
+    }
+    auto tile_of = [&](int r, int j) -> int64_t { return (int64_t)r * per_round + (int64_t)(wv * TW + j) * gridDim.x + blockIdx.x; };
+    auto valid_in = [&](int r) -> int {
+        int nv = 0;
+        for (int j = 0; j < TW; ++j) nv += (r < rounds && tile_of(r, j) < ntiles) ? 1 : 0;
+        return nv;
+    };
+    constexpr int CSTEP = TILED ? 256 * P : CE;
+    ChunkP<T, P> buf[NBUF];
+    const T* xcur = vw.feats;                                         // VIEW: this lane's pointer for the wave's current (tile, slice)
+    if (valid_in(0) > 0) {
+        xcur = vw.ptr(tile_of(0, 0), 0);
+#pragma unroll
+        for (int bq = 0; bq < NBUF; ++bq) {
+            if (TILED) buf[bq].load_tiled(xcur + CSTEP * bq);
+            else buf[bq].load(xcur + CSTEP * bq);
+        }
+    }
+    for (int r = 0; r < rounds; ++r) {
+        const int nval = valid_in(r), nval_next = valid_in(r + 1);
+        doublex4 miss[TW];
+#pragma unroll
+        for (int j = 0; j < TW; ++j) miss[j] = {0.0, 0.0, 0.0, 0.0};
+        double denom = 0.0;
+        for (int s = 0; s < a.S; ++s) {
+            doublex4 ssum[TW];
+            int cnt[TW][4];
+#pragma unroll
+            for (int j = 0; j < TW; ++j) {
+                ssum[j] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) cnt[j][rr] = 0;
+            }
+            for (int e = 0; e < a.E; ++e) {
+                const int v = s * a.E + e;
+                __syncthreads();
+                for (int i = threadIdx.x; i < a.Q * D; i += blockDim.x) {
+                    const int q = i / D, k = i - q * D;
+                    tq[query_row(q, D) + batch_query_pos<T>(k)] = a.t[((size_t)q * NV + v) * D + k];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < TW; ++j) {
+                    if (j >= nval) continue;
+                    const int64_t tile = tile_of(r, j);
+                    const T* x = xcur;                                // VIEW: made one step ago
+                    int64_t tn = tile;
+                    int vn = v;
+                    if (j + 1 < nval) tn = tile_of(r, j + 1);
+                    else if (v + 1 < NV) { tn = tile_of(r, 0); vn = v + 1; }
+                    else if (nval_next > 0) { tn = tile_of(r + 1, 0); vn = 0; }
+                    const T* xn = xcur = vw.ptr(tn, vn);              // VIEW: what the next step of this wave walks
+                    doublex4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+                    for (int ch0 = 0; ch0 < NCHUNK; ch0 += NBUF) {
+                        const T* src = ch0 + NBUF < NCHUNK ? x + CSTEP * (ch0 + NBUF) : xn;
+#pragma unroll
+                        for (int bq = 0; bq < NBUF; ++bq) {
+                            int off = CE * (ch0 + bq);
+                            asm volatile("" : "+v"(off));             // keeps every LDS read next to its MFMA (batch_fused_kernel)
+                            const double* tbc = tb + off;
+#pragma unroll
+                            for (int m = 0; m < P; ++m)
+#pragma unroll
+                                for (int ee = 0; ee < 4; ++ee)
+                                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(buf[bq].at(m, ee), tbc[16 * m + ee], acc, 0, 0, 0);
+                            if (TILED) buf[bq].load_tiled(src + CSTEP * bq);
+                            else buf[bq].load(src + CSTEP * bq);
+                        }
+                    }
+                    [[maybe_unused]] ViewTile pvt;
+                    if constexpr (PRES) pvt = vw.tile(tile);
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        bool here = true;
+                        if (PRES) here = a.present[(vw.mask_row(pvt, kk + 4 * rr) * a.S + s) * a.E + e] != 0;      // VIEW: by database row
+                        if (here) {
+                            ssum[j][rr] = ssum[j][rr] + acc[rr];
+                            if (PRES) ++cnt[j][rr];
+                        }
+                    }
+                }
+            }
+            const double ws = col < a.Q ? a.w[col * 8 + s] : 0.0;
+            denom = denom + ws * ws;
+            int kko = kk;
+            asm volatile("" : "+v"(kko));                             // the store addresses are made here, where the stream closes (batch_fused_kernel)
+#pragma unroll
+            for (int j = 0; j < TW; ++j) {
+                ViewTile vt = {};
+                if (j < nval) vt = vw.tile(tile_of(r, j));
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const double av = ssum[j][rr] / (double)(PRES ? cnt[j][rr] : a.E);
+                    if (j < nval) {                                   // VIEW: to the clip's position in this lane's query's view, if it has one
+                        const int64_t o = vw.entry(vt, kko + 4 * rr);
+                        if (o >= 0) a.avg[o * a.S + s] = av;
+                    }
+                    const double term = ws * (1.0 - av);
+                    miss[j][rr] = miss[j][rr] + term * term;
+                }
+            }
+        }
+        if (col < a.Q) {
+#pragma unroll
+            for (int j = 0; j < TW; ++j) {
+                if (j >= nval) continue;
+                const ViewTile vt = vw.tile(tile_of(r, j));
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int64_t o = vw.entry(vt, kk + 4 * rr);      // VIEW
+                    if (o >= 0) a.scores[o] = 1.0 - sqrt(miss[j][rr] / denom);
                 }
             }
         }
@@ -1259,6 +1502,161 @@ __global__ __launch_bounds__(256) void batch_ne_kernel(const uint8_t* present, i
     ne[i] = c;
 }
 
+// ---- a batched round over one row view per query (vq_db_query_round_views, include/vq_amd_round_views.h) ---------------------------------
+// THE PLAN, built on the device per call: inv[q][row] = the position of database row `row` in query q's view (-1: not a member),
+// filled by scattering each view's resident row list; then the union of the views -- its rows (row-major databases) or the tiles it
+// touches (tiled ones) -- by a stable compaction of "some query holds this row": count / scan / scatter, a thread per tile of 16 rows.
+struct ViewPlanArgs {
+    const int64_t* rows[16];  // the resident row list of query q's view; null: the whole database, or an empty view
+    int64_t m[16];            // the rows of query q's piece (N for the whole database)
+    int64_t start[17];        // the first entry of query q's piece; start[Q] = the sum of m
+    int32_t Q;
+    int64_t n, stride;        // the database's rows; the rows of inv per query (n rounded up to whole tiles)
+    int32_t* inv;             // [16][stride]
+    int64_t* start_dev;       // [17]: start, for the kernels that index it per lane
+};
+
+__global__ __launch_bounds__(256) void view_scatter_kernel(ViewPlanArgs a) {
+    const int q = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.start_dev[q] = a.start[q];
+        if (q == a.Q - 1) a.start_dev[a.Q] = a.start[a.Q];
+    }
+    const int64_t* rows = a.rows[q];
+    if (!rows) return;
+    const int64_t m = a.m[q];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        a.inv[(int64_t)q * a.stride + rows[i]] = (int32_t)i;
+}
+
+struct ViewUnionArgs {
+    const int32_t* inv;       // [16][stride], stride % 16 == 0, -1 behind row n
+    int64_t stride;
+    int64_t ntiles;           // tiles of the database
+    uint32_t members;         // bit q: query q has a row list scattered into inv
+    int2* blk;                // [nblk]: per block of 256 tiles (union rows, touched tiles) -> their exclusive scan
+    int nblk;
+    int32_t* rows_out;        // the union's rows, ascending, padded to a multiple of 16 with the last one | null
+    int32_t* tiles_out;       // the touched tiles, ascending | null
+    int64_t* counts;          // [0] union rows, [1] touched tiles
+};
+
+// bit i: row 16 tile + i is in some view of the round
+__device__ __forceinline__ unsigned view_union_flags(const ViewUnionArgs& a, int64_t tile) {
+    unsigned f = 0;
+    if (tile >= a.ntiles) return 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        if (!((a.members >> q) & 1u)) continue;
+        const int4* p = reinterpret_cast<const int4*>(a.inv + (int64_t)q * a.stride + tile * 16);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int4 v = p[g];
+            f |= (v.x >= 0 ? 1u : 0u) << (4 * g) | (v.y >= 0 ? 2u : 0u) << (4 * g) | (v.z >= 0 ? 4u : 0u) << (4 * g) | (v.w >= 0 ? 8u : 0u) << (4 * g);
+        }
+    }
+    return f;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void view_union_count_kernel(ViewUnionArgs a) {
+    const unsigned f = view_union_flags(a, (int64_t)blockIdx.x * SEL_BLOCK + threadIdx.x);
+    int2 tot;
+    block_scan_excl2(make_int2(__popc(f), f ? 1 : 0), &tot);
+    if (threadIdx.x == 0) a.blk[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void view_union_scan_kernel(ViewUnionArgs a) {   // one workgroup
+    __shared__ int2 carry;
+    if (threadIdx.x == 0) carry = make_int2(0, 0);
+    __syncthreads();
+    for (int b0 = 0; b0 < a.nblk; b0 += SEL_BLOCK) {
+        const int b = b0 + threadIdx.x;
+        int2 tot;
+        const int2 ex = block_scan_excl2(b < a.nblk ? a.blk[b] : make_int2(0, 0), &tot);
+        const int2 c0 = carry;
+        if (b < a.nblk) a.blk[b] = make_int2(c0.x + ex.x, c0.y + ex.y);
+        __syncthreads();
+        if (threadIdx.x == 0) carry = make_int2(c0.x + tot.x, c0.y + tot.y);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        a.counts[0] = carry.x;
+        a.counts[1] = carry.y;
+    }
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void view_union_scatter_kernel(ViewUnionArgs a) {
+    const int64_t tile = (int64_t)blockIdx.x * SEL_BLOCK + threadIdx.x;
+    const unsigned f = view_union_flags(a, tile);
+    int2 tot;
+    const int2 ex = block_scan_excl2(make_int2(__popc(f), f ? 1 : 0), &tot);
+    int64_t o = (int64_t)a.blk[blockIdx.x].x + ex.x;
+    if (a.tiles_out && f) a.tiles_out[(int64_t)a.blk[blockIdx.x].y + ex.y] = (int32_t)tile;
+    if (a.rows_out && f) {
+        int32_t last = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if ((f >> i) & 1u) a.rows_out[o++] = last = (int32_t)(tile * 16 + i);
+        const int64_t total = a.counts[0];                    // written by the scan launch before this one
+        if (o == total)                                       // the thread that holds the union's last row pads the last virtual tile with it
+            for (int64_t k = total; k < (total + 15) / 16 * 16; ++k) a.rows_out[k] = last;
+    }
+}
+
+// n_e per query: the splits present per (position of the view, stream), read by database row
+__global__ __launch_bounds__(256) void view_ne_kernel(ViewPlanArgs a, const uint8_t* present, int32_t* ne, int S, int E) {
+    const int q = blockIdx.y;
+    const int64_t* rows = a.rows[q];
+    const int64_t total = a.m[q] * S;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pos = i / S;
+        const int s = (int)(i - pos * S);
+        int c = E;
+        if (present) {
+            const int64_t row = rows ? rows[pos] : pos;
+            c = 0;
+            for (int e = 0; e < E; ++e) c += present[(row * S + s) * E + e] != 0 ? 1 : 0;
+        }
+        ne[(a.start[q] + pos) * S + s] = c;
+    }
+}
+
+// The partition of select_*_batch_kernel with a length and an offset per query: query q partitions its piece scores[start[q] ..
+// start[q + 1]) into positions of its view.  The one-workgroup form for a piece of at most kSelSmallN entries, the three passes for a
+// longer one, per query: a workgroup of the form its query does not take returns at once.
+struct SelViewArgs {
+    SelBatchArgs b;           // scores, out0, out1: the concatenated pieces; blk_*: the blocks of the long pieces, query after query
+    int64_t start[17];
+    int32_t bstart[17];       // the first block of query q (a short piece has none)
+};
+
+__global__ __launch_bounds__(kSelSmallThreads) void select_small_view_kernel(SelViewArgs v) {
+    const int q = blockIdx.x;
+    const int64_t s0 = v.start[q], m = v.start[q + 1] - s0;
+    if (m > kSelSmallN) return;
+    select_small_block(v.b.scores + s0, (int)m, batch_pred(v.b, q), v.b.result + 4 * q, v.b.out0 + s0, v.b.out1 + s0, v.b.pre0 + q * v.b.prefix,
+                       v.b.pre1 + q * v.b.prefix, (int)v.b.prefix);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_count_view_kernel(SelViewArgs v) {
+    const int q = blockIdx.y, b0 = v.bstart[q];
+    if ((int)blockIdx.x >= v.bstart[q + 1] - b0) return;
+    select_count_block(v.b.scores + v.start[q], v.start[q + 1] - v.start[q], batch_pred(v.b, q), v.b.blk_cnt + b0, v.b.blk_max + b0, v.b.blk_arg + b0);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_scan_view_kernel(SelViewArgs v) {
+    const int q = blockIdx.x, b0 = v.bstart[q], nb = v.bstart[q + 1] - b0;
+    if (nb == 0) return;
+    select_scan_block(v.b.blk_cnt + b0, v.b.blk_max + b0, v.b.blk_arg + b0, nb, v.b.result + 4 * q, -1);
+}
+
+__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_view_kernel(SelViewArgs v) {
+    const int q = blockIdx.y, b0 = v.bstart[q];
+    if ((int)blockIdx.x >= v.bstart[q + 1] - b0) return;
+    const int64_t s0 = v.start[q];
+    select_scatter_block(v.b.scores + s0, v.start[q + 1] - s0, batch_pred(v.b, q), v.b.blk_cnt + b0, v.b.out0 + s0, v.b.out1 + s0, -1,
+                         v.b.pre0 + q * v.b.prefix, v.b.pre1 + q * v.b.prefix, v.b.prefix);
+}
+
 // ------------------------------------------------------------------------------------------------
 // top-k: MSB-first radix select on the order-mapped scores, then the stable compaction above
 // ------------------------------------------------------------------------------------------------
@@ -1475,7 +1873,7 @@ static void round_layout(int64_t n, int S, int64_t off[8]) {
 static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);
     void* ptrs[] = {db->present, db->t,       db->sims,  db->round_dev, db->blk_cnt,
-                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev};
+                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev, db->vround_plan};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t ev : db->bround_ev)
@@ -2647,6 +3045,7 @@ int vq_db_query_round_batch(vq_db* db, int32_t n_queries, void* block, int64_t b
     for (int q = 0; q < kBatchSlots; ++q) {
         db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
         db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
+        db->bround_qoff[q] = (int64_t)q * n;
     }
     db->bround_q = Q;
     return VQ_OK;
@@ -2662,11 +3061,11 @@ int vq_db_batch_round_fetch(vq_db* db, int32_t query, int64_t* match_rows_host, 
     DeviceGuard g(db->device);
     if (match_rows_host) {
         VQ_REQUIRE(cap_match >= n0, "match buffer too small (%lld < %lld)", (long long)cap_match, (long long)n0);
-        if (n0) VQ_HIP(hipMemcpyAsync(match_rows_host, db->bround_dev + db->bround_rows0 + (int64_t)query * db->n * 8, (size_t)n0 * 8, hipMemcpyDeviceToHost, db->stream));
+        if (n0) VQ_HIP(hipMemcpyAsync(match_rows_host, db->bround_dev + db->bround_rows0 + db->bround_qoff[query] * 8, (size_t)n0 * 8, hipMemcpyDeviceToHost, db->stream));
     }
     if (near_rows_host) {
         VQ_REQUIRE(cap_near >= n1, "near buffer too small (%lld < %lld)", (long long)cap_near, (long long)n1);
-        if (n1) VQ_HIP(hipMemcpyAsync(near_rows_host, db->bround_dev + db->bround_rows1 + (int64_t)query * db->n * 8, (size_t)n1 * 8, hipMemcpyDeviceToHost, db->stream));
+        if (n1) VQ_HIP(hipMemcpyAsync(near_rows_host, db->bround_dev + db->bround_rows1 + db->bround_qoff[query] * 8, (size_t)n1 * 8, hipMemcpyDeviceToHost, db->stream));
     }
     VQ_HIP(hipStreamSynchronize(db->stream));
     return VQ_OK;
@@ -2677,6 +3076,312 @@ int vq_db_batch_round_times(vq_db* db, float* ms) {
     std::lock_guard<std::mutex> lk(db->mu);
     if (!db->bround_timed) return fail(VQ_E_STATE, "the last batched round was not timed (flag 8)");
     for (int i = 0; i < 3; ++i) VQ_HIP(hipEventElapsedTime(&ms[i], db->bround_ev[i], db->bround_ev[i + 1]));
+    return VQ_OK;
+}
+
+}  // extern "C"
+
+// ---- batched rounds over a row view per query (include/vq_amd_round_views.h) ---------------------------------------------------------
+// the VIEW instantiation of the 16-query pass for a database: the tiled layout exists for fp32 rows of 1024 elements only (vq_db_set_layout)
+template <typename T, int CH, int TW>
+static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
+    if constexpr (std::is_same_v<T, float> && CH == 4) {
+        if (tiled) return pres ? batch_view_kernel<T, CH, TW, true, 8, true> : batch_view_kernel<T, CH, TW, false, 8, true>;
+    }
+    return pres ? batch_view_kernel<T, CH, TW, true, 8, false> : batch_view_kernel<T, CH, TW, false, 8, false>;
+}
+
+// One pass over the union of the round's views.  max_tiles bounds the tiles the plan can hold (the kernel reads their number from the
+// device): it only sizes the grid.  Caller holds the lock and has checked the shape.
+static int launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
+    const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;
+    const int ch = db->D / 256;
+    const bool tiled = db->layout == VQ_LAYOUT_TILED;
+    if (tiled && !(db->dtype == VQ_F32 && ch == 4)) return fail(VQ_E_UNSUPPORTED, "a tiled database holds float32 rows of 1024 elements");
+    constexpr int TW = 2;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((max_tiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
+    // every (T, CH, mask, layout) is launched by a case of tests/test_view_round_gpu.py (the table above VIEW_KERNELS there): a new one
+    // gets a new case there
+#define VQ_VIEW_LAUNCH(T, CH)                                                                                              \
+    {                                                                                                                      \
+        auto kern = view_kernel_for<T, CH, TW>(db->present != nullptr, tiled);                                             \
+        VQ_DYN_LDS(kern, (kBatchSlots * CH * 256 + 32) * 8);                                                                \
+        kern<<<blocks, 1024, lds, db->stream>>>(f);                                                                        \
+    }
+    if (db->dtype == VQ_F16) {
+        if (ch == 4) VQ_VIEW_LAUNCH(__half, 4) else if (ch == 3) VQ_VIEW_LAUNCH(__half, 3) else if (ch == 2) VQ_VIEW_LAUNCH(__half, 2) else VQ_VIEW_LAUNCH(__half, 1)
+    } else if (db->dtype == VQ_F32) {
+        if (ch == 4) VQ_VIEW_LAUNCH(float, 4) else if (ch == 3) VQ_VIEW_LAUNCH(float, 3) else if (ch == 2) VQ_VIEW_LAUNCH(float, 2) else VQ_VIEW_LAUNCH(float, 1)
+    } else {
+        if (ch == 4) VQ_VIEW_LAUNCH(double, 4) else if (ch == 3) VQ_VIEW_LAUNCH(double, 3) else if (ch == 2) VQ_VIEW_LAUNCH(double, 2) else VQ_VIEW_LAUNCH(double, 1)
+    }
+#undef VQ_VIEW_LAUNCH
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
+}
+
+// m[q]: the rows of query q's piece.  Caller holds the lock.
+static int view_round_sizes(vq_db* db, int Q, const int32_t* views, int64_t m[16]) {
+    for (int q = 0; q < Q; ++q) {
+        const int32_t v = views[q];
+        if (v == -1) m[q] = db->n;
+        else if (v < 0 || (size_t)v >= db->views.size() || !db->views[v].defined)
+            return fail(VQ_E_INVALID, "query %d: no row view %d on this handle", q, v);
+        else m[q] = db->views[v].m;
+    }
+    return VQ_OK;
+}
+
+static void view_round_layout(const vq_db* db, int Q, const int64_t* m, int64_t off[12], int64_t start[17]) {
+    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
+    start[0] = 0;
+    for (int q = 0; q < kBatchSlots; ++q) start[q + 1] = start[q] + (q < Q ? m[q] : 0);
+    const int64_t sm = start[Q];
+    off[0] = 0;
+    off[1] = off[0] + up((int64_t)Q * db->S * db->E * db->D * 8);
+    off[2] = off[1] + up((int64_t)Q * 8 * 8);
+    off[3] = off[2] + up((int64_t)Q * 2 * 8);
+    off[4] = off[3] + up(sm * db->S * 4);
+    off[5] = off[4] + up(sm * db->S * 8);
+    off[6] = off[5] + up(sm * 8);
+    off[7] = off[6] + up((int64_t)Q * 4 * 8);
+    off[8] = off[7] + up((int64_t)Q * kRoundPrefix * 8);
+    off[9] = off[8] + up((int64_t)Q * kRoundPrefix * 8);
+    off[10] = kRoundPrefix;
+    off[11] = sm;
+}
+
+extern "C" {
+
+int vq_db_view_round_layout(vq_db* db, int32_t n_queries, const int32_t* views_host, int64_t* off, int64_t* start) {
+    VQ_REQUIRE(db && views_host && off && start, "NULL argument");
+    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
+    std::lock_guard<std::mutex> lk(db->mu);
+    int64_t m[16];
+    const int rc = view_round_sizes(db, n_queries, views_host, m);
+    if (rc != VQ_OK) return rc;
+    view_round_layout(db, n_queries, m, off, start);
+    return VQ_OK;
+}
+
+int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_host, void* block, int64_t block_bytes, int32_t flags) {
+    VQ_REQUIRE(db && views_host && block, "NULL argument");
+    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
+    VQ_REQUIRE(db->D % 256 == 0 && db->D <= 1024, "a batched round needs D in {256,512,768,1024} (got %d)", db->D);
+    VQ_REQUIRE(db->S <= 8, "at most 8 streams");
+    VQ_REQUIRE(db->n < (int64_t)2147483647 - 16, "a view round indexes the database's rows with 32 bits (%lld rows)", (long long)db->n);
+    VQ_REQUIRE((flags & ~15) == 0, "flags: 1 = avg and n_e back, 2 = scores back, 4 = partition, 8 = timed (got %d)", flags);
+    const int Q = n_queries;
+    const bool want_avg = flags & 1, want_scores = flags & 2, do_select = flags & 4, timed = flags & 8;
+    std::lock_guard<std::mutex> lk(db->mu);
+    int64_t m[16], off[12], start[17];
+    {
+        const int rc = view_round_sizes(db, Q, views_host, m);
+        if (rc != VQ_OK) return rc;
+    }
+    view_round_layout(db, Q, m, off, start);
+    VQ_REQUIRE(block_bytes >= off[9], "the block of this view round of %d queries needs %lld bytes (vq_db_view_round_layout), got %lld", Q,
+               (long long)off[9], (long long)block_bytes);
+    DeviceGuard g(db->device);
+    const int64_t n = db->n, sm = start[Q];
+    const bool tiled = db->layout == VQ_LAYOUT_TILED;
+    uint32_t whole = 0, members = 0;                  // queries over the whole database | queries whose row list goes into the plan
+    int64_t member_rows = 0, max_m = 0;
+    for (int q = 0; q < Q; ++q) {
+        if (views_host[q] < 0) whole |= 1u << q;
+        else if (m[q] > 0) {
+            members |= 1u << q;
+            member_rows += m[q];
+        }
+        max_m = std::max(max_m, m[q]);
+    }
+    // behind the image of the host block: the full lists [sum M] each and the scratch of the three-pass selection of the long pieces
+    SelViewArgs sel;
+    sel.bstart[0] = 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        sel.start[q] = start[q];
+        sel.bstart[q + 1] = sel.bstart[q] + (q < Q && m[q] > kSelSmallN ? cdiv(m[q], SEL_CHUNK) : 0);
+    }
+    sel.start[kBatchSlots] = start[kBatchSlots];
+    const int nbt = sel.bstart[kBatchSlots];
+    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
+    const int64_t o_rows0 = off[9], o_rows1 = o_rows0 + up(sm * 8), o_cnt = o_rows1 + up(sm * 8);
+    const int64_t o_max = o_cnt + (int64_t)nbt * 8, o_arg = o_max + (int64_t)nbt * 8, need = o_arg + (int64_t)nbt * 8 + 64;
+    db->bround_q = 0;                                 // the lists of the round before are gone from here on
+    db->batch_scores = nullptr;                       // vq_db_batch_scores_devptr names [Q][N] scores: none until the next whole-database pass
+    db->batch_q = 0;
+    db->bround_timed = false;
+    db->vround_have = false;
+    if (sm == 0) {                                    // every view is empty: nothing to launch
+        if (do_select) {
+            int64_t* res = (int64_t*)((char*)block + off[6]);
+            for (int q = 0; q < Q; ++q) {
+                res[4 * q] = res[4 * q + 1] = res[4 * q + 3] = 0;
+                res[4 * q + 2] = -1;
+            }
+        }
+        for (int q = 0; q < kBatchSlots; ++q) {
+            db->bround_n0[q] = db->bround_n1[q] = do_select && q < Q ? 0 : -1;
+            db->bround_qoff[q] = 0;
+        }
+        db->bround_rows0 = db->bround_rows1 = 0;
+        db->bround_q = Q;
+        db->vround_have = true;
+        db->vround_union = db->vround_tiles = 0;
+        return VQ_OK;
+    }
+    if (db->bround_cap < need) {
+        if (db->bround_dev) VQ_HIP(hipFree(db->bround_dev));
+        db->bround_dev = nullptr;
+        db->bround_cap = 0;
+        VQ_HIP(vq::malloc_trim((void**)&db->bround_dev, (size_t)need));
+        db->bround_cap = need;
+    }
+    // the plan's block (vq_db.h): 64 MB of inverse map at 16 x 1M rows, allocated on the first view round
+    const int64_t stride = (n + 15) / 16 * 16, db_tiles = stride / 16;
+    const int nblk_u = cdiv(db_tiles, SEL_BLOCK);
+    const int64_t p_rows = (int64_t)kBatchSlots * stride * 4, p_tiles = p_rows + up((stride + 16) * 4), p_counts = p_tiles + up(db_tiles * 4);
+    const int64_t p_start = p_counts + 64, p_blk = p_start + up(17 * 8), p_need = p_blk + (int64_t)nblk_u * 8 + 64;
+    if (!db->vround_plan) VQ_HIP(vq::malloc_trim((void**)&db->vround_plan, (size_t)p_need));
+    char* plan = db->vround_plan;
+    if (timed && !db->bround_ev[0])
+        for (auto& ev : db->bround_ev) VQ_HIP(hipEventCreate(&ev));
+    char* host = (char*)block;
+    char* dev = db->bround_dev;
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[0], db->stream));
+    VQ_HIP(hipMemcpyAsync(dev, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));       // queries | weights | bands: adjacent
+    // the plan
+    ViewPlanArgs pa;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        pa.rows[q] = (members >> q) & 1u ? db->views[views_host[q]].rows : nullptr;
+        pa.m[q] = q < Q ? m[q] : 0;
+        pa.start[q] = start[q];
+    }
+    pa.start[kBatchSlots] = start[kBatchSlots];
+    pa.Q = Q;
+    pa.n = n;
+    pa.stride = stride;
+    pa.inv = (int32_t*)plan;
+    pa.start_dev = (int64_t*)(plan + p_start);
+    for (int q = 0; q < Q; ++q)
+        if ((members >> q) & 1u) VQ_HIP(hipMemsetAsync(plan + (int64_t)q * stride * 4, 0xFF, (size_t)stride * 4, db->stream));
+    const int fill_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
+    view_scatter_kernel<<<dim3(fill_blocks, Q), 256, 0, db->stream>>>(pa);
+    VQ_CHECK_LAUNCH();
+    int64_t max_tiles = db_tiles;                     // a whole-database query: the union is the database, addressed as ever
+    if (!whole) {
+        ViewUnionArgs ua;
+        ua.inv = pa.inv;
+        ua.stride = stride;
+        ua.ntiles = db_tiles;
+        ua.members = members;
+        ua.blk = (int2*)(plan + p_blk);
+        ua.nblk = nblk_u;
+        ua.rows_out = tiled ? nullptr : (int32_t*)(plan + p_rows);
+        ua.tiles_out = tiled ? (int32_t*)(plan + p_tiles) : nullptr;
+        ua.counts = (int64_t*)(plan + p_counts);
+        view_union_count_kernel<<<nblk_u, SEL_BLOCK, 0, db->stream>>>(ua);
+        VQ_CHECK_LAUNCH();
+        view_union_scan_kernel<<<1, SEL_BLOCK, 0, db->stream>>>(ua);
+        VQ_CHECK_LAUNCH();
+        view_union_scatter_kernel<<<nblk_u, SEL_BLOCK, 0, db->stream>>>(ua);
+        VQ_CHECK_LAUNCH();
+        max_tiles = tiled ? std::min(db_tiles, member_rows) : (std::min(n, member_rows) + 15) / 16;
+    }
+    {
+        BatchViewArgs f;
+        f.feats = db->feats;
+        f.t = (const double*)(dev + off[0]);
+        f.w = (const double*)(dev + off[1]);
+        f.present = db->present;
+        f.scores = (double*)(dev + off[5]);
+        f.n = n;
+        f.Q = Q;
+        f.S = db->S;
+        f.E = db->E;
+        f.D = db->D;
+        f.avg = (double*)(dev + off[4]);
+        f.items = whole ? nullptr : (tiled ? (const int32_t*)(plan + p_tiles) : (const int32_t*)(plan + p_rows));
+        f.counts = (const int64_t*)(plan + p_counts);
+        f.inv = pa.inv;
+        f.inv_stride = stride;
+        f.start = pa.start_dev;
+        f.whole = whole;
+        f.members = members;
+        const int rc = launch_view_pass(db, f, max_tiles);
+        if (rc != VQ_OK) return rc;
+    }
+    view_ne_kernel<<<dim3((int)std::max<int64_t>(1, std::min<int64_t>((max_m * db->S + 255) / 256, (int64_t)db->cus * 8)), Q), 256, 0, db->stream>>>(
+        pa, db->present, (int32_t*)(dev + off[3]), db->S, db->E);
+    VQ_CHECK_LAUNCH();
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[1], db->stream));
+    if (do_select) {
+        sel.b.scores = (const double*)(dev + off[5]);
+        sel.b.band = (const double*)(dev + off[2]);
+        sel.b.n = 0;
+        sel.b.nblk = nbt;
+        sel.b.blk_cnt = (int2*)(dev + o_cnt);
+        sel.b.blk_max = (double*)(dev + o_max);
+        sel.b.blk_arg = (int64_t*)(dev + o_arg);
+        sel.b.result = (int64_t*)(dev + off[6]);
+        sel.b.out0 = (int64_t*)(dev + o_rows0);
+        sel.b.out1 = (int64_t*)(dev + o_rows1);
+        sel.b.pre0 = (int64_t*)(dev + off[7]);
+        sel.b.pre1 = (int64_t*)(dev + off[8]);
+        sel.b.prefix = kRoundPrefix;
+        VQ_HIP(hipMemsetAsync(dev + off[6], 0, (size_t)Q * 4 * 8, db->stream));
+        select_small_view_kernel<<<Q, kSelSmallThreads, 0, db->stream>>>(sel);       // the pieces of at most kSelSmallN entries (an empty one: 0, 0, -1)
+        VQ_CHECK_LAUNCH();
+        if (nbt > 0) {                                // count / scan / scatter for the longer ones
+            int max_nb = 0;
+            for (int q = 0; q < Q; ++q) max_nb = std::max(max_nb, sel.bstart[q + 1] - sel.bstart[q]);
+            select_count_view_kernel<<<dim3(max_nb, Q), SEL_BLOCK, 0, db->stream>>>(sel);
+            VQ_CHECK_LAUNCH();
+            select_scan_view_kernel<<<Q, SEL_BLOCK, 0, db->stream>>>(sel);
+            VQ_CHECK_LAUNCH();
+            select_scatter_view_kernel<<<dim3(max_nb, Q), SEL_BLOCK, 0, db->stream>>>(sel);
+            VQ_CHECK_LAUNCH();
+        }
+    }
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[2], db->stream));
+    const int64_t piece[3][2] = {{off[3], off[5]}, {off[5], off[6]}, {off[6], off[9]}};
+    const bool want[3] = {want_avg, want_scores, do_select};
+    for (int i = 0; i < 3;) {
+        if (!want[i]) {
+            ++i;
+            continue;
+        }
+        int j = i;
+        while (j + 1 < 3 && want[j + 1]) ++j;
+        VQ_HIP(hipMemcpyAsync(host + piece[i][0], dev + piece[i][0], (size_t)(piece[j][1] - piece[i][0]), hipMemcpyDeviceToHost, db->stream));
+        i = j + 1;
+    }
+    int64_t counts[2] = {n, db_tiles};
+    if (!whole) VQ_HIP(hipMemcpyAsync(counts, plan + p_counts, 16, hipMemcpyDeviceToHost, db->stream));
+    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[3], db->stream));
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    db->bround_timed = timed;
+    db->bround_rows0 = o_rows0;
+    db->bround_rows1 = o_rows1;
+    const int64_t* res = (const int64_t*)(host + off[6]);
+    for (int q = 0; q < kBatchSlots; ++q) {
+        db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
+        db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
+        db->bround_qoff[q] = start[q];
+    }
+    db->bround_q = Q;
+    db->vround_have = true;
+    db->vround_union = counts[0];
+    db->vround_tiles = counts[1];
+    return VQ_OK;
+}
+
+int vq_db_view_round_union(vq_db* db, int64_t* n_union, int64_t* n_tiles) {
+    VQ_REQUIRE(db, "db is NULL");
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (!db->vround_have) return fail(VQ_E_STATE, "no view round has run on this handle");
+    if (n_union) *n_union = db->vround_union;
+    if (n_tiles) *n_tiles = db->vround_tiles;
     return VQ_OK;
 }
 

@@ -178,6 +178,16 @@ class FeatureDB:
                 self._set_in_use, self._na = set_id, view.n
             return view
 
+    def search_set_view(self, set_id) -> SearchSetView:
+        """The view of a defined search set (``None``: the whole database) without selecting it: no library call, the set in use
+        and the handle's results stay as they are."""
+        with self.lock:
+            if set_id is None:
+                if self._whole is None:
+                    self._whole = whole_view(self)
+                return self._whole
+            return self._sets[set_id]
+
     def drop_search_set(self, set_id):
         with self.lock:
             view = self._sets[set_id]
@@ -683,6 +693,99 @@ class FeatureDB:
                 out.append(r)
             return out
 
+    def query_round_batch_sets(self, targets: np.ndarray, weights: np.ndarray, set_ids, selects=None, want_avg: bool = True,
+                               timed: bool = False) -> list:
+        """:meth:`query_round_batch` with a search set per query (vq_db_query_round_views, include/vq_amd_round_views.h): ONE read of
+        the UNION of the sets, every query scored, averaged and partitioned over its own set only.  ``set_ids[q]`` is a defined search
+        set id, or ``None`` for the whole database.  One :class:`RoundResult` per query: ``avg`` [M_q,S], ``n_e`` [M_q,S] and ``scores``
+        [M_q] are compact (entry i belongs to row ``rows[i]`` of the set's view) and every row in ``match_rows`` / ``near_rows`` /
+        ``near_argmax`` is a position in that view, as under :meth:`use_search_set`.  avg and scores have the bits
+        :meth:`query_round_batch` gives the same (clip, query slot) on this handle.  The set in use and the one-query state of the
+        handle are left alone.  :attr:`last_view_round_union` then says what the pass read."""
+        t = np.asarray(targets, dtype=np.float64)
+        w = np.asarray(weights, dtype=np.float64)
+        if t.ndim != 4 or t.shape[1:] != (self.S, self.E, self.D) or w.shape != (t.shape[0], self.S):
+            raise ValueError("targets must be [Q,%d,%d,%d] and weights [Q,%d]" % (self.S, self.E, self.D, self.S))
+        Q = int(t.shape[0])
+        set_ids = list(set_ids)
+        if len(set_ids) != Q:
+            raise ValueError("one search set id (or None) per query")
+        bands = None if selects is None else np.asarray(selects, dtype=np.float64)
+        if bands is not None and bands.shape != (Q, 2):
+            raise ValueError("selects must be [Q,2]: (threshold, lower) per query")
+        with self.lock:
+            tokens = (C.c_int32 * max(Q, 1))()
+            for q, sid in enumerate(set_ids):
+                if sid is not None and not self.has_search_set(sid):
+                    raise _lib.VqError(-1, "query %d: search set %r is not defined on this database" % (q, sid))
+                tokens[q] = -1 if sid is None else self._sets[sid].token
+            off, start = (C.c_int64 * 12)(), (C.c_int64 * 17)()
+            call("vq_db_view_round_layout", self._h, Q, tokens, off, start)          # Q outside [1, 16]: the library's own refusal
+            off, start = [int(v) for v in off], [int(v) for v in start]
+            pools = self.__dict__.setdefault("_view_round_pools", {})
+            nbytes = (off[9] + 65535) // 65536 * 65536                                # pooled by size: the layout depends on the sets
+            if nbytes not in pools and len(pools) >= 8:                               # many layouts: the idle blocks of the old ones go
+                for size in list(pools):
+                    old = pools.pop(size)
+                    old["closed"] = True                                              # blocks still referenced free themselves
+                    while old["free"]:
+                        _lib.load().vq_host_free(C.c_void_p(old["free"].pop()[0]))
+            pool = pools.setdefault(nbytes, {"free": [], "closed": False})
+            if pool["free"]:
+                ptr, _ = pool["free"].pop()
+            else:
+                p = C.c_void_p()
+                call("vq_host_alloc", C.byref(p), nbytes)
+                ptr = p.value
+            blk = _RoundBlock(ptr, nbytes, pool)
+            raw = blk.bytes()
+            S = self.S
+
+            def view(piece, dtype, shape, first=0):
+                count, size = int(np.prod(shape)), np.dtype(dtype).itemsize
+                lo = off[piece] + first * size
+                return raw[lo:lo + count * size].view(dtype).reshape(shape)
+            view(0, np.float64, (Q, S, self.E, self.D))[...] = t
+            wv = view(1, np.float64, (Q, 8))
+            wv[...] = 0.0
+            wv[:, :S] = w
+            flags = _lib.VQ_BROUND_SCORES | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
+            if bands is not None:
+                view(2, np.float64, (Q, 2))[...] = bands
+                flags |= _lib.VQ_BROUND_SELECT
+            call("vq_db_query_round_views", self._h, Q, tokens, C.c_void_p(blk.ptr), blk.nbytes, flags)
+            res = view(6, np.int64, (Q, 4))
+            prefix = off[10]
+            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            out = []
+            for q in range(Q):
+                m = start[q + 1] - start[q]
+                r = RoundResult()
+                r.avg = view(4, np.float64, (m, S), start[q] * S) if want_avg else None
+                r.n_e = view(3, np.int32, (m, S), start[q] * S) if want_avg else None
+                r.scores = view(5, np.float64, (m,), start[q])
+                r.match_rows = r.near_rows = None
+                r.near_argmax = -1
+                if bands is not None:
+                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
+                    if nm <= prefix and nn <= prefix:
+                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
+                    else:                                     # a list longer than its prefix: the full lists are still on the device
+                        mr = np.empty(nm, dtype=np.int64)
+                        kr = np.empty(nn, dtype=np.int64)
+                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(mr) if nm else None, nm, _np_ptr(kr) if nn else None, nn)
+                        r.match_rows, r.near_rows = mr, kr
+                out.append(r)
+            return out
+
+    @property
+    def last_view_round_union(self):
+        """(rows, tiles) of the last :meth:`query_round_batch_sets`: the rows in the union of its sets, and the tiles of 16 rows the
+        union touches (what the pass read of a tiled database)."""
+        rows, tiles = C.c_int64(), C.c_int64()
+        call("vq_db_view_round_union", self._h, C.byref(rows), C.byref(tiles))
+        return int(rows.value), int(tiles.value)
+
     def batch_round_times(self):
         """(pass, selection, copy-back) in ms of the last ``query_round_batch(..., timed=True)``: device time between HIP events."""
         ms = (C.c_float * 3)()
@@ -778,7 +881,8 @@ class FeatureDB:
 
     def close(self):
         if self._h:
-            pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()]
+            pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()] + \
+                list(getattr(self, "_view_round_pools", {}).values())
             for pool in pools:
                 if pool is None:
                     continue

@@ -321,9 +321,15 @@ class TicketScoring:
 
 # -- several tickets in one pass over a resident database -----------------------------------------------------------------------------
 BATCH_PASS = 16       # queries per pass of the batched round (include/vq_amd_rounds.h)
+# share_search_sets: a group with search-set members shares ONE pass over the union of their sets (include/vq_amd_round_views.h) when
+# sum M_q >= SHARE_SETS_FACTOR * distinct, M_q = the members' set sizes (N for a whole-database member) and distinct = min(N, sum of M
+# over the distinct set ids of the group).  `distinct` bounds the rows the union can hold, so a shared pass then reads at most half
+# the rows the members' own rounds would read.  The two kernels run at 0.75 (16-query pass) against 0.85 (one-query scan) of the HBM
+# peak (README), which puts break-even near sum M_q = 1.13 |U|: well inside the factor of 2, and the rule needs no union on the host.
+SHARE_SETS_FACTOR = 2
 
 
-def _batchable(ticket, hyperparameters):
+def _batchable(ticket, hyperparameters, share_search_sets=False):
     """(database, stream names, query, slots in use, look-ahead) when the ticket's round can share a 16-query pass, else None: it has
     a resident database with ``query_round_batch`` that meets the pass's preconditions, runs over the WHOLE database (no search set
     defined for it) and its hyperparameters say which weights and band come next."""
@@ -331,7 +337,8 @@ def _batchable(ticket, hyperparameters):
     if db is None or not hasattr(db, "query_round_batch"):
         return None
     if hasattr(db, "has_search_set") and db.has_search_set(getattr(ticket, "search_set", None)):
-        return None
+        if not (share_search_sets and hasattr(db, "query_round_batch_sets")):
+            return None
     supported = getattr(db, "batch_round_supported", None)
     if supported is not None and not supported():
         return None
@@ -371,7 +378,67 @@ def _batched_pass(group):
         tk.similarities = SimilarityMap(view.clip_ids, stream_names, r.avg, r.n_e, view.row_of)
 
 
-def compute_similarities_batch(tickets, hyperparameters):
+def _set_of(db, ticket):
+    """The id of the ticket's search set if the database has it defined, else None (the whole database)."""
+    set_id = getattr(ticket, "search_set", None)
+    return set_id if hasattr(db, "has_search_set") and db.has_search_set(set_id) else None
+
+
+def _shared_sets_pass(group):
+    """ONE pass over the union of the members' search sets (FeatureDB.query_round_batch_sets): what compute_similarities does for each
+    member under its own set -- ``_view`` is its set's view, everything else is indexed by position in it."""
+    db, slot_used = group[0][2][0], group[0][2][3]
+    targets = np.stack([g[2][2] for g in group])
+    weights = np.stack([g[2][4][0] for g in group])
+    bands = np.array([[g[2][4][1], g[2][4][2]] for g in group], dtype=np.float64)
+    for tk, _hp, _prep in group:
+        tk._ahead = None
+    with _db_lock(db):
+        set_ids = [_set_of(db, tk) for tk, _hp, _prep in group]
+        views = [db.search_set_view(sid) for sid in set_ids]          # the view objects: the set the handle has in use stays
+        db.restrict_slots(slot_used)                                  # once per group
+        results = db.query_round_batch_sets(targets, weights, set_ids, bands, want_avg=True)
+        db.sims_owner = db.scores_owner = None                        # as after _batched_pass: nobody's round
+    for (tk, hp, prep), view, r in zip(group, views, results):
+        _db, stream_names, _t, _used, (w, th, lower) = prep
+        tk._round = object()
+        tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": (th, lower), "match_rows": r.match_rows,
+                     "near_rows": r.near_rows, "near_argmax": r.near_argmax}
+        tk._hp = hp
+        tk._stream_names = stream_names
+        tk._avg, tk._n_e = r.avg, r.n_e
+        tk._stream_gap = None
+        tk._view = view
+        tk.similarities = SimilarityMap(view.clip_ids, stream_names, r.avg, r.n_e, view.row_of)
+
+
+def _flush(group):
+    """Run a group of tickets that share a database object and a slot mask.  Without search-set members: one pass, or the ticket's own
+    round when it is alone.  With them (share_search_sets): one pass over the union if the sharing rule holds, else the search-set
+    members' own rounds in list order and the whole-database members as a group of today's kind."""
+    db = group[0][2][0]
+    set_ids = [_set_of(db, tk) for tk, _hp, _prep in group]
+    if any(sid is not None for sid in set_ids):
+        n = len(db.clip_ids)
+        sizes = {sid: db.search_set_view(sid).n for sid in set(set_ids) if sid is not None}
+        total = sum(n if sid is None else sizes[sid] for sid in set_ids)
+        distinct = min(n, sum(sizes.values()) + (n if None in set_ids else 0))
+        if len(group) > 1 and total >= SHARE_SETS_FACTOR * distinct:
+            _shared_sets_pass(group)
+            return
+        for (tk, hp, _prep), sid in zip(group, set_ids):
+            if sid is not None:
+                tk.compute_similarities(hp)
+        group = [g for g, sid in zip(group, set_ids) if sid is None]
+        if not group:
+            return
+    if len(group) == 1:                                   # nobody to share a pass with: the ticket's own round, bit for bit
+        group[0][0].compute_similarities(group[0][1])
+    else:
+        _batched_pass(group)
+
+
+def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False):
     """``compute_similarities`` for a list of tickets, those that can sharing passes over their resident database: a broker with
     several pending tickets pays one read of the database per 16 of them instead of one each.  ``hyperparameters`` is one object or
     one per ticket.  Every ticket ends with exactly the attributes its own ``compute_similarities`` sets (``similarities``, ``_avg``,
@@ -383,14 +450,20 @@ def compute_similarities_batch(tickets, hyperparameters):
     search set defined for them, the same slot mask and a look-ahead; at most 16 per pass, in list order.  Every other ticket -- on
     a ShardedFeatureDB or another database without the method, with a search set, without a resident database (``from_records``)
     -- runs its own ``compute_similarities``, in list order; so does, at the end, a ticket left alone in its group (a pass of one
-    gains nothing)."""
+    gains nothing).
+
+    ``share_search_sets=True``: a ticket whose search set is defined on its database (which must have ``query_round_batch_sets``)
+    joins its group too, keyed as ever.  A group with such members runs ONE pass over the union of the members' sets when
+    sum M_q >= SHARE_SETS_FACTOR * distinct (see the constant); otherwise its search-set members run their own rounds in list order
+    and its whole-database members share a pass as above.  After a shared pass every member has the attributes its own
+    ``compute_similarities`` sets, ``_view`` = its set's view and rows as positions in it."""
     tickets = list(tickets)
     hps = list(hyperparameters) if isinstance(hyperparameters, (list, tuple)) else [hyperparameters] * len(tickets)
     if len(hps) != len(tickets):
         raise ValueError("one hyperparameters object, or one per ticket")
     pending = {}                                          # (database object, slot mask) -> the tickets waiting for a pass, in list order
     for tk, hp in zip(tickets, hps):
-        prep = _batchable(tk, hp)
+        prep = _batchable(tk, hp, share_search_sets)
         if prep is None:
             tk.compute_similarities(hp)
             continue
@@ -398,12 +471,9 @@ def compute_similarities_batch(tickets, hyperparameters):
         group = pending.setdefault(key, [])
         group.append((tk, hp, prep))
         if len(group) == BATCH_PASS:
-            _batched_pass(pending.pop(key))
+            _flush(pending.pop(key))
     for group in pending.values():
-        if len(group) == 1:                               # nobody to share a pass with: the ticket's own round, bit for bit
-            group[0][0].compute_similarities(group[0][1])
-        else:
-            _batched_pass(group)
+        _flush(group)
 
 
 class Ticket(TicketScoring):
