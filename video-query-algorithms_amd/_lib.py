@@ -138,6 +138,11 @@ VIEW_ROUND_SIGNATURES = {
     "vq_db_view_round_layout": [_P, _I32, _P, _P, _P], "vq_db_query_round_views": [_P, _I32, _P, _P, _I64, _I32],
     "vq_db_view_round_union": [_P, _pI64, _pI64],
 }
+# include/vq_amd_round_fit.h: the weight fit and the re-weighting of a batched round's queries -- additive to ABI 12, bound like the tables above
+ROUND_FIT_SIGNATURES = {
+    "vq_db_batch_fit_layout": [_P, _I32, _I32, _I32, _I64, _P], "vq_db_batch_round_fit": [_P, _I32, _I32, _I32, _I64, _P, _I64],
+    "vq_db_batch_round_rescore": [_P, _I32, _P, _I64, _I32],
+}
 _SPECIAL = {"vq_last_error": ([], C.c_char_p), "vq_abi_version": ([], C.c_int)}
 
 _lib = None
@@ -190,7 +195,7 @@ def load(path: str | None = None):
         for name, (args, res) in _SPECIAL.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, res
-        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()) + list(CSV_SIGNATURES.items()) + list(BATCH_ROUND_SIGNATURES.items()) + list(VIEW_ROUND_SIGNATURES.items()):
+        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()) + list(CSV_SIGNATURES.items()) + list(BATCH_ROUND_SIGNATURES.items()) + list(VIEW_ROUND_SIGNATURES.items()) + list(ROUND_FIT_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = ABI mismatch; fail loudly
             fn.argtypes, fn.restype = args, C.c_int
         if lib.vq_abi_version() != ABI_VERSION:

@@ -27,7 +27,11 @@ def _choose_weights(kind, update, tk, hp):
         hp.weights = hp.default_weights
         hp.threshold = hp.default_threshold
     elif kind in ("revise", "finalize"):
-        hp.optimize_weights(tk)
+        fit = getattr(tk, "_fit", None)
+        if fit is not None and getattr(tk, "_fit_round", None) is tk._round:
+            hp.weights, hp.threshold = fit                                  # fitted behind this round's batched pass (fit_weights)
+        else:
+            hp.optimize_weights(tk)
     else:
         raise Exception('update type is invalid')
 
@@ -88,7 +92,8 @@ def _one_update(kind, update, url, hp, ticket_factory, target_factory):
     _finish_update(kind, update, tk, hp)
 
 
-def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False, share_search_sets=False):
+def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False, share_search_sets=False,
+                    fit_weights=False):
     """One broker pass.  ``batch=True`` runs it in three phases so that the pending tickets share passes over their resident database
     (``ticket.compute_similarities_batch``): (1) every pending update gets its ticket, process state 3, its checks and its target
     features; (2) ONE ``compute_similarities_batch`` over the tickets that survived; (3) every ticket is finished in the original
@@ -97,7 +102,19 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     look-ahead is taken from the hyperparameters object as it stands before phase 3 changes it (a ticket whose weights come out
     different re-weights its own similarities, as ever).  Values agree with the default path to rounding (<= 1e-12).
     ``share_search_sets=True`` (with ``batch``): tickets whose search sets are defined on their database share passes too
-    (``compute_similarities_batch(..., share_search_sets=True)``)."""
+    (``compute_similarities_batch(..., share_search_sets=True)``).
+    ``fit_weights=True`` (with ``batch``; ``ValueError`` without): the revise and finalize updates that have ``matches`` get their
+    weight update behind their group's pass, on the similarities it left on the device (``compute_similarities_batch(..., fit=...)``:
+    two calls per group instead of four per ticket), and ``_choose_weights`` takes ``hp.weights`` / ``hp.threshold`` from the ticket's
+    ``_fit``.  A ticket without one for its current round -- alone in its group, without a resident database, on a sharded one,
+    without labels -- calls ``hp.optimize_weights`` as ever.  Per ticket the order of phase 3, the ledger and the consumption of
+    ``random`` are unchanged; weights, threshold and matches are those of ``batch=True`` bit for bit (both fit on the pass's
+    similarities).  Two differences: between the fit and ``compute_scores`` ``ticket.scores`` is not left at the last grid weight
+    (compute_matches.py:77 overwrites it on the next line), and a finalize ticket's scores come back with the group's while its
+    review band -- which depends on ``lowest_scoring_user_match`` under the fitted scores -- is still partitioned by its own
+    ``select``."""
+    if fit_weights and not batch:
+        raise ValueError("fit_weights=True needs batch=True: the fit runs behind a batched pass")
     pending = query_updates.get_status()                                    # :34
     if ticket_factory is None:
         from .ticket import Ticket as _Ticket
@@ -118,7 +135,9 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
             tk = _begin_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
             if tk is not None:
                 started.append((kind, update, tk))
-    compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets)
+    fit = [fit_weights and kind in ("revise", "finalize") and bool(update["matches"]) for kind, update, _tk in started]
+    compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets,
+                               **({"fit": fit} if fit_weights else {}))
     for kind, update, tk in started:
         _finish_update(kind, update, tk, hyperparameters)
 

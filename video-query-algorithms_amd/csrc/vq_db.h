@@ -59,6 +59,15 @@ struct vq_db {
     hipEvent_t bround_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // flag 8: start | pass done | selection done | copies done
     bool bround_timed = false;
     int64_t bround_qoff[16] = {0};   // where query q's full lists start inside the two list arrays (entries): q N, or a view round's start[q]
+    // The layout of the last batched round, for the calls of include/vq_amd_round_fit.h that work on its device data: the offsets of
+    // its block, the rows per query (bround_qoff[q] is also where query q's avg / scores entries start), whether it was a view
+    // round, and where the scratch of the three-pass selection sits (query q's blocks start at bround_bstart[q]; none for a piece
+    // of at most kSelSmallN rows).
+    int64_t bround_off[12] = {0};
+    int64_t bround_m[16] = {0};
+    bool bround_views = false;
+    int64_t bround_cnt = 0, bround_max = 0, bround_arg = 0;     // byte offsets of blk_cnt, blk_max, blk_arg
+    int32_t bround_bstart[17] = {0};
     // View rounds (vq_db_query_round_views, include/vq_amd_round_views.h): the plan's device block, allocated on the first one --
     // inv [16][stride] i32 | union rows [stride + 16] i32 | touched tiles [stride / 16] i32 | counts [2] i64 | start [17] i64 | the
     // per-block counts of the compaction [tiles / 256] int2 -- and what the last one covered

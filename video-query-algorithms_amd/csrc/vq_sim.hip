@@ -1101,6 +1101,86 @@ __global__ void loss_surface_kernel(const double* avg, const double* w_grid, con
     }
 }
 
+// ---- the same two steps for the queries of a batched round, on the avg that round left on the device (include/vq_amd_round_fit.h) ----
+// loss_surface_kernel for every query with labels in ONE launch: block (g, q) = grid weight g of query q, over the avg entries of that
+// query (qoff[q] on).  The labels walk through LDS in chunks of kFitChunk: all threads fill the chunk's scores, then thread t adds the
+// chunk's terms to its running sum for threshold t IN LABEL ORDER -- the chunking changes nothing in a cell's sequence of fp64
+// operations, so a cell has loss_surface_kernel's bits on the same avg, for any number of labels in 32 KB of LDS.
+constexpr int kFitChunk = 4096, kFitThreads = 256, kFitMaxGrid = 64;
+struct FitBatchArgs {
+    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round
+    const double* w_grid;     // [Q][G][8]
+    const double* th_grid;    // [Q][T]
+    const double* ballast;    // [Q]
+    const int64_t* rows;      // [sum L]: positions inside each query's piece
+    const double* labels;     // [sum L]
+    double* out;              // [Q][G][T]
+    int64_t qoff[16];         // the first avg entry of query q
+    int64_t lstart[17];       // the first label of query q (lstart[q + 1] - lstart[q] = L_q; 0: nothing to do)
+    int G, T, S;
+};
+
+__global__ __launch_bounds__(kFitThreads) void loss_surface_batch_kernel(FitBatchArgs a) {
+    __shared__ double ls_scores[kFitChunk];
+    const int g = blockIdx.x, q = blockIdx.y, S = a.S;
+    const int64_t l0 = a.lstart[q], L = a.lstart[q + 1] - l0;
+    if (L <= 0) return;                                        // the whole workgroup: a skipped query writes nothing
+    double w[8];
+    for (int s = 0; s < S; ++s) w[s] = a.w_grid[((int64_t)q * a.G + g) * 8 + s];
+    const int t = threadIdx.x;
+    const bool mine = t < a.T;                                 // T <= kFitMaxGrid < kFitThreads: one thread per threshold
+    const double th = mine ? a.th_grid[q * a.T + t] : 0.0;
+    const double ballast = a.ballast[q];
+    const double* avg = a.avg + a.qoff[q] * S;
+    double surf = 0.5 * th;
+    for (int64_t c0 = 0; c0 < L; c0 += kFitChunk) {
+        const int len = (int)(L - c0 < kFitChunk ? L - c0 : kFitChunk);
+        for (int l = threadIdx.x; l < len; l += kFitThreads) {
+            double av[8];
+            const int64_t row = a.rows[l0 + c0 + l];
+            for (int s = 0; s < S; ++s) av[s] = avg[row * S + s];
+            ls_scores[l] = score_from_avg(av, w, S);
+        }
+        __syncthreads();
+        if (mine) {
+            for (int l = 0; l < len; ++l) {
+                const double y = a.labels[l0 + c0 + l];
+                const double margin = ls_scores[l] - th;
+                const double h = margin < 0.0 ? 0.0 : (margin >= 0.0 ? 1.0 : margin);     // np.heaviside(margin, 1); NaN stays NaN
+                const double c = 1.0 + y * ballast;
+                surf = surf + ((h - y) * margin) * c;
+            }
+        }
+        __syncthreads();                                       // the next chunk overwrites the scores
+    }
+    if (mine) a.out[((int64_t)q * a.G + g) * a.T + t] = surf;
+}
+
+// rescore_kernel for the masked queries of a batched round: query q = blockIdx.y rescores its m[q] avg entries under w[q] into the
+// round's own score array; a query outside the mask is left alone.
+struct RescoreBatchArgs {
+    const double* avg;
+    const double* w;          // [16][8]
+    double* scores;
+    int64_t qoff[16];         // the first avg / score entry of query q
+    int64_t m[16];
+    uint32_t mask;
+    int S;
+};
+
+__global__ __launch_bounds__(256) void rescore_batch_kernel(RescoreBatchArgs a) {
+    const int q = blockIdx.y, S = a.S;
+    if (!((a.mask >> q) & 1u)) return;
+    double w[8];
+    for (int s = 0; s < S; ++s) w[s] = a.w[q * 8 + s];
+    const int64_t m = a.m[q], base = a.qoff[q];
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < m; c += (int64_t)gridDim.x * blockDim.x) {
+        double av[8];
+        for (int s = 0; s < S; ++s) av[s] = a.avg[(base + c) * S + s];
+        a.scores[base + c] = score_from_avg(av, w, S);
+    }
+}
+
 // target_clip.py:311-313: t = r / (r . r), one block per (s,e) vector of row `row`, fp64 throughout.
 // element k of vector (row, v): row-major, or inside the tiled layout [tile][v][k / 4][row % 16][4]
 __device__ __forceinline__ int64_t feat_index(bool tiled, int64_t row, int v, int k, int NV, int D) {
@@ -3046,7 +3126,14 @@ int vq_db_query_round_batch(vq_db* db, int32_t n_queries, void* block, int64_t b
         db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
         db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
         db->bround_qoff[q] = (int64_t)q * n;
+        db->bround_m[q] = q < Q ? n : 0;
+        db->bround_bstart[q + 1] = n > kSelSmallN && q < Q ? (q + 1) * nblk : db->bround_bstart[q];
     }
+    memcpy(db->bround_off, off, sizeof(off));
+    db->bround_views = false;
+    db->bround_cnt = o_cnt;
+    db->bround_max = o_max;
+    db->bround_arg = o_arg;
     db->bround_q = Q;
     return VQ_OK;
 }
@@ -3223,8 +3310,12 @@ int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_h
         for (int q = 0; q < kBatchSlots; ++q) {
             db->bround_n0[q] = db->bround_n1[q] = do_select && q < Q ? 0 : -1;
             db->bround_qoff[q] = 0;
+            db->bround_m[q] = 0;
+            db->bround_bstart[q + 1] = 0;
         }
         db->bround_rows0 = db->bround_rows1 = 0;
+        memcpy(db->bround_off, off, sizeof(off));
+        db->bround_views = true;
         db->bround_q = Q;
         db->vround_have = true;
         db->vround_union = db->vround_tiles = 0;
@@ -3368,7 +3459,14 @@ int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_h
         db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
         db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
         db->bround_qoff[q] = start[q];
+        db->bround_m[q] = q < Q ? m[q] : 0;
+        db->bround_bstart[q + 1] = sel.bstart[q + 1];
     }
+    memcpy(db->bround_off, off, sizeof(off));
+    db->bround_views = true;
+    db->bround_cnt = o_cnt;
+    db->bround_max = o_max;
+    db->bround_arg = o_arg;
     db->bround_q = Q;
     db->vround_have = true;
     db->vround_union = counts[0];
@@ -3382,6 +3480,231 @@ int vq_db_view_round_union(vq_db* db, int64_t* n_union, int64_t* n_tiles) {
     if (!db->vround_have) return fail(VQ_E_STATE, "no view round has run on this handle");
     if (n_union) *n_union = db->vround_union;
     if (n_tiles) *n_tiles = db->vround_tiles;
+    return VQ_OK;
+}
+
+}  // extern "C"
+
+// ---- the weight fit and the re-weighting of a batched round's queries (include/vq_amd_round_fit.h) -----------------------------------
+static void batch_fit_layout(int Q, int G, int T, int64_t n_labels, int64_t off[8]) {
+    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
+    off[0] = 0;
+    off[1] = off[0] + up((int64_t)Q * G * 8 * 8);
+    off[2] = off[1] + up((int64_t)Q * T * 8);
+    off[3] = off[2] + up((int64_t)Q * 8);
+    off[4] = off[3] + up((int64_t)Q * 8);
+    off[5] = off[4] + up(n_labels * 8);
+    off[6] = off[5] + up(n_labels * 8);
+    off[7] = off[6] + up((int64_t)Q * G * T * 8);
+}
+
+static int batch_fit_shape(int Q, int G, int T, int64_t n_labels) {
+    VQ_REQUIRE(Q >= 1 && Q <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, Q);
+    VQ_REQUIRE(G >= 1 && G <= kFitMaxGrid && T >= 1 && T <= kFitMaxGrid, "the grids of a batched fit hold 1 to %d weights and thresholds (got %d, %d)",
+               kFitMaxGrid, G, T);
+    VQ_REQUIRE(n_labels >= 0, "n_labels must not be negative");
+    return VQ_OK;
+}
+
+extern "C" {
+
+int vq_db_batch_fit_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
+    if (rc != VQ_OK) return rc;
+    batch_fit_layout(n_queries, n_grid, n_thresholds, n_labels, off);
+    return VQ_OK;
+}
+
+int vq_db_batch_round_fit(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, void* block, int64_t block_bytes) {
+    VQ_REQUIRE(db && block, "NULL argument");
+    {
+        const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
+        if (rc != VQ_OK) return rc;
+    }
+    const int Q = n_queries, G = n_grid, T = n_thresholds;
+    int64_t off[8];
+    batch_fit_layout(Q, G, T, n_labels, off);
+    VQ_REQUIRE(block_bytes >= off[7], "the block of this batched fit needs %lld bytes (vq_db_batch_fit_layout), got %lld", (long long)off[7],
+               (long long)block_bytes);
+    char* host = (char*)block;
+    const int64_t* L = (const int64_t*)(host + off[3]);
+    const int64_t* rows = (const int64_t*)(host + off[4]);
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    FitBatchArgs a;
+    a.lstart[0] = 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        const int64_t lq = q < Q ? L[q] : 0;
+        VQ_REQUIRE(lq >= 0 && lq <= n_labels, "query %d: L = %lld outside [0, n_labels = %lld]", q, (long long)lq, (long long)n_labels);
+        if (lq > 0 && q >= db->bround_q) return fail(VQ_E_STATE, "the last batched round had %d queries (labels for query %d)", db->bround_q, q);
+        a.lstart[q + 1] = a.lstart[q] + lq;
+        a.qoff[q] = db->bround_qoff[q];
+    }
+    VQ_REQUIRE(a.lstart[kBatchSlots] == n_labels, "the L of the queries add up to %lld, n_labels is %lld", (long long)a.lstart[kBatchSlots], (long long)n_labels);
+    for (int q = 0; q < Q; ++q)
+        for (int64_t l = a.lstart[q]; l < a.lstart[q + 1]; ++l)
+            VQ_REQUIRE(rows[l] >= 0 && rows[l] < db->bround_m[q], "query %d: row %lld (label %lld) outside [0,%lld)", q, (long long)rows[l],
+                       (long long)(l - a.lstart[q]), (long long)db->bround_m[q]);
+    if (n_labels == 0) return VQ_OK;                  // every query skipped: nothing to launch
+    DeviceGuard g(db->device);
+    {
+        const int rc = ensure_grid_buf(db, off[7]);
+        if (rc != VQ_OK) return rc;
+    }
+    char* base = (char*)db->grid_buf;
+    VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[6], hipMemcpyHostToDevice, db->stream));      // grids | ballast | L | rows | labels: adjacent
+    a.avg = (const double*)(db->bround_dev + db->bround_off[4]);
+    a.w_grid = (const double*)(base + off[0]);
+    a.th_grid = (const double*)(base + off[1]);
+    a.ballast = (const double*)(base + off[2]);
+    a.rows = (const int64_t*)(base + off[4]);
+    a.labels = (const double*)(base + off[5]);
+    a.out = (double*)(base + off[6]);
+    a.G = G;
+    a.T = T;
+    a.S = db->S;
+    loss_surface_batch_kernel<<<dim3(G, Q), kFitThreads, 0, db->stream>>>(a);
+    VQ_CHECK_LAUNCH();
+    const int64_t cell = (int64_t)G * T * 8;
+    for (int q = 0; q < Q;) {                         // the surfaces of the queries served, adjacent ones in one copy
+        if (L[q] == 0) {
+            ++q;
+            continue;
+        }
+        int e = q;
+        while (e + 1 < Q && L[e + 1] > 0) ++e;
+        VQ_HIP(hipMemcpyAsync(host + off[6] + q * cell, base + off[6] + q * cell, (size_t)((e + 1 - q) * cell), hipMemcpyDeviceToHost, db->stream));
+        q = e + 1;
+    }
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    return VQ_OK;
+}
+
+int vq_db_batch_round_rescore(vq_db* db, int32_t mask, void* block, int64_t block_bytes, int32_t flags) {
+    VQ_REQUIRE(db && block, "NULL argument");
+    VQ_REQUIRE((flags & ~(VQ_BROUND_SCORES | VQ_BROUND_SELECT)) == 0, "flags: 2 = scores back, 4 = partition (got %d)", flags);
+    VQ_REQUIRE(mask > 0 && mask < (1 << kBatchSlots), "mask: bit q = query q of the round, at least one of %d (got %d)", kBatchSlots, mask);
+    const bool want_scores = flags & VQ_BROUND_SCORES, do_select = flags & VQ_BROUND_SELECT;
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    const int Q = db->bround_q;
+    if (mask >> Q) return fail(VQ_E_STATE, "the last batched round had %d queries (mask 0x%x)", Q, mask);
+    const int64_t* off = db->bround_off;
+    VQ_REQUIRE(block_bytes >= off[9], "the block of the last batched round needs %lld bytes, got %lld", (long long)off[9], (long long)block_bytes);
+    char* host = (char*)block;
+    auto in_mask = [&](int q) { return q < Q && ((mask >> q) & 1); };
+    int64_t max_m = 0;
+    for (int q = 0; q < Q; ++q)
+        if (in_mask(q)) max_m = std::max(max_m, db->bround_m[q]);
+    if (max_m == 0) {                                 // only empty views: nothing to launch
+        int64_t* res = (int64_t*)(host + off[6]);
+        for (int q = 0; q < Q; ++q)
+            if (in_mask(q) && do_select) {
+                res[4 * q] = res[4 * q + 1] = res[4 * q + 3] = 0;
+                res[4 * q + 2] = -1;
+                db->bround_n0[q] = db->bround_n1[q] = 0;
+            }
+        return VQ_OK;
+    }
+    DeviceGuard g(db->device);
+    const int64_t up_bytes = off[3] - off[1];         // weights | bands of the round's block: adjacent
+    {
+        const int rc = ensure_grid_buf(db, up_bytes);
+        if (rc != VQ_OK) return rc;
+    }
+    // staged beside the round's image, whose weights and bands of the other queries stay what the round saw
+    char* stage = (char*)db->grid_buf;
+    char* dev = db->bround_dev;
+    VQ_HIP(hipMemcpyAsync(stage, host + off[1], (size_t)up_bytes, hipMemcpyHostToDevice, db->stream));
+    const double* d_band = (const double*)(stage + (off[2] - off[1]));
+    {
+        RescoreBatchArgs a;
+        a.avg = (const double*)(dev + off[4]);
+        a.w = (const double*)stage;
+        a.scores = (double*)(dev + off[5]);
+        for (int q = 0; q < kBatchSlots; ++q) {
+            a.qoff[q] = db->bround_qoff[q];
+            a.m[q] = db->bround_m[q];
+        }
+        a.mask = (uint32_t)mask;
+        a.S = db->S;
+        const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
+        rescore_batch_kernel<<<dim3(bx, Q), 256, 0, db->stream>>>(a);
+        VQ_CHECK_LAUNCH();
+    }
+    int64_t start[kBatchSlots + 1];                   // the entries of query q: start[q] .. start[q + 1], for either kind of round
+    for (int q = 0; q < kBatchSlots; ++q) start[q] = db->bround_qoff[q];
+    start[kBatchSlots] = db->bround_qoff[kBatchSlots - 1] + db->bround_m[kBatchSlots - 1];
+    const int64_t P = off[10];
+    // per run [q0, q1] of adjacent masked queries: the view form of the batched selection kernels with the run's queries as its
+    // queries (a whole-database round is the view round whose pieces all have N rows), then the run's results in adjacent copies
+    for (int q0 = 0; q0 < Q;) {
+        if (!in_mask(q0)) {
+            ++q0;
+            continue;
+        }
+        int q1 = q0;
+        while (in_mask(q1 + 1)) ++q1;
+        const int nq = q1 - q0 + 1;
+        if (do_select) {
+            SelViewArgs sel;
+            bool any_small = false;
+            int max_nb = 0;
+            for (int i = 0; i <= kBatchSlots; ++i) {
+                const int q = std::min(q0 + i, kBatchSlots);
+                sel.start[i] = start[q];
+                sel.bstart[i] = db->bround_bstart[q];
+            }
+            for (int q = q0; q <= q1; ++q) {
+                any_small |= db->bround_m[q] <= kSelSmallN;
+                max_nb = std::max(max_nb, db->bround_bstart[q + 1] - db->bround_bstart[q]);
+            }
+            sel.b.scores = (const double*)(dev + off[5]);
+            sel.b.band = d_band + 2 * q0;
+            sel.b.n = 0;
+            sel.b.nblk = 0;
+            sel.b.blk_cnt = (int2*)(dev + db->bround_cnt);
+            sel.b.blk_max = (double*)(dev + db->bround_max);
+            sel.b.blk_arg = (int64_t*)(dev + db->bround_arg);
+            sel.b.result = (int64_t*)(dev + off[6]) + 4 * q0;
+            sel.b.out0 = (int64_t*)(dev + db->bround_rows0);
+            sel.b.out1 = (int64_t*)(dev + db->bround_rows1);
+            sel.b.pre0 = (int64_t*)(dev + off[7]) + q0 * P;
+            sel.b.pre1 = (int64_t*)(dev + off[8]) + q0 * P;
+            sel.b.prefix = P;
+            VQ_HIP(hipMemsetAsync(dev + off[6] + (int64_t)q0 * 32, 0, (size_t)nq * 32, db->stream));
+            if (any_small) {
+                select_small_view_kernel<<<nq, kSelSmallThreads, 0, db->stream>>>(sel);
+                VQ_CHECK_LAUNCH();
+            }
+            if (max_nb > 0) {
+                select_count_view_kernel<<<dim3(max_nb, nq), SEL_BLOCK, 0, db->stream>>>(sel);
+                VQ_CHECK_LAUNCH();
+                select_scan_view_kernel<<<nq, SEL_BLOCK, 0, db->stream>>>(sel);
+                VQ_CHECK_LAUNCH();
+                select_scatter_view_kernel<<<dim3(max_nb, nq), SEL_BLOCK, 0, db->stream>>>(sel);
+                VQ_CHECK_LAUNCH();
+            }
+        }
+        const int64_t s_lo = start[q0] * 8, s_len = (start[q1] + db->bround_m[q1]) * 8 - s_lo;
+        if (want_scores && s_len) VQ_HIP(hipMemcpyAsync(host + off[5] + s_lo, dev + off[5] + s_lo, (size_t)s_len, hipMemcpyDeviceToHost, db->stream));
+        if (do_select) {
+            VQ_HIP(hipMemcpyAsync(host + off[6] + (int64_t)q0 * 32, dev + off[6] + (int64_t)q0 * 32, (size_t)nq * 32, hipMemcpyDeviceToHost, db->stream));
+            for (int piece = 7; piece <= 8; ++piece)
+                VQ_HIP(hipMemcpyAsync(host + off[piece] + q0 * P * 8, dev + off[piece] + q0 * P * 8, (size_t)(nq * P * 8), hipMemcpyDeviceToHost, db->stream));
+        }
+        q0 = q1 + 1;
+    }
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    if (do_select) {
+        const int64_t* res = (const int64_t*)(host + off[6]);
+        for (int q = 0; q < Q; ++q)
+            if (in_mask(q)) {
+                db->bround_n0[q] = res[4 * q];
+                db->bround_n1[q] = res[4 * q + 1];
+            }
+    }
     return VQ_OK;
 }
 

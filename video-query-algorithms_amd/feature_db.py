@@ -651,6 +651,7 @@ class FeatureDB:
         if not 1 <= Q <= 16:
             call("vq_db_batch_round_layout", self._h, Q, (C.c_int64 * 12)())      # the library's own refusal (VqError)
         with self.lock:
+            self._bround_last = None                          # the round before is gone (its block may serve this one)
             blk, off = self._batch_round_block(Q)
             raw = blk.bytes()
             n, S = self.n, self.S
@@ -691,6 +692,8 @@ class FeatureDB:
                         call("vq_db_batch_round_fetch", self._h, q, _np_ptr(m) if nm else None, nm, _np_ptr(k) if nn else None, nn)
                         r.match_rows, r.near_rows = m, k
                 out.append(r)
+            # what batch_round_rescore lays its block out by, and the round's avg / n_e its results carry
+            self._bround_last = (Q, off, [q * n for q in range(Q + 1)], None, [(r.avg, r.n_e) for r in out])
             return out
 
     def query_round_batch_sets(self, targets: np.ndarray, weights: np.ndarray, set_ids, selects=None, want_avg: bool = True,
@@ -714,6 +717,7 @@ class FeatureDB:
         if bands is not None and bands.shape != (Q, 2):
             raise ValueError("selects must be [Q,2]: (threshold, lower) per query")
         with self.lock:
+            self._bround_last = None                          # the round before is gone (its block may serve this one)
             tokens = (C.c_int32 * max(Q, 1))()
             for q, sid in enumerate(set_ids):
                 if sid is not None and not self.has_search_set(sid):
@@ -776,6 +780,7 @@ class FeatureDB:
                         call("vq_db_batch_round_fetch", self._h, q, _np_ptr(mr) if nm else None, nm, _np_ptr(kr) if nn else None, nn)
                         r.match_rows, r.near_rows = mr, kr
                 out.append(r)
+            self._bround_last = (Q, off, start, pool, [(r.avg, r.n_e) for r in out])       # as after query_round_batch
             return out
 
     @property
@@ -791,6 +796,146 @@ class FeatureDB:
         ms = (C.c_float * 3)()
         call("vq_db_batch_round_times", self._h, ms)
         return tuple(float(v) for v in ms)
+
+    # ------------------------------------------------------------------ weight fits and re-weighting on a batched round's device data
+    def _pooled_block(self, name: str, nbytes: int) -> _RoundBlock:
+        """A page-locked block of at least ``nbytes`` from the pool ``name`` keeps by size (rounded up to 64 KiB)."""
+        pools = self.__dict__.setdefault(name, {})
+        nbytes = (max(nbytes, 1) + 65535) // 65536 * 65536
+        if nbytes not in pools and len(pools) >= 8:               # many sizes: the idle blocks of the old ones go
+            for size in list(pools):
+                old = pools.pop(size)
+                old["closed"] = True
+                while old["free"]:
+                    _lib.load().vq_host_free(C.c_void_p(old["free"].pop()[0]))
+        pool = pools.setdefault(nbytes, {"free": [], "closed": False})
+        if pool["free"]:
+            ptr, _ = pool["free"].pop()
+        else:
+            p = C.c_void_p()
+            call("vq_host_alloc", C.byref(p), nbytes)
+            ptr = p.value
+        return _RoundBlock(ptr, nbytes, pool)
+
+    def batch_round_fit(self, queries, rows, labels, w_grids, th_grids, ballasts) -> list:
+        """hyperparameter.py:57-64 for several queries of the LAST batched round (either kind) in one call and one launch
+        (vq_db_batch_round_fit, include/vq_amd_round_fit.h), on the averaged similarities that round left on the device.  Per entry
+        i: ``queries[i]`` the query's index in that round, ``rows[i]`` / ``labels[i]`` its labelled rows (positions in the query's
+        view, as in the round's results) and their labels, ``w_grids[i]`` [G,S], ``th_grids[i]`` [T] and ``ballasts[i]``; G and T are
+        common to the call.  Returns one [G,T] array per entry: the raw sums of :meth:`loss_surface` on the same similarities, bit
+        for bit, for any number of labels (the caller divides by it).  An entry without labels gets None."""
+        queries = [int(q) for q in queries]
+        k = len(queries)
+        if not (k and len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == k) or len(set(queries)) != k:
+            raise ValueError("one rows / labels / w_grid / th_grid / ballast per query, every query once")
+        wg = [np.asarray(w, dtype=np.float64) for w in w_grids]
+        th = [np.asarray(t, dtype=np.float64).reshape(-1) for t in th_grids]
+        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
+        G, T = int(wg[0].shape[0]), int(th[0].size)
+        if any(w.ndim != 2 or w.shape != (G, self.S) for w in wg) or any(t.size != T for t in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
+            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
+        if min(queries) < 0:
+            raise ValueError("a query is its index in the last batched round")
+        with self.lock:
+            Q = max(queries) + 1                              # slot q of the block = query q of the round; the library refuses what that round lacks
+            order = sorted(range(k), key=lambda i: queries[i])
+            total = int(sum(r.size for r in rs))
+            off = (C.c_int64 * 8)()
+            call("vq_db_batch_fit_layout", self._h, Q, G, T, total, off)
+            off = [int(v) for v in off]
+            blk = self._pooled_block("_fit_pools", off[7])
+            raw = blk.bytes()
+
+            def view(piece, dtype, shape):
+                count = int(np.prod(shape))
+                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            w_in, th_in, b_in, l_in = view(0, np.float64, (Q, G, 8)), view(1, np.float64, (Q, T)), view(2, np.float64, (Q,)), view(3, np.int64, (Q,))
+            r_in, y_in = view(4, np.int64, (total,)), view(5, np.float64, (total,))
+            w_in[...] = 0.0
+            th_in[...] = 0.0
+            b_in[...] = 0.0
+            l_in[...] = 0
+            at = 0
+            for i in order:
+                q = queries[i]
+                w_in[q, :, :self.S], th_in[q], b_in[q], l_in[q] = wg[i], th[i], float(ballasts[i]), rs[i].size
+                r_in[at:at + rs[i].size], y_in[at:at + rs[i].size] = rs[i], ys[i]
+                at += rs[i].size
+            call("vq_db_batch_round_fit", self._h, Q, G, T, total, C.c_void_p(blk.ptr), blk.nbytes)
+            surface = view(6, np.float64, (Q, G, T))
+            return [surface[queries[i]] if rs[i].size else None for i in range(k)]
+
+    def batch_round_rescore(self, queries, weights, selects=None) -> list:
+        """compute_matches.py:77 and ticket.py:311-356 for several queries of the LAST batched round (either kind) in one call
+        (vq_db_batch_round_rescore): query ``queries[i]`` of that round is rescored under ``weights[i]`` [S] on the averaged
+        similarities the round left on the device and, with ``selects`` [k,2] = (threshold, lower), partitioned again.  One
+        :class:`RoundResult` per entry: ``scores`` (the bits of :meth:`rescore` + :meth:`scores` on the same similarities),
+        ``match_rows`` / ``near_rows`` / ``near_argmax`` (those of :meth:`select` on them), ``avg`` and ``n_e`` the round's own.  The
+        round's other queries keep their scores and lists on the device."""
+        queries = [int(q) for q in queries]
+        k = len(queries)
+        w = np.asarray(weights, dtype=np.float64)
+        bands = None if selects is None else np.asarray(selects, dtype=np.float64)
+        if not k or len(set(queries)) != k or w.shape != (k, self.S) or (bands is not None and bands.shape != (k, 2)):
+            raise ValueError("weights must be [k,%d] and selects [k,2] for k distinct queries" % self.S)
+        if min(queries) < 0 or max(queries) >= 16:
+            raise ValueError("a query is its index in the last batched round")
+        flags = _lib.VQ_BROUND_SCORES | (_lib.VQ_BROUND_SELECT if bands is not None else 0)
+        with self.lock:
+            last = getattr(self, "_bround_last", None)
+            if last is None or max(queries) >= last[0]:
+                # no batched round, or a query it did not have: the library's own refusal (VQ_E_STATE), which reads nothing of the block
+                blk = self._pooled_block("_fit_pools", 64)
+                call("vq_db_batch_round_rescore", self._h, sum(1 << q for q in queries), C.c_void_p(blk.ptr), blk.nbytes, flags)
+                raise _lib.VqError(-4, "the last batched round does not have queries %r" % (queries,))
+            Q, off, start, pool, sims = last
+            if pool is None:
+                blk, _off = self._batch_round_block(Q)
+            else:
+                if pool["free"]:
+                    ptr, nbytes = pool["free"].pop()
+                else:
+                    p = C.c_void_p()
+                    nbytes = (off[9] + 65535) // 65536 * 65536
+                    call("vq_host_alloc", C.byref(p), nbytes)
+                    ptr = p.value
+                blk = _RoundBlock(ptr, nbytes, pool)
+            raw = blk.bytes()
+
+            def view(piece, dtype, shape, first=0):
+                count, size = int(np.prod(shape)), np.dtype(dtype).itemsize
+                lo = off[piece] + first * size
+                return raw[lo:lo + count * size].view(dtype).reshape(shape)
+            wv, bv = view(1, np.float64, (Q, 8)), view(2, np.float64, (Q, 2))
+            wv[...] = 0.0
+            bv[...] = 0.0
+            for i, q in enumerate(queries):
+                wv[q, :self.S] = w[i]
+                if bands is not None:
+                    bv[q] = bands[i]
+            call("vq_db_batch_round_rescore", self._h, sum(1 << q for q in queries), C.c_void_p(blk.ptr), blk.nbytes, flags)
+            res = view(6, np.int64, (Q, 4))
+            prefix = off[10]
+            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            out = []
+            for q in queries:
+                r = RoundResult()
+                r.avg, r.n_e = sims[q]
+                r.scores = view(5, np.float64, (start[q + 1] - start[q],), start[q])
+                r.match_rows = r.near_rows = None
+                r.near_argmax = -1
+                if bands is not None:
+                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
+                    if nm <= prefix and nn <= prefix:
+                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
+                    else:                                     # a list longer than its prefix: the full lists are still on the device
+                        mr = np.empty(nm, dtype=np.int64)
+                        kr = np.empty(nn, dtype=np.int64)
+                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(mr) if nm else None, nm, _np_ptr(kr) if nn else None, nn)
+                        r.match_rows, r.near_rows = mr, kr
+                out.append(r)
+            return out
 
     def rescore(self, weights: Sequence[float]):
         w = np.ascontiguousarray(weights, dtype=np.float64)
@@ -882,7 +1027,8 @@ class FeatureDB:
     def close(self):
         if self._h:
             pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()] + \
-                list(getattr(self, "_view_round_pools", {}).values())
+                list(getattr(self, "_view_round_pools", {}).values()) + list(getattr(self, "_fit_pools", {}).values())
+            self._bround_last = None
             for pool in pools:
                 if pool is None:
                     continue

@@ -75,12 +75,17 @@ class Hyperparameter:
 
     def _pick(self, ticket, surface):
         """Weights and threshold from the loss surface (hyperparameter.py:66-76)."""
-        iw, it = np.unravel_index(np.argmin(surface), surface.shape)                # first minimum, row-major
         ticket.compute_scores({self.streams[0]: 1.0, self.streams[1]: self.weight_grid[-1]})   # what the 40 passes leave
+        self.weights, self.threshold = self._pick_from(surface)
+
+    def _pick_from(self, surface):
+        """(weights, threshold) of the loss surface's minimum (hyperparameter.py:66-76): the first minimum in row-major order, refined
+        unless it lies on the rim of the grid.  Touches neither the ticket nor this object, so the surfaces of several tickets can be
+        picked before any of them is finished (ticket.compute_similarities_batch(..., fit=...))."""
+        iw, it = np.unravel_index(np.argmin(surface), surface.shape)                # first minimum, row-major
         on_rim = iw in (0, len(self.weight_grid) - 1) or it in (0, len(self.threshold_grid) - 1)
         w_best, th_best = (self.weight_grid[iw], self.threshold_grid[it]) if on_rim else self._refine(surface, iw, it)
-        self.weights = {self.streams[0]: 1.0, self.streams[1]: w_best}
-        self.threshold = th_best - float(os.environ["COMPUTE_EPS"])                 # hyperparameter.py:5,75
+        return {self.streams[0]: 1.0, self.streams[1]: w_best}, th_best - float(os.environ["COMPUTE_EPS"])     # hyperparameter.py:5,75
 
     @staticmethod
     def _labelled_rows(ticket):

@@ -130,6 +130,8 @@ class TicketScoring:
     _round = None                            # token of this ticket's latest compute_similarities (see _own_similarities)
     _score_weights = None
     _view = None                             # the search-set view this round is bound to (feature_db.SearchSetView)
+    _fit = None                              # (weights, threshold) fitted behind a batched pass (compute_similarities_batch(fit=))
+    _fit_round = None                        # the _round token that fit belongs to
     feature_db_dtype = np.float64            # dtype used when the DB is built from API records
     device = 0
 
@@ -349,23 +351,9 @@ def _batchable(ticket, hyperparameters, share_search_sets=False):
     return db, stream_names, t, slot_used, ahead
 
 
-def _batched_pass(group):
-    """One pass for up to BATCH_PASS tickets that share a database object and a slot mask: what compute_similarities does for each,
-    the look-ahead scores and partition included."""
-    db, slot_used = group[0][2][0], group[0][2][3]
-    targets = np.stack([g[2][2] for g in group])
-    weights = np.stack([g[2][4][0] for g in group])
-    bands = np.array([[g[2][4][1], g[2][4][2]] for g in group], dtype=np.float64)
-    for tk, _hp, _prep in group:
-        tk._ahead = None
-    with _db_lock(db):
-        views = [tk._bind_view(db) for tk, _hp, _prep in group]       # the whole database: no set is defined for any of them
-        db.restrict_slots(slot_used)                                  # once per group
-        results = db.query_round_batch(targets, weights, bands, want_avg=True)
-        # the handle's one-query state is nobody's round now: a later device-side step of any of these tickets puts its
-        # similarities back first (_own_similarities / _own_scores)
-        db.sims_owner = db.scores_owner = None
-    for (tk, hp, prep), view, r in zip(group, views, results):
+def _adopt(group, views, results):
+    """Every member of a pass gets the attributes its own compute_similarities sets, from its result of the pass."""
+    for (tk, hp, prep, _fit), view, r in zip(group, views, results):
         _db, stream_names, _t, _used, (w, th, lower) = prep
         tk._round = object()
         tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": (th, lower), "match_rows": r.match_rows,
@@ -376,6 +364,71 @@ def _batched_pass(group):
         tk._stream_gap = None
         tk._view = view
         tk.similarities = SimilarityMap(view.clip_ids, stream_names, r.avg, r.n_e, view.row_of)
+
+
+def _fit_group(db, group):
+    """The weight update of the members with ``fit`` set (hyperparameter.py:29-76, then compute_matches.py:77-88) on the averaged
+    similarities their pass left on the device: ONE ``batch_round_fit`` for the loss surfaces of all of them, the pick on the host
+    (``Hyperparameter._pick_from``), ONE ``batch_round_rescore`` under the fitted weights and the review band of the fitted
+    threshold.  Such a ticket ends with ``_fit`` = (weights, threshold) for this round and ``_ahead`` = the rescore's scores and
+    partition.  A member without labelled clips, with a label on an unknown clip (optimize_weights raises that in its own place) or
+    with grids of another size than the first one's stays as the pass left it; so does every member on a database without the two
+    methods.  Call behind the group's own pass with the database's lock still held: the next pass on the handle replaces what this
+    reads."""
+    if not (hasattr(db, "batch_round_fit") and hasattr(db, "batch_round_rescore")):
+        return
+    members = []
+    for q, (tk, hp, prep, fit) in enumerate(group):
+        if not fit or not hasattr(hp, "_pick_from"):
+            continue
+        try:
+            rows, labels = hp._labelled_rows(tk)
+            first, second = (prep[1].index(st) for st in hp.streams[:2])
+        except (KeyError, ValueError):
+            continue
+        if not rows or (members and (len(hp.weight_grid), len(hp.threshold_grid)) != members[0][5].shape[:1] + members[0][6].shape):
+            continue
+        candidates = np.zeros((len(hp.weight_grid), db.S))
+        candidates[:, first], candidates[:, second] = 1.0, hp.weight_grid
+        members.append((q, tk, hp, rows, [float(v) for v in labels], candidates, np.asarray(hp.threshold_grid, dtype=np.float64)))
+    if not members:
+        return
+    surfaces = db.batch_round_fit([m[0] for m in members], [m[3] for m in members], [m[4] for m in members], [m[5] for m in members],
+                                  [m[6] for m in members], [m[2].ballast for m in members])
+    fits, weights, bands = [], [], []
+    for (q, tk, hp, rows, labels, _cand, _ths), surface in zip(members, surfaces):
+        picked, th = hp._pick_from(np.asarray(surface) / len(labels))
+        w = np.zeros(db.S, dtype=np.float64)                          # as compute_scores builds it from the dict
+        for stream_type, ws in picked.items():
+            w[tk._stream_names.index(stream_type)] = ws
+        fits.append((picked, th))
+        weights.append(w)
+        bands.append((float(th), float(th) - float(hp.near_miss_default) * (1 - float(th))))       # _review_band's expression
+    results = db.batch_round_rescore([m[0] for m in members], np.stack(weights), np.array(bands, dtype=np.float64))
+    for (q, tk, _hp, _rows, _labels, _cand, _ths), fit, w, band, r in zip(members, fits, weights, bands, results):
+        tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": band, "match_rows": r.match_rows, "near_rows": r.near_rows,
+                     "near_argmax": r.near_argmax}
+        tk._fit, tk._fit_round = fit, tk._round
+
+
+def _batched_pass(group):
+    """One pass for up to BATCH_PASS tickets that share a database object and a slot mask: what compute_similarities does for each,
+    the look-ahead scores and partition included."""
+    db, slot_used = group[0][2][0], group[0][2][3]
+    targets = np.stack([g[2][2] for g in group])
+    weights = np.stack([g[2][4][0] for g in group])
+    bands = np.array([[g[2][4][1], g[2][4][2]] for g in group], dtype=np.float64)
+    for tk, _hp, _prep, _fit in group:
+        tk._ahead = None
+    with _db_lock(db):
+        views = [tk._bind_view(db) for tk, _hp, _prep, _fit in group]       # the whole database: no set is defined for any of them
+        db.restrict_slots(slot_used)                                  # once per group
+        results = db.query_round_batch(targets, weights, bands, want_avg=True)
+        # the handle's one-query state is nobody's round now: a later device-side step of any of these tickets puts its
+        # similarities back first (_own_similarities / _own_scores)
+        db.sims_owner = db.scores_owner = None
+        _adopt(group, views, results)
+        _fit_group(db, group)                                         # fit=: behind its own pass, in the same hold of the lock
 
 
 def _set_of(db, ticket):
@@ -391,25 +444,16 @@ def _shared_sets_pass(group):
     targets = np.stack([g[2][2] for g in group])
     weights = np.stack([g[2][4][0] for g in group])
     bands = np.array([[g[2][4][1], g[2][4][2]] for g in group], dtype=np.float64)
-    for tk, _hp, _prep in group:
+    for tk, _hp, _prep, _fit in group:
         tk._ahead = None
     with _db_lock(db):
-        set_ids = [_set_of(db, tk) for tk, _hp, _prep in group]
+        set_ids = [_set_of(db, tk) for tk, _hp, _prep, _fit in group]
         views = [db.search_set_view(sid) for sid in set_ids]          # the view objects: the set the handle has in use stays
         db.restrict_slots(slot_used)                                  # once per group
         results = db.query_round_batch_sets(targets, weights, set_ids, bands, want_avg=True)
         db.sims_owner = db.scores_owner = None                        # as after _batched_pass: nobody's round
-    for (tk, hp, prep), view, r in zip(group, views, results):
-        _db, stream_names, _t, _used, (w, th, lower) = prep
-        tk._round = object()
-        tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": (th, lower), "match_rows": r.match_rows,
-                     "near_rows": r.near_rows, "near_argmax": r.near_argmax}
-        tk._hp = hp
-        tk._stream_names = stream_names
-        tk._avg, tk._n_e = r.avg, r.n_e
-        tk._stream_gap = None
-        tk._view = view
-        tk.similarities = SimilarityMap(view.clip_ids, stream_names, r.avg, r.n_e, view.row_of)
+        _adopt(group, views, results)
+        _fit_group(db, group)                                         # fit=: behind its own pass, in the same hold of the lock
 
 
 def _flush(group):
@@ -417,7 +461,7 @@ def _flush(group):
     round when it is alone.  With them (share_search_sets): one pass over the union if the sharing rule holds, else the search-set
     members' own rounds in list order and the whole-database members as a group of today's kind."""
     db = group[0][2][0]
-    set_ids = [_set_of(db, tk) for tk, _hp, _prep in group]
+    set_ids = [_set_of(db, tk) for tk, _hp, _prep, _fit in group]
     if any(sid is not None for sid in set_ids):
         n = len(db.clip_ids)
         sizes = {sid: db.search_set_view(sid).n for sid in set(set_ids) if sid is not None}
@@ -426,7 +470,7 @@ def _flush(group):
         if len(group) > 1 and total >= SHARE_SETS_FACTOR * distinct:
             _shared_sets_pass(group)
             return
-        for (tk, hp, _prep), sid in zip(group, set_ids):
+        for (tk, hp, _prep, _fit), sid in zip(group, set_ids):
             if sid is not None:
                 tk.compute_similarities(hp)
         group = [g for g, sid in zip(group, set_ids) if sid is None]
@@ -438,7 +482,7 @@ def _flush(group):
         _batched_pass(group)
 
 
-def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False):
+def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False, fit=None):
     """``compute_similarities`` for a list of tickets, those that can sharing passes over their resident database: a broker with
     several pending tickets pays one read of the database per 16 of them instead of one each.  ``hyperparameters`` is one object or
     one per ticket.  Every ticket ends with exactly the attributes its own ``compute_similarities`` sets (``similarities``, ``_avg``,
@@ -456,20 +500,32 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     joins its group too, keyed as ever.  A group with such members runs ONE pass over the union of the members' sets when
     sum M_q >= SHARE_SETS_FACTOR * distinct (see the constant); otherwise its search-set members run their own rounds in list order
     and its whole-database members share a pass as above.  After a shared pass every member has the attributes its own
-    ``compute_similarities`` sets, ``_view`` = its set's view and rows as positions in it."""
+    ``compute_similarities`` sets, ``_view`` = its set's view and rows as positions in it.
+
+    ``fit``: one boolean per ticket.  The members of a pass with ``fit[i]`` true and at least one labelled clip (``ticket.matches``,
+    read by ``Hyperparameter._labelled_rows``) get their weight update right behind the pass, on the similarities it left on the
+    device (``_fit_group``): one ``batch_round_fit`` and one ``batch_round_rescore`` for the whole group instead of every ticket's
+    ``write_avg``, ``loss_surface`` and two ``query_round`` calls.  Such a ticket ends with ``_fit`` = (weights dict, threshold) for
+    this round -- what ``optimize_weights`` would set on its hyperparameters object, on the pass's own similarities -- and with
+    ``_ahead`` rebuilt under those weights and the review band of that threshold, so ``compute_scores(weights)`` and
+    ``select_clips_to_review(threshold, ., near_miss_default)`` ask the device for nothing.  Every other ticket is unchanged and its
+    caller runs ``optimize_weights``: one that ran its own round, one on a database without the two methods, one without labels."""
     tickets = list(tickets)
+    fits = [False] * len(tickets) if fit is None else [bool(f) for f in fit]
+    if len(fits) != len(tickets):
+        raise ValueError("fit: one boolean per ticket")
     hps = list(hyperparameters) if isinstance(hyperparameters, (list, tuple)) else [hyperparameters] * len(tickets)
     if len(hps) != len(tickets):
         raise ValueError("one hyperparameters object, or one per ticket")
     pending = {}                                          # (database object, slot mask) -> the tickets waiting for a pass, in list order
-    for tk, hp in zip(tickets, hps):
+    for tk, hp, want_fit in zip(tickets, hps, fits):
         prep = _batchable(tk, hp, share_search_sets)
         if prep is None:
             tk.compute_similarities(hp)
             continue
         key = (id(prep[0]), prep[3].tobytes())
         group = pending.setdefault(key, [])
-        group.append((tk, hp, prep))
+        group.append((tk, hp, prep, want_fit))
         if len(group) == BATCH_PASS:
             _flush(pending.pop(key))
     for group in pending.values():
@@ -591,10 +647,10 @@ def install(ticket_cls, hyperparameter_cls=None, target_clip_cls=None):
                  "_own_similarities", "_own_scores", "_look_ahead", "_bind_view"):
         setattr(ticket_cls, name, getattr(TicketScoring, name))
     ticket_cls._review_band = staticmethod(TicketScoring._review_band)
-    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap", "_view"):
+    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap", "_view", "_fit", "_fit_round"):
         if not hasattr(ticket_cls, name):
             setattr(ticket_cls, name, getattr(TicketScoring, name))
     if hyperparameter_cls is not None:
         from .hyperparameter import Hyperparameter
-        for name in ("optimize_weights", "_labelled_rows", "_refine", "_pick"):
+        for name in ("optimize_weights", "_labelled_rows", "_refine", "_pick", "_pick_from"):
             setattr(hyperparameter_cls, name, Hyperparameter.__dict__[name])
