@@ -606,4 +606,5 @@ int vq_broadcast_query(vq_comm* comm, void* buf_dev, int64_t bytes, int32_t root
 #include "vq_amd_rounds.h"    /* batched query rounds: up to 16 tickets per pass over a resident database (additive to ABI 12) */
 #include "vq_amd_round_views.h" /* the same with a row view (search set) per query: one pass over the union (additive to ABI 12) */
 #include "vq_amd_round_fit.h" /* the weight fit and the re-weighting of a batched round's tickets on its device data (additive to ABI 12) */
+#include "vq_amd_round_targets.h" /* the bootstrapped targets of a group of tickets, every draw of every pool in one call (additive to ABI 12) */
 #endif /* VQ_AMD_H */

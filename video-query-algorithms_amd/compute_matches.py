@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import os
 
-from .target_clip import TargetClip
+from .target_clip import TargetClip, solve_targets_batch
 
 _IN_PROGRESS, _PROCESSED, _ERROR, _FINALIZED = 3, 4, 5, 7      # process states, compute_matches.py:42,50,104,107
 
@@ -46,9 +46,10 @@ def _review_budget(kind, tk, hp):
     return float("inf"), reach
 
 
-def _begin_update(kind, update, url, hp, ticket_factory, target_factory):
+def _begin_update(kind, update, url, hp, ticket_factory, target_factory, plan_only=False):
     """Phase 1 of a round: the ticket, process state 3, the consistency checks (:47-52) and the target's features (:55-56).  Returns
-    the ticket, or None when the round ended with a fatal error."""
+    the ticket, or None when the round ended with a fatal error.  ``plan_only``: a target that can plan its round
+    (``plan_target_features``: the REST requests and the draws) does just that; the caller solves the planned targets together."""
     tk = ticket_factory(update, url)
     tk.change_process_state(_IN_PROGRESS)
     fatal, warning = tk.catch_errors(kind)                                  # :47-52
@@ -59,7 +60,10 @@ def _begin_update(kind, update, url, hp, ticket_factory, target_factory):
         tk.add_note(warning)
 
     tk.target = target_factory(tk, hp)                                      # :55-58
-    tk.target.get_target_features()
+    if plan_only and hasattr(tk.target, "plan_target_features"):
+        tk.target.plan_target_features()
+    else:
+        tk.target.get_target_features()
     return tk
 
 
@@ -93,7 +97,7 @@ def _one_update(kind, update, url, hp, ticket_factory, target_factory):
 
 
 def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False, share_search_sets=False,
-                    fit_weights=False):
+                    fit_weights=False, batch_targets=False):
     """One broker pass.  ``batch=True`` runs it in three phases so that the pending tickets share passes over their resident database
     (``ticket.compute_similarities_batch``): (1) every pending update gets its ticket, process state 3, its checks and its target
     features; (2) ONE ``compute_similarities_batch`` over the tickets that survived; (3) every ticket is finished in the original
@@ -112,9 +116,18 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     similarities).  Two differences: between the fit and ``compute_scores`` ``ticket.scores`` is not left at the last grid weight
     (compute_matches.py:77 overwrites it on the next line), and a finalize ticket's scores come back with the group's while its
     review band -- which depends on ``lowest_scoring_user_match`` under the fitted scores -- is still partitioned by its own
-    ``select``."""
+    ``select``.
+    ``batch_targets=True`` (with ``batch``; ``ValueError`` without): phase 1 only PLANS every ticket's target (the REST requests and the
+    draws from ``random``, at the same place and in the same order as ever), and one ``target_clip.solve_targets_batch`` in front of
+    the pass solves them: the tickets with ``dynamic_target_adjustment`` whose validated clips are rows of one resident database get
+    every draw of their bootstrapping in ONE ``FeatureDB.batch_targets`` call per 16 tickets instead of one call per draw.  Per
+    ticket the ledger, the consumption of ``random``, ``target_features``, weights, threshold and matches are those of
+    ``batch=True`` bit for bit.  One difference: a solve that raises (a singular system, a key the previous target lacks) does so
+    after every ticket of the pass has been planned, not in the middle of phase 1."""
     if fit_weights and not batch:
         raise ValueError("fit_weights=True needs batch=True: the fit runs behind a batched pass")
+    if batch_targets and not batch:
+        raise ValueError("batch_targets=True needs batch=True: the targets are solved together in front of a batched pass")
     pending = query_updates.get_status()                                    # :34
     if ticket_factory is None:
         from .ticket import Ticket as _Ticket
@@ -132,9 +145,11 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     started = []
     for kind, update in pending.items():
         if update is not None:
-            tk = _begin_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory)
+            tk = _begin_update(kind, update, query_updates.url, hyperparameters, ticket_factory, target_factory, plan_only=batch_targets)
             if tk is not None:
                 started.append((kind, update, tk))
+    if batch_targets:
+        solve_targets_batch([tk.target for _kind, _update, tk in started])
     fit = [fit_weights and kind in ("revise", "finalize") and bool(update["matches"]) for kind, update, _tk in started]
     compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets,
                                **({"fit": fit} if fit_weights else {}))

@@ -76,6 +76,13 @@ struct vq_db {
     int64_t vround_union = 0, vround_tiles = 0;
     double* grid_buf = nullptr;      // scratch for grid / gathers
     int64_t grid_cap = 0;
+    // Batched targets (vq_db_batch_targets, include/vq_amd_round_targets.h; csrc/vq_round_targets.hip): the image of the call's block |
+    // the pools' Gram matrices | the coefficients of every draw | a status per (draw, slot), and the scratch area of the draws whose
+    // systems do not fit into local memory.  Both grow on demand and go with the handle.
+    char* targets_buf = nullptr;
+    int64_t targets_cap = 0;         // bytes
+    double* targets_ws = nullptr;
+    int64_t targets_ws_cap = 0;      // bytes
     // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over
     // (-1: the whole database) and `na` the number of clips it then covers -- M, or N: what every result-side entry point counts with.
     struct RowView {
@@ -91,3 +98,12 @@ struct vq_db {
     int64_t na = 0;
     size_t elem() const { return dtype == VQ_F64 ? 8 : dtype == VQ_F16 ? 2 : 4; }
 };
+
+namespace vq {
+
+// csrc/vq_sim.hip: rows (by number) -> a dense row-major [L][S][E][D] block in the handle's gather scratch, whatever the layout; the
+// caller holds the handle's lock and has its device current.  rows_dev: the same L row numbers already on the device (ordered on the
+// handle's stream) -- they are then read there and nothing is uploaded.  Shared with csrc/vq_round_targets.hip.
+int gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense, const int64_t* rows_dev = nullptr);
+
+}  // namespace vq

@@ -1953,7 +1953,8 @@ static void round_layout(int64_t n, int S, int64_t off[8]) {
 static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);
     void* ptrs[] = {db->present, db->t,       db->sims,  db->round_dev, db->blk_cnt,
-                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev, db->vround_plan};
+                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev, db->vround_plan,
+                    db->targets_buf, db->targets_ws};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t ev : db->bround_ev)
@@ -1966,20 +1967,21 @@ static int db_free(vq_db* db) {
 static int ensure_grid_buf(vq_db* db, int64_t bytes);
 
 // rows (by number) -> a dense row-major [L][S][E][D] block in the handle's scratch, whatever the layout; caller holds the lock
-static int gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense) {
+int vq::gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense, const int64_t* rows_dev) {
     const int64_t row_bytes = (int64_t)db->S * db->E * db->D * (int64_t)db->elem();      // D % 4 == 0: whole 16-byte pieces (fp16: 8-byte)
     const int64_t rb = ((int64_t)L * 8 + 15) / 16 * 16;
     const int rc = ensure_grid_buf(db, rb + (int64_t)L * row_bytes);
     if (rc != VQ_OK) return rc;
     char* base = (char*)db->grid_buf;
-    VQ_HIP(hipMemcpyAsync(base, rows_host, (size_t)L * 8, hipMemcpyHostToDevice, db->stream));
+    if (!rows_dev) VQ_HIP(hipMemcpyAsync(base, rows_host, (size_t)L * 8, hipMemcpyHostToDevice, db->stream));
+    const int64_t* rows = rows_dev ? rows_dev : (const int64_t*)base;
     const bool tiled = db->layout == VQ_LAYOUT_TILED;
     if (row_bytes % 16) {
         const int64_t vec = row_bytes / 8;
-        gather_rows_kernel<uint2><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint2*)db->feats, (const int64_t*)base, L, vec, (uint2*)(base + rb), 0, 0);
+        gather_rows_kernel<uint2><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint2*)db->feats, rows, L, vec, (uint2*)(base + rb), 0, 0);
     } else {
         const int64_t vec = row_bytes / 16;
-        gather_rows_kernel<uint4><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint4*)db->feats, (const int64_t*)base, L, vec, (uint4*)(base + rb),
+        gather_rows_kernel<uint4><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint4*)db->feats, rows, L, vec, (uint4*)(base + rb),
                                                                                       tiled ? db->S * db->E : 0, db->D / 4);
     }
     VQ_CHECK_LAUNCH();

@@ -866,6 +866,84 @@ class FeatureDB:
             surface = view(6, np.float64, (Q, G, T))
             return [surface[queries[i]] if rs[i].size else None for i in range(k)]
 
+    # ------------------------------------------------------------------ the bootstrapped targets of a group of tickets
+    def batch_targets_lds_rows(self) -> int:
+        """The largest draw (rows) whose systems ``batch_targets`` solves in a workgroup's local memory; longer draws solve in a
+        scratch area in device memory (the library's constant, read through vq_db_batch_targets_layout)."""
+        off = (C.c_int64 * 11)()
+        call("vq_db_batch_targets_layout", self._h, 1, 1, 1, 1, off)
+        return int(off[10])
+
+    def batch_targets(self, pools, draws, mus, previous=None, keeps=None) -> list:
+        """Target bootstrapping (target_clip.py:26-82) for up to 16 queries in ONE call (vq_db_batch_targets,
+        include/vq_amd_round_targets.h).  Per query q: ``pools[q]`` = (valid_rows, invalid_rows), the database rows of its validated
+        matches and non-matches; ``draws[q]`` = a list of (picked_valid, picked_invalid), positions into those two lists in the row
+        order of the problem (``target_clip.draw_indices``); ``mus[q]``; and, to blend, ``previous[q]`` [S,E,D] with ``keeps[q]``
+        (target = keep * target + (1 - keep) * previous).  Returns one [S,E,D] array per query: the mean over its draws of what
+        :meth:`bootstrap_target` gives on each draw's rows, bit for bit (numpy's mean over axis 0; one draw: that draw's target).
+        A singular system in a query raises ``VqError`` (VQ_E_INVALID) for the first such query, naming it; the handle's query,
+        scores, last batched round and search set in use are left alone."""
+        status, targets = self._batch_targets_raw(pools, draws, mus, previous, keeps)
+        for q in range(len(targets)):
+            if status[q, 0] != 0:
+                raise _lib.VqError(-1, "query %d, draw %d: problem %d: singular system (linearly dependent validated clips) -- numpy.linalg.inv "
+                                   "raises here too" % (q, int(status[q, 1]), int(status[q, 2])))
+        return targets
+
+    def _batch_targets_raw(self, pools, draws, mus, previous=None, keeps=None):
+        """:meth:`batch_targets` up to the library's answer: (status [Q,4] int32 -- 0 solved / 1 singular, the first failing draw, its
+        slot -- and the list of [S,E,D] targets; the target of a query with a status holds no result)."""
+        Q = len(pools)
+        if not Q or len(draws) != Q or len(mus) != Q or (previous is not None and len(previous) != Q) or (keeps is not None and len(keeps) != Q):
+            raise ValueError("one pool, one list of draws and one mu per query (and one previous / keep when given)")
+        valid = [np.asarray(p[0], dtype=np.int64).reshape(-1) for p in pools]
+        invalid = [np.asarray(p[1], dtype=np.int64).reshape(-1) for p in pools]
+        picks = [[(np.asarray(pv, dtype=np.int32).reshape(-1), np.asarray(pi, dtype=np.int32).reshape(-1)) for pv, pi in ds] for ds in draws]
+        before = [None if previous is None or previous[q] is None else np.asarray(previous[q], dtype=np.float64) for q in range(Q)]
+        if any(b is not None and b.shape != (self.S, self.E, self.D) for b in before):
+            raise ValueError("previous targets must be [%d,%d,%d]" % (self.S, self.E, self.D))
+        if any(b is not None and (keeps is None or keeps[q] is None) for q, b in enumerate(before)):
+            raise ValueError("a previous target needs its keep")
+        n_rows = int(sum(v.size + i.size for v, i in zip(valid, invalid)))
+        n_draws = int(sum(len(ds) for ds in picks))
+        n_entries = int(sum(pv.size + pi.size for ds in picks for pv, pi in ds))
+        with self.lock:
+            off = (C.c_int64 * 11)()
+            call("vq_db_batch_targets_layout", self._h, Q, n_rows, n_draws, n_entries, off)
+            off = [int(v) for v in off]
+            blk = self._pooled_block("_target_pools", off[9])
+            raw = blk.bytes()
+
+            def view(piece, dtype, shape):
+                count = int(np.prod(shape))
+                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            q_in, p_in = view(0, np.int32, (Q, 8)), view(1, np.float64, (Q, 4))
+            r_in, d_in, e_in = view(2, np.int64, (n_rows,)), view(3, np.int32, (n_draws, 2)), view(4, np.int32, (n_entries,))
+            prev_in = view(6, np.float64, (Q, self.S, self.E, self.D))
+            q_in[...] = 0
+            p_in[...] = 0.0
+            r_at = d_at = e_at = 0
+            for q in range(Q):
+                m, n = valid[q].size, invalid[q].size
+                q_in[q, :4] = (m + n, m, len(picks[q]), 0 if before[q] is None else 1)
+                p_in[q, 0] = float(mus[q])
+                if before[q] is not None:
+                    keep = keeps[q]
+                    p_in[q, 1], p_in[q, 2] = keep, (1 - keep)
+                    prev_in[q] = before[q]
+                r_in[r_at:r_at + m], r_in[r_at + m:r_at + m + n] = valid[q], invalid[q]
+                r_at += m + n
+                for pv, pi in picks[q]:
+                    d_in[d_at] = (pv.size + pi.size, pv.size)
+                    e_in[e_at:e_at + pv.size] = pv
+                    e_in[e_at + pv.size:e_at + pv.size + pi.size] = pi + m
+                    d_at += 1
+                    e_at += pv.size + pi.size
+            call("vq_db_batch_targets", self._h, Q, n_rows, n_draws, n_entries, C.c_void_p(blk.ptr), blk.nbytes)
+            status = view(7, np.int32, (Q, 4))
+            target = view(8, np.float64, (Q, self.S, self.E, self.D))
+            return status, [target[q] for q in range(Q)]
+
     def batch_round_rescore(self, queries, weights, selects=None) -> list:
         """compute_matches.py:77 and ticket.py:311-356 for several queries of the LAST batched round (either kind) in one call
         (vq_db_batch_round_rescore): query ``queries[i]`` of that round is rescored under ``weights[i]`` [S] on the averaged

@@ -12,7 +12,10 @@ What ``compute_matches`` and ``Ticket`` read from the object is kept -- ``Target
   target_clip.py:297-309 so that a seeded broker picks the same clips), and every (draw, stream, split) problem of
   the round is solved by ONE launch of the closed-form kernel (csrc/vq_boot.hip: Gram matrix + Woodbury instead of
   the 1024 x 1024 inverses of target_clip.py:192-197 / :245-260);
-* bagging averages the draws, ``partial_update`` blends with the previous round's target (target_clip.py:75-82).
+* bagging averages the draws, ``partial_update`` blends with the previous round's target (target_clip.py:75-82);
+* a round is PLANNED (REST, draws) and then SOLVED: alone (``get_target_features``), or with the planned rounds of the other tickets
+  of a broker pass whose clips are rows of the same resident database (:func:`solve_targets_batch`: one
+  ``FeatureDB.batch_targets`` call for up to 16 tickets instead of one call per draw).
 
 SURVEY.md 8(a) row B1 (``t = r / (r . r)`` of the reference clip, target_clip.py:137-143, :263-286, :311-313) is
 the no-adjustment case; 8(f) row 1 is the rest.
@@ -89,45 +92,74 @@ class TargetClip:
         self.previous_target_features = earlier or None
         self.ref_clip_features, self.splits = self._get_clip_features(ticket.ref_clip_id)
         self.target_features: dict = {}
+        self._planned = None                 # (kind, valid pool, invalid pool, draws) between plan_target_features and the solve
 
     # ------------------------------------------------------------------ the seam
     def get_target_features(self):
-        """Sets ``self.target_features`` for this round (decision ladder of target_clip.py:26-73)."""
+        """Sets ``self.target_features`` for this round (decision ladder of target_clip.py:26-73): the round is planned, then solved
+        on its own.  ``compute_matches(batch_targets=True)`` plans every ticket's target first and solves the planned ones of a group
+        in one call (:func:`solve_targets_batch`)."""
+        if self.plan_target_features():
+            self.solve_planned_target()
+
+    def plan_target_features(self) -> bool:
+        """Everything of the round that talks to the API or draws from ``random``, in the order of the reference: the validated
+        clips (REST), the check of ``bootstrap_type``, the draws of the adjustment mode.  Without validated matches the target is the
+        scaled reference clip and nothing is left to do (False); otherwise the round's problems are kept on the object until
+        ``solve_planned_target`` or ``solve_targets_batch`` solves them (True)."""
+        self._planned = None
         pools = self._validated_pools() if self.bootstrap_target and self.latest_query_result is not None else None
         if not pools or not len(pools[0]):
             self.target_features = self.scaled_ref_clip_features()
-            return
-        kind = self.hyperparameters.bootstrap_type
+            return False
+        hp = self.hyperparameters
+        kind = hp.bootstrap_type
         if kind not in ADJUSTMENTS:
             raise Exception("Error: bootstrap_type should be one of 'simple', 'partial_update', or 'bagging'")
-        getattr(self, "_adjust_" + kind)(*pools)
+        valid, invalid = pools
+        if kind == "bagging":
+            draws = [self._draw(valid, invalid, 1, True) for _ in range(hp.nbags)]
+        else:
+            draws = [self._draw(valid, invalid, hp.f_bootstrap, False)]
+        self._planned = (kind, valid, invalid, draws)
+        return True
+
+    def solve_planned_target(self):
+        """The planned round solved on its own: one launch for a record-fed pool, one call per draw on resident rows."""
+        kind, valid, invalid, draws = self._planned
+        self._planned = None
+        self._adopt_solved(kind, valid, self._solve(valid, invalid, draws))
 
     def scaled_ref_clip_features(self):
         return {st: {sp: unit_response(v) for sp, v in per_split.items()}
                 for st, per_split in self.ref_clip_features.items()}
 
     # ------------------------------------------------------------------ the three adjustment modes
-    def _adjust_simple(self, valid, invalid):
+    def _adopt_solved(self, kind, valid, bags):
+        """The draws' targets -> ``target_features``: the one draw of ``simple``, the mean of the bags (target_clip.py:64-73), the
+        blend with the previous round's target of ``partial_update`` (target_clip.py:75-82)."""
         hp = self.hyperparameters
-        self.target_features = self._solve(valid, invalid, [self._draw(valid, invalid, hp.f_bootstrap, False)])[0]
+        if kind == "bagging":
+            self.target_features = {st: {sp: np.average([b[st][sp] for b in bags], axis=0).tolist() for sp in valid.splits}
+                                    for st in hp.streams}
+            return
+        self.target_features = bags[0]
+        if kind == "partial_update":
+            keep = hp.f_memory
+            for st, sp, old in self._previous_vectors(valid):
+                mine = self.target_features[st]
+                mine[sp] = (np.multiply(keep, mine[sp]) + np.multiply((1 - keep), old)).tolist()
 
-    def _adjust_partial_update(self, valid, invalid):
-        self._adjust_simple(valid, invalid)
+    def _previous_vectors(self, valid):
+        """(stream, split, the previous round's vector) for every slot a ``partial_update`` round blends, in its order; nothing when
+        there is no previous target.  A stream or split the previous target lacks raises KeyError."""
         before = self.previous_target_features
         if not before:
             return
-        keep = self.hyperparameters.f_memory
         for st in self.hyperparameters.streams:
-            mine, theirs = self.target_features[st], before[st]
+            theirs = before[st]
             for sp in valid.splits:
-                old = theirs[sp] if sp in theirs else theirs[str(sp)]        # JSON round trips turn keys into strings
-                mine[sp] = (np.multiply(keep, mine[sp]) + np.multiply((1 - keep), old)).tolist()
-
-    def _adjust_bagging(self, valid, invalid):
-        hp = self.hyperparameters
-        bags = self._solve(valid, invalid, [self._draw(valid, invalid, 1, True) for _ in range(hp.nbags)])
-        self.target_features = {st: {sp: np.average([b[st][sp] for b in bags], axis=0).tolist() for sp in valid.splits}
-                                for st in hp.streams}
+                yield st, sp, (theirs[sp] if sp in theirs else theirs[str(sp)])      # JSON round trips turn keys into strings
 
     # ------------------------------------------------------------------ draws and the device solve
     @staticmethod
@@ -223,5 +255,80 @@ class TargetClip:
 
 # what install() grafts onto the reference's TargetClip: the round logic; its own __init__ (wrapped to remember the
 # ticket), _get_clip_features and _request (REST) stay the reference's
-GRAFTED = ("get_target_features", "scaled_ref_clip_features", "_adjust_simple", "_adjust_partial_update", "_adjust_bagging",
-           "_draw", "_solve", "_solve_resident", "_validated_pools", "_resident_ok", "_match_verdicts", "_host")
+GRAFTED = ("get_target_features", "plan_target_features", "solve_planned_target", "scaled_ref_clip_features", "_adopt_solved",
+           "_previous_vectors", "_draw", "_solve", "_solve_resident", "_validated_pools", "_resident_ok", "_match_verdicts", "_host")
+
+
+def _batch_entry(target):
+    """What ``FeatureDB.batch_targets`` needs of a planned, row-fed target: (pool, draws, mu, previous [S,E,D] or None, keep)."""
+    kind, valid, invalid, draws = target._planned
+    hp, db = target.hyperparameters, target._host().feature_db
+    previous = None
+    if kind == "partial_update":
+        blended = list(target._previous_vectors(valid))
+        if blended:
+            previous = np.zeros((db.S, db.E, db.D), dtype=np.float64)
+            for st, sp, old in blended:
+                s = db.stream_names.index(st)
+                previous[s, db.slot_splits[s].index(sp)] = old
+    return (valid.rows, invalid.rows), draws, hp.mu, previous, hp.f_memory
+
+
+def _adopt_batched(target, t):
+    """``t`` [S,E,D] of ``batch_targets`` -> the nested dict of lists a solve of the target's own leaves, key order included."""
+    kind, valid, _invalid, _draws = target._planned
+    target._planned = None
+    db = target._host().feature_db
+    hp = target.hyperparameters
+    index = {st: db.stream_names.index(st) for st in hp.streams}
+    if kind == "bagging":
+        target.target_features = {st: {sp: t[index[st], db.slot_splits[index[st]].index(sp)].tolist() for sp in valid.splits} for st in hp.streams}
+    else:
+        target.target_features = {st: {sp: t[index[st], e].tolist() for e, sp in enumerate(db.slot_splits[index[st]])} for st in hp.streams}
+
+
+def _batchable_db(target):
+    """The database whose ``batch_targets`` can solve this target with others: it is planned, its pools are rows of the ticket's
+    resident database, and that database has the call (a ShardedFeatureDB and the numpy stand-ins of the tests do not)."""
+    planned = getattr(target, "_planned", None)
+    if planned is None or not planned[1].rows:
+        return None
+    db = getattr(target._host(), "feature_db", None)
+    return db if callable(getattr(db, "batch_targets", None)) else None
+
+
+def solve_targets_batch(targets):
+    """Solves the planned targets of a broker pass (``plan_target_features`` returned True; the others are skipped).  Targets whose
+    pools are rows of the SAME resident ``FeatureDB`` object share calls of ``FeatureDB.batch_targets`` -- at most 16 per call, in
+    list order, a call as soon as it is full, under the database's lock: every draw of every such ticket in one call instead of one
+    call per draw.  Every other target -- a record-fed pool, a database without the call, the only one of its database -- solves on
+    its own as in ``get_target_features``, in list order.  ``target_features`` is what the target's own solve leaves, bit for bit.  A
+    singular system raises ``VqError`` as the one-draw call does; a missing key of ``previous_target_features`` raises its KeyError."""
+    from .ticket import _db_lock
+    waiting: Dict[int, list] = {}
+
+    def flush(group):
+        if len(group) == 1:
+            group[0].solve_planned_target()
+            return
+        db = group[0]._host().feature_db
+        entries = [_batch_entry(t) for t in group]
+        with _db_lock(db):
+            solved = db.batch_targets([e[0] for e in entries], [e[1] for e in entries], [e[2] for e in entries],
+                                      previous=[e[3] for e in entries], keeps=[e[4] for e in entries])
+        for t, arr in zip(group, solved):
+            _adopt_batched(t, arr)
+
+    for target in targets:
+        if getattr(target, "_planned", None) is None:
+            continue
+        db = _batchable_db(target)
+        if db is None:
+            target.solve_planned_target()
+            continue
+        group = waiting.setdefault(id(db), [])
+        group.append(target)
+        if len(group) == 16:
+            flush(waiting.pop(id(db)))
+    for group in waiting.values():
+        flush(group)
