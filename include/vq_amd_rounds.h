@@ -34,8 +34,9 @@
  * batched round vq_db_batch_scores_devptr names ITS scores.
  *
  * A row view per query: vq_db_query_round_views (vq_amd_round_views.h).  The weight fit (a batched vq_db_loss_surface) and the
- * re-weighting of a round's queries on the data it left on the device: vq_amd_round_fit.h.  OUT OF SCOPE: sharded databases (one handle
- * only); a top-k per query; more than 16 queries per pass (split the list: a pass costs one read of the database). */
+ * re-weighting of a round's queries on the data it left on the device: vq_amd_round_fit.h.  The k best clips of every query, ranked on
+ * the scores the round left on the device: vq_amd_round_topk.h.  OUT OF SCOPE: sharded databases (one handle only); more than 16
+ * queries per pass (split the list: a pass costs one read of the database). */
 #ifndef VQ_AMD_ROUNDS_H
 #define VQ_AMD_ROUNDS_H
 

@@ -97,7 +97,7 @@ def _one_update(kind, update, url, hp, ticket_factory, target_factory):
 
 
 def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_factory=TargetClip, batch=False, share_search_sets=False,
-                    fit_weights=False, batch_targets=False):
+                    fit_weights=False, batch_targets=False, top=None):
     """One broker pass.  ``batch=True`` runs it in three phases so that the pending tickets share passes over their resident database
     (``ticket.compute_similarities_batch``): (1) every pending update gets its ticket, process state 3, its checks and its target
     features; (2) ONE ``compute_similarities_batch`` over the tickets that survived; (3) every ticket is finished in the original
@@ -123,7 +123,12 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     every draw of their bootstrapping in ONE ``FeatureDB.batch_targets`` call per 16 tickets instead of one call per draw.  Per
     ticket the ledger, the consumption of ``random``, ``target_features``, weights, threshold and matches are those of
     ``batch=True`` bit for bit.  One difference: a solve that raises (a singular system, a key the previous target lacks) does so
-    after every ticket of the pass has been planned, not in the middle of phase 1."""
+    after every ticket of the pass has been planned, not in the middle of phase 1.
+    ``top`` (with ``batch``; ``ValueError`` without): an int, or one per started ticket -- every ticket also gets the ``top`` best
+    clips of its search set, ranked on the device behind its group's pass and fit (``compute_similarities_batch(..., top=...)``);
+    ``ticket.top_clips(k)`` serves them.  Nothing else of the pass changes."""
+    if top is not None and not batch:
+        raise ValueError("top needs batch=True: the ranking is taken behind a batched pass")
     if fit_weights and not batch:
         raise ValueError("fit_weights=True needs batch=True: the fit runs behind a batched pass")
     if batch_targets and not batch:
@@ -152,7 +157,7 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
         solve_targets_batch([tk.target for _kind, _update, tk in started])
     fit = [fit_weights and kind in ("revise", "finalize") and bool(update["matches"]) for kind, update, _tk in started]
     compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets,
-                               **({"fit": fit} if fit_weights else {}))
+                               **({"fit": fit} if fit_weights else {}), **({"top": top} if top is not None else {}))
     for kind, update, tk in started:
         _finish_update(kind, update, tk, hyperparameters)
 

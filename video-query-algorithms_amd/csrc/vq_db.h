@@ -83,6 +83,11 @@ struct vq_db {
     int64_t targets_cap = 0;         // bytes
     double* targets_ws = nullptr;
     int64_t targets_ws_cap = 0;      // bytes
+    // Batched top-k (vq_db_batch_round_topk, include/vq_amd_round_topk.h; csrc/vq_round_topk.hip): the image of the call's block | the
+    // survivors of the long pieces | the state and the histograms of the eight radix passes | the block counts of the compaction.
+    // Allocated by the first call, grows on demand, goes with the handle.
+    char* btopk_buf = nullptr;
+    int64_t btopk_cap = 0;           // bytes
     // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over
     // (-1: the whole database) and `na` the number of clips it then covers -- M, or N: what every result-side entry point counts with.
     struct RowView {

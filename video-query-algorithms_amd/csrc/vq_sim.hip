@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "vq_common.h"
+#include "vq_select.h"
 
 namespace vq {
 std::string& last_error_ref() {
@@ -1238,58 +1239,7 @@ __global__ void generate_kernel(T* feats, int64_t total, uint64_t seed_mul, uint
 // ------------------------------------------------------------------------------------------------
 // selection: stable partition of the score array (ticket.py:325-340)
 // ------------------------------------------------------------------------------------------------
-constexpr int SEL_ITEMS = 8;                       // consecutive rows per thread (keeps order)
-constexpr int SEL_BLOCK = 256;
-constexpr int SEL_CHUNK = SEL_ITEMS * SEL_BLOCK;   // rows per block
-
-// predicate mode 0: bit0 = v >= th, bit1 = lower <= v < th   (select)
-// predicate mode 1: bit0 = key > pivot,  bit1 = key == pivot  (top-k; keys are order-mapped scores)
-__device__ __forceinline__ uint64_t order_key(double v) {
-    if (v != v) return 0ull;                                  // NaN sorts last
-    if (v == 0.0) v = 0.0;                                     // -0 == +0
-    uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);       // ascending in v; > 0 for every non-NaN
-}
-
-struct SelPred {
-    int mode;
-    double th, lower;
-    uint64_t pivot;
-    __device__ __forceinline__ int operator()(double v) const {
-        if (mode == 0) return (v >= th ? 1 : 0) | ((lower <= v && v < th) ? 2 : 0);
-        const uint64_t k = order_key(v);
-        return (k > pivot ? 1 : 0) | ((k == pivot && k != 0ull) ? 2 : 0);
-    }
-};
-
-__device__ __forceinline__ int2 block_scan_excl2(int2 v, int2* total) {
-    // exclusive scan of two counters over the 256 threads of a block (4 waves)
-    __shared__ int2 wsum[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int2 inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int ax = __shfl_up(inc.x, off, 64), ay = __shfl_up(inc.y, off, 64);
-        if (lane >= off) {
-            inc.x += ax;
-            inc.y += ay;
-        }
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int2 base = make_int2(0, 0), tot = make_int2(0, 0);
-    for (int i = 0; i < 4; ++i) {
-        if (i < wid) {
-            base.x += wsum[i].x;
-            base.y += wsum[i].y;
-        }
-        tot.x += wsum[i].x;
-        tot.y += wsum[i].y;
-    }
-    __syncthreads();
-    *total = tot;
-    return make_int2(base.x + inc.x - v.x, base.y + inc.y - v.y);
-}
+// SEL_ITEMS / SEL_BLOCK / SEL_CHUNK, order_key, the two predicates (SelPred) and block_scan_excl2: csrc/vq_select.h
 
 // pass 1: per-block counts of both classes + block-local first-argmax of class 1 (near band)
 __device__ __forceinline__ void select_count_block(const double* scores, int64_t n, SelPred pred, int2* blk_cnt, double* blk_max,
@@ -1775,7 +1725,7 @@ __global__ void topk_pick_kernel(int pass, uint64_t* state, unsigned int* hist) 
 // LDS, the eight histogram passes and the stable compaction are separated by barriers instead of 19 launches and three
 // synchronisations (a 10k-clip top-20: ~0.15 ms of launch sequence -> one launch and one copy).  Same survivors in the same (row)
 // order as the general path: keys above the pivot first, then the first `need` rows that tie with it.
-constexpr int kTopkSmallN = 16384, kTopkSmallK = 1024, kTopkSmallThreads = 1024;
+// kTopkSmallN, kTopkSmallK, kTopkSmallThreads: csrc/vq_select.h (the batched top-k takes its short form at the same sizes)
 __global__ __launch_bounds__(kTopkSmallThreads) void topk_small_kernel(const double* scores, int n, int k, int64_t* out_rows, double* out_vals,
                                                                        int64_t* out_count) {
     extern __shared__ __attribute__((aligned(16))) unsigned char topk_lds[];
@@ -1796,65 +1746,15 @@ __global__ __launch_bounds__(kTopkSmallThreads) void topk_small_kernel(const dou
         const int shift = 56 - 8 * pass;
         const uint64_t prefix = s_prefix;
         const uint64_t mask = pass == 0 ? 0ull : (~0ull << (shift + 8));
-        // the keys of a pass crowd into few bins (every score of a ranking shares its sign and most of its exponent): the lanes that
-        // agree with the wave's first live lane are counted by ONE atomic, the others add themselves
+        // one atomic per wave for the lanes that agree with its first live lane (radix_hist_add, csrc/vq_select.h)
         for (int i0 = 0; i0 < n; i0 += kTopkSmallThreads) {
             const int i = i0 + tid;
             const uint64_t key = i < n ? keys[i] : 0ull;
             const bool live = key != 0ull && (key & mask) == prefix;
-            const int digit = live ? (int)((key >> shift) & 255) : -1;
-            const unsigned long long act = __ballot(live);
-            if (act) {
-                const int lead = __ffsll((long long)act) - 1;
-                const int first = __shfl(digit, lead, 64);
-                const unsigned long long same = __ballot(digit == first);
-                if ((tid & 63) == lead)
-                    atomicAdd(&hist[first], (unsigned)__popcll(same));
-                else if (live && digit != first)
-                    atomicAdd(&hist[digit], 1u);
-            }
+            radix_hist_add(hist, live, live ? (int)((key >> shift) & 255) : -1, tid & 63);
         }
         __syncthreads();
-        if (tid < 64) {                                              // topk_pick_kernel, by one wave: lane l owns bins 4l .. 4l+3
-            const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            unsigned above = h0 + h1 + h2 + h3;                      // inclusive suffix sum over the lanes: bins >= 4l
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned o = __shfl_down(above, off, 64);
-                if (tid + off < 64) above += o;
-            }
-            const unsigned need = s_need;
-            const unsigned gt3 = above - (h0 + h1 + h2 + h3);        // elements in bins > 4l+3
-            // the bin b the serial walk from 255 downwards stops in: the highest b with count(bins >= b) >= need (b = 0 if none)
-            int found = -1;
-            unsigned rest = 0;
-            if (gt3 + h3 >= need) {
-                found = 4 * tid + 3;
-                rest = need - gt3;
-            } else if (gt3 + h3 + h2 >= need) {
-                found = 4 * tid + 2;
-                rest = need - gt3 - h3;
-            } else if (gt3 + h3 + h2 + h1 >= need) {
-                found = 4 * tid + 1;
-                rest = need - gt3 - h3 - h2;
-            } else if (gt3 + h3 + h2 + h1 + h0 >= need) {
-                found = 4 * tid;
-                rest = need - gt3 - h3 - h2 - h1;
-            }
-            const unsigned long long have = __ballot(found >= 0 && gt3 < need);   // lanes whose own bins contain the stop
-            // the stop lies in the HIGHEST lane for which bins above it hold fewer than `need` and its own close the gap
-            const int top = have ? 63 - __builtin_clzll(have) : -1;
-            if (top < 0) {
-                if (tid == 0) {                                      // fewer than `need` keys under this prefix: bin 0, need minus all above it
-                    s_prefix = prefix;
-                    s_need = need - (above - h0);
-                }
-            } else if (tid == top) {
-                if (found == 0) rest = need - (above - h0);          // the serial walk never tests bin 0: it takes what is left
-                s_prefix = prefix | ((uint64_t)found << shift);
-                s_need = rest;
-            }
-        }
+        if (tid < 64) radix_pick_wave(hist, tid, s_need, prefix, shift, &s_prefix, &s_need);      // topk_pick_kernel, by one wave
         __syncthreads();
     }
     const uint64_t pivot = s_prefix;
@@ -1954,7 +1854,7 @@ static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);
     void* ptrs[] = {db->present, db->t,       db->sims,  db->round_dev, db->blk_cnt,
                     db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev, db->vround_plan,
-                    db->targets_buf, db->targets_ws};
+                    db->targets_buf, db->targets_ws, db->btopk_buf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t ev : db->bround_ev)

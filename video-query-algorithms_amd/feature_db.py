@@ -631,7 +631,8 @@ class FeatureDB:
             ptr = p.value
         return _RoundBlock(ptr, nbytes, pool), off
 
-    def query_round_batch(self, targets: np.ndarray, weights: np.ndarray, selects=None, want_avg: bool = True, timed: bool = False) -> list:
+    def query_round_batch(self, targets: np.ndarray, weights: np.ndarray, selects=None, want_avg: bool = True, timed: bool = False,
+                          want_scores: bool = True) -> list:
         """Up to 16 query rounds in ONE read of the database (vq_db_query_round_batch): ``targets`` [Q,S,E,D] fp64, ``weights`` [Q,S],
         ``selects`` [Q,2] = (threshold, lower) per query or None.  One :class:`RoundResult` per query with the fields
         :meth:`query_round` fills: ``avg`` [N,S] (None without ``want_avg``), ``n_e`` [N,S] (ONE array shared by all results: it does not
@@ -639,7 +640,9 @@ class FeatureDB:
         :meth:`scan_batch`'s bit for bit, scores and avg the one-query round's to rounding (<= 1e-12); the partition is exact on the
         returned scores.  The arrays are views of one pooled page-locked block that lives as long as they do; a list longer than
         the prefix is fetched.  The whole database only (a search set in use: ``VqError``); the one-query state of the handle is left
-        alone.  ``timed``: :meth:`batch_round_times` then gives the split of the call."""
+        alone.  ``timed``: :meth:`batch_round_times` then gives the split of the call.  ``want_scores=False``: the scores are not
+        copied back (``scores`` is None); they stay on the device for :meth:`batch_round_topk`, :meth:`batch_round_rescore` and
+        ``vq_db_batch_scores_devptr``, so a ranked search never moves an N-sized array."""
         t = np.asarray(targets, dtype=np.float64)
         w = np.asarray(weights, dtype=np.float64)
         if t.ndim != 4 or t.shape[1:] != (self.S, self.E, self.D) or w.shape != (t.shape[0], self.S):
@@ -663,14 +666,14 @@ class FeatureDB:
             wv = view(1, np.float64, (Q, 8))
             wv[...] = 0.0
             wv[:, :S] = w
-            flags = _lib.VQ_BROUND_SCORES | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
+            flags = (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
             if bands is not None:
                 view(2, np.float64, (Q, 2))[...] = bands
                 flags |= _lib.VQ_BROUND_SELECT
             call("vq_db_query_round_batch", self._h, Q, C.c_void_p(blk.ptr), blk.nbytes, flags)
             n_e = view(3, np.int32, (n, S)) if want_avg else None
             avg = view(4, np.float64, (Q, n, S)) if want_avg else None
-            scores = view(5, np.float64, (Q, n))
+            scores = view(5, np.float64, (Q, n)) if want_scores else None
             res = view(6, np.int64, (Q, 4))
             prefix = off[10]
             pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
@@ -679,7 +682,7 @@ class FeatureDB:
                 r = RoundResult()
                 r.avg = avg[q] if want_avg else None
                 r.n_e = n_e
-                r.scores = scores[q]
+                r.scores = scores[q] if want_scores else None
                 r.match_rows = r.near_rows = None
                 r.near_argmax = -1
                 if bands is not None:
@@ -697,14 +700,15 @@ class FeatureDB:
             return out
 
     def query_round_batch_sets(self, targets: np.ndarray, weights: np.ndarray, set_ids, selects=None, want_avg: bool = True,
-                               timed: bool = False) -> list:
+                               timed: bool = False, want_scores: bool = True) -> list:
         """:meth:`query_round_batch` with a search set per query (vq_db_query_round_views, include/vq_amd_round_views.h): ONE read of
         the UNION of the sets, every query scored, averaged and partitioned over its own set only.  ``set_ids[q]`` is a defined search
         set id, or ``None`` for the whole database.  One :class:`RoundResult` per query: ``avg`` [M_q,S], ``n_e`` [M_q,S] and ``scores``
         [M_q] are compact (entry i belongs to row ``rows[i]`` of the set's view) and every row in ``match_rows`` / ``near_rows`` /
         ``near_argmax`` is a position in that view, as under :meth:`use_search_set`.  avg and scores have the bits
         :meth:`query_round_batch` gives the same (clip, query slot) on this handle.  The set in use and the one-query state of the
-        handle are left alone.  :attr:`last_view_round_union` then says what the pass read."""
+        handle are left alone.  :attr:`last_view_round_union` then says what the pass read.  ``want_scores=False``: as for
+        :meth:`query_round_batch` (``scores`` is None, the scores stay on the device)."""
         t = np.asarray(targets, dtype=np.float64)
         w = np.asarray(weights, dtype=np.float64)
         if t.ndim != 4 or t.shape[1:] != (self.S, self.E, self.D) or w.shape != (t.shape[0], self.S):
@@ -753,7 +757,7 @@ class FeatureDB:
             wv = view(1, np.float64, (Q, 8))
             wv[...] = 0.0
             wv[:, :S] = w
-            flags = _lib.VQ_BROUND_SCORES | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
+            flags = (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
             if bands is not None:
                 view(2, np.float64, (Q, 2))[...] = bands
                 flags |= _lib.VQ_BROUND_SELECT
@@ -767,7 +771,7 @@ class FeatureDB:
                 r = RoundResult()
                 r.avg = view(4, np.float64, (m, S), start[q] * S) if want_avg else None
                 r.n_e = view(3, np.int32, (m, S), start[q] * S) if want_avg else None
-                r.scores = view(5, np.float64, (m,), start[q])
+                r.scores = view(5, np.float64, (m,), start[q]) if want_scores else None
                 r.match_rows = r.near_rows = None
                 r.near_argmax = -1
                 if bands is not None:
@@ -1015,6 +1019,54 @@ class FeatureDB:
                 out.append(r)
             return out
 
+    # ------------------------------------------------------------------ the k best clips of every query of a batched round
+    def batch_topk_cap(self) -> int:
+        """The largest k :meth:`batch_round_topk` ranks (the library's constant, read through vq_db_batch_topk_layout)."""
+        off = (C.c_int64 * 6)()
+        call("vq_db_batch_topk_layout", self._h, 1, 1, off)
+        return int(off[5])
+
+    def batch_round_topk(self, ks, queries=None) -> list:
+        """ticket.py:266 for several queries of the LAST batched round (either kind, whether or not it copied its scores back) in ONE
+        call (vq_db_batch_round_topk, include/vq_amd_round_topk.h): the ``ks[i]`` best clips of query ``queries[i]`` of that round
+        (``queries`` None: all of them, in order; ``ks`` an int: the same k for each), ranked on the device from the scores the
+        round -- or a :meth:`batch_round_rescore` behind it -- left there.  One (rows, vals) per entry, as :meth:`topk` gives them:
+        positions in the query's view (as in every result of that round) by descending score, ties by ascending position, NaN
+        excluded, and the scores at those positions bit for bit.  A k above the rows of the query's view is clamped to them; one
+        above :meth:`batch_topk_cap` is the library's refusal.  Without a batched round: ``VqError`` (VQ_E_STATE)."""
+        with self.lock:
+            last = getattr(self, "_bround_last", None)
+            if queries is None:
+                queries = list(range(last[0])) if last is not None else [0]
+            queries = [int(q) for q in queries]
+            n = len(queries)
+            kk = [int(ks)] * n if np.ndim(ks) == 0 else [int(v) for v in ks]
+            if not n or len(kk) != n or len(set(queries)) != n or min(queries) < 0 or max(queries) >= 16:
+                raise ValueError("one k per query (or one int), every query -- its index in the last batched round -- once")
+            if min(kk) < 0:
+                raise ValueError("k must not be negative")
+            if last is not None:                              # min(k, M_q); a query the round did not have keeps its k: the library refuses it
+                start = last[2]
+                kk = [min(k, start[q + 1] - start[q]) if q < last[0] else max(k, 1) for k, q in zip(kk, queries)]
+            Q, k_max = max(queries) + 1, max(max(kk), 1)
+            off = (C.c_int64 * 6)()
+            call("vq_db_batch_topk_layout", self._h, Q, k_max, off)
+            off = [int(v) for v in off]
+            blk = self._pooled_block("_topk_pools", off[4])
+            raw = blk.bytes()
+
+            def view(piece, dtype, shape):
+                count = int(np.prod(shape))
+                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            k_in, count = view(0, np.int64, (Q,)), view(1, np.int64, (Q,))
+            k_in[...] = 0
+            count[...] = 0
+            for q, k in zip(queries, kk):
+                k_in[q] = k
+            call("vq_db_batch_round_topk", self._h, Q, k_max, C.c_void_p(blk.ptr), blk.nbytes)
+            rows, vals = view(2, np.int64, (Q, k_max)), view(3, np.float64, (Q, k_max))
+            return [(rows[q, :int(count[q])], vals[q, :int(count[q])]) for q in queries]
+
     def rescore(self, weights: Sequence[float]):
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (self.S,):
@@ -1105,7 +1157,8 @@ class FeatureDB:
     def close(self):
         if self._h:
             pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()] + \
-                list(getattr(self, "_view_round_pools", {}).values()) + list(getattr(self, "_fit_pools", {}).values())
+                list(getattr(self, "_view_round_pools", {}).values()) + list(getattr(self, "_fit_pools", {}).values()) + \
+                list(getattr(self, "_topk_pools", {}).values())
             self._bround_last = None
             for pool in pools:
                 if pool is None:

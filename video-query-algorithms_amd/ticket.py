@@ -132,6 +132,9 @@ class TicketScoring:
     _view = None                             # the search-set view this round is bound to (feature_db.SearchSetView)
     _fit = None                              # (weights, threshold) fitted behind a batched pass (compute_similarities_batch(fit=))
     _fit_round = None                        # the _round token that fit belongs to
+    _top = None                              # (clip ids, scores) of the best clips, ranked behind a pass (compute_similarities_batch(top=))
+    _top_round = None                        # the _round token that ranking belongs to
+    _top_weights = None                      # the score weights (bytes) it was taken under
     feature_db_dtype = np.float64            # dtype used when the DB is built from API records
     device = 0
 
@@ -273,6 +276,23 @@ class TicketScoring:
             db.rescore(self._score_weights)
             db.scores_owner = mine
 
+    # -- ticket.py:266 (the report's order) on the whole search set --------------------------------
+    def top_clips(self, k):
+        """(clip ids, scores) of the ``k`` best clips of this round under the ticket's current score weights: descending score, ties
+        in search-set order, clips without a score left out.  Served from the ranking ``compute_similarities_batch(top=)`` took with
+        the pass when that belongs to this round, holds enough entries and was taken under these weights; otherwise the database
+        ranks the ticket's scores (``topk``) under its lock."""
+        k = int(k)
+        top, w = self._top, self._score_weights
+        if top is not None and self._round is not None and self._top_round is self._round and len(top[0]) >= min(k, self._view.n) \
+                and (w is None or w.tobytes() == self._top_weights):   # no compute_scores yet: the scores are the look-ahead ones
+            return top[0][:k], top[1][:k]
+        db = self.feature_db
+        with _db_lock(db):
+            self._own_scores()
+            rows, vals = db.topk(k)
+            return self._view.clip_ids[rows], np.array(vals)
+
     # -- ticket.py:301-309 ------------------------------------------------------------------
     def lowest_scoring_user_match(self):
         view = self._view                            # positions in the ticket's search set
@@ -411,7 +431,39 @@ def _fit_group(db, group):
         tk._fit, tk._fit_round = fit, tk._round
 
 
-def _batched_pass(group):
+def _set_top(tk, rows, vals):
+    """``_top`` of a ticket from positions in its view and their scores, under the weights of its look-ahead scores."""
+    tk._top = (tk._view.clip_ids[np.asarray(rows, dtype=np.int64)], np.array(vals))
+    tk._top_round, tk._top_weights = tk._round, tk._ahead["w"]
+
+
+def _rank_group(db, group, tops):
+    """The ``top`` best clips of every member of a pass (ticket.py:266 on the whole search set) in ONE ``batch_round_topk`` on the
+    scores the pass -- and the rescore of ``_fit_group`` behind it -- left on the device.  Every member ends with ``_top`` = (clip
+    ids, scores), ``_top_round`` = its ``_round`` and ``_top_weights`` = the weights those scores stand under (its ``_ahead``'s).
+    Call behind ``_fit_group`` with the database's lock still held."""
+    if tops is None or not hasattr(db, "batch_round_topk"):
+        return
+    ranked = db.batch_round_topk([int(k) for k in tops])
+    for (tk, _hp, _prep, _fit), (rows, vals) in zip(group, ranked):
+        _set_top(tk, rows, vals)
+
+
+def _rank_alone(tk, k):
+    """The same for a ticket that ran its own round: ``topk`` of its database, under its lock, on the look-ahead scores."""
+    db = tk.feature_db
+    ahead = getattr(tk, "_ahead", None)
+    if k is None or db is None or ahead is None or not hasattr(db, "topk"):
+        return
+    with _db_lock(db):
+        mine = (tk._round, ahead["w"])
+        if getattr(db, "scores_owner", mine) != mine:                  # somebody else's scores on the handle by now: top_clips will ask
+            return
+        rows, vals = db.topk(int(k))
+        _set_top(tk, rows, vals)
+
+
+def _batched_pass(group, tops=None):
     """One pass for up to BATCH_PASS tickets that share a database object and a slot mask: what compute_similarities does for each,
     the look-ahead scores and partition included."""
     db, slot_used = group[0][2][0], group[0][2][3]
@@ -429,6 +481,7 @@ def _batched_pass(group):
         db.sims_owner = db.scores_owner = None
         _adopt(group, views, results)
         _fit_group(db, group)                                         # fit=: behind its own pass, in the same hold of the lock
+        _rank_group(db, group, tops)                                  # top=: behind the fit, so a fitted member ranks under its fitted weights
 
 
 def _set_of(db, ticket):
@@ -437,7 +490,7 @@ def _set_of(db, ticket):
     return set_id if hasattr(db, "has_search_set") and db.has_search_set(set_id) else None
 
 
-def _shared_sets_pass(group):
+def _shared_sets_pass(group, tops=None):
     """ONE pass over the union of the members' search sets (FeatureDB.query_round_batch_sets): what compute_similarities does for each
     member under its own set -- ``_view`` is its set's view, everything else is indexed by position in it."""
     db, slot_used = group[0][2][0], group[0][2][3]
@@ -454,13 +507,23 @@ def _shared_sets_pass(group):
         db.sims_owner = db.scores_owner = None                        # as after _batched_pass: nobody's round
         _adopt(group, views, results)
         _fit_group(db, group)                                         # fit=: behind its own pass, in the same hold of the lock
+        _rank_group(db, group, tops)                                  # top=: behind the fit, as in _batched_pass
 
 
-def _flush(group):
+def _flush(group, top_of=None):
     """Run a group of tickets that share a database object and a slot mask.  Without search-set members: one pass, or the ticket's own
     round when it is alone.  With them (share_search_sets): one pass over the union if the sharing rule holds, else the search-set
-    members' own rounds in list order and the whole-database members as a group of today's kind."""
+    members' own rounds in list order and the whole-database members as a group of today's kind.  ``top_of``: id(ticket) -> how many
+    best clips to rank behind its round (None: no ranking)."""
     db = group[0][2][0]
+
+    def tops(members):
+        return None if top_of is None else [top_of[id(tk)] for tk, _hp, _prep, _fit in members]
+
+    def alone(tk, hp):
+        tk.compute_similarities(hp)
+        if top_of is not None:
+            _rank_alone(tk, top_of[id(tk)])
     set_ids = [_set_of(db, tk) for tk, _hp, _prep, _fit in group]
     if any(sid is not None for sid in set_ids):
         n = len(db.clip_ids)
@@ -468,21 +531,21 @@ def _flush(group):
         total = sum(n if sid is None else sizes[sid] for sid in set_ids)
         distinct = min(n, sum(sizes.values()) + (n if None in set_ids else 0))
         if len(group) > 1 and total >= SHARE_SETS_FACTOR * distinct:
-            _shared_sets_pass(group)
+            _shared_sets_pass(group, tops(group))
             return
         for (tk, hp, _prep, _fit), sid in zip(group, set_ids):
             if sid is not None:
-                tk.compute_similarities(hp)
+                alone(tk, hp)
         group = [g for g, sid in zip(group, set_ids) if sid is None]
         if not group:
             return
     if len(group) == 1:                                   # nobody to share a pass with: the ticket's own round, bit for bit
-        group[0][0].compute_similarities(group[0][1])
+        alone(group[0][0], group[0][1])
     else:
-        _batched_pass(group)
+        _batched_pass(group, tops(group))
 
 
-def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False, fit=None):
+def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False, fit=None, top=None):
     """``compute_similarities`` for a list of tickets, those that can sharing passes over their resident database: a broker with
     several pending tickets pays one read of the database per 16 of them instead of one each.  ``hyperparameters`` is one object or
     one per ticket.  Every ticket ends with exactly the attributes its own ``compute_similarities`` sets (``similarities``, ``_avg``,
@@ -509,7 +572,15 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     this round -- what ``optimize_weights`` would set on its hyperparameters object, on the pass's own similarities -- and with
     ``_ahead`` rebuilt under those weights and the review band of that threshold, so ``compute_scores(weights)`` and
     ``select_clips_to_review(threshold, ., near_miss_default)`` ask the device for nothing.  Every other ticket is unchanged and its
-    caller runs ``optimize_weights``: one that ran its own round, one on a database without the two methods, one without labels."""
+    caller runs ``optimize_weights``: one that ran its own round, one on a database without the two methods, one without labels.
+
+    ``top``: an int, or one per ticket.  Every member of a pass also gets the ``top`` best clips of its search set, ranked on the
+    device in the same hold of the lock, BEHIND the fit -- a fitted member is ranked under its fitted weights: one
+    ``batch_round_topk`` per pass, so no N-sized array comes back for the ranking.  Such a ticket ends with ``_top`` = (clip ids
+    [count], scores [count]) by descending score, ties in search-set order, and ``_top_round`` = its ``_round``;
+    ``top_clips(k)`` serves ``k <= top`` from it while the ticket's score weights are the ones it was taken under.  A ticket that
+    ran its own round gets the same from its database's ``topk`` (when it has one and the round looked ahead).  ``None``: no
+    ranking; ``_top`` is left as it was and belongs to no round of this call."""
     tickets = list(tickets)
     fits = [False] * len(tickets) if fit is None else [bool(f) for f in fit]
     if len(fits) != len(tickets):
@@ -517,19 +588,27 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     hps = list(hyperparameters) if isinstance(hyperparameters, (list, tuple)) else [hyperparameters] * len(tickets)
     if len(hps) != len(tickets):
         raise ValueError("one hyperparameters object, or one per ticket")
+    top_of = None
+    if top is not None:
+        counts = [int(top)] * len(tickets) if np.ndim(top) == 0 else [int(k) for k in top]
+        if len(counts) != len(tickets) or any(k < 1 for k in counts):
+            raise ValueError("top: one positive int, or one per ticket")
+        top_of = {id(tk): k for tk, k in zip(tickets, counts)}
     pending = {}                                          # (database object, slot mask) -> the tickets waiting for a pass, in list order
     for tk, hp, want_fit in zip(tickets, hps, fits):
         prep = _batchable(tk, hp, share_search_sets)
         if prep is None:
             tk.compute_similarities(hp)
+            if top_of is not None:
+                _rank_alone(tk, top_of[id(tk)])
             continue
         key = (id(prep[0]), prep[3].tobytes())
         group = pending.setdefault(key, [])
         group.append((tk, hp, prep, want_fit))
         if len(group) == BATCH_PASS:
-            _flush(pending.pop(key))
+            _flush(pending.pop(key), top_of)
     for group in pending.values():
-        _flush(group)
+        _flush(group, top_of)
 
 
 class Ticket(TicketScoring):
@@ -644,10 +723,11 @@ def install(ticket_cls, hyperparameter_cls=None, target_clip_cls=None):
             self._ticket = ticket                          # lets the round use rows of a resident ticket.feature_db
         target_clip_cls.__init__ = remember_ticket
     for name in ("compute_similarities", "compute_scores", "lowest_scoring_user_match", "select_clips_to_review",
-                 "_own_similarities", "_own_scores", "_look_ahead", "_bind_view"):
+                 "_own_similarities", "_own_scores", "_look_ahead", "_bind_view", "top_clips"):
         setattr(ticket_cls, name, getattr(TicketScoring, name))
     ticket_cls._review_band = staticmethod(TicketScoring._review_band)
-    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap", "_view", "_fit", "_fit_round"):
+    for name in ("feature_db", "feature_db_dtype", "device", "_round", "_score_weights", "_ahead", "_hp", "_stream_gap", "_view", "_fit", "_fit_round", "_top", "_top_round",
+                 "_top_weights"):
         if not hasattr(ticket_cls, name):
             setattr(ticket_cls, name, getattr(TicketScoring, name))
     if hyperparameter_cls is not None:
