@@ -49,6 +49,19 @@ def np_topk(scores, k):
     return order.astype(np.int64), v[order]
 
 
+def tie_ks(scores, cap):
+    """k in the middle of the best run of equal scores, at its end, one past it, and the same around the end of the third run"""
+    vals, counts = np.unique(scores[~np.isnan(scores)], return_counts=True)
+    if not counts.size:
+        return []
+    runs = counts[::-1]                                               # best value first
+    ends = np.cumsum(runs)
+    ks = [max(1, int(runs[0]) // 2), int(ends[0]), int(ends[0]) + 1]
+    if len(ends) >= 3:
+        ks += [int(ends[2]) - 1, int(ends[2]), int(ends[2]) + 1]
+    return [k for k in ks if 1 <= k <= min(cap, scores.size)]
+
+
 def np_select(scores, th, lower):
     v = np.asarray(scores)
     with np.errstate(invalid="ignore"):

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _search_set_cases import np_topk, presence_mask, same_bits, view_lists
+from _search_set_cases import np_topk, presence_mask, same_bits, tie_ks, view_lists
 
 pytestmark = pytest.mark.gpu
 S, E, D = 2, 1, 256
@@ -94,17 +94,6 @@ def test_sizes_at_every_cut(vqa, m):
         assert ei.value.code == VQ_E_INVALID
         check(db, [np.array(r[0].scores)], [cap])
     db.close()
-
-
-def tie_ks(scores, cap):
-    """k in the middle of the best run of equal scores, at its end, one past it, and the same around the end of the third run"""
-    vals, counts = np.unique(scores[~np.isnan(scores)], return_counts=True)
-    runs = counts[::-1]                                               # best value first
-    ends = np.cumsum(runs)
-    ks = [max(1, int(runs[0]) // 2), int(ends[0]), int(ends[0]) + 1]
-    if len(ends) >= 3:
-        ks += [int(ends[2]) - 1, int(ends[2]), int(ends[2]) + 1]
-    return [k for k in ks if 1 <= k <= min(cap, scores.size)]
 
 
 @pytest.mark.parametrize("m", [3000, 20_000], ids=["short", "long"])

@@ -133,6 +133,12 @@ class FeatureDB:
         self._set_in_use = None
         self._whole = None
         self._na = self.n
+        # the layout of a one-query round's block and the pool of its page-locked blocks: made here, so that the first rounds of two
+        # threads share one pool
+        off = (C.c_int64 * 10)()
+        call("vq_db_round_layout", self._h, off)
+        self._round_off = [int(v) for v in off]
+        self._round_pool = {"free": [], "closed": False}
 
     # ------------------------------------------------------------------ search sets
     def define_search_set(self, set_id, clip_ids):
@@ -511,12 +517,14 @@ class FeatureDB:
         t = np.ascontiguousarray(t, dtype=np.float64)
         if t.shape != (self.S, self.E, self.D):
             raise ValueError("query must be [%d,%d,%d]" % (self.S, self.E, self.D))
-        call("vq_db_set_query", self._h, _np_ptr(t))
+        with self.lock:
+            call("vq_db_set_query", self._h, _np_ptr(t))
 
     def set_query_from_row(self, row: int, want: bool = True):
         """t = r/(r.r) of a resident row (target_clip.py:311-313), computed on the device."""
         out = np.empty((self.S, self.E, self.D), dtype=np.float64) if want else None
-        call("vq_db_set_query_from_row", self._h, int(row), _np_ptr(out) if want else None)
+        with self.lock:
+            call("vq_db_set_query_from_row", self._h, int(row), _np_ptr(out) if want else None)
         return out
 
     def bootstrap_target(self, valid_rows: Sequence[int], invalid_rows: Sequence[int] = (), mu: float = 0.0,
@@ -526,8 +534,9 @@ class FeatureDB:
         v = np.ascontiguousarray(valid_rows, dtype=np.int64)
         iv = np.ascontiguousarray(invalid_rows, dtype=np.int64)
         out = np.empty((self.S, self.E, self.D), dtype=np.float64)
-        call("vq_db_bootstrap_target", self._h, _np_ptr(v), int(v.size), _np_ptr(iv) if iv.size else None, int(iv.size), float(mu),
-             _np_ptr(out), 1 if set_query else 0)
+        with self.lock:
+            call("vq_db_bootstrap_target", self._h, _np_ptr(v), int(v.size), _np_ptr(iv) if iv.size else None, int(iv.size), float(mu),
+                 _np_ptr(out), 1 if set_query else 0)
         return out
 
     def scan(self, weights: Sequence[float] | None = None, keep_sims: bool = False):
@@ -535,7 +544,8 @@ class FeatureDB:
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
         if w is not None and w.shape != (self.S,):
             raise ValueError("one weight per stream")
-        call("vq_db_scan", self._h, _np_ptr(w) if w is not None else None, 1 if keep_sims else 0)
+        with self.lock:
+            call("vq_db_scan", self._h, _np_ptr(w) if w is not None else None, 1 if keep_sims else 0)
 
     def scan_batch(self, targets: np.ndarray, weights: np.ndarray, want: bool = True):
         """Q <= 16 queries in one pass over the database: targets [Q,S,E,D] fp64, weights [Q,S] -> scores [Q,N].  The dots
@@ -551,14 +561,9 @@ class FeatureDB:
 
     # ------------------------------------------------------------------ a query round in one call
     def _round_block(self) -> _RoundBlock:
-        if getattr(self, "_round_off", None) is None:
-            off = (C.c_int64 * 10)()
-            call("vq_db_round_layout", self._h, off)
-            self._round_off = [int(v) for v in off]
-            self._round_pool = {"free": [], "closed": False}
-        if self._round_pool["free"]:
-            ptr, nbytes = self._round_pool["free"].pop()
-        else:
+        try:
+            ptr, nbytes = self._round_pool["free"].pop()     # list.pop is atomic: two threads never take the same block
+        except IndexError:
             p = C.c_void_p()
             nbytes = self._round_off[8]
             call("vq_host_alloc", C.byref(p), nbytes)
@@ -569,11 +574,13 @@ class FeatureDB:
         """ticket.py:120-180,311-356 as ONE call of the library (vq_db_query_round): one lock, one synchronisation, one copy back.
         ``t`` [S,E,D]: scan under this query (None: the similarities the handle holds); ``weights`` [S]: scores under them;
         ``select`` = (threshold, lower): the order-preserving partition.  Bit for bit what set_query / scan / similarities / rescore /
-        scores / select return one by one (tested); the arrays are views of page-locked memory that stay valid as long as they live."""
+        scores / select return one by one (tested); the arrays are views of page-locked memory that stay valid as long as they live.
+        The round and the fetch of a list longer than its 1024-row prefix run under ``self.lock``, which every method that replaces
+        the handle's scores or selection lists takes: the lists are this round's whatever other threads ask of the handle."""
         blk = self._round_block()
         off = self._round_off
         raw = blk.bytes()
-        n, S = self._na, self.S                               # the block is laid out for N; a search set fills the first M of each array
+        S = self.S
 
         def view(piece, dtype, count, shape):
             return raw[off[piece]:off[piece] + count * dtype().itemsize].view(dtype).reshape(shape)
@@ -587,24 +594,28 @@ class FeatureDB:
         th, lower = (float(select[0]), float(select[1])) if select is not None else (0.0, 0.0)
         if select is not None:
             flags |= 4
-        call("vq_db_query_round", self._h, C.c_void_p(blk.ptr), blk.nbytes, flags, th, lower)
-        r = RoundResult()
-        r.avg = view(2, np.float64, n * S, (n, S)) if t is not None else None
-        r.n_e = view(3, np.int32, n * S, (n, S)) if t is not None else None
-        r.scores = view(4, np.float64, n, (n,)) if weights is not None else None
-        r.match_rows = r.near_rows = None
-        r.near_argmax = -1
-        if select is not None:
-            res = view(5, np.int64, 4, (4,))
-            nm, nn, r.near_argmax = int(res[0]), int(res[1]), int(res[2])
-            if nm <= off[9] and nn <= off[9]:
-                r.match_rows = view(6, np.int64, nm, (nm,))
-                r.near_rows = view(7, np.int64, nn, (nn,))
-            else:                                             # a list longer than its prefix: the full lists are still on the device
-                m = np.empty(nm, dtype=np.int64)
-                q = np.empty(nn, dtype=np.int64)
-                call("vq_db_select_fetch", self._h, _np_ptr(m) if nm else None, nm, _np_ptr(q) if nn else None, nn)
-                r.match_rows, r.near_rows = m, q
+        # one lock from the round to the fetch of a list that outgrew its prefix: a selection, a top-k or a round of another thread on
+        # this handle in between would replace (or invalidate) the lists on the device that the fetch copies
+        with self.lock:
+            n = self._na                                      # the block is laid out for N; a search set fills the first M of each array
+            call("vq_db_query_round", self._h, C.c_void_p(blk.ptr), blk.nbytes, flags, th, lower)
+            r = RoundResult()
+            r.avg = view(2, np.float64, n * S, (n, S)) if t is not None else None
+            r.n_e = view(3, np.int32, n * S, (n, S)) if t is not None else None
+            r.scores = view(4, np.float64, n, (n,)) if weights is not None else None
+            r.match_rows = r.near_rows = None
+            r.near_argmax = -1
+            if select is not None:
+                res = view(5, np.int64, 4, (4,))
+                nm, nn, r.near_argmax = int(res[0]), int(res[1]), int(res[2])
+                if nm <= off[9] and nn <= off[9]:
+                    r.match_rows = view(6, np.int64, nm, (nm,))
+                    r.near_rows = view(7, np.int64, nn, (nn,))
+                else:                                         # a list longer than its prefix: the full lists are still on the device
+                    m = np.empty(nm, dtype=np.int64)
+                    q = np.empty(nn, dtype=np.int64)
+                    call("vq_db_select_fetch", self._h, _np_ptr(m) if nm else None, nm, _np_ptr(q) if nn else None, nn)
+                    r.match_rows, r.near_rows = m, q
         return r
 
     # ------------------------------------------------------------------ up to 16 query rounds in one pass
@@ -1071,7 +1082,8 @@ class FeatureDB:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (self.S,):
             raise ValueError("one weight per stream")
-        call("vq_db_rescore", self._h, _np_ptr(w))
+        with self.lock:
+            call("vq_db_rescore", self._h, _np_ptr(w))
 
     def similarities(self, sims: bool = False):
         avg = np.empty((self._na, self.S), dtype=np.float64)
@@ -1083,9 +1095,10 @@ class FeatureDB:
     def write_avg(self, avg: np.ndarray, n_e: np.ndarray | None = None):
         a = np.ascontiguousarray(avg, dtype=np.float64)
         ne = None if n_e is None else np.ascontiguousarray(n_e, dtype=np.int32)
-        if a.size != self._na * self.S or (ne is not None and ne.size != a.size):
-            raise ValueError("avg / n_e must be [%d,%d]: what the database (or the search set in use) covers" % (self._na, self.S))
-        call("vq_db_write_avg", self._h, _np_ptr(a), _np_ptr(ne) if ne is not None else None)
+        with self.lock:
+            if a.size != self._na * self.S or (ne is not None and ne.size != a.size):
+                raise ValueError("avg / n_e must be [%d,%d]: what the database (or the search set in use) covers" % (self._na, self.S))
+            call("vq_db_write_avg", self._h, _np_ptr(a), _np_ptr(ne) if ne is not None else None)
 
     def scores(self) -> np.ndarray:
         out = np.empty(self._na, dtype=np.float64)
@@ -1116,22 +1129,25 @@ class FeatureDB:
 
     def select(self, threshold: float, lower: float):
         """Order-preserving partition (ticket.py:325-340): (match_rows, near_rows, near_argmax).  Partition and
-        copy-out are one locked call of the library, so handles shared between broker threads stay consistent."""
+        copy-out are one locked call of the library, so handles shared between broker threads stay consistent; ``self.lock`` keeps
+        it out of another thread's :meth:`query_round`, whose lists it would replace."""
         nm, nn, am = C.c_int64(), C.c_int64(), C.c_int64()
-        m = np.empty(max(self._na, 1), dtype=np.int64)
-        r = np.empty(max(self._na, 1), dtype=np.int64)
-        call("vq_db_select_rows", self._h, float(threshold), float(lower), _np_ptr(m), m.size, _np_ptr(r), r.size,
-             C.byref(nm), C.byref(nn), C.byref(am))
+        with self.lock:
+            m = np.empty(max(self._na, 1), dtype=np.int64)
+            r = np.empty(max(self._na, 1), dtype=np.int64)
+            call("vq_db_select_rows", self._h, float(threshold), float(lower), _np_ptr(m), m.size, _np_ptr(r), r.size,
+                 C.byref(nm), C.byref(nn), C.byref(am))
         return m[:nm.value].copy(), r[:nn.value].copy(), am.value
 
     def topk(self, k: int):
-        k = int(min(k, self._na))
-        if k <= 0 and self._na == 0:                          # an empty search set has no best clips
-            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
-        rows = np.empty(k, dtype=np.int64)
-        vals = np.empty(k, dtype=np.float64)
-        kk = C.c_int64()
-        call("vq_db_topk", self._h, k, _np_ptr(rows), _np_ptr(vals), C.byref(kk))
+        with self.lock:                                       # the radix form reuses (and invalidates) the selection lists of the handle
+            k = int(min(k, self._na))
+            if k <= 0 and self._na == 0:                      # an empty search set has no best clips
+                return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+            rows = np.empty(k, dtype=np.int64)
+            vals = np.empty(k, dtype=np.float64)
+            kk = C.c_int64()
+            call("vq_db_topk", self._h, k, _np_ptr(rows), _np_ptr(vals), C.byref(kk))
         return rows[:kk.value], vals[:kk.value]
 
     def min_score(self, rows: Sequence[int]) -> float:
