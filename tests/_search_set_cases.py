@@ -62,6 +62,26 @@ def tie_ks(scores, cap):
     return [k for k in ks if 1 <= k <= min(cap, scores.size)]
 
 
+ROUND_PREFIX = 1024
+
+
+def round_layout(Q, S, E, D, m=None, n=None):
+    """(off[12], start[17]) of a batched round's block as the comments of include/vq_amd_rounds.h (``n``: a whole-database round,
+    n_e once per database, off[11] = 0) and include/vq_amd_round_views.h (``m``: the rows of each query's piece, n_e once per piece,
+    off[11] = sum M) state them: nine pieces, each rounded up to 64 bytes, then off[9] = their bytes, off[10] = P."""
+    pieces = [n] * Q if m is None else list(m)
+    start = [0]
+    for q in range(16):
+        start.append(start[-1] + (pieces[q] if q < Q else 0))
+    sm = start[Q]
+    P = ROUND_PREFIX
+    sizes = [Q * S * E * D * 8, Q * 8 * 8, Q * 2 * 8, (n if m is None else sm) * S * 4, sm * S * 8, sm * 8, Q * 4 * 8, Q * P * 8, Q * P * 8]
+    off = [0]
+    for b in sizes:
+        off.append(off[-1] + (b + 63) // 64 * 64)
+    return off + [P, 0 if m is None else sm], start
+
+
 def np_select(scores, th, lower):
     v = np.asarray(scores)
     with np.errstate(invalid="ignore"):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import sim_oracle as so
-from _search_set_cases import np_select, same_bits
+from _search_set_cases import np_select, round_layout, same_bits
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12           # what tests/test_sim_gpu.py holds the batched pass to
@@ -139,6 +139,9 @@ def test_batched_round_against_single_rounds_oracle_and_numpy_partition(vqa, cus
     if Q > 2 and n >= 4100:
         bands[2] = (want_scores[2].min() - 1.0, want_scores[2].min() - 2.0)      # everything matches: longer than the prefix
 
+    off = (C.c_int64 * 12)()
+    vqa._lib.call("vq_db_batch_round_layout", db._h, Q, off)
+    assert list(off) == round_layout(Q, S, E, D, n=n)[0]
     got = db.query_round_batch(targets, weights, bands)
     assert len(got) == Q
     for q, r in enumerate(got):
@@ -290,8 +293,9 @@ def test_one_query_rounds_and_batched_rounds_from_two_threads(vqa):
 
 
 # ---------------------------------------------------------------------------------------------------------------- awkward inputs
-# fp32, S = 2, E = 3, D = 256, Q = 5 on both sides of kSelSmallN = 16 384: the one-workgroup selection and the three-pass one
-AWKWARD_N = [700, 16_400]
+# fp32, S = 2, E = 3, D = 256, Q = 5 on both sides of kSelSmallN = 16 384: the one-workgroup selection and the three-pass one, with the
+# last size of the first (16 384) and the first size of the second (16 385: nine blocks, the last holding one row)
+AWKWARD_N = [700, 16_384, 16_385, 16_400]
 
 
 def _lost_rows(n):
@@ -369,6 +373,8 @@ def test_batched_round_with_scores_exactly_on_the_band(vqa, n):
         bands[q] = (hi, lo)
     bands[0] = (first[0].scores[i], first[0].scores[j])
     bands[1] = (first[1].scores.max(), first[1].scores.max())
+    if n > 1024:                                              # a threshold below the minimum: all n rows match, longer than the prefix
+        bands[2] = (first[2].scores.min() - 1.0, first[2].scores.min() - 2.0)
     got = db.query_round_batch(targets, weights, bands)
     # the planted values are the scores this call partitioned, bit for bit
     assert all(same_bits(r.scores, f.scores) for r, f in zip(got, first))
@@ -377,6 +383,8 @@ def test_batched_round_with_scores_exactly_on_the_band(vqa, n):
     assert int((got[1].scores == got[1].scores.max()).sum()) == 1
     assert len(got[1].match_rows) == 1 and got[1].match_rows[0] == int(np.argmax(got[1].scores)) and len(got[1].near_rows) == 0
     assert got[1].near_argmax == -1
+    if n > 1024:                                              # the fetched list is every row, and the other queries' lists stay their own
+        assert len(got[2].match_rows) == n and (got[2].match_rows == np.arange(n)).all() and len(got[2].near_rows) == 0
     _check_partitions(got, bands)
     db.close()
 
@@ -392,6 +400,7 @@ def test_every_flag_subset_of_a_batched_round_through_the_c_abi(vqa, n):
     off = (C.c_int64 * 12)()
     vqa._lib.call("vq_db_batch_round_layout", db._h, Q, off)
     off = [int(v) for v in off]
+    assert off == round_layout(Q, S, E, D, n=n)[0]
     p = C.c_void_p()
     vqa._lib.call("vq_host_alloc", C.byref(p), off[9])
     raw = np.ctypeslib.as_array((C.c_ubyte * off[9]).from_address(p.value))

@@ -76,7 +76,7 @@ def test_order_key_has_one_definition():
     csrc = os.path.join(ROOT, "video-query-algorithms_amd", "csrc")
     found = [fn for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h")) and re.search(r"uint64_t\s+order_key\s*\(", open(os.path.join(csrc, fn)).read())]
     assert found == ["vq_select.h"]
-    for unit in ("vq_sim.hip", "vq_round_topk.hip"):
+    for unit in ("vq_sim.hip", "vq_rounds.hip", "vq_round_topk.hip"):
         assert '#include "vq_select.h"' in open(os.path.join(csrc, unit)).read(), unit
 
 

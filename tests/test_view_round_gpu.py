@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import sim_oracle as so
-from _search_set_cases import np_select, same_bits
+from _search_set_cases import np_select, round_layout, same_bits
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12           # what tests/test_batch_round_gpu.py holds the batched pass to
@@ -57,6 +57,9 @@ def families(n):
     for i in range(15):                                       # 100-row views, 1 000 rows apart
         if (i + 1) * 1000 <= n:
             fam["hundred%d" % i] = rows[i * 1000 + 17:i * 1000 + 117]
+    if n > 16_384:                                            # the last size of the one-workgroup selection, the first of the three passes
+        fam["cap"] = rows[:16_384]
+        fam["past_cap"] = rows[:16_385]
     if n > 135_000:
         fam["even"] = rows[::2]
         fam["long_run"] = rows[:135_000]
@@ -75,6 +78,8 @@ CASES = [
     # a whole-database query (three-pass selection) beside 100-row views (one-workgroup selection)
     (np.float32, 16, 16_400, 2, 1, 256, False, "rows", ["all_but_one", "whole"] + ["hundred%d" % i for i in range(14)]),
     (np.float32, 9, 4100, 2, 2, 1024, True, "tiled", ["all_but_one", "empty", "all_but_one", "mod37", "run", "edges", "whole", "mod37_b", "last"]),
+    # short and long pieces on both sides of kSelSmallN, an empty one and a whole one in one launch set
+    (np.float32, 5, 16_400, 1, 1, 256, False, "rows", ["cap", "past_cap", "empty", "whole", "first"]),
     # tiled, no view is whole: untouched tiles, and tiles touched in one clip (mod37, first, last)
     (np.float32, 16, 16_400, 2, 1, 1024, False, "tiled", ["run", "mod37", "first", "last", "mod37_b", "empty"] + ["hundred%d" % i for i in range(10)]),
     # no whole view and a union of more than 512 clips per compute unit: a second round of union tiles
@@ -139,6 +144,10 @@ def test_view_round_against_the_batched_round_single_rounds_oracle_and_numpy_par
         lowest = ref[2].scores[rows[2]].min()
         bands[2] = (lowest - 1.0, lowest - 2.0)               # everything matches: longer than the prefix
 
+    off, start = (C.c_int64 * 12)(), (C.c_int64 * 17)()
+    tokens = (C.c_int32 * Q)(*[-1 if s is None else db._sets[s].token for s in set_ids])
+    vqa._lib.call("vq_db_view_round_layout", db._h, Q, tokens, off, start)
+    assert (list(off), list(start)) == round_layout(Q, S, E, D, m=[r.size for r in rows])
     got = db.query_round_batch_sets(targets, weights, set_ids, bands)
     assert len(got) == Q
     union = np.unique(np.concatenate(rows))

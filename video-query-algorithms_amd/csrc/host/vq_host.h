@@ -3,6 +3,7 @@
 // tests/sanitize/host_main.cc for the sanitizer builds.
 #pragma once
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <string>
 
@@ -10,6 +11,7 @@ namespace vq {
 std::string& last_error_ref();
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }      // every piece of a host or device block starts on a 64-byte boundary
 
 inline int host_fail(int code, const char* fmt, ...) {
     char buf[1024];

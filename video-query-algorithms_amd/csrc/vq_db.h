@@ -1,10 +1,56 @@
 // The handle of a resident feature database (vq_db_*): what csrc/vq_sim.hip keeps per database, shared with the device loader of
-// feature CSV files (csrc/vq_csv.hip), which stores into the handle's block under the handle's lock.
+// feature CSV files (csrc/vq_csv.hip), which stores into the handle's block under the handle's lock, and with the units of the
+// batched rounds (csrc/vq_rounds.hip, csrc/vq_round_targets.hip, csrc/vq_round_topk.hip).
 #pragma once
 #include <mutex>
 #include <vector>
 
 #include "vq_common.h"
+
+constexpr int kBatchSlots = 16;            // queries of a batched scan or round
+constexpr int64_t kRoundPrefix = 1024;     // rows of each list that a round copies back next to the counts
+
+// The pieces of a batched round, for every kind of round: what a round is laid out by and what the handle remembers of the last one.
+// Query q's avg / scores / list entries are start[q] .. start[q + 1] of the concatenated pieces (a whole-database round: q N on);
+// the entries behind the last query repeat its end.  A piece of more than kSelSmallN entries has blocks bstart[q] .. bstart[q + 1] of the three-pass
+// selection's scratch, a shorter one has none.
+struct BatchRound {
+    int q = 0;                       // queries (0 on the handle: no round yet, or its lists are gone)
+    bool views = false, timed = false;
+    int64_t off[12] = {0};           // the host block: include/vq_amd_rounds.h, include/vq_amd_round_views.h
+    int64_t start[17] = {0};
+    int32_t bstart[17] = {0};
+    int64_t n0[16] = {0}, n1[16] = {0};      // the counts of the last partition per query (-1: that round did not partition)
+    int64_t rows0 = 0, rows1 = 0;    // byte offsets behind the image of the host block: the full match and near lists ...
+    int64_t cnt = 0, max = 0, arg = 0;       // ... and blk_cnt | blk_max | blk_arg
+    int64_t need = 0;                // bytes of the device block
+    int64_t m(int i) const { return start[i + 1] - start[i]; }
+};
+
+// The arguments of the 16-query passes (batch_fused_kernel, batch_view_kernel: csrc/vq_sim.hip).
+struct BatchFusedArgs {
+    const void* feats;
+    const double* t;          // [Q][NV][D]
+    const double* w;          // [Q][S]
+    const uint8_t* present;   // [n][S][E] or null
+    double* scores;           // [Q][n]
+    int64_t n;
+    int32_t Q, S, E, D;
+    double* avg;              // ROUND only: [Q][n][S]
+};
+
+// A round over the UNION of up to 16 row views (vq_db_query_round_views, include/vq_amd_round_views.h): n stays the database's N, the
+// tiles the pass walks are those of `items`, and query q's avg / scores are compact pieces that start at entry start[q].
+struct BatchViewArgs : BatchFusedArgs {
+    const int32_t* items;     // rows: the union's database rows, ascending, padded to a multiple of 16 with its last row | tiled: the tiles
+                              // the union touches, ascending | null: the whole database (a view of the round is -1)
+    const int64_t* counts;    // device, written by the plan: [0] rows of the union, [1] tiles it touches (read only with items)
+    const int32_t* inv;       // [16][inv_stride]: the position of a database row in query q's view, -1 = not a member (unused for a whole query)
+    int64_t inv_stride;
+    const int64_t* start;     // device [17]: the first entry of query q's piece
+    uint32_t whole;           // bit q: query q covers the whole database (position = row)
+    uint32_t members;         // bit q: query q's row list is in inv; a query with neither bit (an empty view) stores nothing
+};
 
 struct vq_db {
     std::mutex mu;
@@ -48,26 +94,14 @@ struct vq_db {
     double* batch_scores = nullptr;  // where the scores of the last batched scan start inside batch_buf
     int64_t batch_cap = 0;           // doubles
     int batch_q = 0;                 // queries of the last batched scan
-    // Batched rounds (vq_db_query_round_batch, include/vq_amd_rounds.h): ONE lazy allocation that starts with the image of the host
-    // block (queries | weights | bands | n_e | avg | scores | results | prefixes: what comes and goes in one copy each way) followed by
-    // the full match / near lists [Q][N] each and the per-block scratch of the three-pass selection.
+    // Batched rounds (csrc/vq_rounds.hip; include/vq_amd_rounds.h, vq_amd_round_views.h, vq_amd_round_fit.h): ONE lazy allocation that
+    // starts with the image of the host block (queries | weights | bands | n_e | avg | scores | results | prefixes: what comes and goes
+    // in one copy each way) followed by the full match / near lists and the per-block scratch of the three-pass selection; `round` says
+    // where each of these sits for the last round.
     char* bround_dev = nullptr;
     int64_t bround_cap = 0;          // bytes
-    int bround_q = 0;                // queries of the last batched round (0: none, or its lists are gone)
-    int64_t bround_rows0 = 0, bround_rows1 = 0;      // byte offsets of the full lists of the last round
-    int64_t bround_n0[16] = {0}, bround_n1[16] = {0};  // its counts per query (-1: that round did not partition)
     hipEvent_t bround_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // flag 8: start | pass done | selection done | copies done
-    bool bround_timed = false;
-    int64_t bround_qoff[16] = {0};   // where query q's full lists start inside the two list arrays (entries): q N, or a view round's start[q]
-    // The layout of the last batched round, for the calls of include/vq_amd_round_fit.h that work on its device data: the offsets of
-    // its block, the rows per query (bround_qoff[q] is also where query q's avg / scores entries start), whether it was a view
-    // round, and where the scratch of the three-pass selection sits (query q's blocks start at bround_bstart[q]; none for a piece
-    // of at most kSelSmallN rows).
-    int64_t bround_off[12] = {0};
-    int64_t bround_m[16] = {0};
-    bool bround_views = false;
-    int64_t bround_cnt = 0, bround_max = 0, bround_arg = 0;     // byte offsets of blk_cnt, blk_max, blk_arg
-    int32_t bround_bstart[17] = {0};
+    BatchRound round;
     // View rounds (vq_db_query_round_views, include/vq_amd_round_views.h): the plan's device block, allocated on the first one --
     // inv [16][stride] i32 | union rows [stride + 16] i32 | touched tiles [stride / 16] i32 | counts [2] i64 | start [17] i64 | the
     // per-block counts of the compaction [tiles / 256] int2 -- and what the last one covered
@@ -110,5 +144,17 @@ namespace vq {
 // caller holds the handle's lock and has its device current.  rows_dev: the same L row numbers already on the device (ordered on the
 // handle's stream) -- they are then read there and nothing is uploaded.  Shared with csrc/vq_round_targets.hip.
 int gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense, const int64_t* rows_dev = nullptr);
+
+// csrc/vq_sim.hip, for the rounds of csrc/vq_rounds.hip; the caller holds the handle's lock, has its device current and has checked
+// the shape (D in {256,512,768,1024}, S <= 8).  The 16-query pass of a round over the whole database: d_t [Q][NV][D], d_w [Q][8] ->
+// d_scores [Q][n], d_avg [Q][n][S].  The pass over the union of a round's views; max_tiles bounds the tiles its plan can hold.  The
+// handle's gather scratch, grown to at least `bytes`.
+int launch_round_pass(vq_db* db, int Q, const double* d_t, const double* d_w, double* d_scores, double* d_avg);
+int launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles);
+int ensure_grid_buf(vq_db* db, int64_t bytes);
+
+// csrc/vq_rounds.hip: what the batched rounds allocated on the handle (their device block, the plan of the view rounds, the events of
+// the timed ones) goes; for db_free, with the handle's device current.
+void free_round_state(vq_db* db);
 
 }  // namespace vq

@@ -40,8 +40,6 @@ constexpr int kTargetsMaxDraws = 64;       // draws per query
 constexpr int kTargetsLdsRows = 86;
 constexpr int kTargetsWsGroups = 256;      // workgroups of the scratch-area launch (one per CU): each owns one scratch slot and walks problems
 
-inline int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
-
 // off[11]: see include/vq_amd_round_targets.h
 void targets_layout(int Q, int64_t n_rows, int n_draws, int64_t n_entries, int64_t nvd, int64_t* off) {
     off[0] = 0;

@@ -32,8 +32,6 @@ constexpr int kTopkCap = 4096;             // the largest k: 48 KB of (key, posi
 constexpr int kTopkSortThreads = 1024;
 constexpr int kTopkHistBlocks = 256;       // workgroups per query of a histogram pass, at the most (each walks its piece grid-strided)
 
-inline int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
-
 // off[6]: see include/vq_amd_round_topk.h
 void topk_layout(int Q, int64_t k_max, int64_t* off) {
     off[0] = 0;
@@ -426,7 +424,7 @@ int vq_db_batch_round_topk(vq_db* db, int32_t n_queries, int64_t k_max, void* bl
     char* host = (char*)block;
     const int64_t* k = (const int64_t*)(host + off[0]);
     std::lock_guard<std::mutex> lk(db->mu);
-    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    if (db->round.q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
     // ---- every check, and the plan of the launches, on the host
     TopkBatchArgs a;
     a.bstart[0] = 0;
@@ -436,10 +434,10 @@ int vq_db_batch_round_topk(vq_db* db, int32_t n_queries, int64_t k_max, void* bl
     for (int q = 0; q < kTopkSlots; ++q) {
         const int64_t kq = q < Q ? k[q] : 0;
         VQ_REQUIRE(kq >= 0 && kq <= k_max, "query %d: k = %lld outside [0, k_max = %lld]", q, (long long)kq, (long long)k_max);
-        if (kq > 0 && q >= db->bround_q) return fail(VQ_E_STATE, "the last batched round had %d queries (k for query %d)", db->bround_q, q);
-        const int64_t m = kq > 0 ? db->bround_m[q] : 0;
+        if (kq > 0 && q >= db->round.q) return fail(VQ_E_STATE, "the last batched round had %d queries (k for query %d)", db->round.q, q);
+        const int64_t m = kq > 0 ? db->round.m(q) : 0;
         if (m > INT_MAX) return fail(VQ_E_UNSUPPORTED, "query %d: a batched top-k ranks at most %d positions (got %lld)", q, INT_MAX, (long long)m);
-        a.qoff[q] = db->bround_qoff[q];
+        a.qoff[q] = db->round.start[q];
         a.m[q] = m;
         int nb = 0;
         if (kq > 0) {
@@ -467,7 +465,7 @@ int vq_db_batch_round_topk(vq_db* db, int32_t n_queries, int64_t k_max, void* bl
     }
     char* base = db->btopk_buf;
     VQ_HIP(hipMemcpyAsync(base + off[0], host + off[0], (size_t)(off[1] - off[0]), hipMemcpyHostToDevice, db->stream));      // the k's
-    a.scores = (const double*)(db->bround_dev + db->bround_off[5]);
+    a.scores = (const double*)(db->bround_dev + db->round.off[5]);
     a.k = (const int64_t*)(base + off[0]);
     a.count = (int64_t*)(base + off[1]);
     a.rows = (int64_t*)(base + off[2]);

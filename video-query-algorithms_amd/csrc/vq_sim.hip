@@ -19,7 +19,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "vq_common.h"
+#include "vq_db.h"
+#include "vq_score.h"
 #include "vq_select.h"
 
 namespace vq {
@@ -38,17 +39,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
-}
-
-// ticket.py:172-180 -- same IEEE operations in the same order (contraction is off for this file).
-__device__ __forceinline__ double score_from_avg(const double* a, const double* w, int S) {
-    double ssum = 0.0, denom = 0.0;
-    for (int s = 0; s < S; ++s) {
-        const double term = w[s] * (1.0 - a[s]);
-        ssum = ssum + term * term;
-        denom = denom + w[s] * w[s];
-    }
-    return 1.0 - sqrt(ssum / denom);
 }
 
 // LDS image of the query: element k of vector v lives at lds_index(v, k).  Inside each 256-element
@@ -470,7 +460,6 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
 // (<= 1e-12, tested), not bit for bit.  (Round 2 ran this as ten slice launches into a [slice][query][clip] matrix plus a finalising
 // launch -- 2.6 GB written and read back per pass at cfg 4; batch_fused_kernel below replaced it in round 3 and was checked against
 // it bit for bit until the two-kernel form was removed in round 5.)
-constexpr int kBatchSlots = 16;
 #ifndef VQ_TILED_GROUP
 #define VQ_TILED_GROUP 4
 #endif
@@ -631,29 +620,8 @@ __global__ void scatter_rows_tiled_kernel(const float4* staged, float4* tiled, i
 // the wave while the last chunks of the current one are multiplied, so the loads are in flight across the two barriers (a
 // plain __syncthreads() does not wait for vector memory) and HBM stays busy while the matrix pipe waits for the new rows.
 // Tiles are dealt so that a short last round spreads over ALL workgroups (tile = base + slot * gridDim + block).
-struct BatchFusedArgs {
-    const void* feats;
-    const double* t;          // [Q][NV][D]
-    const double* w;          // [Q][S]
-    const uint8_t* present;   // [n][S][E] or null
-    double* scores;           // [Q][n]
-    int64_t n;
-    int32_t Q, S, E, D;
-    double* avg;              // ROUND only: [Q][n][S]
-};
+// BatchFusedArgs and BatchViewArgs (the pass over the union of a round's views): csrc/vq_db.h
 
-// A round over the UNION of up to 16 row views (vq_db_query_round_views, include/vq_amd_round_views.h): n stays the database's N, the
-// tiles the pass walks are those of `items`, and query q's avg / scores are compact pieces that start at entry start[q].
-struct BatchViewArgs : BatchFusedArgs {
-    const int32_t* items;     // rows: the union's database rows, ascending, padded to a multiple of 16 with its last row | tiled: the tiles
-                              // the union touches, ascending | null: the whole database (a view of the round is -1)
-    const int64_t* counts;    // device, written by the plan: [0] rows of the union, [1] tiles it touches (read only with items)
-    const int32_t* inv;       // [16][inv_stride]: the position of a database row in query q's view, -1 = not a member (unused for a whole query)
-    int64_t inv_stride;
-    const int64_t* start;     // device [17]: the first entry of query q's piece
-    uint32_t whole;           // bit q: query q covers the whole database (position = row)
-    uint32_t members;         // bit q: query q's row list is in inv; a query with neither bit (an empty view) stores nothing
-};
 
 // Loads whose address is wave-uniform and whose memory no launch in flight writes (the plan of a view round): through the constant
 // address space they are scalar loads for certain, so they never enter the in-order vector-memory queue between the feature loads
@@ -1102,86 +1070,6 @@ __global__ void loss_surface_kernel(const double* avg, const double* w_grid, con
     }
 }
 
-// ---- the same two steps for the queries of a batched round, on the avg that round left on the device (include/vq_amd_round_fit.h) ----
-// loss_surface_kernel for every query with labels in ONE launch: block (g, q) = grid weight g of query q, over the avg entries of that
-// query (qoff[q] on).  The labels walk through LDS in chunks of kFitChunk: all threads fill the chunk's scores, then thread t adds the
-// chunk's terms to its running sum for threshold t IN LABEL ORDER -- the chunking changes nothing in a cell's sequence of fp64
-// operations, so a cell has loss_surface_kernel's bits on the same avg, for any number of labels in 32 KB of LDS.
-constexpr int kFitChunk = 4096, kFitThreads = 256, kFitMaxGrid = 64;
-struct FitBatchArgs {
-    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round
-    const double* w_grid;     // [Q][G][8]
-    const double* th_grid;    // [Q][T]
-    const double* ballast;    // [Q]
-    const int64_t* rows;      // [sum L]: positions inside each query's piece
-    const double* labels;     // [sum L]
-    double* out;              // [Q][G][T]
-    int64_t qoff[16];         // the first avg entry of query q
-    int64_t lstart[17];       // the first label of query q (lstart[q + 1] - lstart[q] = L_q; 0: nothing to do)
-    int G, T, S;
-};
-
-__global__ __launch_bounds__(kFitThreads) void loss_surface_batch_kernel(FitBatchArgs a) {
-    __shared__ double ls_scores[kFitChunk];
-    const int g = blockIdx.x, q = blockIdx.y, S = a.S;
-    const int64_t l0 = a.lstart[q], L = a.lstart[q + 1] - l0;
-    if (L <= 0) return;                                        // the whole workgroup: a skipped query writes nothing
-    double w[8];
-    for (int s = 0; s < S; ++s) w[s] = a.w_grid[((int64_t)q * a.G + g) * 8 + s];
-    const int t = threadIdx.x;
-    const bool mine = t < a.T;                                 // T <= kFitMaxGrid < kFitThreads: one thread per threshold
-    const double th = mine ? a.th_grid[q * a.T + t] : 0.0;
-    const double ballast = a.ballast[q];
-    const double* avg = a.avg + a.qoff[q] * S;
-    double surf = 0.5 * th;
-    for (int64_t c0 = 0; c0 < L; c0 += kFitChunk) {
-        const int len = (int)(L - c0 < kFitChunk ? L - c0 : kFitChunk);
-        for (int l = threadIdx.x; l < len; l += kFitThreads) {
-            double av[8];
-            const int64_t row = a.rows[l0 + c0 + l];
-            for (int s = 0; s < S; ++s) av[s] = avg[row * S + s];
-            ls_scores[l] = score_from_avg(av, w, S);
-        }
-        __syncthreads();
-        if (mine) {
-            for (int l = 0; l < len; ++l) {
-                const double y = a.labels[l0 + c0 + l];
-                const double margin = ls_scores[l] - th;
-                const double h = margin < 0.0 ? 0.0 : (margin >= 0.0 ? 1.0 : margin);     // np.heaviside(margin, 1); NaN stays NaN
-                const double c = 1.0 + y * ballast;
-                surf = surf + ((h - y) * margin) * c;
-            }
-        }
-        __syncthreads();                                       // the next chunk overwrites the scores
-    }
-    if (mine) a.out[((int64_t)q * a.G + g) * a.T + t] = surf;
-}
-
-// rescore_kernel for the masked queries of a batched round: query q = blockIdx.y rescores its m[q] avg entries under w[q] into the
-// round's own score array; a query outside the mask is left alone.
-struct RescoreBatchArgs {
-    const double* avg;
-    const double* w;          // [16][8]
-    double* scores;
-    int64_t qoff[16];         // the first avg / score entry of query q
-    int64_t m[16];
-    uint32_t mask;
-    int S;
-};
-
-__global__ __launch_bounds__(256) void rescore_batch_kernel(RescoreBatchArgs a) {
-    const int q = blockIdx.y, S = a.S;
-    if (!((a.mask >> q) & 1u)) return;
-    double w[8];
-    for (int s = 0; s < S; ++s) w[s] = a.w[q * 8 + s];
-    const int64_t m = a.m[q], base = a.qoff[q];
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < m; c += (int64_t)gridDim.x * blockDim.x) {
-        double av[8];
-        for (int s = 0; s < S; ++s) av[s] = a.avg[(base + c) * S + s];
-        a.scores[base + c] = score_from_avg(av, w, S);
-    }
-}
-
 // target_clip.py:311-313: t = r / (r . r), one block per (s,e) vector of row `row`, fp64 throughout.
 // element k of vector (row, v): row-major, or inside the tiled layout [tile][v][k / 4][row % 16][4]
 __device__ __forceinline__ int64_t feat_index(bool tiled, int64_t row, int v, int k, int NV, int D) {
@@ -1239,98 +1127,12 @@ __global__ void generate_kernel(T* feats, int64_t total, uint64_t seed_mul, uint
 // ------------------------------------------------------------------------------------------------
 // selection: stable partition of the score array (ticket.py:325-340)
 // ------------------------------------------------------------------------------------------------
-// SEL_ITEMS / SEL_BLOCK / SEL_CHUNK, order_key, the two predicates (SelPred) and block_scan_excl2: csrc/vq_select.h
-
-// pass 1: per-block counts of both classes + block-local first-argmax of class 1 (near band)
-__device__ __forceinline__ void select_count_block(const double* scores, int64_t n, SelPred pred, int2* blk_cnt, double* blk_max,
-                                                   int64_t* blk_arg) {
-    const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + (int64_t)threadIdx.x * SEL_ITEMS;
-    int2 cnt = make_int2(0, 0);
-    double bmax = -INFINITY;
-    int64_t barg = -1;
-#pragma unroll
-    for (int i = 0; i < SEL_ITEMS; ++i) {
-        const int64_t r = base + i;
-        if (r < n) {
-            const double v = scores[r];
-            const int f = pred(v);
-            cnt.x += f & 1;
-            cnt.y += (f >> 1) & 1;
-            if ((f & 2) && (barg < 0 || v > bmax)) {
-                bmax = v;
-                barg = r;
-            }
-        }
-    }
-    int2 tot;
-    block_scan_excl2(cnt, &tot);
-    // first-argmax across the block: larger value wins, ties go to the smaller row
-    __shared__ double smax[SEL_BLOCK];
-    __shared__ int64_t sarg[SEL_BLOCK];
-    smax[threadIdx.x] = bmax;
-    sarg[threadIdx.x] = barg;
-    __syncthreads();
-    for (int off = SEL_BLOCK / 2; off >= 1; off >>= 1) {
-        if (threadIdx.x < off) {
-            const double ov = smax[threadIdx.x + off];
-            const int64_t oa = sarg[threadIdx.x + off];
-            const int64_t ma = sarg[threadIdx.x];
-            if (oa >= 0 && (ma < 0 || ov > smax[threadIdx.x] || (ov == smax[threadIdx.x] && oa < ma))) {
-                smax[threadIdx.x] = ov;
-                sarg[threadIdx.x] = oa;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        blk_cnt[blockIdx.x] = tot;
-        blk_max[blockIdx.x] = smax[0];
-        blk_arg[blockIdx.x] = sarg[0];
-    }
-}
+// SEL_ITEMS / SEL_BLOCK / SEL_CHUNK, order_key, the two predicates (SelPred), block_scan_excl2 and the blocks of the three passes and of
+// the one-workgroup form (n <= kSelSmallN): csrc/vq_select.h.  The partitions of the batched rounds: csrc/vq_rounds.hip
 
 __global__ __launch_bounds__(SEL_BLOCK) void select_count_kernel(const double* scores, int64_t n, SelPred pred,
                                                                   int2* blk_cnt, double* blk_max, int64_t* blk_arg) {
     select_count_block(scores, n, pred, blk_cnt, blk_max, blk_arg);
-}
-
-// pass 2 (one block): exclusive scan of the block counts, totals and global first-argmax
-// result[0] = n_class0, result[1] = n_class1, result[2] = argmax row (-1 if none)
-__device__ __forceinline__ void select_scan_block(int2* blk_cnt, const double* blk_max, const int64_t* blk_arg, int nblk, int64_t* result,
-                                                  int64_t limit1 /* cap on class-1 picks, <0 = none */) {
-    __shared__ int2 carry;
-    __shared__ double gmax;
-    __shared__ int64_t garg;
-    if (threadIdx.x == 0) {
-        carry = make_int2(0, 0);
-        gmax = -INFINITY;
-        garg = -1;
-    }
-    __syncthreads();
-    for (int b0 = 0; b0 < nblk; b0 += SEL_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        int2 v = b < nblk ? blk_cnt[b] : make_int2(0, 0);
-        int2 tot;
-        const int2 ex = block_scan_excl2(v, &tot);
-        const int2 c0 = carry;
-        if (b < nblk) blk_cnt[b] = make_int2(c0.x + ex.x, c0.y + ex.y);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            carry = make_int2(c0.x + tot.x, c0.y + tot.y);
-            for (int i = b0; i < min(nblk, b0 + SEL_BLOCK); ++i) {   // serial, in order: first max wins
-                if (blk_arg[i] >= 0 && (garg < 0 || blk_max[i] > gmax)) {
-                    gmax = blk_max[i];
-                    garg = blk_arg[i];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        result[0] = carry.x;
-        result[1] = (limit1 >= 0 && carry.y > limit1) ? limit1 : carry.y;
-        result[2] = garg;
-    }
 }
 
 __global__ __launch_bounds__(SEL_BLOCK) void select_scan_kernel(int2* blk_cnt, const double* blk_max,
@@ -1339,352 +1141,15 @@ __global__ __launch_bounds__(SEL_BLOCK) void select_scan_kernel(int2* blk_cnt, c
     select_scan_block(blk_cnt, blk_max, blk_arg, nblk, result, limit1);
 }
 
-// pass 3: scatter rows in original order.  class-1 rows beyond `limit1` (in order) are dropped.
-__device__ __forceinline__ void select_scatter_block(const double* scores, int64_t n, SelPred pred, const int2* blk_off, int64_t* out0,
-                                                     int64_t* out1, int64_t limit1, int64_t* pre0, int64_t* pre1, int64_t prefix) {
-    const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + (int64_t)threadIdx.x * SEL_ITEMS;
-    int flags[SEL_ITEMS];
-    int2 cnt = make_int2(0, 0);
-#pragma unroll
-    for (int i = 0; i < SEL_ITEMS; ++i) {
-        const int64_t r = base + i;
-        flags[i] = r < n ? pred(scores[r]) : 0;
-        cnt.x += flags[i] & 1;
-        cnt.y += (flags[i] >> 1) & 1;
-    }
-    int2 tot;
-    const int2 ex = block_scan_excl2(cnt, &tot);
-    int64_t o0 = (int64_t)blk_off[blockIdx.x].x + ex.x;
-    int64_t o1 = (int64_t)blk_off[blockIdx.x].y + ex.y;
-#pragma unroll
-    for (int i = 0; i < SEL_ITEMS; ++i) {
-        if (flags[i] & 1) {
-            if (o0 < prefix) pre0[o0] = base + i;            // the head of each list a second time, next to the counts (one copy back)
-            out0[o0++] = base + i;
-        }
-        if (flags[i] & 2) {
-            if (limit1 < 0 || o1 < limit1) {
-                out1[o1] = base + i;
-                if (o1 < prefix) pre1[o1] = base + i;
-            }
-            ++o1;
-        }
-    }
-}
-
 __global__ __launch_bounds__(SEL_BLOCK) void select_scatter_kernel(const double* scores, int64_t n, SelPred pred,
                                                                     const int2* blk_off, int64_t* out0, int64_t* out1,
                                                                     int64_t limit1, int64_t* pre0, int64_t* pre1, int64_t prefix) {
     select_scatter_block(scores, n, pred, blk_off, out0, out1, limit1, pre0, pre1, prefix);
 }
 
-// The three passes above as ONE launch of one workgroup for a small database (n <= kSelSmallN): a thread owns a run of consecutive
-// rows, counts / first-arg-max / offsets meet in LDS.  Same lists, same counts, same arg-max as the three-kernel form (tested).
-constexpr int kSelSmallN = 16384, kSelSmallThreads = 1024;
-__device__ __forceinline__ void select_small_block(const double* scores, int n, SelPred pred, int64_t* result, int64_t* out0, int64_t* out1,
-                                                   int64_t* pre0, int64_t* pre1, int prefix) {
-    __shared__ int2 s_wave[kSelSmallThreads / 64];
-    __shared__ double s_max[kSelSmallThreads / 64];
-    __shared__ int s_arg[kSelSmallThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int per = (n + kSelSmallThreads - 1) / kSelSmallThreads;          // <= 16
-    const int r0 = tid * per, r1 = min(n, r0 + per);
-    int2 cnt = make_int2(0, 0);
-    unsigned flags = 0;                                                     // 2 bits per row of the run
-    double bmax = -INFINITY;
-    int barg = -1;
-    for (int r = r0; r < r1; ++r) {
-        const double v = scores[r];
-        const int f = pred(v);
-        flags |= (unsigned)f << (2 * (r - r0));
-        cnt.x += f & 1;
-        cnt.y += (f >> 1) & 1;
-        if ((f & 2) && (barg < 0 || v > bmax)) {                             // first maximum of the run
-            bmax = v;
-            barg = r;
-        }
-    }
-    int2 inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int ax = __shfl_up(inc.x, off, 64), ay = __shfl_up(inc.y, off, 64);
-        if (lane >= off) {
-            inc.x += ax;
-            inc.y += ay;
-        }
-    }
-    // first arg-max across the wave: larger value wins, ties go to the smaller row
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ov = __shfl_down(bmax, off, 64);
-        const int oa = __shfl_down(barg, off, 64);
-        if (lane + off < 64 && oa >= 0 && (barg < 0 || ov > bmax || (ov == bmax && oa < barg))) {
-            bmax = ov;
-            barg = oa;
-        }
-    }
-    if (lane == 63) s_wave[wid] = inc;
-    if (lane == 0) {
-        s_max[wid] = bmax;
-        s_arg[wid] = barg;
-    }
-    __syncthreads();
-    int2 base = make_int2(0, 0), tot = make_int2(0, 0);
-    for (int i = 0; i < kSelSmallThreads / 64; ++i) {
-        if (i < wid) {
-            base.x += s_wave[i].x;
-            base.y += s_wave[i].y;
-        }
-        tot.x += s_wave[i].x;
-        tot.y += s_wave[i].y;
-    }
-    int o0 = base.x + inc.x - cnt.x, o1 = base.y + inc.y - cnt.y;
-    for (int r = r0; r < r1; ++r) {
-        const unsigned f = (flags >> (2 * (r - r0))) & 3u;
-        if (f & 1u) {
-            if (o0 < prefix) pre0[o0] = r;
-            out0[o0++] = r;
-        }
-        if (f & 2u) {
-            if (o1 < prefix) pre1[o1] = r;
-            out1[o1++] = r;
-        }
-    }
-    if (tid == 0) {
-        double gmax = -INFINITY;
-        int garg = -1;
-        for (int i = 0; i < kSelSmallThreads / 64; ++i)                      // in row order: the first maximum wins
-            if (s_arg[i] >= 0 && (garg < 0 || s_max[i] > gmax)) {
-                gmax = s_max[i];
-                garg = s_arg[i];
-            }
-        result[0] = tot.x;
-        result[1] = tot.y;
-        result[2] = garg;
-    }
-}
-
 __global__ __launch_bounds__(kSelSmallThreads) void select_small_kernel(const double* scores, int n, SelPred pred, int64_t* result, int64_t* out0,
                                                                         int64_t* out1, int64_t* pre0, int64_t* pre1, int prefix) {
     select_small_block(scores, n, pred, result, out0, out1, pre0, pre1, prefix);
-}
-
-// ---- the same partition for the Q score rows of a batched round (vq_db_query_round_batch): query q = blockIdx.y partitions scores[q][n]
-// under its own band[q] = (threshold, lower) into its own rows of every output.  The blocks above, unchanged: per query the lists,
-// counts and arg-max are those of the one-query launches on that row of scores.
-struct SelBatchArgs {
-    const double* scores;     // [Q][n]
-    const double* band;       // [Q][2]: threshold, lower
-    int64_t n;
-    int nblk;                 // blocks of SEL_CHUNK rows per query (three-pass form)
-    int2* blk_cnt;            // [Q][nblk]
-    double* blk_max;          // [Q][nblk]
-    int64_t* blk_arg;         // [Q][nblk]
-    int64_t* result;          // [Q][4]: n_match, n_near, near_argmax, 0 (cleared by the host)
-    int64_t* out0;            // [Q][n] match rows
-    int64_t* out1;            // [Q][n] near rows
-    int64_t* pre0;            // [Q][prefix]
-    int64_t* pre1;            // [Q][prefix]
-    int64_t prefix;
-};
-
-__device__ __forceinline__ SelPred batch_pred(const SelBatchArgs& a, int q) {
-    SelPred pred;
-    pred.mode = 0;
-    pred.th = a.band[2 * q];
-    pred.lower = a.band[2 * q + 1];
-    pred.pivot = 0;
-    return pred;
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_count_batch_kernel(SelBatchArgs a) {
-    const int q = blockIdx.y;
-    select_count_block(a.scores + (int64_t)q * a.n, a.n, batch_pred(a, q), a.blk_cnt + (int64_t)q * a.nblk, a.blk_max + (int64_t)q * a.nblk,
-                       a.blk_arg + (int64_t)q * a.nblk);
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_scan_batch_kernel(SelBatchArgs a) {
-    const int q = blockIdx.x;                                               // one workgroup per query
-    select_scan_block(a.blk_cnt + (int64_t)q * a.nblk, a.blk_max + (int64_t)q * a.nblk, a.blk_arg + (int64_t)q * a.nblk, a.nblk, a.result + 4 * q, -1);
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_batch_kernel(SelBatchArgs a) {
-    const int q = blockIdx.y;
-    select_scatter_block(a.scores + (int64_t)q * a.n, a.n, batch_pred(a, q), a.blk_cnt + (int64_t)q * a.nblk, a.out0 + (int64_t)q * a.n,
-                         a.out1 + (int64_t)q * a.n, -1, a.pre0 + q * a.prefix, a.pre1 + q * a.prefix, a.prefix);
-}
-
-__global__ __launch_bounds__(kSelSmallThreads) void select_small_batch_kernel(SelBatchArgs a) {
-    const int q = blockIdx.x;                                               // one workgroup per query, n <= kSelSmallN
-    select_small_block(a.scores + (int64_t)q * a.n, (int)a.n, batch_pred(a, q), a.result + 4 * q, a.out0 + (int64_t)q * a.n, a.out1 + (int64_t)q * a.n,
-                       a.pre0 + q * a.prefix, a.pre1 + q * a.prefix, (int)a.prefix);
-}
-
-// n_e of a batched round: the splits present per (clip, stream) under the handle's mask -- the same for every query of the pass
-__global__ __launch_bounds__(256) void batch_ne_kernel(const uint8_t* present, int32_t* ne, int64_t total /* n * S */, int E) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int c = E;
-    if (present) {
-        c = 0;
-        for (int e = 0; e < E; ++e) c += present[i * E + e] != 0 ? 1 : 0;
-    }
-    ne[i] = c;
-}
-
-// ---- a batched round over one row view per query (vq_db_query_round_views, include/vq_amd_round_views.h) ---------------------------------
-// THE PLAN, built on the device per call: inv[q][row] = the position of database row `row` in query q's view (-1: not a member),
-// filled by scattering each view's resident row list; then the union of the views -- its rows (row-major databases) or the tiles it
-// touches (tiled ones) -- by a stable compaction of "some query holds this row": count / scan / scatter, a thread per tile of 16 rows.
-struct ViewPlanArgs {
-    const int64_t* rows[16];  // the resident row list of query q's view; null: the whole database, or an empty view
-    int64_t m[16];            // the rows of query q's piece (N for the whole database)
-    int64_t start[17];        // the first entry of query q's piece; start[Q] = the sum of m
-    int32_t Q;
-    int64_t n, stride;        // the database's rows; the rows of inv per query (n rounded up to whole tiles)
-    int32_t* inv;             // [16][stride]
-    int64_t* start_dev;       // [17]: start, for the kernels that index it per lane
-};
-
-__global__ __launch_bounds__(256) void view_scatter_kernel(ViewPlanArgs a) {
-    const int q = blockIdx.y;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a.start_dev[q] = a.start[q];
-        if (q == a.Q - 1) a.start_dev[a.Q] = a.start[a.Q];
-    }
-    const int64_t* rows = a.rows[q];
-    if (!rows) return;
-    const int64_t m = a.m[q];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
-        a.inv[(int64_t)q * a.stride + rows[i]] = (int32_t)i;
-}
-
-struct ViewUnionArgs {
-    const int32_t* inv;       // [16][stride], stride % 16 == 0, -1 behind row n
-    int64_t stride;
-    int64_t ntiles;           // tiles of the database
-    uint32_t members;         // bit q: query q has a row list scattered into inv
-    int2* blk;                // [nblk]: per block of 256 tiles (union rows, touched tiles) -> their exclusive scan
-    int nblk;
-    int32_t* rows_out;        // the union's rows, ascending, padded to a multiple of 16 with the last one | null
-    int32_t* tiles_out;       // the touched tiles, ascending | null
-    int64_t* counts;          // [0] union rows, [1] touched tiles
-};
-
-// bit i: row 16 tile + i is in some view of the round
-__device__ __forceinline__ unsigned view_union_flags(const ViewUnionArgs& a, int64_t tile) {
-    unsigned f = 0;
-    if (tile >= a.ntiles) return 0;
-    for (int q = 0; q < kBatchSlots; ++q) {
-        if (!((a.members >> q) & 1u)) continue;
-        const int4* p = reinterpret_cast<const int4*>(a.inv + (int64_t)q * a.stride + tile * 16);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int4 v = p[g];
-            f |= (v.x >= 0 ? 1u : 0u) << (4 * g) | (v.y >= 0 ? 2u : 0u) << (4 * g) | (v.z >= 0 ? 4u : 0u) << (4 * g) | (v.w >= 0 ? 8u : 0u) << (4 * g);
-        }
-    }
-    return f;
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void view_union_count_kernel(ViewUnionArgs a) {
-    const unsigned f = view_union_flags(a, (int64_t)blockIdx.x * SEL_BLOCK + threadIdx.x);
-    int2 tot;
-    block_scan_excl2(make_int2(__popc(f), f ? 1 : 0), &tot);
-    if (threadIdx.x == 0) a.blk[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void view_union_scan_kernel(ViewUnionArgs a) {   // one workgroup
-    __shared__ int2 carry;
-    if (threadIdx.x == 0) carry = make_int2(0, 0);
-    __syncthreads();
-    for (int b0 = 0; b0 < a.nblk; b0 += SEL_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        int2 tot;
-        const int2 ex = block_scan_excl2(b < a.nblk ? a.blk[b] : make_int2(0, 0), &tot);
-        const int2 c0 = carry;
-        if (b < a.nblk) a.blk[b] = make_int2(c0.x + ex.x, c0.y + ex.y);
-        __syncthreads();
-        if (threadIdx.x == 0) carry = make_int2(c0.x + tot.x, c0.y + tot.y);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.counts[0] = carry.x;
-        a.counts[1] = carry.y;
-    }
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void view_union_scatter_kernel(ViewUnionArgs a) {
-    const int64_t tile = (int64_t)blockIdx.x * SEL_BLOCK + threadIdx.x;
-    const unsigned f = view_union_flags(a, tile);
-    int2 tot;
-    const int2 ex = block_scan_excl2(make_int2(__popc(f), f ? 1 : 0), &tot);
-    int64_t o = (int64_t)a.blk[blockIdx.x].x + ex.x;
-    if (a.tiles_out && f) a.tiles_out[(int64_t)a.blk[blockIdx.x].y + ex.y] = (int32_t)tile;
-    if (a.rows_out && f) {
-        int32_t last = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if ((f >> i) & 1u) a.rows_out[o++] = last = (int32_t)(tile * 16 + i);
-        const int64_t total = a.counts[0];                    // written by the scan launch before this one
-        if (o == total)                                       // the thread that holds the union's last row pads the last virtual tile with it
-            for (int64_t k = total; k < (total + 15) / 16 * 16; ++k) a.rows_out[k] = last;
-    }
-}
-
-// n_e per query: the splits present per (position of the view, stream), read by database row
-__global__ __launch_bounds__(256) void view_ne_kernel(ViewPlanArgs a, const uint8_t* present, int32_t* ne, int S, int E) {
-    const int q = blockIdx.y;
-    const int64_t* rows = a.rows[q];
-    const int64_t total = a.m[q] * S;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t pos = i / S;
-        const int s = (int)(i - pos * S);
-        int c = E;
-        if (present) {
-            const int64_t row = rows ? rows[pos] : pos;
-            c = 0;
-            for (int e = 0; e < E; ++e) c += present[(row * S + s) * E + e] != 0 ? 1 : 0;
-        }
-        ne[(a.start[q] + pos) * S + s] = c;
-    }
-}
-
-// The partition of select_*_batch_kernel with a length and an offset per query: query q partitions its piece scores[start[q] ..
-// start[q + 1]) into positions of its view.  The one-workgroup form for a piece of at most kSelSmallN entries, the three passes for a
-// longer one, per query: a workgroup of the form its query does not take returns at once.
-struct SelViewArgs {
-    SelBatchArgs b;           // scores, out0, out1: the concatenated pieces; blk_*: the blocks of the long pieces, query after query
-    int64_t start[17];
-    int32_t bstart[17];       // the first block of query q (a short piece has none)
-};
-
-__global__ __launch_bounds__(kSelSmallThreads) void select_small_view_kernel(SelViewArgs v) {
-    const int q = blockIdx.x;
-    const int64_t s0 = v.start[q], m = v.start[q + 1] - s0;
-    if (m > kSelSmallN) return;
-    select_small_block(v.b.scores + s0, (int)m, batch_pred(v.b, q), v.b.result + 4 * q, v.b.out0 + s0, v.b.out1 + s0, v.b.pre0 + q * v.b.prefix,
-                       v.b.pre1 + q * v.b.prefix, (int)v.b.prefix);
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_count_view_kernel(SelViewArgs v) {
-    const int q = blockIdx.y, b0 = v.bstart[q];
-    if ((int)blockIdx.x >= v.bstart[q + 1] - b0) return;
-    select_count_block(v.b.scores + v.start[q], v.start[q + 1] - v.start[q], batch_pred(v.b, q), v.b.blk_cnt + b0, v.b.blk_max + b0, v.b.blk_arg + b0);
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_scan_view_kernel(SelViewArgs v) {
-    const int q = blockIdx.x, b0 = v.bstart[q], nb = v.bstart[q + 1] - b0;
-    if (nb == 0) return;
-    select_scan_block(v.b.blk_cnt + b0, v.b.blk_max + b0, v.b.blk_arg + b0, nb, v.b.result + 4 * q, -1);
-}
-
-__global__ __launch_bounds__(SEL_BLOCK) void select_scatter_view_kernel(SelViewArgs v) {
-    const int q = blockIdx.y, b0 = v.bstart[q];
-    if ((int)blockIdx.x >= v.bstart[q + 1] - b0) return;
-    const int64_t s0 = v.start[q];
-    select_scatter_block(v.b.scores + s0, v.start[q + 1] - s0, batch_pred(v.b, q), v.b.blk_cnt + b0, v.b.out0 + s0, v.b.out1 + s0, -1,
-                         v.b.pre0 + q * v.b.prefix, v.b.pre1 + q * v.b.prefix, v.b.prefix);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1835,36 +1300,29 @@ __global__ void gather_scores_kernel(const double* scores, const int64_t* rows, 
 // The results of a query round, device block and (behind the query and the weights) host block alike: avg [N][S] f64 | ne [N][S] i32 |
 // scores [N] f64 | result [4] i64 (n_match, n_near, near_argmax, 0) | first kRoundPrefix match rows | first kRoundPrefix near rows;
 // every piece starts on a 64-byte boundary.  off[0..5] = the pieces, off[6] = bytes.
-constexpr int64_t kRoundPrefix = 1024;
 static void round_layout(int64_t n, int S, int64_t off[8]) {
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
     off[0] = 0;
-    off[1] = off[0] + up(n * S * 8);
-    off[2] = off[1] + up(n * S * 4);
-    off[3] = off[2] + up(n * 8);
+    off[1] = off[0] + up64(n * S * 8);
+    off[2] = off[1] + up64(n * S * 4);
+    off[3] = off[2] + up64(n * 8);
     off[4] = off[3] + 64;
     off[5] = off[4] + kRoundPrefix * 8;
     off[6] = off[5] + kRoundPrefix * 8;
     off[7] = 0;
 }
 
-#include "vq_db.h"      // struct vq_db
-
 static int db_free(vq_db* db) {
     if (db->owns_feats && db->feats) (void)hipFree(db->feats);
     void* ptrs[] = {db->present, db->t,       db->sims,  db->round_dev, db->blk_cnt,
-                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf, db->bround_dev, db->vround_plan,
+                    db->blk_max, db->blk_arg, db->rows0, db->rows1, db->tk_state, db->tk_hist, db->grid_buf, db->batch_buf,
                     db->targets_buf, db->targets_ws, db->btopk_buf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : db->bround_ev)
-        if (ev) (void)hipEventDestroy(ev);
+    free_round_state(db);
     for (auto& v : db->views)
         if (v.rows) (void)hipFree(v.rows);
     return VQ_OK;
 }
-
-static int ensure_grid_buf(vq_db* db, int64_t bytes);
 
 // rows (by number) -> a dense row-major [L][S][E][D] block in the handle's scratch, whatever the layout; caller holds the lock
 int vq::gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense, const int64_t* rows_dev) {
@@ -2492,6 +1950,10 @@ static int launch_fused_pass(vq_db* db, int Q, const double* d_t, const double* 
     return VQ_OK;
 }
 
+int vq::launch_round_pass(vq_db* db, int Q, const double* d_t, const double* d_w, double* d_scores, double* d_avg) {
+    return launch_fused_pass<true>(db, Q, d_t, d_w, d_scores, d_avg);
+}
+
 extern "C" {
 
 int vq_db_scan_batch(vq_db* db, int32_t n_queries, const double* t_host, const double* w_host, double* scores_host) {
@@ -2670,7 +2132,7 @@ int vq_db_write_avg(vq_db* db, const double* avg_host, const int32_t* ne_host) {
 }
 
 }  // extern "C"
-static int ensure_grid_buf(vq_db* db, int64_t bytes) {
+int vq::ensure_grid_buf(vq_db* db, int64_t bytes) {
     if (db->grid_cap >= bytes) return VQ_OK;
     if (db->grid_buf) VQ_HIP(hipFree(db->grid_buf));
     db->grid_buf = nullptr;
@@ -2798,8 +2260,7 @@ int vq_host_free(void* ptr) {
 
 int vq_db_round_layout(vq_db* db, int64_t off[10]) {
     VQ_REQUIRE(db && off, "NULL argument");
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
-    const int64_t head = up((int64_t)db->S * db->E * db->D * 8) + 64;         // query | weights [8]
+    const int64_t head = up64((int64_t)db->S * db->E * db->D * 8) + 64;         // query | weights [8]
     off[0] = 0;
     off[1] = head - 64;
     for (int i = 0; i < 6; ++i) off[2 + i] = head + db->round_off[i];
@@ -2900,177 +2361,9 @@ static int fetch_selected(vq_db* db, int64_t* match_rows_host, int64_t cap_match
     return VQ_OK;
 }
 
-// ---- batched rounds (include/vq_amd_rounds.h) ----------------------------------------------------------------------------------------
-// off[0..8]: the pieces of the host block (and of the head of the device block), off[9] = their bytes, off[10] = prefix length
-static void batch_round_layout(const vq_db* db, int Q, int64_t off[12]) {
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
-    const int64_t n = db->n;
-    off[0] = 0;
-    off[1] = off[0] + up((int64_t)Q * db->S * db->E * db->D * 8);
-    off[2] = off[1] + up((int64_t)Q * 8 * 8);
-    off[3] = off[2] + up((int64_t)Q * 2 * 8);
-    off[4] = off[3] + up(n * db->S * 4);
-    off[5] = off[4] + up((int64_t)Q * n * db->S * 8);
-    off[6] = off[5] + up((int64_t)Q * n * 8);
-    off[7] = off[6] + up((int64_t)Q * 4 * 8);
-    off[8] = off[7] + up((int64_t)Q * kRoundPrefix * 8);
-    off[9] = off[8] + up((int64_t)Q * kRoundPrefix * 8);
-    off[10] = kRoundPrefix;
-    off[11] = 0;
-}
-
-int vq_db_batch_round_layout(vq_db* db, int32_t n_queries, int64_t* off) {
-    VQ_REQUIRE(db && off, "NULL argument");
-    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
-    batch_round_layout(db, n_queries, off);
-    return VQ_OK;
-}
-
-int vq_db_query_round_batch(vq_db* db, int32_t n_queries, void* block, int64_t block_bytes, int32_t flags) {
-    VQ_REQUIRE(db && block, "NULL argument");
-    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
-    VQ_REQUIRE(db->D % 256 == 0 && db->D <= 1024, "a batched round needs D in {256,512,768,1024} (got %d)", db->D);
-    VQ_REQUIRE(db->S <= 8, "at most 8 streams");
-    VQ_REQUIRE((flags & ~15) == 0, "flags: 1 = avg and n_e back, 2 = scores back, 4 = partition, 8 = timed (got %d)", flags);
-    const int Q = n_queries;
-    int64_t off[12];
-    batch_round_layout(db, Q, off);
-    VQ_REQUIRE(block_bytes >= off[9], "the block of a batched round of %d queries needs %lld bytes (vq_db_batch_round_layout), got %lld", Q,
-               (long long)off[9], (long long)block_bytes);
-    const bool want_avg = flags & 1, want_scores = flags & 2, do_select = flags & 4, timed = flags & 8;
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (db->active >= 0)
-        return fail(VQ_E_UNSUPPORTED, "vq_db_query_round_batch runs over the whole database: row view %d is in use (vq_db_rows_use(db, -1) first)", db->active);
-    DeviceGuard g(db->device);
-    const int64_t n = db->n;
-    const int nblk = cdiv(n, SEL_CHUNK);
-    // behind the image of the host block: the full lists and the scratch of the three-pass selection
-    const int64_t o_rows0 = off[9], o_rows1 = o_rows0 + (int64_t)Q * n * 8, o_cnt = o_rows1 + (int64_t)Q * n * 8;
-    const int64_t o_max = o_cnt + (int64_t)Q * nblk * 8, o_arg = o_max + (int64_t)Q * nblk * 8, need = o_arg + (int64_t)Q * nblk * 8;
-    db->bround_q = 0;                                 // the lists of the round before are gone from here on
-    if (db->bround_cap < need) {
-        if (db->bround_dev && (char*)db->batch_scores >= db->bround_dev && (char*)db->batch_scores < db->bround_dev + db->bround_cap) {
-            db->batch_scores = nullptr;               // the scores of the round before lived in the block that goes
-            db->batch_q = 0;
-        }
-        if (db->bround_dev) VQ_HIP(hipFree(db->bround_dev));
-        db->bround_dev = nullptr;
-        db->bround_cap = 0;
-        VQ_HIP(vq::malloc_trim((void**)&db->bround_dev, (size_t)need));
-        db->bround_cap = need;
-    }
-    if (timed && !db->bround_ev[0])
-        for (auto& ev : db->bround_ev) VQ_HIP(hipEventCreate(&ev));
-    db->bround_timed = false;
-    char* host = (char*)block;
-    char* dev = db->bround_dev;
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[0], db->stream));
-    VQ_HIP(hipMemcpyAsync(dev, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));       // queries | weights | bands: adjacent
-    double* d_scores = (double*)(dev + off[5]);
-    {
-        const int rc = launch_fused_pass<true>(db, Q, (const double*)(dev + off[0]), (const double*)(dev + off[1]), d_scores, (double*)(dev + off[4]));
-        if (rc != VQ_OK) return rc;
-    }
-    db->batch_scores = d_scores;                      // vq_db_batch_scores_devptr: the scores of the last batched pass
-    db->batch_q = Q;
-    batch_ne_kernel<<<cdiv(n * db->S, 256), 256, 0, db->stream>>>(db->present, (int32_t*)(dev + off[3]), n * db->S, db->E);
-    VQ_CHECK_LAUNCH();
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[1], db->stream));
-    if (do_select) {
-        SelBatchArgs a;
-        a.scores = d_scores;
-        a.band = (const double*)(dev + off[2]);
-        a.n = n;
-        a.nblk = nblk;
-        a.blk_cnt = (int2*)(dev + o_cnt);
-        a.blk_max = (double*)(dev + o_max);
-        a.blk_arg = (int64_t*)(dev + o_arg);
-        a.result = (int64_t*)(dev + off[6]);
-        a.out0 = (int64_t*)(dev + o_rows0);
-        a.out1 = (int64_t*)(dev + o_rows1);
-        a.pre0 = (int64_t*)(dev + off[7]);
-        a.pre1 = (int64_t*)(dev + off[8]);
-        a.prefix = kRoundPrefix;
-        VQ_HIP(hipMemsetAsync(dev + off[6], 0, (size_t)Q * 4 * 8, db->stream));
-        if (n <= kSelSmallN) {                        // one workgroup per query
-            select_small_batch_kernel<<<Q, kSelSmallThreads, 0, db->stream>>>(a);
-            VQ_CHECK_LAUNCH();
-        } else {                                      // count / scan / scatter, the query on blockIdx.y
-            select_count_batch_kernel<<<dim3(nblk, Q), SEL_BLOCK, 0, db->stream>>>(a);
-            VQ_CHECK_LAUNCH();
-            select_scan_batch_kernel<<<Q, SEL_BLOCK, 0, db->stream>>>(a);
-            VQ_CHECK_LAUNCH();
-            select_scatter_batch_kernel<<<dim3(nblk, Q), SEL_BLOCK, 0, db->stream>>>(a);
-            VQ_CHECK_LAUNCH();
-        }
-    }
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[2], db->stream));
-    // back: n_e | avg, scores, results | prefixes -- the pieces asked for, adjacent ones in one copy
-    const int64_t piece[3][2] = {{off[3], off[5]}, {off[5], off[6]}, {off[6], off[9]}};
-    const bool want[3] = {want_avg, want_scores, do_select};
-    for (int i = 0; i < 3;) {
-        if (!want[i]) {
-            ++i;
-            continue;
-        }
-        int j = i;
-        while (j + 1 < 3 && want[j + 1]) ++j;
-        VQ_HIP(hipMemcpyAsync(host + piece[i][0], dev + piece[i][0], (size_t)(piece[j][1] - piece[i][0]), hipMemcpyDeviceToHost, db->stream));
-        i = j + 1;
-    }
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[3], db->stream));
-    VQ_HIP(hipStreamSynchronize(db->stream));
-    db->bround_timed = timed;
-    db->bround_rows0 = o_rows0;
-    db->bround_rows1 = o_rows1;
-    const int64_t* res = (const int64_t*)(host + off[6]);
-    for (int q = 0; q < kBatchSlots; ++q) {
-        db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
-        db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
-        db->bround_qoff[q] = (int64_t)q * n;
-        db->bround_m[q] = q < Q ? n : 0;
-        db->bround_bstart[q + 1] = n > kSelSmallN && q < Q ? (q + 1) * nblk : db->bround_bstart[q];
-    }
-    memcpy(db->bround_off, off, sizeof(off));
-    db->bround_views = false;
-    db->bround_cnt = o_cnt;
-    db->bround_max = o_max;
-    db->bround_arg = o_arg;
-    db->bround_q = Q;
-    return VQ_OK;
-}
-
-int vq_db_batch_round_fetch(vq_db* db, int32_t query, int64_t* match_rows_host, int64_t cap_match, int64_t* near_rows_host, int64_t cap_near) {
-    VQ_REQUIRE(db, "db is NULL");
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
-    if (query < 0 || query >= db->bround_q) return fail(VQ_E_STATE, "the last batched round had %d queries (asked for query %d)", db->bround_q, query);
-    const int64_t n0 = db->bround_n0[query], n1 = db->bround_n1[query];
-    if (n0 < 0 || n1 < 0) return fail(VQ_E_STATE, "the last batched round did not partition (flag 4)");
-    DeviceGuard g(db->device);
-    if (match_rows_host) {
-        VQ_REQUIRE(cap_match >= n0, "match buffer too small (%lld < %lld)", (long long)cap_match, (long long)n0);
-        if (n0) VQ_HIP(hipMemcpyAsync(match_rows_host, db->bround_dev + db->bround_rows0 + db->bround_qoff[query] * 8, (size_t)n0 * 8, hipMemcpyDeviceToHost, db->stream));
-    }
-    if (near_rows_host) {
-        VQ_REQUIRE(cap_near >= n1, "near buffer too small (%lld < %lld)", (long long)cap_near, (long long)n1);
-        if (n1) VQ_HIP(hipMemcpyAsync(near_rows_host, db->bround_dev + db->bround_rows1 + db->bround_qoff[query] * 8, (size_t)n1 * 8, hipMemcpyDeviceToHost, db->stream));
-    }
-    VQ_HIP(hipStreamSynchronize(db->stream));
-    return VQ_OK;
-}
-
-int vq_db_batch_round_times(vq_db* db, float* ms) {
-    VQ_REQUIRE(db && ms, "NULL argument");
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (!db->bround_timed) return fail(VQ_E_STATE, "the last batched round was not timed (flag 8)");
-    for (int i = 0; i < 3; ++i) VQ_HIP(hipEventElapsedTime(&ms[i], db->bround_ev[i], db->bround_ev[i + 1]));
-    return VQ_OK;
-}
-
 }  // extern "C"
 
-// ---- batched rounds over a row view per query (include/vq_amd_round_views.h) ---------------------------------------------------------
+// ---- the pass of a batched round over a row view per query (csrc/vq_rounds.hip, include/vq_amd_round_views.h) -------------------------
 // the VIEW instantiation of the 16-query pass for a database: the tiled layout exists for fp32 rows of 1024 elements only (vq_db_set_layout)
 template <typename T, int CH, int TW>
 static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
@@ -3082,7 +2375,7 @@ static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
 
 // One pass over the union of the round's views.  max_tiles bounds the tiles the plan can hold (the kernel reads their number from the
 // device): it only sizes the grid.  Caller holds the lock and has checked the shape.
-static int launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
+int vq::launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
     const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;
     const int ch = db->D / 256;
     const bool tiled = db->layout == VQ_LAYOUT_TILED;
@@ -3109,506 +2402,7 @@ static int launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
     return VQ_OK;
 }
 
-// m[q]: the rows of query q's piece.  Caller holds the lock.
-static int view_round_sizes(vq_db* db, int Q, const int32_t* views, int64_t m[16]) {
-    for (int q = 0; q < Q; ++q) {
-        const int32_t v = views[q];
-        if (v == -1) m[q] = db->n;
-        else if (v < 0 || (size_t)v >= db->views.size() || !db->views[v].defined)
-            return fail(VQ_E_INVALID, "query %d: no row view %d on this handle", q, v);
-        else m[q] = db->views[v].m;
-    }
-    return VQ_OK;
-}
-
-static void view_round_layout(const vq_db* db, int Q, const int64_t* m, int64_t off[12], int64_t start[17]) {
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
-    start[0] = 0;
-    for (int q = 0; q < kBatchSlots; ++q) start[q + 1] = start[q] + (q < Q ? m[q] : 0);
-    const int64_t sm = start[Q];
-    off[0] = 0;
-    off[1] = off[0] + up((int64_t)Q * db->S * db->E * db->D * 8);
-    off[2] = off[1] + up((int64_t)Q * 8 * 8);
-    off[3] = off[2] + up((int64_t)Q * 2 * 8);
-    off[4] = off[3] + up(sm * db->S * 4);
-    off[5] = off[4] + up(sm * db->S * 8);
-    off[6] = off[5] + up(sm * 8);
-    off[7] = off[6] + up((int64_t)Q * 4 * 8);
-    off[8] = off[7] + up((int64_t)Q * kRoundPrefix * 8);
-    off[9] = off[8] + up((int64_t)Q * kRoundPrefix * 8);
-    off[10] = kRoundPrefix;
-    off[11] = sm;
-}
-
 extern "C" {
-
-int vq_db_view_round_layout(vq_db* db, int32_t n_queries, const int32_t* views_host, int64_t* off, int64_t* start) {
-    VQ_REQUIRE(db && views_host && off && start, "NULL argument");
-    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
-    std::lock_guard<std::mutex> lk(db->mu);
-    int64_t m[16];
-    const int rc = view_round_sizes(db, n_queries, views_host, m);
-    if (rc != VQ_OK) return rc;
-    view_round_layout(db, n_queries, m, off, start);
-    return VQ_OK;
-}
-
-int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_host, void* block, int64_t block_bytes, int32_t flags) {
-    VQ_REQUIRE(db && views_host && block, "NULL argument");
-    VQ_REQUIRE(n_queries >= 1 && n_queries <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, n_queries);
-    VQ_REQUIRE(db->D % 256 == 0 && db->D <= 1024, "a batched round needs D in {256,512,768,1024} (got %d)", db->D);
-    VQ_REQUIRE(db->S <= 8, "at most 8 streams");
-    VQ_REQUIRE(db->n < (int64_t)2147483647 - 16, "a view round indexes the database's rows with 32 bits (%lld rows)", (long long)db->n);
-    VQ_REQUIRE((flags & ~15) == 0, "flags: 1 = avg and n_e back, 2 = scores back, 4 = partition, 8 = timed (got %d)", flags);
-    const int Q = n_queries;
-    const bool want_avg = flags & 1, want_scores = flags & 2, do_select = flags & 4, timed = flags & 8;
-    std::lock_guard<std::mutex> lk(db->mu);
-    int64_t m[16], off[12], start[17];
-    {
-        const int rc = view_round_sizes(db, Q, views_host, m);
-        if (rc != VQ_OK) return rc;
-    }
-    view_round_layout(db, Q, m, off, start);
-    VQ_REQUIRE(block_bytes >= off[9], "the block of this view round of %d queries needs %lld bytes (vq_db_view_round_layout), got %lld", Q,
-               (long long)off[9], (long long)block_bytes);
-    DeviceGuard g(db->device);
-    const int64_t n = db->n, sm = start[Q];
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;
-    uint32_t whole = 0, members = 0;                  // queries over the whole database | queries whose row list goes into the plan
-    int64_t member_rows = 0, max_m = 0;
-    for (int q = 0; q < Q; ++q) {
-        if (views_host[q] < 0) whole |= 1u << q;
-        else if (m[q] > 0) {
-            members |= 1u << q;
-            member_rows += m[q];
-        }
-        max_m = std::max(max_m, m[q]);
-    }
-    // behind the image of the host block: the full lists [sum M] each and the scratch of the three-pass selection of the long pieces
-    SelViewArgs sel;
-    sel.bstart[0] = 0;
-    for (int q = 0; q < kBatchSlots; ++q) {
-        sel.start[q] = start[q];
-        sel.bstart[q + 1] = sel.bstart[q] + (q < Q && m[q] > kSelSmallN ? cdiv(m[q], SEL_CHUNK) : 0);
-    }
-    sel.start[kBatchSlots] = start[kBatchSlots];
-    const int nbt = sel.bstart[kBatchSlots];
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
-    const int64_t o_rows0 = off[9], o_rows1 = o_rows0 + up(sm * 8), o_cnt = o_rows1 + up(sm * 8);
-    const int64_t o_max = o_cnt + (int64_t)nbt * 8, o_arg = o_max + (int64_t)nbt * 8, need = o_arg + (int64_t)nbt * 8 + 64;
-    db->bround_q = 0;                                 // the lists of the round before are gone from here on
-    db->batch_scores = nullptr;                       // vq_db_batch_scores_devptr names [Q][N] scores: none until the next whole-database pass
-    db->batch_q = 0;
-    db->bround_timed = false;
-    db->vround_have = false;
-    if (sm == 0) {                                    // every view is empty: nothing to launch
-        if (do_select) {
-            int64_t* res = (int64_t*)((char*)block + off[6]);
-            for (int q = 0; q < Q; ++q) {
-                res[4 * q] = res[4 * q + 1] = res[4 * q + 3] = 0;
-                res[4 * q + 2] = -1;
-            }
-        }
-        for (int q = 0; q < kBatchSlots; ++q) {
-            db->bround_n0[q] = db->bround_n1[q] = do_select && q < Q ? 0 : -1;
-            db->bround_qoff[q] = 0;
-            db->bround_m[q] = 0;
-            db->bround_bstart[q + 1] = 0;
-        }
-        db->bround_rows0 = db->bround_rows1 = 0;
-        memcpy(db->bround_off, off, sizeof(off));
-        db->bround_views = true;
-        db->bround_q = Q;
-        db->vround_have = true;
-        db->vround_union = db->vround_tiles = 0;
-        return VQ_OK;
-    }
-    if (db->bround_cap < need) {
-        if (db->bround_dev) VQ_HIP(hipFree(db->bround_dev));
-        db->bround_dev = nullptr;
-        db->bround_cap = 0;
-        VQ_HIP(vq::malloc_trim((void**)&db->bround_dev, (size_t)need));
-        db->bround_cap = need;
-    }
-    // the plan's block (vq_db.h): 64 MB of inverse map at 16 x 1M rows, allocated on the first view round
-    const int64_t stride = (n + 15) / 16 * 16, db_tiles = stride / 16;
-    const int nblk_u = cdiv(db_tiles, SEL_BLOCK);
-    const int64_t p_rows = (int64_t)kBatchSlots * stride * 4, p_tiles = p_rows + up((stride + 16) * 4), p_counts = p_tiles + up(db_tiles * 4);
-    const int64_t p_start = p_counts + 64, p_blk = p_start + up(17 * 8), p_need = p_blk + (int64_t)nblk_u * 8 + 64;
-    if (!db->vround_plan) VQ_HIP(vq::malloc_trim((void**)&db->vround_plan, (size_t)p_need));
-    char* plan = db->vround_plan;
-    if (timed && !db->bround_ev[0])
-        for (auto& ev : db->bround_ev) VQ_HIP(hipEventCreate(&ev));
-    char* host = (char*)block;
-    char* dev = db->bround_dev;
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[0], db->stream));
-    VQ_HIP(hipMemcpyAsync(dev, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));       // queries | weights | bands: adjacent
-    // the plan
-    ViewPlanArgs pa;
-    for (int q = 0; q < kBatchSlots; ++q) {
-        pa.rows[q] = (members >> q) & 1u ? db->views[views_host[q]].rows : nullptr;
-        pa.m[q] = q < Q ? m[q] : 0;
-        pa.start[q] = start[q];
-    }
-    pa.start[kBatchSlots] = start[kBatchSlots];
-    pa.Q = Q;
-    pa.n = n;
-    pa.stride = stride;
-    pa.inv = (int32_t*)plan;
-    pa.start_dev = (int64_t*)(plan + p_start);
-    for (int q = 0; q < Q; ++q)
-        if ((members >> q) & 1u) VQ_HIP(hipMemsetAsync(plan + (int64_t)q * stride * 4, 0xFF, (size_t)stride * 4, db->stream));
-    const int fill_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
-    view_scatter_kernel<<<dim3(fill_blocks, Q), 256, 0, db->stream>>>(pa);
-    VQ_CHECK_LAUNCH();
-    int64_t max_tiles = db_tiles;                     // a whole-database query: the union is the database, addressed as ever
-    if (!whole) {
-        ViewUnionArgs ua;
-        ua.inv = pa.inv;
-        ua.stride = stride;
-        ua.ntiles = db_tiles;
-        ua.members = members;
-        ua.blk = (int2*)(plan + p_blk);
-        ua.nblk = nblk_u;
-        ua.rows_out = tiled ? nullptr : (int32_t*)(plan + p_rows);
-        ua.tiles_out = tiled ? (int32_t*)(plan + p_tiles) : nullptr;
-        ua.counts = (int64_t*)(plan + p_counts);
-        view_union_count_kernel<<<nblk_u, SEL_BLOCK, 0, db->stream>>>(ua);
-        VQ_CHECK_LAUNCH();
-        view_union_scan_kernel<<<1, SEL_BLOCK, 0, db->stream>>>(ua);
-        VQ_CHECK_LAUNCH();
-        view_union_scatter_kernel<<<nblk_u, SEL_BLOCK, 0, db->stream>>>(ua);
-        VQ_CHECK_LAUNCH();
-        max_tiles = tiled ? std::min(db_tiles, member_rows) : (std::min(n, member_rows) + 15) / 16;
-    }
-    {
-        BatchViewArgs f;
-        f.feats = db->feats;
-        f.t = (const double*)(dev + off[0]);
-        f.w = (const double*)(dev + off[1]);
-        f.present = db->present;
-        f.scores = (double*)(dev + off[5]);
-        f.n = n;
-        f.Q = Q;
-        f.S = db->S;
-        f.E = db->E;
-        f.D = db->D;
-        f.avg = (double*)(dev + off[4]);
-        f.items = whole ? nullptr : (tiled ? (const int32_t*)(plan + p_tiles) : (const int32_t*)(plan + p_rows));
-        f.counts = (const int64_t*)(plan + p_counts);
-        f.inv = pa.inv;
-        f.inv_stride = stride;
-        f.start = pa.start_dev;
-        f.whole = whole;
-        f.members = members;
-        const int rc = launch_view_pass(db, f, max_tiles);
-        if (rc != VQ_OK) return rc;
-    }
-    view_ne_kernel<<<dim3((int)std::max<int64_t>(1, std::min<int64_t>((max_m * db->S + 255) / 256, (int64_t)db->cus * 8)), Q), 256, 0, db->stream>>>(
-        pa, db->present, (int32_t*)(dev + off[3]), db->S, db->E);
-    VQ_CHECK_LAUNCH();
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[1], db->stream));
-    if (do_select) {
-        sel.b.scores = (const double*)(dev + off[5]);
-        sel.b.band = (const double*)(dev + off[2]);
-        sel.b.n = 0;
-        sel.b.nblk = nbt;
-        sel.b.blk_cnt = (int2*)(dev + o_cnt);
-        sel.b.blk_max = (double*)(dev + o_max);
-        sel.b.blk_arg = (int64_t*)(dev + o_arg);
-        sel.b.result = (int64_t*)(dev + off[6]);
-        sel.b.out0 = (int64_t*)(dev + o_rows0);
-        sel.b.out1 = (int64_t*)(dev + o_rows1);
-        sel.b.pre0 = (int64_t*)(dev + off[7]);
-        sel.b.pre1 = (int64_t*)(dev + off[8]);
-        sel.b.prefix = kRoundPrefix;
-        VQ_HIP(hipMemsetAsync(dev + off[6], 0, (size_t)Q * 4 * 8, db->stream));
-        select_small_view_kernel<<<Q, kSelSmallThreads, 0, db->stream>>>(sel);       // the pieces of at most kSelSmallN entries (an empty one: 0, 0, -1)
-        VQ_CHECK_LAUNCH();
-        if (nbt > 0) {                                // count / scan / scatter for the longer ones
-            int max_nb = 0;
-            for (int q = 0; q < Q; ++q) max_nb = std::max(max_nb, sel.bstart[q + 1] - sel.bstart[q]);
-            select_count_view_kernel<<<dim3(max_nb, Q), SEL_BLOCK, 0, db->stream>>>(sel);
-            VQ_CHECK_LAUNCH();
-            select_scan_view_kernel<<<Q, SEL_BLOCK, 0, db->stream>>>(sel);
-            VQ_CHECK_LAUNCH();
-            select_scatter_view_kernel<<<dim3(max_nb, Q), SEL_BLOCK, 0, db->stream>>>(sel);
-            VQ_CHECK_LAUNCH();
-        }
-    }
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[2], db->stream));
-    const int64_t piece[3][2] = {{off[3], off[5]}, {off[5], off[6]}, {off[6], off[9]}};
-    const bool want[3] = {want_avg, want_scores, do_select};
-    for (int i = 0; i < 3;) {
-        if (!want[i]) {
-            ++i;
-            continue;
-        }
-        int j = i;
-        while (j + 1 < 3 && want[j + 1]) ++j;
-        VQ_HIP(hipMemcpyAsync(host + piece[i][0], dev + piece[i][0], (size_t)(piece[j][1] - piece[i][0]), hipMemcpyDeviceToHost, db->stream));
-        i = j + 1;
-    }
-    int64_t counts[2] = {n, db_tiles};
-    if (!whole) VQ_HIP(hipMemcpyAsync(counts, plan + p_counts, 16, hipMemcpyDeviceToHost, db->stream));
-    if (timed) VQ_HIP(hipEventRecord(db->bround_ev[3], db->stream));
-    VQ_HIP(hipStreamSynchronize(db->stream));
-    db->bround_timed = timed;
-    db->bround_rows0 = o_rows0;
-    db->bround_rows1 = o_rows1;
-    const int64_t* res = (const int64_t*)(host + off[6]);
-    for (int q = 0; q < kBatchSlots; ++q) {
-        db->bround_n0[q] = do_select && q < Q ? res[4 * q] : -1;
-        db->bround_n1[q] = do_select && q < Q ? res[4 * q + 1] : -1;
-        db->bround_qoff[q] = start[q];
-        db->bround_m[q] = q < Q ? m[q] : 0;
-        db->bround_bstart[q + 1] = sel.bstart[q + 1];
-    }
-    memcpy(db->bround_off, off, sizeof(off));
-    db->bround_views = true;
-    db->bround_cnt = o_cnt;
-    db->bround_max = o_max;
-    db->bround_arg = o_arg;
-    db->bround_q = Q;
-    db->vround_have = true;
-    db->vround_union = counts[0];
-    db->vround_tiles = counts[1];
-    return VQ_OK;
-}
-
-int vq_db_view_round_union(vq_db* db, int64_t* n_union, int64_t* n_tiles) {
-    VQ_REQUIRE(db, "db is NULL");
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (!db->vround_have) return fail(VQ_E_STATE, "no view round has run on this handle");
-    if (n_union) *n_union = db->vround_union;
-    if (n_tiles) *n_tiles = db->vround_tiles;
-    return VQ_OK;
-}
-
-}  // extern "C"
-
-// ---- the weight fit and the re-weighting of a batched round's queries (include/vq_amd_round_fit.h) -----------------------------------
-static void batch_fit_layout(int Q, int G, int T, int64_t n_labels, int64_t off[8]) {
-    auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
-    off[0] = 0;
-    off[1] = off[0] + up((int64_t)Q * G * 8 * 8);
-    off[2] = off[1] + up((int64_t)Q * T * 8);
-    off[3] = off[2] + up((int64_t)Q * 8);
-    off[4] = off[3] + up((int64_t)Q * 8);
-    off[5] = off[4] + up(n_labels * 8);
-    off[6] = off[5] + up(n_labels * 8);
-    off[7] = off[6] + up((int64_t)Q * G * T * 8);
-}
-
-static int batch_fit_shape(int Q, int G, int T, int64_t n_labels) {
-    VQ_REQUIRE(Q >= 1 && Q <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, Q);
-    VQ_REQUIRE(G >= 1 && G <= kFitMaxGrid && T >= 1 && T <= kFitMaxGrid, "the grids of a batched fit hold 1 to %d weights and thresholds (got %d, %d)",
-               kFitMaxGrid, G, T);
-    VQ_REQUIRE(n_labels >= 0, "n_labels must not be negative");
-    return VQ_OK;
-}
-
-extern "C" {
-
-int vq_db_batch_fit_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t* off) {
-    VQ_REQUIRE(db && off, "NULL argument");
-    const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
-    if (rc != VQ_OK) return rc;
-    batch_fit_layout(n_queries, n_grid, n_thresholds, n_labels, off);
-    return VQ_OK;
-}
-
-int vq_db_batch_round_fit(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, void* block, int64_t block_bytes) {
-    VQ_REQUIRE(db && block, "NULL argument");
-    {
-        const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
-        if (rc != VQ_OK) return rc;
-    }
-    const int Q = n_queries, G = n_grid, T = n_thresholds;
-    int64_t off[8];
-    batch_fit_layout(Q, G, T, n_labels, off);
-    VQ_REQUIRE(block_bytes >= off[7], "the block of this batched fit needs %lld bytes (vq_db_batch_fit_layout), got %lld", (long long)off[7],
-               (long long)block_bytes);
-    char* host = (char*)block;
-    const int64_t* L = (const int64_t*)(host + off[3]);
-    const int64_t* rows = (const int64_t*)(host + off[4]);
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
-    FitBatchArgs a;
-    a.lstart[0] = 0;
-    for (int q = 0; q < kBatchSlots; ++q) {
-        const int64_t lq = q < Q ? L[q] : 0;
-        VQ_REQUIRE(lq >= 0 && lq <= n_labels, "query %d: L = %lld outside [0, n_labels = %lld]", q, (long long)lq, (long long)n_labels);
-        if (lq > 0 && q >= db->bround_q) return fail(VQ_E_STATE, "the last batched round had %d queries (labels for query %d)", db->bround_q, q);
-        a.lstart[q + 1] = a.lstart[q] + lq;
-        a.qoff[q] = db->bround_qoff[q];
-    }
-    VQ_REQUIRE(a.lstart[kBatchSlots] == n_labels, "the L of the queries add up to %lld, n_labels is %lld", (long long)a.lstart[kBatchSlots], (long long)n_labels);
-    for (int q = 0; q < Q; ++q)
-        for (int64_t l = a.lstart[q]; l < a.lstart[q + 1]; ++l)
-            VQ_REQUIRE(rows[l] >= 0 && rows[l] < db->bround_m[q], "query %d: row %lld (label %lld) outside [0,%lld)", q, (long long)rows[l],
-                       (long long)(l - a.lstart[q]), (long long)db->bround_m[q]);
-    if (n_labels == 0) return VQ_OK;                  // every query skipped: nothing to launch
-    DeviceGuard g(db->device);
-    {
-        const int rc = ensure_grid_buf(db, off[7]);
-        if (rc != VQ_OK) return rc;
-    }
-    char* base = (char*)db->grid_buf;
-    VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[6], hipMemcpyHostToDevice, db->stream));      // grids | ballast | L | rows | labels: adjacent
-    a.avg = (const double*)(db->bround_dev + db->bround_off[4]);
-    a.w_grid = (const double*)(base + off[0]);
-    a.th_grid = (const double*)(base + off[1]);
-    a.ballast = (const double*)(base + off[2]);
-    a.rows = (const int64_t*)(base + off[4]);
-    a.labels = (const double*)(base + off[5]);
-    a.out = (double*)(base + off[6]);
-    a.G = G;
-    a.T = T;
-    a.S = db->S;
-    loss_surface_batch_kernel<<<dim3(G, Q), kFitThreads, 0, db->stream>>>(a);
-    VQ_CHECK_LAUNCH();
-    const int64_t cell = (int64_t)G * T * 8;
-    for (int q = 0; q < Q;) {                         // the surfaces of the queries served, adjacent ones in one copy
-        if (L[q] == 0) {
-            ++q;
-            continue;
-        }
-        int e = q;
-        while (e + 1 < Q && L[e + 1] > 0) ++e;
-        VQ_HIP(hipMemcpyAsync(host + off[6] + q * cell, base + off[6] + q * cell, (size_t)((e + 1 - q) * cell), hipMemcpyDeviceToHost, db->stream));
-        q = e + 1;
-    }
-    VQ_HIP(hipStreamSynchronize(db->stream));
-    return VQ_OK;
-}
-
-int vq_db_batch_round_rescore(vq_db* db, int32_t mask, void* block, int64_t block_bytes, int32_t flags) {
-    VQ_REQUIRE(db && block, "NULL argument");
-    VQ_REQUIRE((flags & ~(VQ_BROUND_SCORES | VQ_BROUND_SELECT)) == 0, "flags: 2 = scores back, 4 = partition (got %d)", flags);
-    VQ_REQUIRE(mask > 0 && mask < (1 << kBatchSlots), "mask: bit q = query q of the round, at least one of %d (got %d)", kBatchSlots, mask);
-    const bool want_scores = flags & VQ_BROUND_SCORES, do_select = flags & VQ_BROUND_SELECT;
-    std::lock_guard<std::mutex> lk(db->mu);
-    if (db->bround_q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
-    const int Q = db->bround_q;
-    if (mask >> Q) return fail(VQ_E_STATE, "the last batched round had %d queries (mask 0x%x)", Q, mask);
-    const int64_t* off = db->bround_off;
-    VQ_REQUIRE(block_bytes >= off[9], "the block of the last batched round needs %lld bytes, got %lld", (long long)off[9], (long long)block_bytes);
-    char* host = (char*)block;
-    auto in_mask = [&](int q) { return q < Q && ((mask >> q) & 1); };
-    int64_t max_m = 0;
-    for (int q = 0; q < Q; ++q)
-        if (in_mask(q)) max_m = std::max(max_m, db->bround_m[q]);
-    if (max_m == 0) {                                 // only empty views: nothing to launch
-        int64_t* res = (int64_t*)(host + off[6]);
-        for (int q = 0; q < Q; ++q)
-            if (in_mask(q) && do_select) {
-                res[4 * q] = res[4 * q + 1] = res[4 * q + 3] = 0;
-                res[4 * q + 2] = -1;
-                db->bround_n0[q] = db->bround_n1[q] = 0;
-            }
-        return VQ_OK;
-    }
-    DeviceGuard g(db->device);
-    const int64_t up_bytes = off[3] - off[1];         // weights | bands of the round's block: adjacent
-    {
-        const int rc = ensure_grid_buf(db, up_bytes);
-        if (rc != VQ_OK) return rc;
-    }
-    // staged beside the round's image, whose weights and bands of the other queries stay what the round saw
-    char* stage = (char*)db->grid_buf;
-    char* dev = db->bround_dev;
-    VQ_HIP(hipMemcpyAsync(stage, host + off[1], (size_t)up_bytes, hipMemcpyHostToDevice, db->stream));
-    const double* d_band = (const double*)(stage + (off[2] - off[1]));
-    {
-        RescoreBatchArgs a;
-        a.avg = (const double*)(dev + off[4]);
-        a.w = (const double*)stage;
-        a.scores = (double*)(dev + off[5]);
-        for (int q = 0; q < kBatchSlots; ++q) {
-            a.qoff[q] = db->bround_qoff[q];
-            a.m[q] = db->bround_m[q];
-        }
-        a.mask = (uint32_t)mask;
-        a.S = db->S;
-        const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
-        rescore_batch_kernel<<<dim3(bx, Q), 256, 0, db->stream>>>(a);
-        VQ_CHECK_LAUNCH();
-    }
-    int64_t start[kBatchSlots + 1];                   // the entries of query q: start[q] .. start[q + 1], for either kind of round
-    for (int q = 0; q < kBatchSlots; ++q) start[q] = db->bround_qoff[q];
-    start[kBatchSlots] = db->bround_qoff[kBatchSlots - 1] + db->bround_m[kBatchSlots - 1];
-    const int64_t P = off[10];
-    // per run [q0, q1] of adjacent masked queries: the view form of the batched selection kernels with the run's queries as its
-    // queries (a whole-database round is the view round whose pieces all have N rows), then the run's results in adjacent copies
-    for (int q0 = 0; q0 < Q;) {
-        if (!in_mask(q0)) {
-            ++q0;
-            continue;
-        }
-        int q1 = q0;
-        while (in_mask(q1 + 1)) ++q1;
-        const int nq = q1 - q0 + 1;
-        if (do_select) {
-            SelViewArgs sel;
-            bool any_small = false;
-            int max_nb = 0;
-            for (int i = 0; i <= kBatchSlots; ++i) {
-                const int q = std::min(q0 + i, kBatchSlots);
-                sel.start[i] = start[q];
-                sel.bstart[i] = db->bround_bstart[q];
-            }
-            for (int q = q0; q <= q1; ++q) {
-                any_small |= db->bround_m[q] <= kSelSmallN;
-                max_nb = std::max(max_nb, db->bround_bstart[q + 1] - db->bround_bstart[q]);
-            }
-            sel.b.scores = (const double*)(dev + off[5]);
-            sel.b.band = d_band + 2 * q0;
-            sel.b.n = 0;
-            sel.b.nblk = 0;
-            sel.b.blk_cnt = (int2*)(dev + db->bround_cnt);
-            sel.b.blk_max = (double*)(dev + db->bround_max);
-            sel.b.blk_arg = (int64_t*)(dev + db->bround_arg);
-            sel.b.result = (int64_t*)(dev + off[6]) + 4 * q0;
-            sel.b.out0 = (int64_t*)(dev + db->bround_rows0);
-            sel.b.out1 = (int64_t*)(dev + db->bround_rows1);
-            sel.b.pre0 = (int64_t*)(dev + off[7]) + q0 * P;
-            sel.b.pre1 = (int64_t*)(dev + off[8]) + q0 * P;
-            sel.b.prefix = P;
-            VQ_HIP(hipMemsetAsync(dev + off[6] + (int64_t)q0 * 32, 0, (size_t)nq * 32, db->stream));
-            if (any_small) {
-                select_small_view_kernel<<<nq, kSelSmallThreads, 0, db->stream>>>(sel);
-                VQ_CHECK_LAUNCH();
-            }
-            if (max_nb > 0) {
-                select_count_view_kernel<<<dim3(max_nb, nq), SEL_BLOCK, 0, db->stream>>>(sel);
-                VQ_CHECK_LAUNCH();
-                select_scan_view_kernel<<<nq, SEL_BLOCK, 0, db->stream>>>(sel);
-                VQ_CHECK_LAUNCH();
-                select_scatter_view_kernel<<<dim3(max_nb, nq), SEL_BLOCK, 0, db->stream>>>(sel);
-                VQ_CHECK_LAUNCH();
-            }
-        }
-        const int64_t s_lo = start[q0] * 8, s_len = (start[q1] + db->bround_m[q1]) * 8 - s_lo;
-        if (want_scores && s_len) VQ_HIP(hipMemcpyAsync(host + off[5] + s_lo, dev + off[5] + s_lo, (size_t)s_len, hipMemcpyDeviceToHost, db->stream));
-        if (do_select) {
-            VQ_HIP(hipMemcpyAsync(host + off[6] + (int64_t)q0 * 32, dev + off[6] + (int64_t)q0 * 32, (size_t)nq * 32, hipMemcpyDeviceToHost, db->stream));
-            for (int piece = 7; piece <= 8; ++piece)
-                VQ_HIP(hipMemcpyAsync(host + off[piece] + q0 * P * 8, dev + off[piece] + q0 * P * 8, (size_t)(nq * P * 8), hipMemcpyDeviceToHost, db->stream));
-        }
-        q0 = q1 + 1;
-    }
-    VQ_HIP(hipStreamSynchronize(db->stream));
-    if (do_select) {
-        const int64_t* res = (const int64_t*)(host + off[6]);
-        for (int q = 0; q < Q; ++q)
-            if (in_mask(q)) {
-                db->bround_n0[q] = res[4 * q];
-                db->bround_n1[q] = res[4 * q + 1];
-            }
-    }
-    return VQ_OK;
-}
 
 int vq_db_topk(vq_db* db, int64_t k, int64_t* rows_host, double* vals_host, int64_t* k_out) {
     VQ_REQUIRE(db && rows_host && vals_host && k_out, "NULL argument");

@@ -624,6 +624,55 @@ class FeatureDB:
         caller selects it first (``use_search_set(None)``)."""
         return self.D in (256, 512, 768, 1024) and self.S <= 8
 
+    @staticmethod
+    def _block_view(raw: np.ndarray, off):
+        """view(piece, dtype, shape, first=0) over a block laid out by ``off``: ``shape`` elements of ``piece``, from its element
+        ``first`` on."""
+        def view(piece, dtype, shape, first=0):
+            count, size = int(np.prod(shape)), np.dtype(dtype).itemsize
+            lo = off[piece] + first * size
+            return raw[lo:lo + count * size].view(dtype).reshape(shape)
+        return view
+
+    def _fill_round_inputs(self, view, Q: int, slots, w, bands, t=None) -> int:
+        """The inputs of a batched round's block of ``Q`` queries: the targets (a round), and for the queries ``slots`` their weights
+        (padded to 8) and bands; ``slots`` indexes the rows of [Q, ...] arrays.  Returns the partition flag the bands ask for."""
+        if t is not None:
+            view(0, np.float64, (Q, self.S, self.E, self.D))[...] = t
+        wv, bv = view(1, np.float64, (Q, 8)), view(2, np.float64, (Q, 2))
+        wv[...] = 0.0
+        bv[...] = 0.0
+        wv[slots, :self.S] = w
+        if bands is None:
+            return 0
+        bv[slots] = bands
+        return _lib.VQ_BROUND_SELECT
+
+    def _partition_decoder(self, view, off, Q: int):
+        """decode(r, q, have): the partition of query q of the last batched round into ``r`` from the block's results and prefixes;
+        a list longer than its prefix is fetched (the full lists are still on the device).  Call under ``self.lock``."""
+        res = view(6, np.int64, (Q, 4))
+        prefix = off[10]
+        pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+
+        def decode(r, q, have):
+            r.match_rows = r.near_rows = None
+            r.near_argmax = -1
+            if not have:
+                return
+            nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
+            if nm <= prefix and nn <= prefix:
+                r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
+            else:
+                m = np.empty(nm, dtype=np.int64)
+                k = np.empty(nn, dtype=np.int64)
+                call("vq_db_batch_round_fetch", self._h, q, _np_ptr(m) if nm else None, nm, _np_ptr(k) if nn else None, nn)
+                r.match_rows, r.near_rows = m, k
+        return decode
+
+    def _round_flags(self, want_avg: bool, want_scores: bool, timed: bool) -> int:
+        return (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
+
     def _batch_round_block(self, q: int):
         """(block, offsets) for a batched round of ``q`` queries: a page-locked block from the pool of its size (_RoundBlock's pooling,
         one pool per number of queries -- the layout depends on it)."""
@@ -667,44 +716,21 @@ class FeatureDB:
         with self.lock:
             self._bround_last = None                          # the round before is gone (its block may serve this one)
             blk, off = self._batch_round_block(Q)
-            raw = blk.bytes()
+            view = self._block_view(blk.bytes(), off)
             n, S = self.n, self.S
-
-            def view(piece, dtype, shape):
-                count = int(np.prod(shape))
-                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
-            view(0, np.float64, (Q, S, self.E, self.D))[...] = t
-            wv = view(1, np.float64, (Q, 8))
-            wv[...] = 0.0
-            wv[:, :S] = w
-            flags = (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
-            if bands is not None:
-                view(2, np.float64, (Q, 2))[...] = bands
-                flags |= _lib.VQ_BROUND_SELECT
+            flags = self._round_flags(want_avg, want_scores, timed) | self._fill_round_inputs(view, Q, slice(None), w, bands, t)
             call("vq_db_query_round_batch", self._h, Q, C.c_void_p(blk.ptr), blk.nbytes, flags)
             n_e = view(3, np.int32, (n, S)) if want_avg else None
             avg = view(4, np.float64, (Q, n, S)) if want_avg else None
             scores = view(5, np.float64, (Q, n)) if want_scores else None
-            res = view(6, np.int64, (Q, 4))
-            prefix = off[10]
-            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            decode = self._partition_decoder(view, off, Q)
             out = []
             for q in range(Q):
                 r = RoundResult()
                 r.avg = avg[q] if want_avg else None
                 r.n_e = n_e
                 r.scores = scores[q] if want_scores else None
-                r.match_rows = r.near_rows = None
-                r.near_argmax = -1
-                if bands is not None:
-                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
-                    if nm <= prefix and nn <= prefix:
-                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
-                    else:                                     # a list longer than its prefix: the full lists are still on the device
-                        m = np.empty(nm, dtype=np.int64)
-                        k = np.empty(nn, dtype=np.int64)
-                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(m) if nm else None, nm, _np_ptr(k) if nn else None, nn)
-                        r.match_rows, r.near_rows = m, k
+                decode(r, q, bands is not None)
                 out.append(r)
             # what batch_round_rescore lays its block out by, and the round's avg / n_e its results carry
             self._bround_last = (Q, off, [q * n for q in range(Q + 1)], None, [(r.avg, r.n_e) for r in out])
@@ -741,41 +767,12 @@ class FeatureDB:
             off, start = (C.c_int64 * 12)(), (C.c_int64 * 17)()
             call("vq_db_view_round_layout", self._h, Q, tokens, off, start)          # Q outside [1, 16]: the library's own refusal
             off, start = [int(v) for v in off], [int(v) for v in start]
-            pools = self.__dict__.setdefault("_view_round_pools", {})
-            nbytes = (off[9] + 65535) // 65536 * 65536                                # pooled by size: the layout depends on the sets
-            if nbytes not in pools and len(pools) >= 8:                               # many layouts: the idle blocks of the old ones go
-                for size in list(pools):
-                    old = pools.pop(size)
-                    old["closed"] = True                                              # blocks still referenced free themselves
-                    while old["free"]:
-                        _lib.load().vq_host_free(C.c_void_p(old["free"].pop()[0]))
-            pool = pools.setdefault(nbytes, {"free": [], "closed": False})
-            if pool["free"]:
-                ptr, _ = pool["free"].pop()
-            else:
-                p = C.c_void_p()
-                call("vq_host_alloc", C.byref(p), nbytes)
-                ptr = p.value
-            blk = _RoundBlock(ptr, nbytes, pool)
-            raw = blk.bytes()
+            blk = self._pooled_block("_view_round_pools", off[9])                     # pooled by size: the layout depends on the sets
+            view = self._block_view(blk.bytes(), off)
             S = self.S
-
-            def view(piece, dtype, shape, first=0):
-                count, size = int(np.prod(shape)), np.dtype(dtype).itemsize
-                lo = off[piece] + first * size
-                return raw[lo:lo + count * size].view(dtype).reshape(shape)
-            view(0, np.float64, (Q, S, self.E, self.D))[...] = t
-            wv = view(1, np.float64, (Q, 8))
-            wv[...] = 0.0
-            wv[:, :S] = w
-            flags = (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BROUND_AVG if want_avg else 0) | (_lib.VQ_BROUND_TIMED if timed else 0)
-            if bands is not None:
-                view(2, np.float64, (Q, 2))[...] = bands
-                flags |= _lib.VQ_BROUND_SELECT
+            flags = self._round_flags(want_avg, want_scores, timed) | self._fill_round_inputs(view, Q, slice(None), w, bands, t)
             call("vq_db_query_round_views", self._h, Q, tokens, C.c_void_p(blk.ptr), blk.nbytes, flags)
-            res = view(6, np.int64, (Q, 4))
-            prefix = off[10]
-            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            decode = self._partition_decoder(view, off, Q)
             out = []
             for q in range(Q):
                 m = start[q + 1] - start[q]
@@ -783,19 +780,9 @@ class FeatureDB:
                 r.avg = view(4, np.float64, (m, S), start[q] * S) if want_avg else None
                 r.n_e = view(3, np.int32, (m, S), start[q] * S) if want_avg else None
                 r.scores = view(5, np.float64, (m,), start[q]) if want_scores else None
-                r.match_rows = r.near_rows = None
-                r.near_argmax = -1
-                if bands is not None:
-                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
-                    if nm <= prefix and nn <= prefix:
-                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
-                    else:                                     # a list longer than its prefix: the full lists are still on the device
-                        mr = np.empty(nm, dtype=np.int64)
-                        kr = np.empty(nn, dtype=np.int64)
-                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(mr) if nm else None, nm, _np_ptr(kr) if nn else None, nn)
-                        r.match_rows, r.near_rows = mr, kr
+                decode(r, q, bands is not None)
                 out.append(r)
-            self._bround_last = (Q, off, start, pool, [(r.avg, r.n_e) for r in out])       # as after query_round_batch
+            self._bround_last = (Q, off, start, blk._pool, [(r.avg, r.n_e) for r in out])       # as after query_round_batch
             return out
 
     @property
@@ -860,11 +847,7 @@ class FeatureDB:
             call("vq_db_batch_fit_layout", self._h, Q, G, T, total, off)
             off = [int(v) for v in off]
             blk = self._pooled_block("_fit_pools", off[7])
-            raw = blk.bytes()
-
-            def view(piece, dtype, shape):
-                count = int(np.prod(shape))
-                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            view = self._block_view(blk.bytes(), off)
             w_in, th_in, b_in, l_in = view(0, np.float64, (Q, G, 8)), view(1, np.float64, (Q, T)), view(2, np.float64, (Q,)), view(3, np.int64, (Q,))
             r_in, y_in = view(4, np.int64, (total,)), view(5, np.float64, (total,))
             w_in[...] = 0.0
@@ -927,11 +910,7 @@ class FeatureDB:
             call("vq_db_batch_targets_layout", self._h, Q, n_rows, n_draws, n_entries, off)
             off = [int(v) for v in off]
             blk = self._pooled_block("_target_pools", off[9])
-            raw = blk.bytes()
-
-            def view(piece, dtype, shape):
-                count = int(np.prod(shape))
-                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            view = self._block_view(blk.bytes(), off)
             q_in, p_in = view(0, np.int32, (Q, 8)), view(1, np.float64, (Q, 4))
             r_in, d_in, e_in = view(2, np.int64, (n_rows,)), view(3, np.int32, (n_draws, 2)), view(4, np.int32, (n_entries,))
             prev_in = view(6, np.float64, (Q, self.S, self.E, self.D))
@@ -983,50 +962,17 @@ class FeatureDB:
                 call("vq_db_batch_round_rescore", self._h, sum(1 << q for q in queries), C.c_void_p(blk.ptr), blk.nbytes, flags)
                 raise _lib.VqError(-4, "the last batched round does not have queries %r" % (queries,))
             Q, off, start, pool, sims = last
-            if pool is None:
-                blk, _off = self._batch_round_block(Q)
-            else:
-                if pool["free"]:
-                    ptr, nbytes = pool["free"].pop()
-                else:
-                    p = C.c_void_p()
-                    nbytes = (off[9] + 65535) // 65536 * 65536
-                    call("vq_host_alloc", C.byref(p), nbytes)
-                    ptr = p.value
-                blk = _RoundBlock(ptr, nbytes, pool)
-            raw = blk.bytes()
-
-            def view(piece, dtype, shape, first=0):
-                count, size = int(np.prod(shape)), np.dtype(dtype).itemsize
-                lo = off[piece] + first * size
-                return raw[lo:lo + count * size].view(dtype).reshape(shape)
-            wv, bv = view(1, np.float64, (Q, 8)), view(2, np.float64, (Q, 2))
-            wv[...] = 0.0
-            bv[...] = 0.0
-            for i, q in enumerate(queries):
-                wv[q, :self.S] = w[i]
-                if bands is not None:
-                    bv[q] = bands[i]
+            blk = self._batch_round_block(Q)[0] if pool is None else self._pooled_block("_view_round_pools", off[9])
+            view = self._block_view(blk.bytes(), off)
+            self._fill_round_inputs(view, Q, queries, w, bands)
             call("vq_db_batch_round_rescore", self._h, sum(1 << q for q in queries), C.c_void_p(blk.ptr), blk.nbytes, flags)
-            res = view(6, np.int64, (Q, 4))
-            prefix = off[10]
-            pre_m, pre_n = view(7, np.int64, (Q, prefix)), view(8, np.int64, (Q, prefix))
+            decode = self._partition_decoder(view, off, Q)
             out = []
             for q in queries:
                 r = RoundResult()
                 r.avg, r.n_e = sims[q]
                 r.scores = view(5, np.float64, (start[q + 1] - start[q],), start[q])
-                r.match_rows = r.near_rows = None
-                r.near_argmax = -1
-                if bands is not None:
-                    nm, nn, r.near_argmax = int(res[q, 0]), int(res[q, 1]), int(res[q, 2])
-                    if nm <= prefix and nn <= prefix:
-                        r.match_rows, r.near_rows = pre_m[q, :nm], pre_n[q, :nn]
-                    else:                                     # a list longer than its prefix: the full lists are still on the device
-                        mr = np.empty(nm, dtype=np.int64)
-                        kr = np.empty(nn, dtype=np.int64)
-                        call("vq_db_batch_round_fetch", self._h, q, _np_ptr(mr) if nm else None, nm, _np_ptr(kr) if nn else None, nn)
-                        r.match_rows, r.near_rows = mr, kr
+                decode(r, q, bands is not None)
                 out.append(r)
             return out
 
@@ -1064,11 +1010,7 @@ class FeatureDB:
             call("vq_db_batch_topk_layout", self._h, Q, k_max, off)
             off = [int(v) for v in off]
             blk = self._pooled_block("_topk_pools", off[4])
-            raw = blk.bytes()
-
-            def view(piece, dtype, shape):
-                count = int(np.prod(shape))
-                return raw[off[piece]:off[piece] + count * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+            view = self._block_view(blk.bytes(), off)
             k_in, count = view(0, np.int64, (Q,)), view(1, np.int64, (Q,))
             k_in[...] = 0
             count[...] = 0
