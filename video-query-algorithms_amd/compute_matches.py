@@ -110,8 +110,8 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     ``fit_weights=True`` (with ``batch``; ``ValueError`` without): the revise and finalize updates that have ``matches`` get their
     weight update behind their group's pass, on the similarities it left on the device (``compute_similarities_batch(..., fit=...)``:
     two calls per group instead of four per ticket), and ``_choose_weights`` takes ``hp.weights`` / ``hp.threshold`` from the ticket's
-    ``_fit``.  A ticket without one for its current round -- alone in its group, without a resident database, on a sharded one,
-    without labels -- calls ``hp.optimize_weights`` as ever.  Per ticket the order of phase 3, the ledger and the consumption of
+    ``_fit``.  A ticket without one for its current round -- alone in its group, without a resident database, on a sharded one that was
+    opened without ``batch_rounds=True``, without labels -- calls ``hp.optimize_weights`` as ever.  Per ticket the order of phase 3, the ledger and the consumption of
     ``random`` are unchanged; weights, threshold and matches are those of ``batch=True`` bit for bit (both fit on the pass's
     similarities).  Two differences: between the fit and ``compute_scores`` ``ticket.scores`` is not left at the last grid weight
     (compute_matches.py:77 overwrites it on the next line), and a finalize ticket's scores come back with the group's while its

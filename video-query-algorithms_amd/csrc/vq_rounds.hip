@@ -1,6 +1,7 @@
 // Batched query rounds on gfx950: up to 16 queries per pass over a resident feature database -- over the whole database
 // (include/vq_amd_rounds.h), over a row view per query (include/vq_amd_round_views.h) -- and the weight fit and the re-weighting of
-// such a round's queries on what it left on the device (include/vq_amd_round_fit.h).
+// such a round's queries on what it left on the device (include/vq_amd_round_fit.h), and the scores of chosen rows of such a round
+// under a grid of weights, which a row-sharded database combines into its fit (include/vq_amd_round_grid.h).
 //
 // Every kind of round is described by ONE table of pieces (BatchRound, csrc/vq_db.h): query q owns the entries start[q] ..
 // start[q + 1] of the concatenated avg / scores / list arrays.  A whole-database round is the round whose pieces all have N rows.
@@ -285,6 +286,29 @@ __global__ __launch_bounds__(256) void rescore_batch_kernel(RescoreBatchArgs a) 
     }
 }
 
+// grid_kernel (csrc/vq_sim.hip) for the queries of a batched round: thread (q = blockIdx.y, i = g L_q + l) scores row rows[l] of query
+// q's avg piece (qoff[q] on) under w_grid[q][g] into the query's [G][L_q] piece of `out`, which starts at entry G lstart[q].  A query
+// without rows has no thread that passes the bound.
+struct GridBatchArgs {
+    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round
+    const double* w_grid;     // [Q][G][8]
+    const int64_t* rows;      // [sum L]: positions inside each query's piece
+    double* out;              // [G sum L]
+    int64_t qoff[16];         // the first avg entry of query q
+    int64_t lstart[17];       // the first row of query q (lstart[q + 1] - lstart[q] = L_q; 0: nothing to do)
+    int G, S;
+};
+
+__global__ __launch_bounds__(256) void grid_scores_batch_kernel(GridBatchArgs a) {
+    const int q = blockIdx.y;
+    const int64_t l0 = a.lstart[q], L = a.lstart[q + 1] - l0;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)a.G * L) return;
+    const int64_t g = i / L, l = i - g * L;
+    const int64_t entry = a.qoff[q] + a.rows[l0 + l];
+    a.out[(int64_t)a.G * l0 + i] = score_from_avg(a.avg + entry * a.S, a.w_grid + ((int64_t)q * a.G + g) * 8, a.S);
+}
+
 // ---- the host steps that every round takes, each stated once ---------------------------------------------------------------------------
 // The round of Q queries whose pieces hold m[q] entries.  off[0..11] is what the two layout calls hand out: the nine pieces of the
 // host block, each rounded up to 64 bytes, off[9] = their bytes, off[10] = the prefix length, off[11] = 0 or the sum of m.  A view
@@ -468,6 +492,22 @@ static int batch_fit_shape(int Q, int G, int T, int64_t n_labels) {
     VQ_REQUIRE(G >= 1 && G <= kFitMaxGrid && T >= 1 && T <= kFitMaxGrid, "the grids of a batched fit hold 1 to %d weights and thresholds (got %d, %d)",
                kFitMaxGrid, G, T);
     VQ_REQUIRE(n_labels >= 0, "n_labels must not be negative");
+    return VQ_OK;
+}
+
+static void batch_grid_layout(int Q, int G, int64_t n_rows, int64_t off[5]) {
+    off[0] = 0;
+    off[1] = off[0] + up64((int64_t)Q * G * 8 * 8);
+    off[2] = off[1] + up64((int64_t)Q * 8);
+    off[3] = off[2] + up64(n_rows * 8);
+    off[4] = off[3] + up64((int64_t)G * n_rows * 8);
+}
+
+static int batch_grid_shape(int Q, int G, int64_t n_rows) {
+    VQ_REQUIRE(Q >= 1 && Q <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, Q);
+    VQ_REQUIRE(G >= 1 && G <= kFitMaxGrid, "the grid of a batched round holds 1 to %d weights (got %d)", kFitMaxGrid, G);
+    // 2^32 rows x 64 weights are 2^30 workgroups of 256: the launch's grid stays inside 31 bits
+    VQ_REQUIRE(n_rows >= 0 && n_rows <= ((int64_t)1 << 32), "n_rows must be in [0, 2^32] (got %lld)", (long long)n_rows);
     return VQ_OK;
 }
 
@@ -894,6 +934,69 @@ int vq_db_batch_round_rescore(vq_db* db, int32_t mask, void* block, int64_t bloc
                 r.n1[q] = res[4 * q + 1];
             }
     }
+    return VQ_OK;
+}
+
+// ---- the scores of chosen rows of a batched round's queries under a grid of weights (include/vq_amd_round_grid.h) --------------------
+int vq_db_batch_grid_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int64_t n_rows, int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    const int rc = batch_grid_shape(n_queries, n_grid, n_rows);
+    if (rc != VQ_OK) return rc;
+    batch_grid_layout(n_queries, n_grid, n_rows, off);
+    return VQ_OK;
+}
+
+int vq_db_batch_round_grid(vq_db* db, int32_t n_queries, int32_t n_grid, int64_t n_rows, void* block, int64_t block_bytes) {
+    VQ_REQUIRE(db && block, "NULL argument");
+    {
+        const int rc = batch_grid_shape(n_queries, n_grid, n_rows);
+        if (rc != VQ_OK) return rc;
+    }
+    const int Q = n_queries, G = n_grid;
+    int64_t off[5];
+    batch_grid_layout(Q, G, n_rows, off);
+    VQ_REQUIRE(block_bytes >= off[4], "the block of these grid scores needs %lld bytes (vq_db_batch_grid_layout), got %lld", (long long)off[4],
+               (long long)block_bytes);
+    char* host = (char*)block;
+    const int64_t* L = (const int64_t*)(host + off[1]);
+    const int64_t* rows = (const int64_t*)(host + off[2]);
+    std::lock_guard<std::mutex> lk(db->mu);
+    const BatchRound& r = db->round;
+    if (r.q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    GridBatchArgs a;
+    a.lstart[0] = 0;
+    int64_t max_l = 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        const int64_t lq = q < Q ? L[q] : 0;
+        VQ_REQUIRE(lq >= 0 && lq <= n_rows, "query %d: L = %lld outside [0, n_rows = %lld]", q, (long long)lq, (long long)n_rows);
+        if (lq > 0 && q >= r.q) return fail(VQ_E_STATE, "the last batched round had %d queries (rows for query %d)", r.q, q);
+        a.lstart[q + 1] = a.lstart[q] + lq;
+        a.qoff[q] = r.start[q];
+        max_l = std::max(max_l, lq);
+    }
+    VQ_REQUIRE(a.lstart[kBatchSlots] == n_rows, "the L of the queries add up to %lld, n_rows is %lld", (long long)a.lstart[kBatchSlots], (long long)n_rows);
+    for (int q = 0; q < Q; ++q)
+        for (int64_t l = a.lstart[q]; l < a.lstart[q + 1]; ++l)
+            VQ_REQUIRE(rows[l] >= 0 && rows[l] < r.m(q), "query %d: row %lld (entry %lld) outside [0,%lld)", q, (long long)rows[l],
+                       (long long)(l - a.lstart[q]), (long long)r.m(q));
+    if (n_rows == 0) return VQ_OK;                    // every query skipped: nothing to launch
+    DeviceGuard g(db->device);
+    {
+        const int rc = ensure_grid_buf(db, off[4]);
+        if (rc != VQ_OK) return rc;
+    }
+    char* base = (char*)db->grid_buf;
+    VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));      // grid | L | rows: adjacent
+    a.avg = (const double*)(db->bround_dev + r.off[4]);
+    a.w_grid = (const double*)(base + off[0]);
+    a.rows = (const int64_t*)(base + off[2]);
+    a.out = (double*)(base + off[3]);
+    a.G = G;
+    a.S = db->S;
+    grid_scores_batch_kernel<<<dim3(cdiv((int64_t)G * max_l, 256), Q), 256, 0, db->stream>>>(a);
+    VQ_CHECK_LAUNCH();
+    VQ_HIP(hipMemcpyAsync(host + off[3], base + off[3], (size_t)((int64_t)G * n_rows * 8), hipMemcpyDeviceToHost, db->stream));
+    VQ_HIP(hipStreamSynchronize(db->stream));
     return VQ_OK;
 }
 

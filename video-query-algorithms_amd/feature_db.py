@@ -864,6 +864,46 @@ class FeatureDB:
             surface = view(6, np.float64, (Q, G, T))
             return [surface[queries[i]] if rs[i].size else None for i in range(k)]
 
+    def batch_round_grid(self, queries, rows, w_grids) -> list:
+        """hyperparameter.py:57-58 on chosen rows for several queries of the LAST batched round (either kind) in one call and one
+        launch (vq_db_batch_round_grid, include/vq_amd_round_grid.h): per entry i, the scores of ``rows[i]`` (positions in the view
+        of query ``queries[i]`` of that round, as in its results; a row may repeat) under each weight of ``w_grids[i]`` [G,S], on the
+        averaged similarities the round left on the device; G is common to the call.  Returns one [G, L_i] array per entry -- the bits
+        of :meth:`scores_grid` on the same similarities, and with the round's (or the rescore's) weights the bits of that round's own
+        scores at those rows -- and None for an entry without rows.  What a row-sharded database combines into its weight fit."""
+        queries = [int(q) for q in queries]
+        k = len(queries)
+        if not (k and len(rows) == len(w_grids) == k) or len(set(queries)) != k:
+            raise ValueError("one rows / w_grid per query, every query once")
+        wg = [np.asarray(w, dtype=np.float64) for w in w_grids]
+        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        G = int(wg[0].shape[0]) if wg[0].ndim == 2 else -1
+        if any(w.ndim != 2 or w.shape != (G, self.S) for w in wg):
+            raise ValueError("w_grids must be [G,%d] with one G for the call" % self.S)
+        if min(queries) < 0:
+            raise ValueError("a query is its index in the last batched round")
+        with self.lock:
+            Q = max(queries) + 1                              # slot q of the block = query q of the round; the library refuses what that round lacks
+            order = sorted(range(k), key=lambda i: queries[i])
+            total = int(sum(r.size for r in rs))
+            off = (C.c_int64 * 5)()
+            call("vq_db_batch_grid_layout", self._h, Q, G, total, off)
+            off = [int(v) for v in off]
+            blk = self._pooled_block("_grid_pools", off[4])
+            view = self._block_view(blk.bytes(), off)
+            w_in, l_in, r_in = view(0, np.float64, (Q, G, 8)), view(1, np.int64, (Q,)), view(2, np.int64, (total,))
+            w_in[...] = 0.0
+            l_in[...] = 0
+            at, first = 0, {}
+            for i in order:
+                q = queries[i]
+                w_in[q, :, :self.S], l_in[q] = wg[i], rs[i].size
+                r_in[at:at + rs[i].size] = rs[i]
+                first[i] = at
+                at += rs[i].size
+            call("vq_db_batch_round_grid", self._h, Q, G, total, C.c_void_p(blk.ptr), blk.nbytes)
+            return [view(3, np.float64, (G, rs[i].size), G * first[i]) if rs[i].size else None for i in range(k)]
+
     # ------------------------------------------------------------------ the bootstrapped targets of a group of tickets
     def batch_targets_lds_rows(self) -> int:
         """The largest draw (rows) whose systems ``batch_targets`` solves in a workgroup's local memory; longer draws solve in a
@@ -1116,7 +1156,7 @@ class FeatureDB:
         if self._h:
             pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()] + \
                 list(getattr(self, "_view_round_pools", {}).values()) + list(getattr(self, "_fit_pools", {}).values()) + \
-                list(getattr(self, "_topk_pools", {}).values())
+                list(getattr(self, "_topk_pools", {}).values()) + list(getattr(self, "_grid_pools", {}).values())
             self._bround_last = None
             for pool in pools:
                 if pool is None:

@@ -29,6 +29,23 @@ def parabola_through(xs, y_lo, y_mid, y_hi):
     return vertex, fall_lo / ((mid - vertex) ** 2 - (lo - vertex) ** 2)
 
 
+def raw_loss_surface(graded, labels, threshold_grid, ballast):
+    """The loss surface of hyperparameter.py:60-64 before its division by the number of labels: ``graded`` [G][L] are the labelled
+    clips' scores under each grid weight, ``labels`` [L] their verdicts in the dict's order -> [G][T] raw sums.  Every clip's term at
+    once ([L][G][T], the same elementwise operations in the same order), then added to the surface ONE CLIP AT A TIME in label order:
+    every cell sees the reference's sequence of fp64 additions.  The host branch of ``optimize_weights`` and the fit of a batched
+    round on a row-sharded database (``ShardedFeatureDB.batch_round_fit``) both run these lines."""
+    graded = np.asarray(graded, dtype=np.float64)
+    th = np.asarray(threshold_grid, dtype=np.float64)[None, :]
+    surface = np.tile(0.5 * th, (graded.shape[0], 1))
+    y = np.array([float(v) for v in labels], dtype=np.float64)[:, None, None]
+    margin = graded.T[:, :, None] - th[None]
+    terms = (np.heaviside(margin, 1) - y) * margin * (1 + y * ballast)
+    for term in terms:
+        surface = surface + term
+    return surface
+
+
 class Hyperparameter:
     def __init__(self, default_weights, default_threshold=0.8, ballast=0.3, near_miss_default=0.5, mu=.3,
                  streams=('rgb', 'warped_optical_flow'), feature_name='global_pool', f_bootstrap=0.5, f_memory=0.5,
@@ -58,18 +75,8 @@ class Hyperparameter:
                 surface = db.loss_surface(candidates, rows, [float(v) for v in labels], self.threshold_grid, self.ballast)
             else:
                 graded = db.scores_grid(candidates, rows)                           # [40][L] in one launch
-        if on_device:
-            surface = surface / len(labels)
-            return self._pick(ticket, surface)
-        th = self.threshold_grid[None, :]
-        surface = np.tile(0.5 * th, (len(self.weight_grid), 1))
-        # every clip's term of hyperparameter.py:60-64 at once ([L][40][31], the same elementwise operations in the same order), then
-        # added to the surface ONE CLIP AT A TIME in dict order: every cell sees the reference's sequence of fp64 additions
-        y = np.array([float(v) for v in labels], dtype=np.float64)[:, None, None]
-        margin = graded.T[:, :, None] - th[None]
-        terms = (np.heaviside(margin, 1) - y) * margin * (1 + y * self.ballast)
-        for term in terms:
-            surface = surface + term
+        if not on_device:
+            surface = raw_loss_surface(graded, labels, self.threshold_grid, self.ballast)
         surface = surface / len(labels)
         return self._pick(ticket, surface)
 

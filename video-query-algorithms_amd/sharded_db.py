@@ -21,6 +21,11 @@ broker code scores on every GPU of the node (half B):
   defines the sub-list that falls into its range on its own GPU, and ``use`` is one announcement carrying the set's number; while a
   set is in use every result is indexed by position in it, the gathers take per-rank counts that every rank derives from the list
   (nothing is exchanged per query) and global view order is rank-major because the list is ascending;
+* batched rounds (``batch_rounds=True``; whole-database rounds only): up to 16 tickets share every rank's one pass over its rows
+  (``query_round_batch``), and their weight fit, re-weighting and ranking follow in one call each (``batch_round_fit`` /
+  ``batch_round_rescore`` / ``batch_round_topk``) -- one announcement and one gather of the per-row results for all of them, two
+  small gathers for all their partitions; a fit adds the labelled clips' terms in label order on the host, from grid scores that
+  every rank computes for the rows it holds (``FeatureDB.batch_round_grid``) and one exact all-reduce combines;
 * target bootstrapping: the handful of user-validated rows are fetched from their owners (``vq_db_read_rows``) and the
   closed forms run on the root's GPU (``csrc/vq_boot.hip``, the same kernel the resident route uses).
 
@@ -30,7 +35,8 @@ Two ways to run it.  **SPMD** (``bench.py``, tests): every rank calls the same m
 gpus=[...])`` starts them as fresh processes (``shard_worker.py``), one per GPU.  An exception on any rank is agreed on
 before the next collective (served mode) and raised on the root, like a one-GPU ``VqError`` would be.
 
-Nothing here computes on the host: the arithmetic is the local :class:`FeatureDB`'s.
+Nothing here computes on the host -- the arithmetic is the local :class:`FeatureDB`'s -- but the label-order sum of a batched fit
+(``hyperparameter.raw_loss_surface``, the lines ``optimize_weights`` runs on a sharded database).
 """
 from __future__ import annotations
 
@@ -46,6 +52,10 @@ from .shard import all_gather_counts, all_gather_rows, merge_topk, shard_range
 
 OP_CLOSE, OP_RESTRICT, OP_SET_QUERY, OP_QUERY_FROM_ROW, OP_SCAN, OP_RESCORE, OP_SIMS, OP_SCORES, OP_GRID, OP_SELECT, OP_TOPK, \
     OP_MIN, OP_FETCH, OP_SCAN_BATCH, OP_LAYOUT, OP_WRITE_AVG, OP_ROUND, OP_DEFINE_SET, OP_USE_SET, OP_DROP_SET = range(20)
+# the four calls of a batched round (batch_rounds=True): the pass, the grid scores of a fit, the re-weighting, the ranking
+OP_ROUND_BATCH, OP_BATCH_GRID, OP_BATCH_RESCORE, OP_BATCH_TOPK = range(20, 24)
+BATCH_SLOTS = 16          # queries of a batched round (include/vq_amd_rounds.h)
+BATCH_TOPK_CAP = 4096     # the largest k of one batch_round_topk call (include/vq_amd_round_topk.h)
 
 
 def _atomic(method):
@@ -66,9 +76,11 @@ class ShardError(RuntimeError):
 class ShardedFeatureDB:
     """``local``: this rank's rows ``[row0, row0 + local.n)`` as a :class:`FeatureDB` (or an object with its local
     surface).  ``clip_ids``: the GLOBAL id list (every rank holds it: N x 8 bytes).  ``served``: rank ``root`` drives,
-    the others must be inside :meth:`serve`."""
+    the others must be inside :meth:`serve`.  ``batch_rounds``: offer the four calls of a batched round (the same value on every
+    rank); off, :meth:`batch_round_supported` says no and ``ticket.compute_similarities_batch`` runs every ticket's own round."""
 
-    def __init__(self, local, n_total: int, row0: int, clip_ids: Sequence[int], group=None, root: int = 0, served: bool = False, stream=None):
+    def __init__(self, local, n_total: int, row0: int, clip_ids: Sequence[int], group=None, root: int = 0, served: bool = False, stream=None,
+                 batch_rounds: bool = False):
         if hasattr(local, "_h"):                          # a real FeatureDB (the CPU tests' stand-in has no library handle)
             from . import _lib
             _lib.require_torch_runtime("ShardedFeatureDB")
@@ -93,6 +105,9 @@ class ShardedFeatureDB:
         self.lock = threading.RLock()
         self.sims_owner = None
         self.scores_owner = None
+        # batched rounds: the switch, and of the last one its number of queries and every query's (avg, n_e) as returned
+        self.batch_rounds = bool(batch_rounds)
+        self._bround_q, self._bround_sims = 0, None
         # search sets: id -> view (workers of a served database know a set by its number only), number -> per-rank counts, and the
         # window of the global result arrays this rank fills: [_pos0, _pos0 + _nloc) of _ntot (no set in use: its rows of N)
         self._sets, self._set_counts, self._next_token = {}, {}, 0
@@ -114,7 +129,8 @@ class ShardedFeatureDB:
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_store(cls, path: str, device: int = 0, group=None, root: int = 0, served: bool = False, chunk_rows: int = 16384):
+    def from_store(cls, path: str, device: int = 0, group=None, root: int = 0, served: bool = False, chunk_rows: int = 16384,
+                   batch_rounds: bool = False):
         """Every rank uploads ITS row range of a binary feature store (feature_store.py) -- the files are memory-mapped, so a
         rank reads only its own N/world rows."""
         import torch.distributed as dist
@@ -123,23 +139,23 @@ class ShardedFeatureDB:
         _meta, feats, ids, _present = open_store(path)
         row0, rows = shard_range(feats.shape[0], dist.get_world_size(group), dist.get_rank(group))
         local = FeatureDB.from_store(path, device=device, row0=row0, rows=rows, chunk_rows=chunk_rows)
-        return cls(local, feats.shape[0], row0, ids, group=group, root=root, served=served)
+        return cls(local, feats.shape[0], row0, ids, group=group, root=root, served=served, batch_rounds=batch_rounds)
 
     @classmethod
     def synthetic(cls, n: int, n_streams: int, n_splits: int, dim: int = 1024, seed: int = 0, scales=(4.0, 1.0), dtype=np.float32,
-                  device: int = 0, group=None, root: int = 0, stream=None):
+                  device: int = 0, group=None, root: int = 0, stream=None, batch_rounds: bool = False):
         """Rows generated on each rank's device by the counter-based hash (BASELINE configs[3]: too big to ship)."""
         import torch.distributed as dist
         from .feature_db import FeatureDB
         row0, rows = shard_range(n, dist.get_world_size(group), dist.get_rank(group))
         local = FeatureDB.synthetic(rows, n_streams, n_splits, dim, seed=seed, scales=scales, row0=row0, dtype=dtype, device=device)
-        return cls(local, n, row0, np.arange(1, n + 1, dtype=np.int64), group=group, root=root, stream=stream)
+        return cls(local, n, row0, np.arange(1, n + 1, dtype=np.int64), group=group, root=root, stream=stream, batch_rounds=batch_rounds)
 
     @classmethod
-    def open(cls, store_path: str, gpus: Sequence[int], backend: Optional[str] = None, timeout_s: float = 600.0):
+    def open(cls, store_path: str, gpus: Sequence[int], backend: Optional[str] = None, timeout_s: float = 600.0, batch_rounds: bool = False):
         """The broker's entry point: start one fresh worker process per further GPU (``shard_worker.py``; call this BEFORE the
         broker's process makes its first GPU call), join them as rank 0 over 127.0.0.1 and return the served database on
-        ``gpus[0]``.  ``close()`` ends the workers."""
+        ``gpus[0]``.  ``close()`` ends the workers.  ``batch_rounds`` goes to every worker with its command line."""
         import datetime
         import torch
         import torch.distributed as dist
@@ -161,7 +177,7 @@ class ShardedFeatureDB:
         procs = []
         if world > 1:
             worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "shard_worker.py")
-            argv = [os.path.abspath(store_path), "--backend", backend, "--timeout", str(timeout_s)]
+            argv = [os.path.abspath(store_path), "--backend", backend, "--timeout", str(timeout_s)] + (["--batch-rounds"] if batch_rounds else [])
             for e, g in zip(envs[1:], gpus[1:]):
                 e["VQ_FANOUT_DEVICE"] = str(g)
             procs = fanout.start_children(worker, argv, envs[1:])
@@ -178,7 +194,7 @@ class ShardedFeatureDB:
             row0, rows = shard_range(feats.shape[0], world, 0)
             local = FeatureDB.from_store(store_path, device=gpus[0], row0=row0, rows=rows)
             _await_workers(store, ["loaded/%d" % r for r in range(1, world)], procs, timeout_s, "load their rows")
-            db = cls(local, feats.shape[0], row0, ids, served=True)
+            db = cls(local, feats.shape[0], row0, ids, served=True, batch_rounds=batch_rounds)
         except BaseException:
             fanout.stop_children(procs)
             if dist.is_initialized():
@@ -530,23 +546,7 @@ class ShardedFeatureDB:
     def _merge_selection(self, m, r, am, best):
         """This rank's (match rows, near rows, first arg-max row or -1, its score) in GLOBAL row numbers -> the lists of all ranks,
         rank-major = database order, and the first arg-max over the ranks (two small gathers: sizes, then bodies)."""
-        torch = self._torch
-        head = torch.from_numpy(np.concatenate([np.array([m.size, r.size, am], dtype=np.int64),
-                                                np.array([best], dtype=np.float64).view(np.int64)])).to(self._cdev)
-        heads = self._host(self._coll(lambda: all_gather_rows(head.reshape(1, 4), self.world, self.group)))
-        width = int((heads[:, 0] + heads[:, 1]).max())
-        body = np.zeros(max(width, 1), dtype=np.int64)
-        body[:m.size], body[m.size:m.size + r.size] = m, r
-        bodies = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(body).reshape(1, -1).to(self._cdev), self.world, self.group)))
-        match = np.concatenate([bodies[g, :heads[g, 0]] for g in range(self.world)])
-        near = np.concatenate([bodies[g, heads[g, 0]:heads[g, 0] + heads[g, 1]] for g in range(self.world)])
-        near_argmax, top = -1, None
-        for g in range(self.world):                                   # first maximum in global order: lowest rank wins a tie
-            if heads[g, 2] >= 0:
-                v = float(heads[g, 3:4].view(np.float64)[0])
-                if top is None or v > top:
-                    near_argmax, top = int(heads[g, 2]), v
-        return match, near, near_argmax
+        return self._merge_selections([(m, r, am, best)])[0]
 
     @_atomic
     def query_round(self, t, weights=None, select=None):
@@ -611,6 +611,272 @@ class ShardedFeatureDB:
             out.match_rows, out.near_rows, out.near_argmax = self._merge_selection(
                 np.asarray(r.match_rows, dtype=np.int64) + self._pos0, np.asarray(r.near_rows, dtype=np.int64) + self._pos0,
                 am + self._pos0 if am >= 0 else -1, best)
+        return out
+
+    # ------------------------------------------------------------------ batched rounds (batch_rounds=True; the whole database only)
+    def batch_round_supported(self) -> bool:
+        """Do the ranks offer the 16-query pass?  The switch of this object and the local database's own answer: both are the same on
+        every rank (one switch for all of them, one shape for all shards)."""
+        supported = getattr(self.local, "batch_round_supported", None)
+        return bool(self.batch_rounds and supported is not None and supported())
+
+    def _batch_round_ready(self, what: str, need_round: bool = True):
+        """The refusals the calls of a batched round share, raised before anything is announced."""
+        if not self.batch_rounds:
+            raise ValueError("%s: this sharded database was opened without batch_rounds=True" % what)
+        if self._set_in_use is not None:
+            raise ValueError("%s runs over the whole database: search set %r is in use (use_search_set(None) first)" % (what, self._set_in_use))
+        if need_round and not self._bround_q:
+            from ._lib import VqError
+            raise VqError(-4, "%s: no batched round has run on this sharded database" % what)
+
+    def _round_queries(self, what: str, queries):
+        queries = [int(q) for q in queries]
+        if not queries or len(set(queries)) != len(queries) or min(queries) < 0:
+            raise ValueError("%s: every query -- its index in the last batched round -- once" % what)
+        if max(queries) >= self._bround_q:
+            from ._lib import VqError
+            raise VqError(-4, "%s: the last batched round had %d queries (asked for %r)" % (what, self._bround_q, queries))
+        return queries
+
+    def _local_selections(self, results, scores, best=None):
+        """Per result of a local batched call: (match rows, near rows, first arg-max row or -1, its score) in GLOBAL row numbers;
+        the score comes from ``scores[i]`` or, when the scores did not come back, from ``best[i]``."""
+        out = []
+        for i, r in enumerate(results):
+            am = int(r.near_argmax)
+            v = 0.0 if am < 0 else float(scores[i][am]) if scores is not None else float(best[i])
+            out.append((np.asarray(r.match_rows, dtype=np.int64) + self._pos0, np.asarray(r.near_rows, dtype=np.int64) + self._pos0,
+                        am + self._pos0 if am >= 0 else -1, v))
+        return out
+
+    def _merge_selections(self, parts):
+        """The partitions of the Q queries of one call, merged in TWO gathers whatever Q is: heads [1, 4Q] (per query: match count,
+        near count, near arg-max row, its score as bits), then one body per rank (per query its match rows, then its near rows).
+        ``parts``: per query this rank's (match rows, near rows, first arg-max row or -1, its score) in GLOBAL row numbers.  Per
+        query the lists of all ranks rank-major = database order, and the first maximum in global order."""
+        torch = self._torch
+        Q = len(parts)
+        head = np.zeros((1, 4 * Q), dtype=np.int64)
+        for q, (m, r, am, best) in enumerate(parts):
+            head[0, 4 * q:4 * q + 3] = (m.size, r.size, am)
+            head[0, 4 * q + 3] = np.array([best], dtype=np.float64).view(np.int64)[0]
+        heads = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(head).to(self._cdev), self.world, self.group)))
+        heads = np.ascontiguousarray(heads).reshape(self.world, Q, 4)
+        width = int((heads[:, :, 0] + heads[:, :, 1]).sum(axis=1).max())
+        body = np.zeros((1, max(width, 1)), dtype=np.int64)
+        at = 0
+        for m, r, _am, _best in parts:
+            body[0, at:at + m.size], body[0, at + m.size:at + m.size + r.size] = m, r
+            at += m.size + r.size
+        bodies = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(body).to(self._cdev), self.world, self.group)))
+        at = [0] * self.world
+        out = []
+        for q in range(Q):
+            match, near = [], []
+            near_argmax, top = -1, None
+            for g in range(self.world):
+                nm, nn, am = (int(v) for v in heads[g, q, :3])
+                match.append(bodies[g, at[g]:at[g] + nm])
+                near.append(bodies[g, at[g] + nm:at[g] + nm + nn])
+                at[g] += nm + nn
+                if am >= 0:                                           # first maximum in global order: lowest rank wins a tie
+                    v = float(heads[g, q, 3:4].view(np.float64)[0])
+                    if top is None or v > top:
+                        near_argmax, top = am, v
+            out.append((np.concatenate(match), np.concatenate(near), near_argmax))
+        return out
+
+    @_atomic
+    def query_round_batch(self, targets, weights, selects=None, want_avg: bool = True, timed: bool = False, want_scores: bool = True) -> list:
+        """:meth:`FeatureDB.query_round_batch` on every rank's rows as ONE operation: one announcement (the Q targets, weights and
+        bands travel with it), every rank's own 16-query pass, ONE gather of the per-row results wanted (``avg | n_e | scores`` of all
+        Q queries, packed [n, Q S + S + Q] doubles) and two small gathers for the Q partitions -- where Q tickets' own rounds are Q
+        announcements, Q gathers of [n, 2S+1] doubles and 2Q small ones.  One :class:`RoundResult` per query, rows as GLOBAL row
+        numbers, ``n_e`` one array shared by all; every array has the bits of the same call on one GPU.  With ``want_avg=False,
+        want_scores=False`` nothing N-sized moves: the scores stay on the ranks for :meth:`batch_round_topk`, and a rank reads the
+        value of its near arg-max with one ``batch_round_grid`` call of one row per query.  The whole database only, ``batch_rounds``
+        on, 1 to 16 queries (``ValueError``); ``timed`` is not offered.  SPMD: every rank passes the same arguments."""
+        from .feature_db import RoundResult
+        torch = self._torch
+        S, E, D = self.S, self.E, self.D
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if t.ndim != 4 or t.shape[1:] != (S, E, D) or w.shape != (t.shape[0], S):
+            raise ValueError("targets must be [Q,%d,%d,%d] and weights [Q,%d]" % (S, E, D, S))
+        Q = int(t.shape[0])
+        bands = None if selects is None else np.ascontiguousarray(selects, dtype=np.float64)
+        if bands is not None and bands.shape != (Q, 2):
+            raise ValueError("selects must be [Q,2]: (threshold, lower) per query")
+        if not 1 <= Q <= BATCH_SLOTS:
+            raise ValueError("a batched round takes 1 to %d queries (got %d)" % (BATCH_SLOTS, Q))
+        self._batch_round_ready("query_round_batch", need_round=False)
+        if timed:
+            raise NotImplementedError("a sharded batched round is not timed (time FeatureDB.query_round_batch on one rank's rows)")
+        flags = (1 if want_avg else 0) | (2 if want_scores else 0) | (4 if bands is not None else 0)
+        self._announce(OP_ROUND_BATCH, ints=[Q, flags],
+                       floats=np.concatenate([t.reshape(-1), w.reshape(-1), np.zeros(0) if bands is None else bands.reshape(-1)]))
+        self._bround_q, self._bround_sims = 0, None                   # the round before is gone from here on
+
+        def part():
+            rs = self.local.query_round_batch(t, w, bands, want_avg=want_avg, want_scores=want_scores)
+            cols = ([r.avg for r in rs] + [np.asarray(rs[0].n_e, dtype=np.float64)] if want_avg else []) + \
+                ([np.asarray(r.scores)[:, None] for r in rs] if want_scores else [])
+            packed = np.ascontiguousarray(np.concatenate(cols, axis=1)) if cols else None
+            if bands is None:
+                return packed, None
+            if want_scores:
+                return packed, self._local_selections(rs, [r.scores for r in rs])
+            best = [0.0] * Q                                          # the scores stayed on the device: one grid call, G = 1, one row per query
+            need = [q for q in range(Q) if int(rs[q].near_argmax) >= 0]
+            if need:
+                graded = self.local.batch_round_grid(need, [[int(rs[q].near_argmax)] for q in need], [w[q][None, :] for q in need])
+                for q, g in zip(need, graded):
+                    best[q] = float(g[0, 0])
+            return packed, self._local_selections(rs, None, best)
+        packed, sel = self._local_step(part)
+        full = None if packed is None else self._host(self._coll(lambda: self._all_rows(torch.from_numpy(packed).to(self._cdev))))
+        merged = None if sel is None else self._merge_selections(sel)
+        n_e = full[:, Q * S:(Q + 1) * S].astype(np.int32) if want_avg else None          # counts <= E: exact as doubles
+        c = (Q + 1) * S if want_avg else 0
+        out = []
+        for q in range(Q):
+            r = RoundResult()
+            r.avg = np.ascontiguousarray(full[:, q * S:(q + 1) * S]) if want_avg else None
+            r.n_e = n_e
+            r.scores = np.ascontiguousarray(full[:, c + q]) if want_scores else None
+            r.match_rows = r.near_rows = None
+            r.near_argmax = -1
+            if merged is not None:
+                r.match_rows, r.near_rows, r.near_argmax = merged[q]
+            out.append(r)
+        self._bround_q, self._bround_sims = Q, [(r.avg, r.n_e) for r in out]
+        return out
+
+    def _batch_grid(self, queries, rows, w_grids):
+        """The scores of GLOBAL rows ``rows[i]`` of query ``queries[i]`` of the last batched round under ``w_grids[i]`` [G,S]: every
+        rank's ``batch_round_grid`` on the rows it holds, ONE exact all-reduce (x + 0) for all queries -> one [G, L_i] array each."""
+        G = int(w_grids[0].shape[0])
+        sizes = [int(r.size) for r in rows]
+        first = np.concatenate([[0], np.cumsum(sizes)]) * G
+
+        def part():
+            buf = np.zeros(int(first[-1]), dtype=np.float64)
+            mine = [self._mine_pos(r) for r in rows]
+            have = [i for i, (pos, _loc) in enumerate(mine) if pos.size]
+            if have:
+                got = self.local.batch_round_grid([queries[i] for i in have], [mine[i][1] for i in have], [w_grids[i] for i in have])
+                for i, g in zip(have, got):
+                    buf[first[i]:first[i + 1]].reshape(G, sizes[i])[:, mine[i][0]] = g
+            return buf
+        full = self._sum(self._local_step(part))
+        return [full[first[i]:first[i + 1]].reshape(G, sizes[i]) for i in range(len(rows))]
+
+    @_atomic
+    def batch_round_fit(self, queries, rows, labels, w_grids, th_grids, ballasts) -> list:
+        """:meth:`FeatureDB.batch_round_fit` for queries of the last sharded batched round, rows as GLOBAL row numbers.  A cell of a
+        loss surface is the sum of one term per labelled clip in label order, so no rank can produce its bits from the rows it holds:
+        every rank computes the labelled rows' scores under every grid weight on its device (``batch_round_grid``), one all-reduce
+        combines the disjoint pieces of all queries exactly, and the terms are added in label order by the lines
+        ``Hyperparameter.optimize_weights`` runs on a sharded database (``hyperparameter.raw_loss_surface``).  Returns one [G,T]
+        array of raw sums per entry (the caller divides by the number of labels), None for an entry without labels."""
+        from .hyperparameter import raw_loss_surface
+        self._batch_round_ready("batch_round_fit")
+        queries = self._round_queries("batch_round_fit", queries)
+        k = len(queries)
+        if not len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == k:
+            raise ValueError("one rows / labels / w_grid / th_grid / ballast per query")
+        wg = [np.ascontiguousarray(g, dtype=np.float64) for g in w_grids]
+        th = [np.asarray(v, dtype=np.float64).reshape(-1) for v in th_grids]
+        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
+        G, T = (int(wg[0].shape[0]) if wg[0].ndim == 2 else -1), int(th[0].size)
+        if any(g.ndim != 2 or g.shape != (G, self.S) for g in wg) or any(v.size != T for v in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
+            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
+        if not (1 <= G <= 64 and 1 <= T <= 64):
+            raise ValueError("the grids of a batched fit hold 1 to 64 weights and thresholds (got %d, %d)" % (G, T))
+        if any(r.size and (r.min() < 0 or r.max() >= self.n) for r in rs):
+            raise ValueError("row outside [0,%d)" % self.n)
+        if not sum(r.size for r in rs):
+            return [None] * k
+        self._announce(OP_BATCH_GRID, ints=np.concatenate([[k, G], queries, [r.size for r in rs]] + rs), floats=np.concatenate([g.reshape(-1) for g in wg]))
+        graded = self._batch_grid(queries, rs, wg)
+        return [raw_loss_surface(graded[i], ys[i], th[i], float(ballasts[i])) if rs[i].size else None for i in range(k)]
+
+    @_atomic
+    def batch_round_rescore(self, queries, weights, selects=None) -> list:
+        """:meth:`FeatureDB.batch_round_rescore` on every rank as ONE operation: one announcement, every rank's own re-weighting of
+        the queries' averaged similarities on its device, ONE gather of their scores ([n, k] doubles) and, with ``selects``, the two
+        small gathers of their partitions.  One :class:`RoundResult` per entry, rows as GLOBAL row numbers, ``avg`` / ``n_e`` the
+        round's own."""
+        from .feature_db import RoundResult
+        torch = self._torch
+        self._batch_round_ready("batch_round_rescore")
+        queries = self._round_queries("batch_round_rescore", queries)
+        k = len(queries)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        bands = None if selects is None else np.ascontiguousarray(selects, dtype=np.float64)
+        if w.shape != (k, self.S) or (bands is not None and bands.shape != (k, 2)):
+            raise ValueError("weights must be [k,%d] and selects [k,2] for k distinct queries" % self.S)
+        self._announce(OP_BATCH_RESCORE, ints=[k, 0 if bands is None else 1] + queries,
+                       floats=np.concatenate([w.reshape(-1), np.zeros(0) if bands is None else bands.reshape(-1)]))
+
+        def part():
+            rs = self.local.batch_round_rescore(queries, w, bands)
+            packed = np.ascontiguousarray(np.stack([np.asarray(r.scores) for r in rs], axis=1))
+            return packed, (None if bands is None else self._local_selections(rs, [r.scores for r in rs]))
+        packed, sel = self._local_step(part)
+        full = self._host(self._coll(lambda: self._all_rows(torch.from_numpy(packed).to(self._cdev))))
+        merged = None if sel is None else self._merge_selections(sel)
+        out = []
+        for i, q in enumerate(queries):
+            r = RoundResult()
+            r.avg, r.n_e = self._bround_sims[q]
+            r.scores = np.ascontiguousarray(full[:, i])
+            r.match_rows = r.near_rows = None
+            r.near_argmax = -1
+            if merged is not None:
+                r.match_rows, r.near_rows, r.near_argmax = merged[i]
+            out.append(r)
+        return out
+
+    @_atomic
+    def batch_round_topk(self, ks, queries=None) -> list:
+        """:meth:`FeatureDB.batch_round_topk` on every rank as ONE operation: every rank ranks ``min(k, its rows)`` clips of each query
+        on its device, ONE gather brings the lists together, and ``shard.merge_topk`` orders each query's by descending score, ties
+        by ascending GLOBAL row.  One (rows, vals) per entry; a k above the rows of the database is clamped to them, one above 4096
+        is refused for the whole call, as on one GPU."""
+        torch = self._torch
+        self._batch_round_ready("batch_round_topk")
+        queries = self._round_queries("batch_round_topk", range(self._bround_q) if queries is None else queries)
+        nq = len(queries)
+        kk = [int(ks)] * nq if np.ndim(ks) == 0 else [int(v) for v in ks]
+        if len(kk) != nq or min(kk) < 0:
+            raise ValueError("one k per query (or one int), none negative")
+        kk = [min(k, self.n) for k in kk]
+        k_max = max(max(kk), 1)
+        if k_max > BATCH_TOPK_CAP:
+            from ._lib import VqError
+            raise VqError(-1, "batch_round_topk ranks at most %d clips per query (got %d)" % (BATCH_TOPK_CAP, k_max))
+        self._announce(OP_BATCH_TOPK, ints=[nq] + queries + kk)
+
+        def part():
+            got = self.local.batch_round_topk([min(k, self._nloc) for k in kk], queries)
+            buf = np.zeros((1, nq, 1 + 2 * k_max), dtype=np.int64)
+            for i, (rows, vals) in enumerate(got):
+                buf[0, i, 0] = len(rows)
+                buf[0, i, 1:1 + len(rows)] = rows
+                buf[0, i, 1 + k_max:1 + k_max + len(rows)] = np.ascontiguousarray(vals, dtype=np.float64).view(np.int64)
+            return buf
+        buf = self._local_step(part)
+        allb = self._host(self._coll(lambda: all_gather_rows(torch.from_numpy(buf).to(self._cdev), self.world, self.group)))
+        row0s = [shard_range(self.n, self.world, g)[0] for g in range(self.world)]
+        out = []
+        for i, k in enumerate(kk):
+            counts = [int(allb[g, i, 0]) for g in range(self.world)]
+            rows = [allb[g, i, 1:1 + counts[g]] for g in range(self.world)]
+            vals = [np.ascontiguousarray(allb[g, i, 1 + k_max:1 + k_max + counts[g]]).view(np.float64) for g in range(self.world)]
+            out.append(merge_topk(rows, vals, row0s, k))
         return out
 
     @_atomic
@@ -770,6 +1036,24 @@ class ShardedFeatureDB:
             self.use_search_set(None if ints[0] < 0 else int(ints[0]))
         elif op == OP_DROP_SET:
             self.drop_search_set(int(ints[0]))
+        elif op == OP_ROUND_BATCH:
+            q, flags = int(ints[0]), int(ints[1])
+            nt, nw = q * S * E * D, q * S
+            self.query_round_batch(floats[:nt].reshape(q, S, E, D), floats[nt:nt + nw].reshape(q, S),
+                                   floats[nt + nw:nt + nw + 2 * q].reshape(q, 2) if flags & 4 else None,
+                                   want_avg=bool(flags & 1), want_scores=bool(flags & 2))
+        elif op == OP_BATCH_GRID:
+            k, g = int(ints[0]), int(ints[1])
+            queries, sizes = [int(v) for v in ints[2:2 + k]], [int(v) for v in ints[2 + k:2 + 2 * k]]
+            cuts = np.cumsum([0] + sizes) + 2 + 2 * k
+            self._batch_grid(queries, [ints[cuts[i]:cuts[i + 1]] for i in range(k)], list(floats.reshape(k, g, S)))
+        elif op == OP_BATCH_RESCORE:
+            k = int(ints[0])
+            self.batch_round_rescore([int(v) for v in ints[2:2 + k]], floats[:k * S].reshape(k, S),
+                                     floats[k * S:k * S + 2 * k].reshape(k, 2) if ints[1] else None)
+        elif op == OP_BATCH_TOPK:
+            nq = int(ints[0])
+            self.batch_round_topk([int(v) for v in ints[1 + nq:1 + 2 * nq]], [int(v) for v in ints[1:1 + nq]])
         else:
             raise RuntimeError("unknown operation %d announced" % op)
 
@@ -821,6 +1105,7 @@ def worker_main(argv=None) -> int:
     ap.add_argument("store")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--timeout", type=float, default=600.0)
+    ap.add_argument("--batch-rounds", action="store_true")
     args = ap.parse_args(argv)
     import torch
     import torch.distributed as dist
@@ -840,7 +1125,7 @@ def worker_main(argv=None) -> int:
     dist.init_process_group(args.backend, **kw)
     local = FeatureDB.from_store(args.store, device=device, row0=row0, rows=rows)
     store.set("loaded/%d" % rank, "1")
-    db = ShardedFeatureDB(local, feats.shape[0], row0, ids, served=True)
+    db = ShardedFeatureDB(local, feats.shape[0], row0, ids, served=True, batch_rounds=args.batch_rounds)
     try:
         db.serve()
     finally:

@@ -555,8 +555,9 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
 
     Tickets share a pass when they have the same database OBJECT with ``query_round_batch`` that meets the pass's preconditions, no
     search set defined for them, the same slot mask and a look-ahead; at most 16 per pass, in list order.  Every other ticket -- on
-    a ShardedFeatureDB or another database without the method, with a search set, without a resident database (``from_records``)
-    -- runs its own ``compute_similarities``, in list order; so does, at the end, a ticket left alone in its group (a pass of one
+    a ShardedFeatureDB opened without ``batch_rounds=True`` (with it the four calls of a batched round exist there too, for rounds
+    over the whole database) or another database without the method, with a search set, without a resident database
+    (``from_records``) -- runs its own ``compute_similarities``, in list order; so does, at the end, a ticket left alone in its group (a pass of one
     gains nothing).
 
     ``share_search_sets=True``: a ticket whose search set is defined on its database (which must have ``query_round_batch_sets``)
