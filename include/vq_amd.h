@@ -609,4 +609,5 @@ int vq_broadcast_query(vq_comm* comm, void* buf_dev, int64_t bytes, int32_t root
 #include "vq_amd_round_targets.h" /* the bootstrapped targets of a group of tickets, every draw of every pool in one call (additive to ABI 12) */
 #include "vq_amd_round_topk.h" /* the k best clips of every query of a batched round, ranked on the device in one call (additive to ABI 12) */
 #include "vq_amd_round_grid.h" /* the scores of chosen rows of a batched round under a grid of weights: what a sharded fit combines (additive to ABI 12) */
+#include "vq_amd_round_update.h" /* a group's whole weight update -- fit, pick, rescore, review bands, partition -- in one call (additive to ABI 12) */
 #endif /* VQ_AMD_H */

@@ -41,7 +41,8 @@
  * VQ_E_INVALID -- a row outside [0, M_q), G or T outside [1, 64], L_q < 0 or sum L != n_labels, a block that is too short, an unknown
  * flag, an empty mask, a NULL argument.  All of them are checked on the host before anything is launched.
  *
- * OUT OF SCOPE: picking and refining the minimum on the device; sharded databases (one handle only: a row-sharded database fits
+ * OUT OF SCOPE: picking and refining the minimum (vq_db_batch_round_update, vq_amd_round_update.h, chains these two calls around it
+ * on the device); sharded databases (one handle only: a row-sharded database fits
  * through vq_db_batch_round_grid, vq_amd_round_grid.h, and sums on the host). */
 #ifndef VQ_AMD_ROUND_FIT_H
 #define VQ_AMD_ROUND_FIT_H

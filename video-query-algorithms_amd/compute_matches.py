@@ -117,6 +117,12 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     (compute_matches.py:77 overwrites it on the next line), and a finalize ticket's scores come back with the group's while its
     review band -- which depends on ``lowest_scoring_user_match`` under the fitted scores -- is still partitioned by its own
     ``select``.
+    ``fit_weights="device"`` (with ``batch``): the same, with the group's update in ONE call where the database has
+    ``batch_round_update`` (``compute_similarities_batch(..., fit_on_device=True)``): the pick and its refinement run on the device, and
+    so does a finalize ticket's review band, which removes the second difference above.  One difference instead: weights and threshold
+    are ``Hyperparameter._pick_exact``'s rather than ``_pick_from``'s (products instead of ``** 2``: equal in most picks, a few ulp apart
+    in the others -- tests/test_pick_exact.py has the measured size); ledger, ``random`` consumption and matches are those of
+    ``fit_weights=True`` whenever the two picks agree.
     ``batch_targets=True`` (with ``batch``; ``ValueError`` without): phase 1 only PLANS every ticket's target (the REST requests and the
     draws from ``random``, at the same place and in the same order as ever), and one ``target_clip.solve_targets_batch`` in front of
     the pass solves them: the tickets with ``dynamic_target_adjustment`` whose validated clips are rows of one resident database get
@@ -157,7 +163,9 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
         solve_targets_batch([tk.target for _kind, _update, tk in started])
     fit = [fit_weights and kind in ("revise", "finalize") and bool(update["matches"]) for kind, update, _tk in started]
     compute_similarities_batch([tk for _kind, _update, tk in started], hyperparameters, share_search_sets=share_search_sets,
-                               **({"fit": fit} if fit_weights else {}), **({"top": top} if top is not None else {}))
+                               **({"fit": fit} if fit_weights else {}), **({"top": top} if top is not None else {}),
+                               **({"fit_on_device": True, "finalize": [kind == "finalize" for kind, _update, _tk in started]}
+                                  if fit_weights == "device" else {}))
     for kind, update, tk in started:
         _finish_update(kind, update, tk, hyperparameters)
 

@@ -1,7 +1,8 @@
 // Batched query rounds on gfx950: up to 16 queries per pass over a resident feature database -- over the whole database
 // (include/vq_amd_rounds.h), over a row view per query (include/vq_amd_round_views.h) -- and the weight fit and the re-weighting of
-// such a round's queries on what it left on the device (include/vq_amd_round_fit.h), and the scores of chosen rows of such a round
-// under a grid of weights, which a row-sharded database combines into its fit (include/vq_amd_round_grid.h).
+// such a round's queries on what it left on the device (include/vq_amd_round_fit.h), the scores of chosen rows of such a round
+// under a grid of weights, which a row-sharded database combines into its fit (include/vq_amd_round_grid.h), and a group's whole
+// weight update -- fit, pick, rescore, review bands, partition -- as one chain on the handle's stream (include/vq_amd_round_update.h).
 //
 // Every kind of round is described by ONE table of pieces (BatchRound, csrc/vq_db.h): query q owns the entries start[q] ..
 // start[q + 1] of the concatenated avg / scores / list arrays.  A whole-database round is the round whose pieces all have N rows.
@@ -286,6 +287,176 @@ __global__ __launch_bounds__(256) void rescore_batch_kernel(RescoreBatchArgs a) 
     }
 }
 
+// ---- the two steps between those kernels that vq_db_batch_round_update keeps on the device (include/vq_amd_round_update.h) ----
+// What both read and write of the update block's image, and the weights | bands staged behind it for the rescore and the partition.
+constexpr int kPickThreads = 256;
+struct UpdateBatchArgs {
+    const double* surface;    // [Q][G][T]: raw sums
+    const double* w_grid;     // [Q][G][8]
+    const double* th_grid;    // [Q][T]
+    const int64_t* L;         // [Q]: the divisor; 0: the slot is skipped
+    const int32_t* second;    // [Q]
+    const double* eps;        // [Q]
+    const int32_t* band_mode; // [Q]
+    const double* near;       // [Q]
+    const int64_t* user_rows; // [sum U]: positions inside each query's piece
+    const double* scores;     // the round's score pieces
+    double* pick;             // [Q][8]
+    int32_t* pick_idx;        // [Q][4]
+    double* w;                // [16][8]: what rescore_batch_kernel reads
+    double* band;             // [16][2]: what the partition reads
+    int64_t qoff[16];         // the first score entry of query q
+    int64_t ustart[17];       // the first user row of query q
+    int G, T;
+};
+
+// is cell (a, i) in front of cell (b, j) in numpy.argmin's order: a NaN before every number, then the smaller value, then the smaller
+// flat index (a < b is false for +-0 and for equal infinities: the index decides)
+__device__ __forceinline__ bool pick_before(double a, int i, double b, int j) {
+    const bool an = a != a, bn = b != b;
+    if (an != bn) return an;
+    if (an) return i < j;
+    return a < b || (a == b && i < j);
+}
+
+// hyperparameter.py:23-29 with the squares as products: vertex and curvature of the parabola through three points of one axis
+__device__ __forceinline__ void parabola_through(double lo, double mid, double hi, double y_lo, double y_mid, double y_hi, double* vertex, double* curve) {
+    const double rise = y_hi - y_lo, fall_hi = y_mid - y_hi, fall_lo = y_mid - y_lo;
+    const double v = 0.5 * (rise * (mid * mid) + fall_hi * (lo * lo) - fall_lo * (hi * hi)) / (rise * mid + fall_hi * lo - fall_lo * hi);
+    *vertex = v;
+    *curve = fall_lo / ((mid - v) * (mid - v) - (lo - v) * (lo - v));
+}
+
+// hyperparameter.py:66-114 behind the arg-min: the grid values of cell (iw, it) on the rim of the grid, else the minimum of the
+// separable parabola through the cell and its four neighbours, clamped to the neighbouring grid lines, or the cell itself when the
+// five points are not reproduced.  surf: the query's raw cells, divided by `div` as they are read; wg [G][8] with the grid in column
+// `second`.  Operation for operation Hyperparameter._pick_exact (the unit is compiled without contraction).
+struct PickedCell {
+    double w_best, th_best;
+    bool on_rim, fell_back;
+};
+
+__device__ __forceinline__ PickedCell refine_cell(const double* surf, double div, const double* wg, const double* ths, int G, int T, int iw, int it,
+                                                  int second) {
+    PickedCell out;
+    out.on_rim = iw == 0 || iw == G - 1 || it == 0 || it == T - 1;
+    out.fell_back = false;
+    out.w_best = wg[iw * 8 + second];
+    out.th_best = ths[it];
+    if (out.on_rim) return out;
+    const double ws0 = wg[(iw - 1) * 8 + second], ws1 = out.w_best, ws2 = wg[(iw + 1) * 8 + second];
+    const double th0g = ths[it - 1], th1g = out.th_best, th2g = ths[it + 1];
+    const double centre = surf[iw * T + it] / div;
+    const double west = surf[(iw - 1) * T + it] / div, east = surf[(iw + 1) * T + it] / div;
+    const double south = surf[iw * T + it - 1] / div, north = surf[iw * T + it + 1] / div;
+    double w0, ca, th0, cb;
+    parabola_through(ws0, ws1, ws2, west, centre, east, &w0, &ca);
+    parabola_through(th0g, th1g, th2g, south, centre, north, &th0, &cb);
+    const double c = centre - ca * ((ws1 - w0) * (ws1 - w0)) - cb * ((th1g - th0) * (th1g - th0));
+    w0 = ws2 < w0 ? ws2 : w0;                                  // max(min(w0, ws[2]), ws[0]) as Python evaluates it: a NaN stays
+    w0 = ws0 > w0 ? ws0 : w0;
+    th0 = th2g < th0 ? th2g : th0;
+    th0 = th0g > th0 ? th0g : th0;
+    auto model = [&](double w, double th) { return ca * ((w - w0) * (w - w0)) + cb * ((th - th0) * (th - th0)) + c; };
+    const double misfit = fabs(west - model(ws0, th1g)) + fabs(south - model(ws1, th0g)) + fabs(centre - model(ws1, th1g)) +
+                          fabs(north - model(ws1, th2g)) + fabs(east - model(ws2, th1g));
+    out.fell_back = misfit > 1e-6;                             // FIT_TOLERANCE; false for a NaN misfit
+    if (!out.fell_back) {
+        out.w_best = w0;
+        out.th_best = th0;
+    }
+    return out;
+}
+
+// Hyperparameter._pick_exact for every slot with labels: one workgroup per query.  All threads divide the cells by L and reduce
+// (value, flat index) in LDS to numpy.argmin's cell; thread 0 then refines it and writes the pick, the query's weight row and its
+// threshold.
+__global__ __launch_bounds__(kPickThreads) void pick_refine_batch_kernel(UpdateBatchArgs a) {
+    __shared__ double ls_val[kPickThreads];
+    __shared__ int ls_idx[kPickThreads];
+    const int q = blockIdx.x, G = a.G, T = a.T, t = threadIdx.x;
+    const int64_t L = a.L[q];
+    if (L <= 0) return;                                        // the whole workgroup
+    const double div = (double)L;
+    const double* surf = a.surface + (int64_t)q * G * T;
+    double best = 0.0;
+    int best_i = 0x7fffffff;                                   // no cell yet: every cell comes in front of it
+    for (int i = t; i < G * T; i += kPickThreads) {
+        const double v = surf[i] / div;                        // IEEE division first: it can create the ties the order then resolves
+        if (best_i == 0x7fffffff || pick_before(v, i, best, best_i)) {
+            best = v;
+            best_i = i;
+        }
+    }
+    ls_val[t] = best;
+    ls_idx[t] = best_i;
+    __syncthreads();
+    for (int s = kPickThreads / 2; s > 0; s >>= 1) {
+        if (t < s && ls_idx[t + s] != 0x7fffffff && (ls_idx[t] == 0x7fffffff || pick_before(ls_val[t + s], ls_idx[t + s], ls_val[t], ls_idx[t]))) {
+            ls_val[t] = ls_val[t + s];
+            ls_idx[t] = ls_idx[t + s];
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const int iw = ls_idx[0] / T, it = ls_idx[0] - iw * T, second = a.second[q];
+    const double* wg = a.w_grid + (int64_t)q * G * 8;
+    const PickedCell cell = refine_cell(surf, div, wg, a.th_grid + (int64_t)q * T, G, T, iw, it, second);
+    const double w_best = cell.w_best, th_best = cell.th_best;
+    const bool on_rim = cell.on_rim, fell_back = cell.fell_back;
+    const double threshold = th_best - a.eps[q];
+    for (int s = 0; s < 8; ++s) a.w[q * 8 + s] = s == second ? w_best : wg[iw * 8 + s];
+    a.band[2 * q] = threshold;
+    double* pick = a.pick + q * 8;
+    pick[0] = w_best;
+    pick[1] = threshold;
+    pick[3] = threshold;
+    pick[5] = pick[6] = pick[7] = 0.0;
+    int32_t* idx = a.pick_idx + q * 4;
+    idx[0] = iw;
+    idx[1] = it;
+    idx[2] = (on_rim ? 1 : 0) | (fell_back ? 2 : 0);
+    idx[3] = 0;
+}
+
+// compute_matches.py:78-88 and ticket.py:301-316 behind the rescore: one workgroup per query.  Mode 1 lowers 1.0 by the scores at the
+// query's user rows; thread t folds a contiguous run of them and the tree joins neighbouring runs, the earlier one on the left, so
+// the value is the in-order fold's (also between +0 and -0).  Thread 0 then writes the band.
+__global__ __launch_bounds__(kPickThreads) void review_band_batch_kernel(UpdateBatchArgs a) {
+    __shared__ double ls_min[kPickThreads];
+    const int q = blockIdx.x, t = threadIdx.x;
+    if (a.L[q] <= 0) return;                                   // the whole workgroup
+    const bool from_user = a.band_mode[q] == 1;
+    double lowest = 1.0;
+    if (from_user) {
+        const int64_t u0 = a.ustart[q], U = a.ustart[q + 1] - u0, per = (U + kPickThreads - 1) / kPickThreads;
+        const double* scores = a.scores + a.qoff[q];
+        const int64_t hi = (t + 1) * per < U ? (t + 1) * per : U;
+        for (int64_t i = t * per; i < hi; ++i) {
+            const double v = scores[a.user_rows[u0 + i]];
+            lowest = v < lowest ? v : lowest;                  // min(min_score, v)
+        }
+        ls_min[t] = lowest;
+        __syncthreads();
+        for (int s = 1; s < kPickThreads; s <<= 1) {
+            if (t % (2 * s) == 0) ls_min[t] = ls_min[t + s] < ls_min[t] ? ls_min[t + s] : ls_min[t];
+            __syncthreads();
+        }
+        lowest = ls_min[0];
+    }
+    if (t != 0) return;
+    const double th = a.band[2 * q];
+    double reach = a.near[q];
+    if (from_user) {
+        const double below = th - lowest, room = 1.0 - th, eps = a.eps[q];
+        reach = (0.0 > below ? 0.0 : below) / (eps > room ? eps : room);                      // max(th - lowest, 0) / max(1 - th, eps)
+    }
+    const double lower = th - reach * (1.0 - th);
+    a.band[2 * q + 1] = lower;
+    a.pick[q * 8 + 2] = lowest;
+    a.pick[q * 8 + 4] = lower;
+}
+
 // grid_kernel (csrc/vq_sim.hip) for the queries of a batched round: thread (q = blockIdx.y, i = g L_q + l) scores row rows[l] of query
 // q's avg piece (qoff[q] on) under w_grid[q][g] into the query's [G][L_q] piece of `out`, which starts at entry G lstart[q].  A query
 // without rows has no thread that passes the bound.
@@ -426,6 +597,67 @@ static int launch_partition(vq_db* db, const BatchRound& r, int q0, int q1, cons
     return VQ_OK;
 }
 
+// rescore_batch_kernel for the queries of `mask` in round r under the weights d_w [16][8] (on the device); max_m: their longest piece
+static int launch_rescore(vq_db* db, const BatchRound& r, uint32_t mask, int64_t max_m, const double* d_w) {
+    RescoreBatchArgs a;
+    a.avg = (const double*)(db->bround_dev + r.off[4]);
+    a.w = d_w;
+    a.scores = (double*)(db->bround_dev + r.off[5]);
+    for (int q = 0; q < kBatchSlots; ++q) {
+        a.qoff[q] = r.start[q];
+        a.m[q] = r.m(q);
+    }
+    a.mask = mask;
+    a.S = db->S;
+    const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
+    rescore_batch_kernel<<<dim3(bx, r.q), 256, 0, db->stream>>>(a);
+    VQ_CHECK_LAUNCH();
+    return VQ_OK;
+}
+
+// Per run [q0, q1] of adjacent queries of `mask` in round r: its partition under the bands d_band [16][2] (on the device), then the
+// run's scores, results and prefixes into the round's host block in adjacent copies.  What vq_db_batch_round_rescore and
+// vq_db_batch_round_update do behind their rescore launch.
+static int partition_runs(vq_db* db, const BatchRound& r, uint32_t mask, const double* d_band, char* host, bool want_scores, bool do_select) {
+    const int Q = r.q;
+    const int64_t* off = r.off;
+    const int64_t P = off[10];
+    char* dev = db->bround_dev;
+    auto in_mask = [&](int q) { return q < Q && ((mask >> q) & 1u); };
+    for (int q0 = 0; q0 < Q;) {
+        if (!in_mask(q0)) {
+            ++q0;
+            continue;
+        }
+        int q1 = q0;
+        while (in_mask(q1 + 1)) ++q1;
+        const int nq = q1 - q0 + 1;
+        if (do_select) {
+            const int rc = launch_partition(db, r, q0, q1, d_band + 2 * q0);
+            if (rc != VQ_OK) return rc;
+        }
+        const int64_t s_lo = r.start[q0] * 8, s_len = r.start[q1 + 1] * 8 - s_lo;
+        if (want_scores && s_len) VQ_HIP(hipMemcpyAsync(host + off[5] + s_lo, dev + off[5] + s_lo, (size_t)s_len, hipMemcpyDeviceToHost, db->stream));
+        if (do_select) {
+            VQ_HIP(hipMemcpyAsync(host + off[6] + (int64_t)q0 * 32, dev + off[6] + (int64_t)q0 * 32, (size_t)nq * 32, hipMemcpyDeviceToHost, db->stream));
+            for (int piece = 7; piece <= 8; ++piece)
+                VQ_HIP(hipMemcpyAsync(host + off[piece] + q0 * P * 8, dev + off[piece] + q0 * P * 8, (size_t)(nq * P * 8), hipMemcpyDeviceToHost, db->stream));
+        }
+        q0 = q1 + 1;
+    }
+    return VQ_OK;
+}
+
+// the handle's counts of the queries of `mask` from the result rows that came back (after the synchronisation)
+static void adopt_counts(BatchRound& r, const char* host, uint32_t mask) {
+    const int64_t* res = (const int64_t*)(host + r.off[6]);
+    for (int q = 0; q < r.q; ++q)
+        if ((mask >> q) & 1u) {
+            r.n0[q] = res[4 * q];
+            r.n1[q] = res[4 * q + 1];
+        }
+}
+
 // back: n_e | avg, scores, results | prefixes -- the pieces asked for, adjacent ones in one copy
 static int copy_round_back(vq_db* db, const BatchRound& r, char* host, bool want_avg, bool want_scores, bool do_select) {
     const int64_t* off = r.off;
@@ -493,6 +725,19 @@ static int batch_fit_shape(int Q, int G, int T, int64_t n_labels) {
                kFitMaxGrid, G, T);
     VQ_REQUIRE(n_labels >= 0, "n_labels must not be negative");
     return VQ_OK;
+}
+
+// the fit block's pieces (off[0] .. off[6] are batch_fit_layout's), then the update's own inputs and its two outputs
+static void batch_update_layout(int Q, int G, int T, int64_t n_labels, int64_t n_user_rows, int64_t off[16]) {
+    batch_fit_layout(Q, G, T, n_labels, off);
+    off[8] = off[7] + up64((int64_t)Q * 4);
+    off[9] = off[8] + up64((int64_t)Q * 8);
+    off[10] = off[9] + up64((int64_t)Q * 4);
+    off[11] = off[10] + up64((int64_t)Q * 8);
+    off[12] = off[11] + up64((int64_t)Q * 8);
+    off[13] = off[12] + up64(n_user_rows * 8);
+    off[14] = off[13] + up64((int64_t)Q * 8 * 8);
+    off[15] = off[14] + up64((int64_t)Q * 4 * 4);
 }
 
 static void batch_grid_layout(int Q, int G, int64_t n_rows, int64_t off[5]) {
@@ -884,55 +1129,165 @@ int vq_db_batch_round_rescore(vq_db* db, int32_t mask, void* block, int64_t bloc
     }
     // staged beside the round's image, whose weights and bands of the other queries stay what the round saw
     char* stage = (char*)db->grid_buf;
-    char* dev = db->bround_dev;
     VQ_HIP(hipMemcpyAsync(stage, host + off[1], (size_t)up_bytes, hipMemcpyHostToDevice, db->stream));
     const double* d_band = (const double*)(stage + (off[2] - off[1]));
     {
-        RescoreBatchArgs a;
-        a.avg = (const double*)(dev + off[4]);
-        a.w = (const double*)stage;
-        a.scores = (double*)(dev + off[5]);
-        for (int q = 0; q < kBatchSlots; ++q) {
-            a.qoff[q] = r.start[q];
-            a.m[q] = r.m(q);
+        const int rc = launch_rescore(db, r, (uint32_t)mask, max_m, (const double*)stage);
+        if (rc != VQ_OK) return rc;
+    }
+    {
+        const int rc = partition_runs(db, r, (uint32_t)mask, d_band, host, want_scores, do_select);
+        if (rc != VQ_OK) return rc;
+    }
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    if (do_select) adopt_counts(r, host, (uint32_t)mask);
+    return VQ_OK;
+}
+
+// ---- a group's whole weight update on a batched round in one call (include/vq_amd_round_update.h) ------------------------------------
+int vq_db_batch_update_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows, int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
+    if (rc != VQ_OK) return rc;
+    VQ_REQUIRE(n_user_rows >= 0, "n_user_rows must not be negative");
+    batch_update_layout(n_queries, n_grid, n_thresholds, n_labels, n_user_rows, off);
+    return VQ_OK;
+}
+
+int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
+                             void* update_block, int64_t update_bytes, void* round_block, int64_t round_bytes, int32_t flags) {
+    VQ_REQUIRE(db && update_block, "NULL argument");
+    {
+        const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
+        if (rc != VQ_OK) return rc;
+    }
+    VQ_REQUIRE(n_user_rows >= 0, "n_user_rows must not be negative");
+    constexpr int kKnown = VQ_BROUND_SCORES | VQ_BROUND_SELECT | VQ_BUPDATE_SURFACE | VQ_BUPDATE_GIVEN_SURFACE;
+    VQ_REQUIRE((flags & ~kKnown) == 0, "flags: 2 = scores back, 4 = partition, 16 = surfaces back, 32 = surfaces given (got %d)", flags);
+    const bool want_scores = flags & VQ_BROUND_SCORES, do_select = flags & VQ_BROUND_SELECT;
+    const bool want_surface = flags & VQ_BUPDATE_SURFACE, given = flags & VQ_BUPDATE_GIVEN_SURFACE;
+    VQ_REQUIRE(!(want_surface && given), "flags: a given surface (32) is not copied back (16)");
+    VQ_REQUIRE(round_block || !(want_scores || do_select), "NULL argument: scores and partitions come back into the block of the round");
+    const int Q = n_queries, G = n_grid, T = n_thresholds;
+    int64_t off[16];
+    batch_update_layout(Q, G, T, n_labels, n_user_rows, off);
+    VQ_REQUIRE(update_bytes >= off[15], "the block of this batched update needs %lld bytes (vq_db_batch_update_layout), got %lld", (long long)off[15],
+               (long long)update_bytes);
+    char* host = (char*)update_block;
+    const int64_t* L = (const int64_t*)(host + off[3]);
+    const int64_t* rows = (const int64_t*)(host + off[4]);
+    const int32_t* second = (const int32_t*)(host + off[7]);
+    const int32_t* band_mode = (const int32_t*)(host + off[9]);
+    const int64_t* U = (const int64_t*)(host + off[11]);
+    const int64_t* user_rows = (const int64_t*)(host + off[12]);
+    std::lock_guard<std::mutex> lk(db->mu);
+    BatchRound& r = db->round;
+    if (r.q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    FitBatchArgs fa;
+    UpdateBatchArgs ua;
+    fa.lstart[0] = ua.ustart[0] = 0;
+    uint32_t mask = 0;
+    int64_t max_m = 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        const int64_t lq = q < Q ? L[q] : 0, uq = q < Q ? U[q] : 0;
+        VQ_REQUIRE(lq >= 0 && uq >= 0 && uq <= n_user_rows, "query %d: L = %lld, U = %lld (n_user_rows = %lld)", q, (long long)lq, (long long)uq,
+                   (long long)n_user_rows);
+        VQ_REQUIRE(given || lq <= n_labels, "query %d: L = %lld outside [0, n_labels = %lld]", q, (long long)lq, (long long)n_labels);
+        if (lq > 0 && q >= r.q) return fail(VQ_E_STATE, "the last batched round had %d queries (labels for query %d)", r.q, q);
+        fa.lstart[q + 1] = fa.lstart[q] + (given ? 0 : lq);
+        ua.ustart[q + 1] = ua.ustart[q] + uq;
+        fa.qoff[q] = ua.qoff[q] = r.start[q];
+        if (lq > 0) {
+            mask |= 1u << q;
+            max_m = std::max(max_m, r.m(q));
         }
-        a.mask = (uint32_t)mask;
-        a.S = db->S;
-        const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((max_m + 255) / 256, (int64_t)db->cus * 8));
-        rescore_batch_kernel<<<dim3(bx, Q), 256, 0, db->stream>>>(a);
+    }
+    VQ_REQUIRE(given || fa.lstart[kBatchSlots] == n_labels, "the L of the queries add up to %lld, n_labels is %lld", (long long)fa.lstart[kBatchSlots],
+               (long long)n_labels);
+    VQ_REQUIRE(ua.ustart[kBatchSlots] == n_user_rows, "the U of the queries add up to %lld, n_user_rows is %lld", (long long)ua.ustart[kBatchSlots],
+               (long long)n_user_rows);
+    for (int q = 0; q < Q; ++q) {
+        if (!((mask >> q) & 1u)) continue;
+        VQ_REQUIRE(second[q] >= 0 && second[q] < db->S, "query %d: second = %d outside [0,%d)", q, second[q], db->S);
+        VQ_REQUIRE(band_mode[q] == 0 || band_mode[q] == 1, "query %d: band_mode %d (0 = a given reach, 1 = from the user's matches)", q, band_mode[q]);
+        for (int64_t l = fa.lstart[q]; l < fa.lstart[q + 1]; ++l)
+            VQ_REQUIRE(rows[l] >= 0 && rows[l] < r.m(q), "query %d: row %lld (label %lld) outside [0,%lld)", q, (long long)rows[l],
+                       (long long)(l - fa.lstart[q]), (long long)r.m(q));
+        for (int64_t u = ua.ustart[q]; u < ua.ustart[q + 1]; ++u)
+            VQ_REQUIRE(user_rows[u] >= 0 && user_rows[u] < r.m(q), "query %d: user row %lld (entry %lld) outside [0,%lld)", q, (long long)user_rows[u],
+                       (long long)(u - ua.ustart[q]), (long long)r.m(q));
+    }
+    if (want_scores || do_select)
+        VQ_REQUIRE(round_bytes >= r.off[9], "the block of the last batched round needs %lld bytes, got %lld", (long long)r.off[9], (long long)round_bytes);
+    if (mask == 0) return VQ_OK;                      // every slot skipped: nothing to launch
+    DeviceGuard g(db->device);
+    const int64_t stage_w = off[15], stage_band = stage_w + kBatchSlots * 8 * 8;             // behind the block's image: weights | bands
+    {
+        const int rc = ensure_grid_buf(db, stage_band + kBatchSlots * 2 * 8);
+        if (rc != VQ_OK) return rc;
+    }
+    char* base = (char*)db->grid_buf;
+    // ONE upload: the fit's inputs, the surface piece (given, or about to be overwritten) and the update's inputs are adjacent
+    VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[13], hipMemcpyHostToDevice, db->stream));
+    const bool have_rows = max_m > 0;                 // false: only empty views, which have neither labels nor scores nor lists
+    if (!given && have_rows) {
+        fa.avg = (const double*)(db->bround_dev + r.off[4]);
+        fa.w_grid = (const double*)(base + off[0]);
+        fa.th_grid = (const double*)(base + off[1]);
+        fa.ballast = (const double*)(base + off[2]);
+        fa.rows = (const int64_t*)(base + off[4]);
+        fa.labels = (const double*)(base + off[5]);
+        fa.out = (double*)(base + off[6]);
+        fa.G = G;
+        fa.T = T;
+        fa.S = db->S;
+        loss_surface_batch_kernel<<<dim3(G, Q), kFitThreads, 0, db->stream>>>(fa);
         VQ_CHECK_LAUNCH();
     }
-    const int64_t P = off[10];
-    // per run [q0, q1] of adjacent masked queries: its partition, then the run's results in adjacent copies
-    for (int q0 = 0; q0 < Q;) {
-        if (!in_mask(q0)) {
-            ++q0;
+    ua.surface = (const double*)(base + off[6]);
+    ua.w_grid = (const double*)(base + off[0]);
+    ua.th_grid = (const double*)(base + off[1]);
+    ua.L = (const int64_t*)(base + off[3]);
+    ua.second = (const int32_t*)(base + off[7]);
+    ua.eps = (const double*)(base + off[8]);
+    ua.band_mode = (const int32_t*)(base + off[9]);
+    ua.near = (const double*)(base + off[10]);
+    ua.user_rows = (const int64_t*)(base + off[12]);
+    ua.scores = have_rows ? (const double*)(db->bround_dev + r.off[5]) : nullptr;
+    ua.pick = (double*)(base + off[13]);
+    ua.pick_idx = (int32_t*)(base + off[14]);
+    ua.w = (double*)(base + stage_w);
+    ua.band = (double*)(base + stage_band);
+    ua.G = G;
+    ua.T = T;
+    pick_refine_batch_kernel<<<Q, kPickThreads, 0, db->stream>>>(ua);
+    VQ_CHECK_LAUNCH();
+    if (have_rows) {
+        const int rc = launch_rescore(db, r, mask, max_m, ua.w);
+        if (rc != VQ_OK) return rc;
+    }
+    review_band_batch_kernel<<<Q, kPickThreads, 0, db->stream>>>(ua);
+    VQ_CHECK_LAUNCH();
+    if (have_rows) {
+        const int rc = partition_runs(db, r, mask, ua.band, (char*)round_block, want_scores, do_select);
+        if (rc != VQ_OK) return rc;
+    }
+    VQ_HIP(hipMemcpyAsync(host + off[13], base + off[13], (size_t)(off[15] - off[13]), hipMemcpyDeviceToHost, db->stream));         // pick | pick_idx
+    const int64_t cell = (int64_t)G * T * 8;
+    for (int q = 0; want_surface && q < Q;) {         // the surfaces of the slots served, adjacent ones in one copy
+        if (!((mask >> q) & 1u)) {
+            ++q;
             continue;
         }
-        int q1 = q0;
-        while (in_mask(q1 + 1)) ++q1;
-        const int nq = q1 - q0 + 1;
-        if (do_select) {
-            const int rc = launch_partition(db, r, q0, q1, d_band + 2 * q0);
-            if (rc != VQ_OK) return rc;
-        }
-        const int64_t s_lo = r.start[q0] * 8, s_len = r.start[q1 + 1] * 8 - s_lo;
-        if (want_scores && s_len) VQ_HIP(hipMemcpyAsync(host + off[5] + s_lo, dev + off[5] + s_lo, (size_t)s_len, hipMemcpyDeviceToHost, db->stream));
-        if (do_select) {
-            VQ_HIP(hipMemcpyAsync(host + off[6] + (int64_t)q0 * 32, dev + off[6] + (int64_t)q0 * 32, (size_t)nq * 32, hipMemcpyDeviceToHost, db->stream));
-            for (int piece = 7; piece <= 8; ++piece)
-                VQ_HIP(hipMemcpyAsync(host + off[piece] + q0 * P * 8, dev + off[piece] + q0 * P * 8, (size_t)(nq * P * 8), hipMemcpyDeviceToHost, db->stream));
-        }
-        q0 = q1 + 1;
+        int e = q;
+        while (e + 1 < Q && ((mask >> (e + 1)) & 1u)) ++e;
+        VQ_HIP(hipMemcpyAsync(host + off[6] + q * cell, base + off[6] + q * cell, (size_t)((e + 1 - q) * cell), hipMemcpyDeviceToHost, db->stream));
+        q = e + 1;
     }
     VQ_HIP(hipStreamSynchronize(db->stream));
     if (do_select) {
-        const int64_t* res = (const int64_t*)(host + off[6]);
-        for (int q = 0; q < Q; ++q)
-            if (in_mask(q)) {
-                r.n0[q] = res[4 * q];
-                r.n1[q] = res[4 * q + 1];
-            }
+        if (have_rows) adopt_counts(r, (const char*)round_block, mask);
+        else empty_results(r, (char*)round_block, mask);
     }
     return VQ_OK;
 }

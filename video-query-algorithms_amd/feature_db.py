@@ -52,6 +52,13 @@ class RoundResult:
     __slots__ = ("avg", "n_e", "scores", "match_rows", "near_rows", "near_argmax")
 
 
+class UpdateResult(RoundResult):
+    """What :meth:`FeatureDB.batch_round_update` brought back for one query: the fields of the rescore's :class:`RoundResult` and the
+    pick -- ``w`` (the fitted grid weight), ``threshold``, ``lowest`` (the lowest-scoring confirmed match of a finalize member, else
+    1.0), ``band`` = (threshold, lower), ``iw`` / ``it`` (the cell), ``on_rim``, ``fell_back``, and ``surface`` [G,T] when asked."""
+    __slots__ = ("w", "threshold", "lowest", "band", "iw", "it", "on_rim", "fell_back", "surface")
+
+
 class SearchSetView:
     """What a ticket sees of a database for one round: the clips of its search set, in database order.  Immutable -- a ticket binds
     to this object, not to the (shared, mutable) state of the handle.  ``clip_ids`` [M] and ``rows`` [M] (the database rows, strictly
@@ -1016,6 +1023,102 @@ class FeatureDB:
                 out.append(r)
             return out
 
+    def batch_round_update(self, queries, rows, labels, w_grids, th_grids, ballasts, seconds, eps, reaches, user_rows, want_scores: bool = True,
+                           want_surface: bool = False, surfaces=None) -> list:
+        """The whole weight update of several queries of the LAST batched round (either kind) in ONE call (vq_db_batch_round_update,
+        include/vq_amd_round_update.h): :meth:`batch_round_fit`, ``Hyperparameter._pick_exact`` of every surface divided by its number
+        of labels, :meth:`batch_round_rescore` under the picked weights, the review band and the partition, chained on the device.
+        Per entry i, beside the arguments of :meth:`batch_round_fit`: ``seconds[i]`` the column of ``w_grids[i]`` that carries the
+        grid, ``eps`` (one float, or one per entry: COMPUTE_EPS), ``reaches[i]`` how far below the threshold the band reaches
+        (``near_miss_default`` of a revise ticket) or ``None`` for a finalize ticket, whose reach comes from the lowest score at
+        ``user_rows[i]`` (positions in the query's view; ``lowest_scoring_user_match``).  ``surfaces``: one raw [G,T] surface per entry
+        instead of the fit (``rows`` is then ignored and ``labels[i]`` may be the NUMBER of labels: it is still the divisor).
+        Returns one :class:`UpdateResult` per entry: scores (None without ``want_scores``; they stay on the device), partition, ``avg``
+        and ``n_e`` as :meth:`batch_round_rescore` gives them under ``w`` and ``band``; the pick has the bits of ``_pick_exact``, ``band``
+        those of the host's expressions over the returned scores.  ``surface`` is the fit's own (``want_surface``) or None."""
+        queries = [int(q) for q in queries]
+        k = len(queries)
+        given = surfaces is not None
+        eps = [float(eps)] * k if np.ndim(eps) == 0 else [float(e) for e in eps]
+        if not (k and len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == len(seconds) == len(eps) == len(reaches)
+                == len(user_rows) == k) or len(set(queries)) != k or (given and (len(surfaces) != k or want_surface)):
+            raise ValueError("one rows / labels / w_grid / th_grid / ballast / second / reach / user_rows (and surface) per query, every query once")
+        wg = [np.asarray(w, dtype=np.float64) for w in w_grids]
+        th = [np.asarray(t, dtype=np.float64).reshape(-1) for t in th_grids]
+        if given:
+            counts = [int(y) if np.ndim(y) == 0 else len(y) for y in labels]
+            rs, ys = [np.zeros(0, dtype=np.int64)] * k, [np.zeros(0)] * k
+        else:
+            rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+            ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
+            counts = [r.size for r in rs]
+        us = [np.zeros(0, dtype=np.int64) if u is None else np.asarray(u, dtype=np.int64).reshape(-1) for u in user_rows]
+        G, T = int(wg[0].shape[0]), int(th[0].size)
+        if any(w.ndim != 2 or w.shape != (G, self.S) for w in wg) or any(t.size != T for t in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
+            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
+        sf = [np.asarray(f, dtype=np.float64) for f in surfaces] if given else None
+        if given and any(f.shape != (G, T) for f in sf):
+            raise ValueError("surfaces must be [G,T]")
+        if min(queries) < 0 or max(queries) >= 16:
+            raise ValueError("a query is its index in the last batched round")
+        flags = _lib.VQ_BROUND_SELECT | (_lib.VQ_BROUND_SCORES if want_scores else 0) | (_lib.VQ_BUPDATE_SURFACE if want_surface else 0) \
+            | (_lib.VQ_BUPDATE_GIVEN_SURFACE if given else 0)
+        with self.lock:
+            Q = max(queries) + 1                              # slot q of the block = query q of the round; the library refuses what that round lacks
+            order = sorted(range(k), key=lambda i: queries[i])
+            total, total_u = int(sum(r.size for r in rs)), int(sum(u.size for u in us))
+            off = (C.c_int64 * 16)()
+            call("vq_db_batch_update_layout", self._h, Q, G, T, total, total_u, off)
+            off = [int(v) for v in off]
+            ublk = self._pooled_block("_update_pools", off[15])
+            view = self._block_view(ublk.bytes(), off)
+            ublk.bytes()[:off[6]] = 0
+            ublk.bytes()[off[7]:off[15]] = 0
+            w_in, th_in, b_in, l_in = view(0, np.float64, (Q, G, 8)), view(1, np.float64, (Q, T)), view(2, np.float64, (Q,)), view(3, np.int64, (Q,))
+            r_in, y_in, surface = view(4, np.int64, (total,)), view(5, np.float64, (total,)), view(6, np.float64, (Q, G, T))
+            sec_in, eps_in, mode_in, near_in = view(7, np.int32, (Q,)), view(8, np.float64, (Q,)), view(9, np.int32, (Q,)), view(10, np.float64, (Q,))
+            u_in, ur_in = view(11, np.int64, (Q,)), view(12, np.int64, (total_u,))
+            at = at_u = 0
+            for i in order:
+                q = queries[i]
+                w_in[q, :, :self.S], th_in[q], b_in[q], l_in[q] = wg[i], th[i], float(ballasts[i]), counts[i]
+                r_in[at:at + rs[i].size], y_in[at:at + rs[i].size] = rs[i], ys[i]
+                at += rs[i].size
+                sec_in[q], eps_in[q] = int(seconds[i]), eps[i]
+                mode_in[q], near_in[q] = (1, 0.0) if reaches[i] is None else (0, float(reaches[i]))
+                u_in[q] = us[i].size
+                ur_in[at_u:at_u + us[i].size] = us[i]
+                at_u += us[i].size
+                if given:
+                    surface[q] = sf[i]
+            last = getattr(self, "_bround_last", None)
+            if last is None or max(queries) >= last[0]:
+                # no batched round, or a query it did not have: VQ_E_STATE as the library gives it, also for an entry without labels
+                # (a slot the library would skip) -- there is no block of that round to hand it
+                raise _lib.VqError(-4, "no batched round has run on this handle" if last is None else
+                                   "the last batched round had %d queries (asked for %r)" % (last[0], queries))
+            _Q, roff, start, pool, sims = last
+            blk = self._batch_round_block(_Q)[0] if pool is None else self._pooled_block("_view_round_pools", roff[9])
+            rview = self._block_view(blk.bytes(), roff)
+            call("vq_db_batch_round_update", self._h, Q, G, T, total, total_u, C.c_void_p(ublk.ptr), ublk.nbytes, C.c_void_p(blk.ptr), blk.nbytes, flags)
+            pick, idx = view(13, np.float64, (Q, 8)), view(14, np.int32, (Q, 4))
+            decode = self._partition_decoder(rview, roff, _Q)
+            out = []
+            for i, q in enumerate(queries):
+                r = UpdateResult()
+                served = counts[i] > 0                        # a slot without labels is skipped: it stays what the round left
+                r.avg, r.n_e = sims[q]
+                r.scores = rview(5, np.float64, (start[q + 1] - start[q],), start[q]) if want_scores and served else None
+                decode(r, q, served)
+                r.surface = surface[q] if want_surface and served else None
+                if served:
+                    r.w, r.threshold, r.lowest, r.band = pick[q, 0], pick[q, 1], pick[q, 2], (float(pick[q, 3]), float(pick[q, 4]))
+                    r.iw, r.it, r.on_rim, r.fell_back = int(idx[q, 0]), int(idx[q, 1]), bool(idx[q, 2] & 1), bool(idx[q, 2] & 2)
+                else:
+                    r.w = r.threshold = r.lowest = r.band = r.iw = r.it = r.on_rim = r.fell_back = None
+                out.append(r)
+            return out
+
     # ------------------------------------------------------------------ the k best clips of every query of a batched round
     def batch_topk_cap(self) -> int:
         """The largest k :meth:`batch_round_topk` ranks (the library's constant, read through vq_db_batch_topk_layout)."""
@@ -1156,7 +1259,8 @@ class FeatureDB:
         if self._h:
             pools = [getattr(self, "_round_pool", None)] + [p for _off, p in getattr(self, "_batch_round_pools", {}).values()] + \
                 list(getattr(self, "_view_round_pools", {}).values()) + list(getattr(self, "_fit_pools", {}).values()) + \
-                list(getattr(self, "_topk_pools", {}).values()) + list(getattr(self, "_grid_pools", {}).values())
+                list(getattr(self, "_topk_pools", {}).values()) + list(getattr(self, "_grid_pools", {}).values()) + \
+                list(getattr(self, "_update_pools", {}).values()) + list(getattr(self, "_target_pools", {}).values())
             self._bround_last = None
             for pool in pools:
                 if pool is None:

@@ -94,6 +94,40 @@ class Hyperparameter:
         w_best, th_best = (self.weight_grid[iw], self.threshold_grid[it]) if on_rim else self._refine(surface, iw, it)
         return {self.streams[0]: 1.0, self.streams[1]: w_best}, th_best - float(os.environ["COMPUTE_EPS"])     # hyperparameter.py:5,75
 
+    def _pick_exact(self, surface):
+        """``_pick_from`` with every ``** 2`` of it, of ``_refine`` and of ``parabola_through`` written as a product and nothing else
+        changed -> (weights, threshold, iw, it, on_rim, fell_back).  numpy's scalar ``** 2`` goes through libm's ``pow``, which is not
+        always correctly rounded (DESIGN.md 2 says the same of the scores); a product is one IEEE multiplication everywhere, so THIS is
+        the definition the device's pick is held to, bit for bit (csrc/vq_rounds.hip: pick_refine_batch_kernel, behind
+        ``FeatureDB.batch_round_update``).  ``fell_back``: the refinement did not reproduce its five points and the cell itself was
+        taken (``_refine`` logs a warning there; the caller of this one does)."""
+        def parabola(xs, y_lo, y_mid, y_hi):
+            lo, mid, hi = xs
+            rise, fall_hi, fall_lo = y_hi - y_lo, y_mid - y_hi, y_mid - y_lo
+            vertex = 0.5 * (rise * (mid * mid) + fall_hi * (lo * lo) - fall_lo * (hi * hi)) / (rise * mid + fall_hi * lo - fall_lo * hi)
+            return vertex, fall_lo / ((mid - vertex) * (mid - vertex) - (lo - vertex) * (lo - vertex))
+        iw, it = np.unravel_index(np.argmin(surface), surface.shape)                # first minimum, row-major
+        on_rim = iw in (0, len(self.weight_grid) - 1) or it in (0, len(self.threshold_grid) - 1)
+        w_best, th_best, fell_back = self.weight_grid[iw], self.threshold_grid[it], False
+        if not on_rim:
+            ws, ths = self.weight_grid[iw - 1:iw + 2], self.threshold_grid[it - 1:it + 2]
+            centre = surface[iw, it]
+            west, east, south, north = surface[iw - 1, it], surface[iw + 1, it], surface[iw, it - 1], surface[iw, it + 1]
+            w0, a = parabola(ws, west, centre, east)
+            th0, b = parabola(ths, south, centre, north)
+            c = centre - a * ((ws[1] - w0) * (ws[1] - w0)) - b * ((ths[1] - th0) * (ths[1] - th0))
+            w0, th0 = max(min(w0, ws[2]), ws[0]), max(min(th0, ths[2]), ths[0])
+
+            def model(w, t):
+                return a * ((w - w0) * (w - w0)) + b * ((t - th0) * (t - th0)) + c
+            misfit = (abs(west - model(ws[0], ths[1])) + abs(south - model(ws[1], ths[0])) + abs(centre - model(ws[1], ths[1]))
+                      + abs(north - model(ws[1], ths[2])) + abs(east - model(ws[2], ths[1])))
+            fell_back = bool(misfit > FIT_TOLERANCE)
+            if not fell_back:
+                w_best, th_best = w0, th0
+        return ({self.streams[0]: 1.0, self.streams[1]: w_best}, th_best - float(os.environ["COMPUTE_EPS"]), int(iw), int(it), bool(on_rim),
+                fell_back)
+
     @staticmethod
     def _labelled_rows(ticket):
         """(DB rows, labels) of the clips of the previous round: the user's verdict where there is one, the engine's own

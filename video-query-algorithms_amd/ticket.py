@@ -12,6 +12,8 @@ variant for offline use whose ``_request`` answers from in-memory records.
 from __future__ import annotations
 
 import contextlib
+import logging
+import os
 import random
 from collections.abc import Mapping
 
@@ -82,6 +84,15 @@ class SimilarityMap(Mapping):
 
     def items(self):
         return ((int(c), self._entry(r)) for r, c in enumerate(self._ids.tolist()))
+
+
+def _user_match_rows(ticket):
+    """The positions, in the ticket's search set, of the clips the user confirmed, ascending: what ``lowest_scoring_user_match``
+    walks, and what a finalize member of a group hands the device for its review band (``_update_group``).  A function of this
+    module, not a method: ``install`` copies only the reference's own method names onto its Ticket class."""
+    view = ticket._view
+    return sorted(view.row_of(int(c)) for c, v in ticket.user_matches.items()
+                  if v is True and view.has_clip(c) and str(int(c)) == c)
 
 
 def _db_lock(db):
@@ -296,8 +307,7 @@ class TicketScoring:
     # -- ticket.py:301-309 ------------------------------------------------------------------
     def lowest_scoring_user_match(self):
         view = self._view                            # positions in the ticket's search set
-        rows = sorted(view.row_of(int(c)) for c, v in self.user_matches.items()
-                      if v is True and view.has_clip(c) and str(int(c)) == c)
+        rows = _user_match_rows(self)
         min_score, min_clip = 1, None
         for r in rows:                               # same order as the walk over self.scores
             min_score = min(min_score, self._score_values[r])
@@ -393,9 +403,11 @@ def _fit_group(db, group):
     threshold.  Such a ticket ends with ``_fit`` = (weights, threshold) for this round and ``_ahead`` = the rescore's scores and
     partition.  A member without labelled clips, with a label on an unknown clip (optimize_weights raises that in its own place) or
     with grids of another size than the first one's stays as the pass left it; so does every member on a database without the two
-    methods.  Call behind the group's own pass with the database's lock still held: the next pass on the handle replaces what this
-    reads."""
-    if not (hasattr(db, "batch_round_fit") and hasattr(db, "batch_round_rescore")):
+    methods.  Members marked ``_OnDevice`` (``fit_on_device``) on a database with ``batch_round_update`` take ``_update_group``
+    instead: one call for all of it.  Call behind the group's own pass with the database's lock still held: the next pass on the
+    handle replaces what this reads."""
+    on_device = hasattr(db, "batch_round_update") and any(isinstance(fit, _OnDevice) for _tk, _hp, _prep, fit in group)
+    if not on_device and not (hasattr(db, "batch_round_fit") and hasattr(db, "batch_round_rescore")):
         return
     members = []
     for q, (tk, hp, prep, fit) in enumerate(group):
@@ -410,13 +422,17 @@ def _fit_group(db, group):
             continue
         candidates = np.zeros((len(hp.weight_grid), db.S))
         candidates[:, first], candidates[:, second] = 1.0, hp.weight_grid
-        members.append((q, tk, hp, rows, [float(v) for v in labels], candidates, np.asarray(hp.threshold_grid, dtype=np.float64)))
+        members.append((q, tk, hp, rows, [float(v) for v in labels], candidates, np.asarray(hp.threshold_grid, dtype=np.float64), second,
+                        getattr(fit, "finalize", False)))
     if not members:
+        return
+    if on_device:
+        _update_group(db, members)
         return
     surfaces = db.batch_round_fit([m[0] for m in members], [m[3] for m in members], [m[4] for m in members], [m[5] for m in members],
                                   [m[6] for m in members], [m[2].ballast for m in members])
     fits, weights, bands = [], [], []
-    for (q, tk, hp, rows, labels, _cand, _ths), surface in zip(members, surfaces):
+    for (q, tk, hp, rows, labels, _cand, _ths, _second, _finalize), surface in zip(members, surfaces):
         picked, th = hp._pick_from(np.asarray(surface) / len(labels))
         w = np.zeros(db.S, dtype=np.float64)                          # as compute_scores builds it from the dict
         for stream_type, ws in picked.items():
@@ -425,10 +441,44 @@ def _fit_group(db, group):
         weights.append(w)
         bands.append((float(th), float(th) - float(hp.near_miss_default) * (1 - float(th))))       # _review_band's expression
     results = db.batch_round_rescore([m[0] for m in members], np.stack(weights), np.array(bands, dtype=np.float64))
-    for (q, tk, _hp, _rows, _labels, _cand, _ths), fit, w, band, r in zip(members, fits, weights, bands, results):
+    for (q, tk, _hp, _rows, _labels, _cand, _ths, _second, _finalize), fit, w, band, r in zip(members, fits, weights, bands, results):
         tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": band, "match_rows": r.match_rows, "near_rows": r.near_rows,
                      "near_argmax": r.near_argmax}
         tk._fit, tk._fit_round = fit, tk._round
+
+
+class _OnDevice:
+    """The ``fit`` entry of a group member under ``fit_on_device``: true like the plain flag, and it says which band the member wants
+    (``_fit_group`` reads it into the member's own tuple)."""
+    __slots__ = ("finalize",)
+
+    def __init__(self, finalize):
+        self.finalize = bool(finalize)
+
+
+def _update_group(db, members):
+    """``_fit_group`` in ONE ``batch_round_update``: surfaces, the pick (``Hyperparameter._pick_exact``'s, not ``_pick_from``'s: the one
+    difference of the mode), the rescore, the band and the partition without a host step in between.  A revise member's band reaches
+    ``near_miss_default`` below its threshold; a finalize member's reaches the lowest score among the user's confirmed matches
+    (``lowest_scoring_user_match``'s rows, ``compute_matches._review_budget``'s expressions), so its ``select_clips_to_review`` finds the
+    partition in ``_ahead`` as a revise member's does."""
+    reaches = [None if m[8] else float(m[2].near_miss_default) for m in members]
+    # a finalize member without user matches reaches nowhere (lowest 1.0); lowest_scoring_user_match raises later where it always did
+    user_rows = [_user_match_rows(m[1]) if m[8] and m[1].user_matches else [] for m in members]
+    results = db.batch_round_update([m[0] for m in members], [m[3] for m in members], [m[4] for m in members], [m[5] for m in members],
+                                    [m[6] for m in members], [m[2].ballast for m in members], [m[7] for m in members],
+                                    float(os.environ["COMPUTE_EPS"]), reaches, user_rows)
+    for (q, tk, hp, _rows, _labels, _cand, _ths, _second, _finalize), r in zip(members, results):
+        if r.fell_back:                                               # the warning of Hyperparameter._refine
+            logging.warning("hyperparameter quadratic fine tuning failed - resort to selecting optimum on grid "
+                            "without further interpolation")
+        picked = {hp.streams[0]: 1.0, hp.streams[1]: r.w}
+        w = np.zeros(db.S, dtype=np.float64)                          # as compute_scores builds it from the dict
+        for stream_type, ws in picked.items():
+            w[tk._stream_names.index(stream_type)] = ws
+        tk._ahead = {"w": w.tobytes(), "scores": r.scores, "select": r.band, "match_rows": r.match_rows, "near_rows": r.near_rows,
+                     "near_argmax": r.near_argmax}
+        tk._fit, tk._fit_round = (picked, r.threshold), tk._round
 
 
 def _set_top(tk, rows, vals):
@@ -545,7 +595,7 @@ def _flush(group, top_of=None):
         _batched_pass(group, tops(group))
 
 
-def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False, fit=None, top=None):
+def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False, fit=None, top=None, fit_on_device=False, finalize=None):
     """``compute_similarities`` for a list of tickets, those that can sharing passes over their resident database: a broker with
     several pending tickets pays one read of the database per 16 of them instead of one each.  ``hyperparameters`` is one object or
     one per ticket.  Every ticket ends with exactly the attributes its own ``compute_similarities`` sets (``similarities``, ``_avg``,
@@ -575,6 +625,14 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     ``select_clips_to_review(threshold, ., near_miss_default)`` ask the device for nothing.  Every other ticket is unchanged and its
     caller runs ``optimize_weights``: one that ran its own round, one on a database without the two methods, one without labels.
 
+    ``fit_on_device=True`` (with ``fit`` and ``finalize``, one boolean per ticket: is it a finalize round): on a database with
+    ``batch_round_update`` the group's update is ONE call -- the minimum of every surface is picked and refined on the device and a
+    finalize member's review band, which reaches down to ``lowest_scoring_user_match`` under the fitted scores, is computed and
+    partitioned there too, so its ``select_clips_to_review`` asks the device for nothing either.  One difference: weights and
+    threshold are ``Hyperparameter._pick_exact``'s, not ``_pick_from``'s (squares as products instead of libm's ``pow``: a few ulp
+    in some refined picks, tests/test_pick_exact.py).  A database without the method (a ``ShardedFeatureDB``) does what it does
+    without the switch.
+
     ``top``: an int, or one per ticket.  Every member of a pass also gets the ``top`` best clips of its search set, ranked on the
     device in the same hold of the lock, BEHIND the fit -- a fitted member is ranked under its fitted weights: one
     ``batch_round_topk`` per pass, so no N-sized array comes back for the ranking.  Such a ticket ends with ``_top`` = (clip ids
@@ -586,6 +644,10 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     fits = [False] * len(tickets) if fit is None else [bool(f) for f in fit]
     if len(fits) != len(tickets):
         raise ValueError("fit: one boolean per ticket")
+    if fit_on_device:
+        if finalize is None or len(finalize) != len(tickets):
+            raise ValueError("fit_on_device: finalize must say for every ticket whether its round is a finalize round")
+        fits = [_OnDevice(fin) if f else False for f, fin in zip(fits, finalize)]
     hps = list(hyperparameters) if isinstance(hyperparameters, (list, tuple)) else [hyperparameters] * len(tickets)
     if len(hps) != len(tickets):
         raise ValueError("one hyperparameters object, or one per ticket")
