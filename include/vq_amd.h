@@ -610,4 +610,5 @@ int vq_broadcast_query(vq_comm* comm, void* buf_dev, int64_t bytes, int32_t root
 #include "vq_amd_round_topk.h" /* the k best clips of every query of a batched round, ranked on the device in one call (additive to ABI 12) */
 #include "vq_amd_round_grid.h" /* the scores of chosen rows of a batched round under a grid of weights: what a sharded fit combines (additive to ABI 12) */
 #include "vq_amd_round_update.h" /* a group's whole weight update -- fit, pick, rescore, review bands, partition -- in one call (additive to ABI 12) */
+#include "vq_amd_round_shard.h" /* the avg rows of a batched round, and the whole weight update on given avg tables: a sharded update in one operation (additive to ABI 12) */
 #endif /* VQ_AMD_H */

@@ -33,8 +33,9 @@
  * [1, 64]; n_rows < 0 (or above 2^32), an L_q < 0, or sum L != n_rows; a row outside [0, M_q); a block shorter than off[4]; a NULL argument.
  *
  * OUT OF SCOPE: the sharded forms of vq_db_query_round_views (FeatureDB.query_round_batch_sets) and of vq_db_batch_targets -- a
- * ShardedFeatureDB batches whole-database rounds only; picking the minimum of a loss surface on the device; a second GPU (the sharded
- * rounds built on this call have run with every rank on one card only). */
+ * ShardedFeatureDB batches whole-database rounds only; picking the minimum of a loss surface on the device (vq_amd_round_update.h on
+ * one handle, vq_amd_round_shard.h for a sharded database, which then needs no grid scores); a second GPU (the sharded rounds built
+ * on this call have run with every rank on one card only). */
 #ifndef VQ_AMD_ROUND_GRID_H
 #define VQ_AMD_ROUND_GRID_H
 

@@ -43,7 +43,9 @@
  * (without a given surface) or n_user_rows, and for a slot with L_q > 0: a row or a user row outside [0, M_q), `second` outside
  * [0, S), a band_mode other than 0 and 1.
  *
- * OUT OF SCOPE: sharded databases (one handle only; the given-surface flag is the piece a sharded fit needs), the k best clips
+ * OUT OF SCOPE: sharded databases (one handle only: a row-sharded database runs this update as one operation on the two calls of
+ * vq_amd_round_shard.h, which carry the rows' averaged similarities with the block; the given-surface flag alone does not give a
+ * finalize member its band), the k best clips
  * (vq_db_batch_round_topk follows this call as it follows the rescore), more than 16 queries. */
 #ifndef VQ_AMD_ROUND_UPDATE_H
 #define VQ_AMD_ROUND_UPDATE_H

@@ -161,6 +161,13 @@ ROUND_UPDATE_SIGNATURES = {
     "vq_db_batch_round_update": [_P, _I32, _I32, _I32, _I64, _I64, _P, _I64, _P, _I64, _I32],
 }
 VQ_BUPDATE_SURFACE, VQ_BUPDATE_GIVEN_SURFACE = 16, 32
+# include/vq_amd_round_shard.h: the avg of chosen rows of the last batched round, and the whole weight update on avg tables that come with the block
+# (what a row-sharded database makes one operation of the update with) -- additive to ABI 12, bound like the tables above
+ROUND_SHARD_SIGNATURES = {
+    "vq_db_batch_avg_rows_layout": [_P, _I32, _I64, _P], "vq_db_batch_round_avg_rows": [_P, _I32, _I64, _P, _I64],
+    "vq_db_batch_update_given_layout": [_P, _I32, _I32, _I32, _I64, _I64, _P],
+    "vq_db_batch_round_update_given": [_P, _I32, _I32, _I32, _I64, _I64, _P, _I64, _P, _I64, _I32],
+}
 _SPECIAL = {"vq_last_error": ([], C.c_char_p), "vq_abi_version": ([], C.c_int)}
 
 _lib = None
@@ -213,7 +220,7 @@ def load(path: str | None = None):
         for name, (args, res) in _SPECIAL.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, res
-        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()) + list(CSV_SIGNATURES.items()) + list(BATCH_ROUND_SIGNATURES.items()) + list(VIEW_ROUND_SIGNATURES.items()) + list(ROUND_FIT_SIGNATURES.items()) + list(ROUND_TARGETS_SIGNATURES.items()) + list(ROUND_TOPK_SIGNATURES.items()) + list(ROUND_GRID_SIGNATURES.items()) + list(ROUND_UPDATE_SIGNATURES.items()):
+        for name, args in list(SIGNATURES.items()) + list(ROW_VIEW_SIGNATURES.items()) + list(CSV_SIGNATURES.items()) + list(BATCH_ROUND_SIGNATURES.items()) + list(VIEW_ROUND_SIGNATURES.items()) + list(ROUND_FIT_SIGNATURES.items()) + list(ROUND_TARGETS_SIGNATURES.items()) + list(ROUND_TOPK_SIGNATURES.items()) + list(ROUND_GRID_SIGNATURES.items()) + list(ROUND_UPDATE_SIGNATURES.items()) + list(ROUND_SHARD_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError here = ABI mismatch; fail loudly
             fn.argtypes, fn.restype = args, C.c_int
         if lib.vq_abi_version() != ABI_VERSION:

@@ -118,7 +118,8 @@ def compute_matches(query_updates, hyperparameters, ticket_factory=None, target_
     review band -- which depends on ``lowest_scoring_user_match`` under the fitted scores -- is still partitioned by its own
     ``select``.
     ``fit_weights="device"`` (with ``batch``): the same, with the group's update in ONE call where the database has
-    ``batch_round_update`` (``compute_similarities_batch(..., fit_on_device=True)``): the pick and its refinement run on the device, and
+    ``batch_round_update`` -- a ``FeatureDB``, or a ``ShardedFeatureDB`` opened with ``batch_rounds=True``, where it is one operation of
+    the sharded database -- (``compute_similarities_batch(..., fit_on_device=True)``): the pick and its refinement run on the device, and
     so does a finalize ticket's review band, which removes the second difference above.  One difference instead: weights and threshold
     are ``Hyperparameter._pick_exact``'s rather than ``_pick_from``'s (products instead of ``** 2``: equal in most picks, a few ulp apart
     in the others -- tests/test_pick_exact.py has the measured size); ledger, ``random`` consumption and matches are those of

@@ -2,7 +2,9 @@
 // (include/vq_amd_rounds.h), over a row view per query (include/vq_amd_round_views.h) -- and the weight fit and the re-weighting of
 // such a round's queries on what it left on the device (include/vq_amd_round_fit.h), the scores of chosen rows of such a round
 // under a grid of weights, which a row-sharded database combines into its fit (include/vq_amd_round_grid.h), and a group's whole
-// weight update -- fit, pick, rescore, review bands, partition -- as one chain on the handle's stream (include/vq_amd_round_update.h).
+// weight update -- fit, pick, rescore, review bands, partition -- as one chain on the handle's stream (include/vq_amd_round_update.h),
+// and the two calls a row-sharded database makes one operation of that update with: the avg of chosen rows, verbatim, and the same
+// chain on avg tables that come with the block (include/vq_amd_round_shard.h).
 //
 // Every kind of round is described by ONE table of pieces (BatchRound, csrc/vq_db.h): query q owns the entries start[q] ..
 // start[q + 1] of the concatenated avg / scores / list arrays.  A whole-database round is the round whose pieces all have N rows.
@@ -214,14 +216,14 @@ __global__ __launch_bounds__(256) void view_ne_kernel(ViewPlanArgs a, const uint
 // operations, so a cell has loss_surface_kernel's bits on the same avg, for any number of labels in 32 KB of LDS.
 constexpr int kFitChunk = 4096, kFitThreads = 256, kFitMaxGrid = 64;
 struct FitBatchArgs {
-    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round
+    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round | a given table [sum L][S]
     const double* w_grid;     // [Q][G][8]
     const double* th_grid;    // [Q][T]
     const double* ballast;    // [Q]
-    const int64_t* rows;      // [sum L]: positions inside each query's piece
+    const int64_t* rows;      // [sum L]: positions inside each query's piece | null: label l of query q is entry l of its piece (a given table)
     const double* labels;     // [sum L]
     double* out;              // [Q][G][T]
-    int64_t qoff[16];         // the first avg entry of query q
+    int64_t qoff[16];         // the first avg entry of query q (a given table: lstart[q])
     int64_t lstart[17];       // the first label of query q (lstart[q + 1] - lstart[q] = L_q; 0: nothing to do)
     int G, T, S;
 };
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(kFitThreads) void loss_surface_batch_kernel(FitBatc
         const int len = (int)(L - c0 < kFitChunk ? L - c0 : kFitChunk);
         for (int l = threadIdx.x; l < len; l += kFitThreads) {
             double av[8];
-            const int64_t row = a.rows[l0 + c0 + l];
+            const int64_t row = a.rows ? a.rows[l0 + c0 + l] : c0 + l;
             for (int s = 0; s < S; ++s) av[s] = avg[row * S + s];
             ls_scores[l] = score_from_avg(av, w, S);
         }
@@ -300,6 +302,7 @@ struct UpdateBatchArgs {
     const int32_t* band_mode; // [Q]
     const double* near;       // [Q]
     const int64_t* user_rows; // [sum U]: positions inside each query's piece
+    const double* user_avg;   // null: a user row's score is read from `scores` | [sum U][S]: it is score_from_avg of this entry under w[q]
     const double* scores;     // the round's score pieces
     double* pick;             // [Q][8]
     int32_t* pick_idx;        // [Q][4]
@@ -307,7 +310,7 @@ struct UpdateBatchArgs {
     double* band;             // [16][2]: what the partition reads
     int64_t qoff[16];         // the first score entry of query q
     int64_t ustart[17];       // the first user row of query q
-    int G, T;
+    int G, T, S;
 };
 
 // is cell (a, i) in front of cell (b, j) in numpy.argmin's order: a NaN before every number, then the smaller value, then the smaller
@@ -421,7 +424,8 @@ __global__ __launch_bounds__(kPickThreads) void pick_refine_batch_kernel(UpdateB
 
 // compute_matches.py:78-88 and ticket.py:301-316 behind the rescore: one workgroup per query.  Mode 1 lowers 1.0 by the scores at the
 // query's user rows; thread t folds a contiguous run of them and the tree joins neighbouring runs, the earlier one on the left, so
-// the value is the in-order fold's (also between +0 and -0).  Thread 0 then writes the band.
+// the value is the in-order fold's (also between +0 and -0).  Thread 0 then writes the band.  With user_avg (the rows may live on
+// another handle: include/vq_amd_round_shard.h) a row's score is what rescore_batch_kernel gives at it, from the same avg and weights.
 __global__ __launch_bounds__(kPickThreads) void review_band_batch_kernel(UpdateBatchArgs a) {
     __shared__ double ls_min[kPickThreads];
     const int q = blockIdx.x, t = threadIdx.x;
@@ -432,8 +436,18 @@ __global__ __launch_bounds__(kPickThreads) void review_band_batch_kernel(UpdateB
         const int64_t u0 = a.ustart[q], U = a.ustart[q + 1] - u0, per = (U + kPickThreads - 1) / kPickThreads;
         const double* scores = a.scores + a.qoff[q];
         const int64_t hi = (t + 1) * per < U ? (t + 1) * per : U;
+        double w[8];
+        if (a.user_avg)
+            for (int s = 0; s < a.S; ++s) w[s] = a.w[q * 8 + s];
         for (int64_t i = t * per; i < hi; ++i) {
-            const double v = scores[a.user_rows[u0 + i]];
+            double v;
+            if (a.user_avg) {
+                double av[8];
+                for (int s = 0; s < a.S; ++s) av[s] = a.user_avg[(u0 + i) * a.S + s];
+                v = score_from_avg(av, w, a.S);
+            } else {
+                v = scores[a.user_rows[u0 + i]];
+            }
             lowest = v < lowest ? v : lowest;                  // min(min_score, v)
         }
         ls_min[t] = lowest;
@@ -478,6 +492,27 @@ __global__ __launch_bounds__(256) void grid_scores_batch_kernel(GridBatchArgs a)
     const int64_t g = i / L, l = i - g * L;
     const int64_t entry = a.qoff[q] + a.rows[l0 + l];
     a.out[(int64_t)a.G * l0 + i] = score_from_avg(a.avg + entry * a.S, a.w_grid + ((int64_t)q * a.G + g) * 8, a.S);
+}
+
+// vq_db_batch_round_avg_rows (include/vq_amd_round_shard.h): thread (q = blockIdx.y, i = l S + s) copies stream s of row rows[l] of query
+// q's avg piece (qoff[q] on) into entry lstart[q] + l of `out`.  Loads and stores only: the bits arrive as they are.
+struct AvgRowsArgs {
+    const double* avg;        // the round's avg piece: [Q][N][S], or the concatenated pieces of a view round
+    const int64_t* rows;      // [sum L]: positions inside each query's piece
+    double* out;              // [sum L][S]
+    int64_t qoff[16];         // the first avg entry of query q
+    int64_t lstart[17];       // the first row of query q (lstart[q + 1] - lstart[q] = L_q; 0: nothing to do)
+    int S;
+};
+
+__global__ __launch_bounds__(256) void avg_rows_batch_kernel(AvgRowsArgs a) {
+    const int q = blockIdx.y, S = a.S;
+    const int64_t l0 = a.lstart[q], total = (a.lstart[q + 1] - l0) * S;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = i / S;
+        const int s = (int)(i - l * S);
+        a.out[(l0 + l) * S + s] = a.avg[(a.qoff[q] + a.rows[l0 + l]) * S + s];
+    }
 }
 
 // ---- the host steps that every round takes, each stated once ---------------------------------------------------------------------------
@@ -708,13 +743,14 @@ static int view_round_sizes(vq_db* db, int Q, const int32_t* views, int64_t m[16
     return VQ_OK;
 }
 
-static void batch_fit_layout(int Q, int G, int T, int64_t n_labels, int64_t off[8]) {
+// row_bytes: what a labelled row brings in piece 4 -- its position (8), or its S averaged similarities (a given table)
+static void batch_fit_layout(int Q, int G, int T, int64_t n_labels, int64_t off[8], int64_t row_bytes = 8) {
     off[0] = 0;
     off[1] = off[0] + up64((int64_t)Q * G * 8 * 8);
     off[2] = off[1] + up64((int64_t)Q * T * 8);
     off[3] = off[2] + up64((int64_t)Q * 8);
     off[4] = off[3] + up64((int64_t)Q * 8);
-    off[5] = off[4] + up64(n_labels * 8);
+    off[5] = off[4] + up64(n_labels * row_bytes);
     off[6] = off[5] + up64(n_labels * 8);
     off[7] = off[6] + up64((int64_t)Q * G * T * 8);
 }
@@ -727,15 +763,16 @@ static int batch_fit_shape(int Q, int G, int T, int64_t n_labels) {
     return VQ_OK;
 }
 
-// the fit block's pieces (off[0] .. off[6] are batch_fit_layout's), then the update's own inputs and its two outputs
-static void batch_update_layout(int Q, int G, int T, int64_t n_labels, int64_t n_user_rows, int64_t off[16]) {
-    batch_fit_layout(Q, G, T, n_labels, off);
+// the fit block's pieces (off[0] .. off[6] are batch_fit_layout's), then the update's own inputs and its two outputs; row_bytes: of a
+// labelled row and of a user row alike
+static void batch_update_layout(int Q, int G, int T, int64_t n_labels, int64_t n_user_rows, int64_t off[16], int64_t row_bytes = 8) {
+    batch_fit_layout(Q, G, T, n_labels, off, row_bytes);
     off[8] = off[7] + up64((int64_t)Q * 4);
     off[9] = off[8] + up64((int64_t)Q * 8);
     off[10] = off[9] + up64((int64_t)Q * 4);
     off[11] = off[10] + up64((int64_t)Q * 8);
     off[12] = off[11] + up64((int64_t)Q * 8);
-    off[13] = off[12] + up64(n_user_rows * 8);
+    off[13] = off[12] + up64(n_user_rows * row_bytes);
     off[14] = off[13] + up64((int64_t)Q * 8 * 8);
     off[15] = off[14] + up64((int64_t)Q * 4 * 4);
 }
@@ -748,11 +785,41 @@ static void batch_grid_layout(int Q, int G, int64_t n_rows, int64_t off[5]) {
     off[4] = off[3] + up64((int64_t)G * n_rows * 8);
 }
 
+static void batch_avg_rows_layout(int Q, int S, int64_t n_rows, int64_t off[4]) {
+    off[0] = 0;
+    off[1] = off[0] + up64((int64_t)Q * 8);
+    off[2] = off[1] + up64(n_rows * 8);
+    off[3] = off[2] + up64(n_rows * S * 8);
+}
+
 static int batch_grid_shape(int Q, int G, int64_t n_rows) {
     VQ_REQUIRE(Q >= 1 && Q <= kBatchSlots, "n_queries must be in [1,%d] (got %d)", kBatchSlots, Q);
     VQ_REQUIRE(G >= 1 && G <= kFitMaxGrid, "the grid of a batched round holds 1 to %d weights (got %d)", kFitMaxGrid, G);
     // 2^32 rows x 64 weights are 2^30 workgroups of 256: the launch's grid stays inside 31 bits
     VQ_REQUIRE(n_rows >= 0 && n_rows <= ((int64_t)1 << 32), "n_rows must be in [0, 2^32] (got %lld)", (long long)n_rows);
+    return VQ_OK;
+}
+
+// The row lists of a call that reads chosen rows of round r (vq_db_batch_round_grid, vq_db_batch_round_avg_rows), checked: every L_q in
+// [0, n_rows] and their sum n_rows, no rows for a slot the round lacked, every row inside its query's piece.  Gives the first row of
+// every slot, the first avg entry of every query and the longest list.  Caller holds the lock and has seen that a round exists.
+static int chosen_rows(const BatchRound& r, int Q, const int64_t* L, const int64_t* rows, int64_t n_rows, int64_t lstart[17], int64_t qoff[16],
+                       int64_t* max_l) {
+    lstart[0] = 0;
+    *max_l = 0;
+    for (int q = 0; q < kBatchSlots; ++q) {
+        const int64_t lq = q < Q ? L[q] : 0;
+        VQ_REQUIRE(lq >= 0 && lq <= n_rows, "query %d: L = %lld outside [0, n_rows = %lld]", q, (long long)lq, (long long)n_rows);
+        if (lq > 0 && q >= r.q) return fail(VQ_E_STATE, "the last batched round had %d queries (rows for query %d)", r.q, q);
+        lstart[q + 1] = lstart[q] + lq;
+        qoff[q] = r.start[q];
+        *max_l = std::max(*max_l, lq);
+    }
+    VQ_REQUIRE(lstart[kBatchSlots] == n_rows, "the L of the queries add up to %lld, n_rows is %lld", (long long)lstart[kBatchSlots], (long long)n_rows);
+    for (int q = 0; q < Q; ++q)
+        for (int64_t l = lstart[q]; l < lstart[q + 1]; ++l)
+            VQ_REQUIRE(rows[l] >= 0 && rows[l] < r.m(q), "query %d: row %lld (entry %lld) outside [0,%lld)", q, (long long)rows[l],
+                       (long long)(l - lstart[q]), (long long)r.m(q));
     return VQ_OK;
 }
 
@@ -1154,25 +1221,34 @@ int vq_db_batch_update_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int3
     return VQ_OK;
 }
 
-int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
-                             void* update_block, int64_t update_bytes, void* round_block, int64_t round_bytes, int32_t flags) {
+// A group's whole weight update on the last batched round, stated once for its two entry points.  tables = false:
+// vq_db_batch_round_update (include/vq_amd_round_update.h), the labelled and the user rows named by position.  tables = true:
+// vq_db_batch_round_update_given (include/vq_amd_round_shard.h): pieces 4 and 12 of the block carry those rows' avg instead, S doubles
+// per row, so there are no positions to check, the surface is never given and L_q counts labels that other handles may hold.
+static int run_batch_update(vq_db* db, bool tables, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
+                            void* update_block, int64_t update_bytes, void* round_block, int64_t round_bytes, int32_t flags) {
     VQ_REQUIRE(db && update_block, "NULL argument");
     {
         const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
         if (rc != VQ_OK) return rc;
     }
     VQ_REQUIRE(n_user_rows >= 0, "n_user_rows must not be negative");
-    constexpr int kKnown = VQ_BROUND_SCORES | VQ_BROUND_SELECT | VQ_BUPDATE_SURFACE | VQ_BUPDATE_GIVEN_SURFACE;
-    VQ_REQUIRE((flags & ~kKnown) == 0, "flags: 2 = scores back, 4 = partition, 16 = surfaces back, 32 = surfaces given (got %d)", flags);
+    if (tables) {
+        constexpr int kKnown = VQ_BROUND_SCORES | VQ_BROUND_SELECT | VQ_BUPDATE_SURFACE;
+        VQ_REQUIRE((flags & ~kKnown) == 0, "flags: 2 = scores back, 4 = partition, 16 = surfaces back (got %d)", flags);
+    } else {
+        constexpr int kKnown = VQ_BROUND_SCORES | VQ_BROUND_SELECT | VQ_BUPDATE_SURFACE | VQ_BUPDATE_GIVEN_SURFACE;
+        VQ_REQUIRE((flags & ~kKnown) == 0, "flags: 2 = scores back, 4 = partition, 16 = surfaces back, 32 = surfaces given (got %d)", flags);
+    }
     const bool want_scores = flags & VQ_BROUND_SCORES, do_select = flags & VQ_BROUND_SELECT;
     const bool want_surface = flags & VQ_BUPDATE_SURFACE, given = flags & VQ_BUPDATE_GIVEN_SURFACE;
     VQ_REQUIRE(!(want_surface && given), "flags: a given surface (32) is not copied back (16)");
     VQ_REQUIRE(round_block || !(want_scores || do_select), "NULL argument: scores and partitions come back into the block of the round");
     const int Q = n_queries, G = n_grid, T = n_thresholds;
     int64_t off[16];
-    batch_update_layout(Q, G, T, n_labels, n_user_rows, off);
-    VQ_REQUIRE(update_bytes >= off[15], "the block of this batched update needs %lld bytes (vq_db_batch_update_layout), got %lld", (long long)off[15],
-               (long long)update_bytes);
+    batch_update_layout(Q, G, T, n_labels, n_user_rows, off, tables ? (int64_t)db->S * 8 : 8);
+    VQ_REQUIRE(update_bytes >= off[15], "the block of this batched update needs %lld bytes (%s), got %lld", (long long)off[15],
+               tables ? "vq_db_batch_update_given_layout" : "vq_db_batch_update_layout", (long long)update_bytes);
     char* host = (char*)update_block;
     const int64_t* L = (const int64_t*)(host + off[3]);
     const int64_t* rows = (const int64_t*)(host + off[4]);
@@ -1196,7 +1272,8 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
         if (lq > 0 && q >= r.q) return fail(VQ_E_STATE, "the last batched round had %d queries (labels for query %d)", r.q, q);
         fa.lstart[q + 1] = fa.lstart[q] + (given ? 0 : lq);
         ua.ustart[q + 1] = ua.ustart[q] + uq;
-        fa.qoff[q] = ua.qoff[q] = r.start[q];
+        ua.qoff[q] = r.start[q];
+        fa.qoff[q] = tables ? fa.lstart[q] : r.start[q];      // a given table holds query q's labelled rows from its first label on
         if (lq > 0) {
             mask |= 1u << q;
             max_m = std::max(max_m, r.m(q));
@@ -1210,6 +1287,7 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
         if (!((mask >> q) & 1u)) continue;
         VQ_REQUIRE(second[q] >= 0 && second[q] < db->S, "query %d: second = %d outside [0,%d)", q, second[q], db->S);
         VQ_REQUIRE(band_mode[q] == 0 || band_mode[q] == 1, "query %d: band_mode %d (0 = a given reach, 1 = from the user's matches)", q, band_mode[q]);
+        if (tables) continue;                         // no positions: the rows' avg came with the block
         for (int64_t l = fa.lstart[q]; l < fa.lstart[q + 1]; ++l)
             VQ_REQUIRE(rows[l] >= 0 && rows[l] < r.m(q), "query %d: row %lld (label %lld) outside [0,%lld)", q, (long long)rows[l],
                        (long long)(l - fa.lstart[q]), (long long)r.m(q));
@@ -1230,12 +1308,12 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
     // ONE upload: the fit's inputs, the surface piece (given, or about to be overwritten) and the update's inputs are adjacent
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[13], hipMemcpyHostToDevice, db->stream));
     const bool have_rows = max_m > 0;                 // false: only empty views, which have neither labels nor scores nor lists
-    if (!given && have_rows) {
-        fa.avg = (const double*)(db->bround_dev + r.off[4]);
+    if (!given && (tables || have_rows)) {            // a given table needs no row of this handle
+        fa.avg = tables ? (const double*)(base + off[4]) : (const double*)(db->bround_dev + r.off[4]);
         fa.w_grid = (const double*)(base + off[0]);
         fa.th_grid = (const double*)(base + off[1]);
         fa.ballast = (const double*)(base + off[2]);
-        fa.rows = (const int64_t*)(base + off[4]);
+        fa.rows = tables ? nullptr : (const int64_t*)(base + off[4]);
         fa.labels = (const double*)(base + off[5]);
         fa.out = (double*)(base + off[6]);
         fa.G = G;
@@ -1252,7 +1330,8 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
     ua.eps = (const double*)(base + off[8]);
     ua.band_mode = (const int32_t*)(base + off[9]);
     ua.near = (const double*)(base + off[10]);
-    ua.user_rows = (const int64_t*)(base + off[12]);
+    ua.user_rows = tables ? nullptr : (const int64_t*)(base + off[12]);
+    ua.user_avg = tables ? (const double*)(base + off[12]) : nullptr;
     ua.scores = have_rows ? (const double*)(db->bround_dev + r.off[5]) : nullptr;
     ua.pick = (double*)(base + off[13]);
     ua.pick_idx = (int32_t*)(base + off[14]);
@@ -1260,6 +1339,7 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
     ua.band = (double*)(base + stage_band);
     ua.G = G;
     ua.T = T;
+    ua.S = db->S;
     pick_refine_batch_kernel<<<Q, kPickThreads, 0, db->stream>>>(ua);
     VQ_CHECK_LAUNCH();
     if (have_rows) {
@@ -1292,6 +1372,78 @@ int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32
     return VQ_OK;
 }
 
+int vq_db_batch_round_update(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
+                             void* update_block, int64_t update_bytes, void* round_block, int64_t round_bytes, int32_t flags) {
+    return run_batch_update(db, false, n_queries, n_grid, n_thresholds, n_labels, n_user_rows, update_block, update_bytes, round_block, round_bytes, flags);
+}
+
+// ---- what a row-sharded database makes one operation of that update with (include/vq_amd_round_shard.h) ------------------------------
+int vq_db_batch_avg_rows_layout(vq_db* db, int32_t n_queries, int64_t n_rows, int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    const int rc = batch_grid_shape(n_queries, 1, n_rows);
+    if (rc != VQ_OK) return rc;
+    batch_avg_rows_layout(n_queries, db->S, n_rows, off);
+    return VQ_OK;
+}
+
+int vq_db_batch_round_avg_rows(vq_db* db, int32_t n_queries, int64_t n_rows, void* block, int64_t block_bytes) {
+    VQ_REQUIRE(db && block, "NULL argument");
+    {
+        const int rc = batch_grid_shape(n_queries, 1, n_rows);
+        if (rc != VQ_OK) return rc;
+    }
+    const int Q = n_queries, S = db->S;
+    int64_t off[4];
+    batch_avg_rows_layout(Q, S, n_rows, off);
+    VQ_REQUIRE(block_bytes >= off[3], "the block of these avg rows needs %lld bytes (vq_db_batch_avg_rows_layout), got %lld", (long long)off[3],
+               (long long)block_bytes);
+    char* host = (char*)block;
+    const int64_t* L = (const int64_t*)(host + off[0]);
+    const int64_t* rows = (const int64_t*)(host + off[1]);
+    std::lock_guard<std::mutex> lk(db->mu);
+    const BatchRound& r = db->round;
+    if (r.q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
+    AvgRowsArgs a;
+    int64_t max_l = 0;
+    {
+        const int rc = chosen_rows(r, Q, L, rows, n_rows, a.lstart, a.qoff, &max_l);
+        if (rc != VQ_OK) return rc;
+    }
+    if (n_rows == 0) return VQ_OK;                    // every query skipped: nothing to launch
+    DeviceGuard g(db->device);
+    {
+        const int rc = ensure_grid_buf(db, off[3]);
+        if (rc != VQ_OK) return rc;
+    }
+    char* base = (char*)db->grid_buf;
+    VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[2], hipMemcpyHostToDevice, db->stream));      // L | rows: adjacent
+    a.avg = (const double*)(db->bround_dev + r.off[4]);
+    a.rows = (const int64_t*)(base + off[1]);
+    a.out = (double*)(base + off[2]);
+    a.S = S;
+    const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((max_l * S + 255) / 256, (int64_t)db->cus * 8));
+    avg_rows_batch_kernel<<<dim3(bx, Q), 256, 0, db->stream>>>(a);
+    VQ_CHECK_LAUNCH();
+    VQ_HIP(hipMemcpyAsync(host + off[2], base + off[2], (size_t)(n_rows * S * 8), hipMemcpyDeviceToHost, db->stream));
+    VQ_HIP(hipStreamSynchronize(db->stream));
+    return VQ_OK;
+}
+
+int vq_db_batch_update_given_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
+                                    int64_t* off) {
+    VQ_REQUIRE(db && off, "NULL argument");
+    const int rc = batch_fit_shape(n_queries, n_grid, n_thresholds, n_labels);
+    if (rc != VQ_OK) return rc;
+    VQ_REQUIRE(n_user_rows >= 0, "n_user_rows must not be negative");
+    batch_update_layout(n_queries, n_grid, n_thresholds, n_labels, n_user_rows, off, (int64_t)db->S * 8);
+    return VQ_OK;
+}
+
+int vq_db_batch_round_update_given(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t n_thresholds, int64_t n_labels, int64_t n_user_rows,
+                                   void* update_block, int64_t update_bytes, void* round_block, int64_t round_bytes, int32_t flags) {
+    return run_batch_update(db, true, n_queries, n_grid, n_thresholds, n_labels, n_user_rows, update_block, update_bytes, round_block, round_bytes, flags);
+}
+
 // ---- the scores of chosen rows of a batched round's queries under a grid of weights (include/vq_amd_round_grid.h) --------------------
 int vq_db_batch_grid_layout(vq_db* db, int32_t n_queries, int32_t n_grid, int64_t n_rows, int64_t* off) {
     VQ_REQUIRE(db && off, "NULL argument");
@@ -1319,21 +1471,11 @@ int vq_db_batch_round_grid(vq_db* db, int32_t n_queries, int32_t n_grid, int64_t
     const BatchRound& r = db->round;
     if (r.q == 0) return fail(VQ_E_STATE, "no batched round has run on this handle");
     GridBatchArgs a;
-    a.lstart[0] = 0;
     int64_t max_l = 0;
-    for (int q = 0; q < kBatchSlots; ++q) {
-        const int64_t lq = q < Q ? L[q] : 0;
-        VQ_REQUIRE(lq >= 0 && lq <= n_rows, "query %d: L = %lld outside [0, n_rows = %lld]", q, (long long)lq, (long long)n_rows);
-        if (lq > 0 && q >= r.q) return fail(VQ_E_STATE, "the last batched round had %d queries (rows for query %d)", r.q, q);
-        a.lstart[q + 1] = a.lstart[q] + lq;
-        a.qoff[q] = r.start[q];
-        max_l = std::max(max_l, lq);
+    {
+        const int rc = chosen_rows(r, Q, L, rows, n_rows, a.lstart, a.qoff, &max_l);
+        if (rc != VQ_OK) return rc;
     }
-    VQ_REQUIRE(a.lstart[kBatchSlots] == n_rows, "the L of the queries add up to %lld, n_rows is %lld", (long long)a.lstart[kBatchSlots], (long long)n_rows);
-    for (int q = 0; q < Q; ++q)
-        for (int64_t l = a.lstart[q]; l < a.lstart[q + 1]; ++l)
-            VQ_REQUIRE(rows[l] >= 0 && rows[l] < r.m(q), "query %d: row %lld (entry %lld) outside [0,%lld)", q, (long long)rows[l],
-                       (long long)(l - a.lstart[q]), (long long)r.m(q));
     if (n_rows == 0) return VQ_OK;                    // every query skipped: nothing to launch
     DeviceGuard g(db->device);
     {

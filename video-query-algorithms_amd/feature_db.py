@@ -911,6 +911,39 @@ class FeatureDB:
             call("vq_db_batch_round_grid", self._h, Q, G, total, C.c_void_p(blk.ptr), blk.nbytes)
             return [view(3, np.float64, (G, rs[i].size), G * first[i]) if rs[i].size else None for i in range(k)]
 
+    def batch_round_avg_rows(self, queries, rows) -> list:
+        """The averaged similarities of chosen rows of several queries of the LAST batched round (either kind) in one call and one
+        launch (vq_db_batch_round_avg_rows, include/vq_amd_round_shard.h): per entry i, ``avg[rows[i]]`` of query ``queries[i]`` of that
+        round (positions in the query's view, as in its results; a row may repeat) as the round left them on the device -- copies,
+        bit for bit, NaN payloads and the sign of zero included.  Returns one [L_i, S] array per entry, None for an entry without
+        rows.  What the ranks of a row-sharded database exchange in front of :meth:`batch_round_update_given`."""
+        queries = [int(q) for q in queries]
+        k = len(queries)
+        if not (k and len(rows) == k) or len(set(queries)) != k:
+            raise ValueError("one list of rows per query, every query once")
+        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        if min(queries) < 0:
+            raise ValueError("a query is its index in the last batched round")
+        with self.lock:
+            Q = max(queries) + 1                              # slot q of the block = query q of the round; the library refuses what that round lacks
+            order = sorted(range(k), key=lambda i: queries[i])
+            total = int(sum(r.size for r in rs))
+            off = (C.c_int64 * 4)()
+            call("vq_db_batch_avg_rows_layout", self._h, Q, total, off)
+            off = [int(v) for v in off]
+            blk = self._pooled_block("_grid_pools", off[3])
+            view = self._block_view(blk.bytes(), off)
+            l_in, r_in = view(0, np.int64, (Q,)), view(1, np.int64, (total,))
+            l_in[...] = 0
+            at, first = 0, {}
+            for i in order:
+                l_in[queries[i]] = rs[i].size
+                r_in[at:at + rs[i].size] = rs[i]
+                first[i] = at
+                at += rs[i].size
+            call("vq_db_batch_round_avg_rows", self._h, Q, total, C.c_void_p(blk.ptr), blk.nbytes)
+            return [view(2, np.float64, (rs[i].size, self.S), self.S * first[i]) if rs[i].size else None for i in range(k)]
+
     # ------------------------------------------------------------------ the bootstrapped targets of a group of tickets
     def batch_targets_lds_rows(self) -> int:
         """The largest draw (rows) whose systems ``batch_targets`` solves in a workgroup's local memory; longer draws solve in a
@@ -1036,9 +1069,28 @@ class FeatureDB:
         Returns one :class:`UpdateResult` per entry: scores (None without ``want_scores``; they stay on the device), partition, ``avg``
         and ``n_e`` as :meth:`batch_round_rescore` gives them under ``w`` and ``band``; the pick has the bits of ``_pick_exact``, ``band``
         those of the host's expressions over the returned scores.  ``surface`` is the fit's own (``want_surface``) or None."""
+        return self._batch_update(queries, rows, labels, w_grids, th_grids, ballasts, seconds, eps, reaches, user_rows, want_scores, want_surface,
+                                  surfaces, tables=False)
+
+    def batch_round_update_given(self, queries, labels, label_avgs, w_grids, th_grids, ballasts, seconds, eps, reaches, user_avgs,
+                                 want_scores: bool = True, want_surface: bool = False) -> list:
+        """:meth:`batch_round_update` with the labelled and the user rows' averaged similarities GIVEN instead of read from the round
+        (vq_db_batch_round_update_given, include/vq_amd_round_shard.h): ``label_avgs[i]`` [L_i, S] in label order and ``user_avgs[i]``
+        [U_i, S] (or None) are what :meth:`batch_round_avg_rows` returns for those rows -- on this handle or, for a row-sharded
+        database, put together from the handles that hold them.  ``L_i`` is the number of labels of the WHOLE database: the divisor.
+        The surface, the pick, ``lowest`` and the band are functions of the tables alone, so every handle fed the same tables picks
+        the same; the rescore and the partition are this handle's own rows'.  Fed the tables of its own rows the call returns what
+        :meth:`batch_round_update` returns, bit for bit."""
+        return self._batch_update(queries, label_avgs, labels, w_grids, th_grids, ballasts, seconds, eps, reaches, user_avgs, want_scores,
+                                  want_surface, None, tables=True)
+
+    def _batch_update(self, queries, rows, labels, w_grids, th_grids, ballasts, seconds, eps, reaches, user_rows, want_scores, want_surface,
+                      surfaces, tables):
+        """The two update calls: ``tables`` says whether ``rows`` / ``user_rows`` carry positions (int64) or [., S] averaged similarities."""
         queries = [int(q) for q in queries]
         k = len(queries)
         given = surfaces is not None
+        row_t, width = (np.float64, self.S) if tables else (np.int64, 1)
         eps = [float(eps)] * k if np.ndim(eps) == 0 else [float(e) for e in eps]
         if not (k and len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == len(seconds) == len(eps) == len(reaches)
                 == len(user_rows) == k) or len(set(queries)) != k or (given and (len(surfaces) != k or want_surface)):
@@ -1049,13 +1101,15 @@ class FeatureDB:
             counts = [int(y) if np.ndim(y) == 0 else len(y) for y in labels]
             rs, ys = [np.zeros(0, dtype=np.int64)] * k, [np.zeros(0)] * k
         else:
-            rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+            rs = [np.asarray(r, dtype=row_t).reshape(-1) for r in rows]
             ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
-            counts = [r.size for r in rs]
-        us = [np.zeros(0, dtype=np.int64) if u is None else np.asarray(u, dtype=np.int64).reshape(-1) for u in user_rows]
+            counts = [r.size // width for r in rs]
+        us = [np.zeros(0, dtype=row_t) if u is None else np.asarray(u, dtype=row_t).reshape(-1) for u in user_rows]
         G, T = int(wg[0].shape[0]), int(th[0].size)
-        if any(w.ndim != 2 or w.shape != (G, self.S) for w in wg) or any(t.size != T for t in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
-            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
+        if any(w.ndim != 2 or w.shape != (G, self.S) for w in wg) or any(t.size != T for t in th) or \
+                any(r.size != y.size * width for r, y in zip(rs, ys)) or any(u.size % width for u in us):
+            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row%s"
+                             % (self.S, " of [., %d] averaged similarities" % self.S if tables else ""))
         sf = [np.asarray(f, dtype=np.float64) for f in surfaces] if given else None
         if given and any(f.shape != (G, T) for f in sf):
             raise ValueError("surfaces must be [G,T]")
@@ -1066,27 +1120,28 @@ class FeatureDB:
         with self.lock:
             Q = max(queries) + 1                              # slot q of the block = query q of the round; the library refuses what that round lacks
             order = sorted(range(k), key=lambda i: queries[i])
-            total, total_u = int(sum(r.size for r in rs)), int(sum(u.size for u in us))
+            total, total_u = int(sum(y.size for y in ys)), int(sum(u.size for u in us)) // width
             off = (C.c_int64 * 16)()
-            call("vq_db_batch_update_layout", self._h, Q, G, T, total, total_u, off)
+            call("vq_db_batch_update_given_layout" if tables else "vq_db_batch_update_layout", self._h, Q, G, T, total, total_u, off)
             off = [int(v) for v in off]
             ublk = self._pooled_block("_update_pools", off[15])
             view = self._block_view(ublk.bytes(), off)
             ublk.bytes()[:off[6]] = 0
             ublk.bytes()[off[7]:off[15]] = 0
             w_in, th_in, b_in, l_in = view(0, np.float64, (Q, G, 8)), view(1, np.float64, (Q, T)), view(2, np.float64, (Q,)), view(3, np.int64, (Q,))
-            r_in, y_in, surface = view(4, np.int64, (total,)), view(5, np.float64, (total,)), view(6, np.float64, (Q, G, T))
+            r_in, y_in, surface = view(4, row_t, (total * width,)), view(5, np.float64, (total,)), view(6, np.float64, (Q, G, T))
             sec_in, eps_in, mode_in, near_in = view(7, np.int32, (Q,)), view(8, np.float64, (Q,)), view(9, np.int32, (Q,)), view(10, np.float64, (Q,))
-            u_in, ur_in = view(11, np.int64, (Q,)), view(12, np.int64, (total_u,))
-            at = at_u = 0
+            u_in, ur_in = view(11, np.int64, (Q,)), view(12, row_t, (total_u * width,))
+            at = at_y = at_u = 0
             for i in order:
                 q = queries[i]
                 w_in[q, :, :self.S], th_in[q], b_in[q], l_in[q] = wg[i], th[i], float(ballasts[i]), counts[i]
-                r_in[at:at + rs[i].size], y_in[at:at + rs[i].size] = rs[i], ys[i]
+                r_in[at:at + rs[i].size], y_in[at_y:at_y + ys[i].size] = rs[i], ys[i]
                 at += rs[i].size
+                at_y += ys[i].size
                 sec_in[q], eps_in[q] = int(seconds[i]), eps[i]
                 mode_in[q], near_in[q] = (1, 0.0) if reaches[i] is None else (0, float(reaches[i]))
-                u_in[q] = us[i].size
+                u_in[q] = us[i].size // width
                 ur_in[at_u:at_u + us[i].size] = us[i]
                 at_u += us[i].size
                 if given:
@@ -1100,7 +1155,8 @@ class FeatureDB:
             _Q, roff, start, pool, sims = last
             blk = self._batch_round_block(_Q)[0] if pool is None else self._pooled_block("_view_round_pools", roff[9])
             rview = self._block_view(blk.bytes(), roff)
-            call("vq_db_batch_round_update", self._h, Q, G, T, total, total_u, C.c_void_p(ublk.ptr), ublk.nbytes, C.c_void_p(blk.ptr), blk.nbytes, flags)
+            call("vq_db_batch_round_update_given" if tables else "vq_db_batch_round_update", self._h, Q, G, T, total, total_u, C.c_void_p(ublk.ptr),
+                 ublk.nbytes, C.c_void_p(blk.ptr), blk.nbytes, flags)
             pick, idx = view(13, np.float64, (Q, 8)), view(14, np.int32, (Q, 4))
             decode = self._partition_decoder(rview, roff, _Q)
             out = []

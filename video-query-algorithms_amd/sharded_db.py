@@ -25,7 +25,10 @@ broker code scores on every GPU of the node (half B):
   (``query_round_batch``), and their weight fit, re-weighting and ranking follow in one call each (``batch_round_fit`` /
   ``batch_round_rescore`` / ``batch_round_topk``) -- one announcement and one gather of the per-row results for all of them, two
   small gathers for all their partitions; a fit adds the labelled clips' terms in label order on the host, from grid scores that
-  every rank computes for the rows it holds (``FeatureDB.batch_round_grid``) and one exact all-reduce combines;
+  every rank computes for the rows it holds (``FeatureDB.batch_round_grid``) and one exact all-reduce combines; a group's whole
+  weight update (``batch_round_update``) is ONE operation: the ranks exchange the labelled and the user rows' averaged
+  similarities once, as bit patterns, and every rank runs the same device chain on identical tables
+  (``FeatureDB.batch_round_update_given``) -- the pick is replicated, only per-row results are gathered;
 * target bootstrapping: the handful of user-validated rows are fetched from their owners (``vq_db_read_rows``) and the
   closed forms run on the root's GPU (``csrc/vq_boot.hip``, the same kernel the resident route uses).
 
@@ -52,8 +55,9 @@ from .shard import all_gather_counts, all_gather_rows, merge_topk, shard_range
 
 OP_CLOSE, OP_RESTRICT, OP_SET_QUERY, OP_QUERY_FROM_ROW, OP_SCAN, OP_RESCORE, OP_SIMS, OP_SCORES, OP_GRID, OP_SELECT, OP_TOPK, \
     OP_MIN, OP_FETCH, OP_SCAN_BATCH, OP_LAYOUT, OP_WRITE_AVG, OP_ROUND, OP_DEFINE_SET, OP_USE_SET, OP_DROP_SET = range(20)
-# the four calls of a batched round (batch_rounds=True): the pass, the grid scores of a fit, the re-weighting, the ranking
+# the calls of a batched round (batch_rounds=True): the pass, the grid scores of a fit, the re-weighting, the ranking
 OP_ROUND_BATCH, OP_BATCH_GRID, OP_BATCH_RESCORE, OP_BATCH_TOPK = range(20, 24)
+OP_BATCH_UPDATE = 24      # a group's whole weight update behind a batched round, as one operation (batch_round_update)
 BATCH_SLOTS = 16          # queries of a batched round (include/vq_amd_rounds.h)
 BATCH_TOPK_CAP = 4096     # the largest k of one batch_round_topk call (include/vq_amd_round_topk.h)
 
@@ -76,8 +80,8 @@ class ShardError(RuntimeError):
 class ShardedFeatureDB:
     """``local``: this rank's rows ``[row0, row0 + local.n)`` as a :class:`FeatureDB` (or an object with its local
     surface).  ``clip_ids``: the GLOBAL id list (every rank holds it: N x 8 bytes).  ``served``: rank ``root`` drives,
-    the others must be inside :meth:`serve`.  ``batch_rounds``: offer the four calls of a batched round (the same value on every
-    rank); off, :meth:`batch_round_supported` says no and ``ticket.compute_similarities_batch`` runs every ticket's own round."""
+    the others must be inside :meth:`serve`.  ``batch_rounds``: offer the calls of a batched round -- the pass, fit, re-weighting and
+    ranking, and the whole weight update as one operation -- (the same value on every rank); off, :meth:`batch_round_supported` says no and ``ticket.compute_similarities_batch`` runs every ticket's own round."""
 
     def __init__(self, local, n_total: int, row0: int, clip_ids: Sequence[int], group=None, root: int = 0, served: bool = False, stream=None,
                  batch_rounds: bool = False):
@@ -841,6 +845,118 @@ class ShardedFeatureDB:
         return out
 
     @_atomic
+    def batch_round_update(self, queries, rows, labels, w_grids, th_grids, ballasts, seconds, eps, reaches, user_rows, want_scores: bool = True,
+                           want_surface: bool = False) -> list:
+        """:meth:`FeatureDB.batch_round_update` for queries of the last sharded batched round as ONE operation, ``rows`` and
+        ``user_rows`` as GLOBAL row numbers.  A cell of a loss surface is a function of the labelled rows' averaged similarities and
+        the grid, ``lowest`` one of the user rows' and the picked weights -- so the exchange happens once, in front of everything:
+        one announcement, every rank's ``batch_round_avg_rows`` for the labelled and the user rows it holds (S doubles a row), ONE
+        all-reduce that combines the disjoint pieces of all entries as bit patterns, then on every rank the SAME
+        ``batch_round_update_given`` on identical tables: surface in label order, pick and refinement, the rescore and the partition
+        of its own rows.  The pick is replicated by construction; what is gathered are the per-row results: with ``want_scores`` ONE
+        gather of [n, k] scores, and the two small gathers of the partitions.  One :class:`UpdateResult` per entry with the bits of
+        the call on one GPU; an entry without labels is skipped as there.  SPMD: every rank passes the same arguments."""
+        self._batch_round_ready("batch_round_update")
+        queries = self._round_queries("batch_round_update", queries)
+        k = len(queries)
+        eps = [float(eps)] * k if np.ndim(eps) == 0 else [float(e) for e in eps]
+        if not len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == len(seconds) == len(eps) == len(reaches) == len(user_rows) == k:
+            raise ValueError("one rows / labels / w_grid / th_grid / ballast / second / reach / user_rows per query")
+        wg = [np.ascontiguousarray(g, dtype=np.float64) for g in w_grids]
+        th = [np.asarray(v, dtype=np.float64).reshape(-1) for v in th_grids]
+        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
+        us = [np.zeros(0, dtype=np.int64) if u is None else np.asarray(u, dtype=np.int64).reshape(-1) for u in user_rows]
+        seconds = [int(s) for s in seconds]
+        G, T = (int(wg[0].shape[0]) if wg[0].ndim == 2 else -1), int(th[0].size)
+        if any(g.ndim != 2 or g.shape != (G, self.S) for g in wg) or any(v.size != T for v in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
+            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
+        if not (1 <= G <= 64 and 1 <= T <= 64):
+            raise ValueError("the grids of a batched update hold 1 to 64 weights and thresholds (got %d, %d)" % (G, T))
+        if any(r.size and (r.min() < 0 or r.max() >= self.n) for r in rs + us):
+            raise ValueError("row outside [0,%d)" % self.n)
+        if any(not 0 <= s < self.S for s in seconds):
+            raise ValueError("second: a column of w_grids, in [0,%d)" % self.S)
+        if not sum(r.size for r in rs):                                 # every entry skipped: nothing to announce
+            return [self._skipped_update(q) for q in queries]
+        near = [0.0 if v is None else float(v) for v in reaches]
+        self._announce(OP_BATCH_UPDATE,
+                       ints=np.concatenate([[k, G, T, (1 if want_scores else 0) | (2 if want_surface else 0)], queries, [r.size for r in rs],
+                                            [u.size for u in us], seconds, [1 if v is None else 0 for v in reaches]] + rs + us),
+                       floats=np.concatenate([g.reshape(-1) for g in wg] + th + ys + [np.asarray(ballasts, dtype=np.float64), np.asarray(eps), np.asarray(near)]))
+        return self._batch_update(queries, rs, ys, wg, th, [float(b) for b in ballasts], seconds, eps, reaches, us, want_scores, want_surface)
+
+    def _skipped_update(self, q):
+        """The result of an entry without labels: what the round left, nothing picked (as FeatureDB.batch_round_update gives it)."""
+        from .feature_db import UpdateResult
+        r = UpdateResult()
+        r.avg, r.n_e = self._bround_sims[q]
+        r.scores = r.match_rows = r.near_rows = r.surface = None
+        r.near_argmax = -1
+        r.w = r.threshold = r.lowest = r.band = r.iw = r.it = r.on_rim = r.fell_back = None
+        return r
+
+    def _batch_update(self, queries, rs, ys, wg, th, ballasts, seconds, eps, reaches, us, want_scores, want_surface):
+        """Behind the announcement of :meth:`batch_round_update`, on every rank: the tables, the local update, the gathers."""
+        torch = self._torch
+        S, k = self.S, len(queries)
+        lists = rs + us                                                 # the labelled rows of every entry, then every entry's user rows
+        first = np.concatenate([[0], np.cumsum([r.size for r in lists])]) * S
+
+        def tables():
+            buf = np.zeros(int(first[-1]), dtype=np.float64)
+            mine = [self._mine_pos(r) for r in lists]
+            have = [i for i in range(k) if mine[i][0].size + mine[k + i][0].size]
+            if have:                                                    # one call: an entry's labelled and user rows in one list
+                got = self.local.batch_round_avg_rows([queries[i] for i in have], [np.concatenate([mine[i][1], mine[k + i][1]]) for i in have])
+                for i, g in zip(have, got):
+                    cut = mine[i][0].size
+                    buf[first[i]:first[i + 1]].reshape(-1, S)[mine[i][0]] = g[:cut]
+                    buf[first[k + i]:first[k + i + 1]].reshape(-1, S)[mine[k + i][0]] = g[cut:]
+            return buf.view(np.int64)
+        # reduced as integers: a bit pattern plus zeros is exact for every value, where x + 0.0 turns -0.0 into +0.0 and may quiet a NaN
+        full = self._sum(self._local_step(tables)).view(np.float64)
+        given = [full[first[j]:first[j + 1]].reshape(-1, S) for j in range(2 * k)]
+        served = [i for i in range(k) if rs[i].size]
+
+        def part():
+            got = self.local.batch_round_update_given(queries, ys, given[:k], wg, th, ballasts, seconds, eps, reaches, given[k:],
+                                                      want_scores=want_scores, want_surface=want_surface)
+            packed = np.ascontiguousarray(np.stack([np.asarray(got[i].scores) for i in served], axis=1)) if want_scores else None
+            best = None
+            if not want_scores:                                         # the scores stayed on the device: one grid call, G = 1, one row per entry
+                best = [0.0] * len(served)
+                need = [j for j, i in enumerate(served) if int(got[i].near_argmax) >= 0]
+                if need:
+                    weights = []
+                    for j in need:
+                        i = served[j]
+                        w = np.array(wg[i][got[i].iw])
+                        w[seconds[i]] = got[i].w
+                        weights.append(w[None, :])
+                    graded = self.local.batch_round_grid([queries[served[j]] for j in need], [[int(got[served[j]].near_argmax)] for j in need], weights)
+                    for j, g in zip(need, graded):
+                        best[j] = float(g[0, 0])
+            sel = self._local_selections([got[i] for i in served], [got[i].scores for i in served] if want_scores else None, best)
+            return got, packed, sel
+        got, packed, sel = self._local_step(part)
+        full = None if packed is None else self._host(self._coll(lambda: self._all_rows(torch.from_numpy(packed).to(self._cdev))))
+        merged = dict(zip(served, self._merge_selections(sel)))
+        out = []
+        for i, q in enumerate(queries):
+            if i not in merged:
+                out.append(self._skipped_update(q))
+                continue
+            r = self._skipped_update(q)
+            a = got[i]                                                  # the pick: the same on every rank
+            r.w, r.threshold, r.lowest, r.band, r.iw, r.it, r.on_rim, r.fell_back = a.w, a.threshold, a.lowest, a.band, a.iw, a.it, a.on_rim, a.fell_back
+            r.surface = a.surface if want_surface else None
+            r.scores = np.ascontiguousarray(full[:, served.index(i)]) if want_scores else None
+            r.match_rows, r.near_rows, r.near_argmax = merged[i]
+            out.append(r)
+        return out
+
+    @_atomic
     def batch_round_topk(self, ks, queries=None) -> list:
         """:meth:`FeatureDB.batch_round_topk` on every rank as ONE operation: every rank ranks ``min(k, its rows)`` clips of each query
         on its device, ONE gather brings the lists together, and ``shard.merge_topk`` orders each query's by descending score, ties
@@ -1054,6 +1170,17 @@ class ShardedFeatureDB:
         elif op == OP_BATCH_TOPK:
             nq = int(ints[0])
             self.batch_round_topk([int(v) for v in ints[1 + nq:1 + 2 * nq]], [int(v) for v in ints[1:1 + nq]])
+        elif op == OP_BATCH_UPDATE:
+            k, g, t, flags = (int(v) for v in ints[:4])
+            queries, n_l, n_u, seconds, modes = ([int(v) for v in ints[4 + j * k:4 + (j + 1) * k]] for j in range(5))
+            cuts = np.cumsum([0] + n_l + n_u) + 4 + 5 * k
+            lists = [ints[cuts[j]:cuts[j + 1]] for j in range(2 * k)]
+            fcuts = np.cumsum([0, k * g * S, k * t] + n_l + [k, k, k])
+            ys = [floats[fcuts[2 + i]:fcuts[3 + i]] for i in range(k)]
+            ballasts, eps, near = (floats[fcuts[2 + k + j]:fcuts[3 + k + j]] for j in range(3))
+            self.batch_round_update(queries, lists[:k], ys, list(floats[:fcuts[1]].reshape(k, g, S)), list(floats[fcuts[1]:fcuts[2]].reshape(k, t)),
+                                    ballasts, seconds, eps, [None if m else float(v) for m, v in zip(modes, near)], lists[k:],
+                                    want_scores=bool(flags & 1), want_surface=bool(flags & 2))
         else:
             raise RuntimeError("unknown operation %d announced" % op)
 

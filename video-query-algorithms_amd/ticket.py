@@ -403,8 +403,8 @@ def _fit_group(db, group):
     threshold.  Such a ticket ends with ``_fit`` = (weights, threshold) for this round and ``_ahead`` = the rescore's scores and
     partition.  A member without labelled clips, with a label on an unknown clip (optimize_weights raises that in its own place) or
     with grids of another size than the first one's stays as the pass left it; so does every member on a database without the two
-    methods.  Members marked ``_OnDevice`` (``fit_on_device``) on a database with ``batch_round_update`` take ``_update_group``
-    instead: one call for all of it.  Call behind the group's own pass with the database's lock still held: the next pass on the
+    methods.  Members marked ``_OnDevice`` (``fit_on_device``) on a database with ``batch_round_update`` -- a ``FeatureDB``, or a
+    ``ShardedFeatureDB`` with batched rounds -- take ``_update_group`` instead: one call for all of it.  Call behind the group's own pass with the database's lock still held: the next pass on the
     handle replaces what this reads."""
     on_device = hasattr(db, "batch_round_update") and any(isinstance(fit, _OnDevice) for _tk, _hp, _prep, fit in group)
     if not on_device and not (hasattr(db, "batch_round_fit") and hasattr(db, "batch_round_rescore")):
@@ -461,7 +461,8 @@ def _update_group(db, members):
     difference of the mode), the rescore, the band and the partition without a host step in between.  A revise member's band reaches
     ``near_miss_default`` below its threshold; a finalize member's reaches the lowest score among the user's confirmed matches
     (``lowest_scoring_user_match``'s rows, ``compute_matches._review_budget``'s expressions), so its ``select_clips_to_review`` finds the
-    partition in ``_ahead`` as a revise member's does."""
+    partition in ``_ahead`` as a revise member's does.  On a ``ShardedFeatureDB`` the rows and user rows are positions in the whole
+    database's view, which are its global row numbers: what ``ShardedFeatureDB.batch_round_update`` takes."""
     reaches = [None if m[8] else float(m[2].near_miss_default) for m in members]
     # a finalize member without user matches reaches nowhere (lowest 1.0); lowest_scoring_user_match raises later where it always did
     user_rows = [_user_match_rows(m[1]) if m[8] and m[1].user_matches else [] for m in members]
@@ -630,8 +631,9 @@ def compute_similarities_batch(tickets, hyperparameters, share_search_sets=False
     finalize member's review band, which reaches down to ``lowest_scoring_user_match`` under the fitted scores, is computed and
     partitioned there too, so its ``select_clips_to_review`` asks the device for nothing either.  One difference: weights and
     threshold are ``Hyperparameter._pick_exact``'s, not ``_pick_from``'s (squares as products instead of libm's ``pow``: a few ulp
-    in some refined picks, tests/test_pick_exact.py).  A database without the method (a ``ShardedFeatureDB``) does what it does
-    without the switch.
+    in some refined picks, tests/test_pick_exact.py).  On a ``ShardedFeatureDB`` opened with ``batch_rounds=True`` the switch means the
+    same: its ``batch_round_update`` is one operation of the sharded database (the rows a ticket names on the whole database are
+    GLOBAL row numbers) with the bits of the call on one GPU.  A database without the method does what it does without the switch.
 
     ``top``: an int, or one per ticket.  Every member of a pass also gets the ``top`` best clips of its search set, ranked on the
     device in the same hold of the lock, BEHIND the fit -- a fitted member is ranked under its fitted weights: one
