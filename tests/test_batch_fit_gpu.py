@@ -134,7 +134,7 @@ def raw_fit(vqa, db, Q, G, T, entries, short=0):
     off = (C.c_int64 * 8)()
     vqa._lib.call("vq_db_batch_fit_layout", db._h, Q, G, T, total, off)
     off = [int(v) for v in off]
-    blk = db._pooled_block("_fit_pools", off[7])
+    blk = db.blocks.take("fit", off[7])
     raw = blk.bytes()
     raw[:off[7]] = 0xA5
     raw[off[3]:off[3] + 8 * Q].view(np.int64)[:] = 0
@@ -261,7 +261,7 @@ def test_rescore_leaves_the_block_of_unmasked_queries_alone_and_ties_go_to_the_f
     and 1500 hold the clip query 3 is made from: both have the largest near score and near_argmax is row 1203, the first."""
     db, ref, t = pair(vqa, SMALL)
     results = run_round(db, t, False)
-    Q, off, start, _pool, _sims = db._bround_last
+    Q, off = db._bround_last.Q, db._bround_last.off
     hand_over(ref, results[3], 3, False)
     ref.rescore(W1[3])
     sc = ref.scores()
@@ -270,7 +270,7 @@ def test_rescore_leaves_the_block_of_unmasked_queries_alone_and_ties_go_to_the_f
     band = (th, float(np.sort(sc)[-31]))                                                      # the 31 best clips are near, none matches
     m, k, am = ref.select(*band)
     assert am == 1203 and 1500 in k and len(m) == 0 and 31 <= len(k) < 40
-    blk = db._pooled_block("_fit_pools", off[9])
+    blk = db.blocks.take("fit", off[9])
     raw = blk.bytes()
     raw[:off[9]] = 0xA5
     wv = raw[off[1]:off[1] + Q * 64].view(np.float64).reshape(Q, 8)
@@ -311,8 +311,8 @@ def test_refusals_are_argument_checks_and_leave_the_round_usable(vqa):
     refused(-1, db.batch_round_fit, [1], [rows], [y], [np.ones((65, 2))], [ths], [BALLAST])  # G = 65
     refused(-1, db.batch_round_fit, [1], [rows], [y], [cand], [np.linspace(0.5, 1.0, 65)], [BALLAST])   # T = 65
     refused(-1, raw_fit, vqa, db, 5, 40, 31, {1: (rows, y, cand, ths, BALLAST)}, short=64)   # a short block
-    Q, off, _start, _pool, _sims = db._bround_last
-    blk = db._pooled_block("_fit_pools", off[9])
+    off = db._bround_last.off
+    blk = db.blocks.take("fit", off[9])
     lib = vqa.load_library()
     assert lib.vq_db_batch_round_rescore(db._h, 2, C.c_void_p(blk.ptr), off[9] - 64, 6) == -1           # a short block
     assert lib.vq_db_batch_round_rescore(db._h, 2, C.c_void_p(blk.ptr), off[9], 8) == -1                # an unknown flag

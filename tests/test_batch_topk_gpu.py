@@ -333,7 +333,7 @@ def raw_call(vqa, db, q, k_max, ks, sentinel=0xA5, short_by=0):
     off = (C.c_int64 * 6)()
     vqa._lib.call("vq_db_batch_topk_layout", db._h, q, k_max, off)
     off = [int(v) for v in off]
-    blk = db._pooled_block("_topk_pools", off[4])
+    blk = db.blocks.take("topk", off[4])
     raw = blk.bytes()
     raw[...] = sentinel
     raw[off[0]:off[0] + 8 * q].view(np.int64)[...] = ks
@@ -392,7 +392,7 @@ def test_errors_leave_the_snapshot_usable(vqa):
     with pytest.raises(vqa.VqError) as ei:                               # above the cap: the library's refusal, from the layout call on
         raw_call(vqa, db, 3, cap + 1, [3, 3, 3])
     assert ei.value.code == VQ_E_INVALID
-    block = db._pooled_block("_topk_pools", 64)
+    block = db.blocks.take("topk", 64)
     assert vqa.load_library().vq_db_batch_round_topk(db._h, 3, cap + 1, C.c_void_p(block.ptr), block.nbytes) == VQ_E_INVALID
     check(db, scores, [5, 6, 7])
     with pytest.raises(ValueError):

@@ -223,7 +223,7 @@ def test_refusals_are_argument_checks_and_leave_the_round_usable(vqa, monkeypatc
     refused(-1, db.batch_round_avg_rows, [1], [np.array([20, N])])            # a row = M_q
     refused(-1, db.batch_round_avg_rows, [1], [np.array([-1, 20])])
     refused(-1, given, second=2)                                              # S = 2
-    fdb = sys.modules[vqa.FeatureDB.__module__]
+    fdb = sys.modules[vqa.FeatureDB.batch_round_update.__module__]
     real = fdb.call
 
     def one_more(name, *a):                                                   # sum L != n_labels | n_rows: the counts of the call and of the block differ

@@ -116,8 +116,9 @@ def device_scores(vqa, db, Q, n):
 
 def poison_round_block(db, Q, views):
     """The next block a call on the last round takes from its pool holds 0xA5 in every byte."""
-    _Q, off, _start, pool, _sims = db._bround_last
-    blk = db._pooled_block("_view_round_pools", off[9]) if views else db._batch_round_block(Q)[0]
+    last = db._bround_last
+    assert last.Q == Q and last.views == views
+    blk = last.block(db.blocks)                                # the route of the call itself
     blk.bytes()[:] = 0xA5
     del blk                                                    # back into its pool, on top
 
@@ -155,7 +156,7 @@ def test_update_equals_fit_pick_rescore_band_and_select(vqa, case):
     got = db.batch_round_update(queries, [x[0] for x in inputs], [x[1] for x in inputs], [cand] * k, [ths] * k, [BALLAST] * k, [1] * k, eps,
                                 [x[2] for x in inputs], [x[3] for x in inputs], want_surface=True)
     raw = got[served[0]].scores.base                           # the block of the round the call wrote into
-    _Q, off, start, _pool, _sims = db._bround_last
+    off, start = db._bround_last.off, db._bround_last.start
     assert raw.dtype == np.uint8 and raw.shape[0] >= off[9]
     weights, bands = [], []
     for i in served:
@@ -288,7 +289,7 @@ def test_refusals_are_argument_checks_and_leave_the_round_usable(vqa, monkeypatc
     refused(-1, cand=np.ones((65, 2)))                                                         # G = 65
     refused(-1, ths=np.linspace(0.5, 1.0, 65))                                                 # T = 65
     import sys
-    fdb = sys.modules[vqa.FeatureDB.__module__]
+    fdb = sys.modules[vqa.FeatureDB.batch_round_update.__module__]
     real = fdb.call
 
     def short_round_block(name, *a):
@@ -356,7 +357,7 @@ def test_compute_matches_with_the_update_on_the_device(vqa):
 
 def test_close_frees_the_update_blocks(vqa):
     """The page-locked blocks of batch_round_update go with the database: close() empties their pool and marks it closed, so a block
-    still held by a result is freed, not pooled, when its last view goes."""
+    still held by a result is freed, not pooled, when its last view goes (the free function of the registry is counted)."""
     db, ref, t = pair(vqa, 200, 1, np.float32, [None])
     ref.close()
     run_round(db, t, 3, [None] * 3)
@@ -365,9 +366,15 @@ def test_close_frees_the_update_blocks(vqa):
     args = ([1], [np.array([20, 31, 199])], [np.array([1.0, 0.0, 1.0])], [cand], [ths], [BALLAST], [1], pc.compute_eps(), [NEAR], [[]])
     held = db.batch_round_update(*args, want_surface=True)[0]                                   # its block is held by the surface
     db.batch_round_update(*args)                                                               # this one's is idle in the pool by now
-    pools = list(db._update_pools.values())
-    assert pools and sum(len(p["free"]) for p in pools) >= 1 and not any(p["closed"] for p in pools)
+    blocks, freed = db.blocks, []
+    real_free = blocks._free
+    blocks._free = lambda ptr: (freed.append(ptr), real_free(ptr))
+    idle = [ptr for ptr, _size in blocks.idle("update")]
+    assert len(idle) >= 1 and not blocks.closed
     db.close()
-    assert all(p["closed"] and not p["free"] for p in pools)
+    assert blocks.closed and not blocks.idle("update") and set(idle) <= set(freed)
+    ptr = held.surface.base.base.ptr                                                           # the update block the surface is a view of
+    assert ptr not in freed and ptr not in idle
     del held
-    assert all(not p["free"] for p in pools)
+    assert freed.count(ptr) == 1                                                               # freed when released ...
+    assert not blocks.idle("update")                                                           # ... and not pooled

@@ -147,11 +147,3 @@ def test_calls_on_a_null_handle_or_with_bad_arguments_fail_cleanly():
     # behind the shape checks a handle without a batched round is VQ_E_STATE for both calls
     assert lib.vq_db_batch_round_avg_rows(buf, 4, 20, small, rows[3]) == -4
     assert lib.vq_db_batch_round_update_given(buf, 4, 40, 31, 20, 3, big, need, buf, 64, 6) == -4
-
-
-def test_close_knows_the_pools_the_new_calls_take_their_blocks_from():
-    import inspect
-    import video_query_algorithms_amd as vqa
-    named = set(re.findall(r'_pooled_block\("(_\w+)"', inspect.getsource(vqa.FeatureDB.batch_round_avg_rows) + inspect.getsource(vqa.FeatureDB._batch_update)))
-    closed = set(re.findall(r'getattr\(self, "(_\w+)"', inspect.getsource(vqa.FeatureDB.close)))
-    assert named and named <= closed, named - closed

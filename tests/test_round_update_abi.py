@@ -96,15 +96,3 @@ def test_calls_on_a_null_handle_or_with_bad_arguments_fail_cleanly():
         assert lib.vq_db_batch_round_update(buf, 4, 40, 31, 20, 3, big, need, buf, 64, flags) == -1, flags
     assert lib.vq_db_batch_round_update(buf, 4, 40, 31, 20, 3, big, need - 64, buf, 64, 6) == -1              # a short update block
     assert "vq_db_batch_update_layout" in (lib.vq_last_error() or b"").decode()
-
-
-def test_close_knows_every_pool_of_page_locked_blocks():
-    """Every pool FeatureDB takes a page-locked block from by name is one close() empties: a pool it does not list leaks its idle
-    blocks on every open / close cycle."""
-    import inspect
-    import video_query_algorithms_amd as vqa
-    source = inspect.getsource(vqa.FeatureDB)
-    named = set(re.findall(r'_pooled_block\("(_\w+)"', source))
-    assert {"_update_pools", "_fit_pools", "_topk_pools", "_grid_pools", "_view_round_pools"} <= named
-    closed = set(re.findall(r'getattr\(self, "(_\w+)"', inspect.getsource(vqa.FeatureDB.close)))
-    assert named <= closed, named - closed

@@ -46,7 +46,8 @@ class _Target:
 
 
 def bench(vqa, n, e, repeats, warmup=2):
-    from video_query_algorithms_amd import feature_db as fdb
+    # the modules whose library calls are counted: the handle's own and the one that makes the batched-round calls
+    mods = {sys.modules[m] for m in (vqa.FeatureDB.__module__, vqa.FeatureDB.batch_round_update.__module__)}
     from video_query_algorithms_amd.compute_matches import _review_budget
     from video_query_algorithms_amd.ticket import compute_similarities_batch
     s, d = 2, 1024
@@ -72,7 +73,7 @@ def bench(vqa, n, e, repeats, warmup=2):
         hps.append(vqa.Hyperparameter(default, th, 0.3, bands[-1][1], 0.0, STREAMS, "global_pool", 1, 0.7, "bagging", 3))
     del probe
     calls = []
-    real_call = fdb.call
+    real_call = vqa._lib.call
 
     def counting(name, *a):
         calls.append(name)
@@ -101,7 +102,8 @@ def bench(vqa, n, e, repeats, warmup=2):
     for _ in range(warmup):
         form(**two), form(**one), form()
     a, b, c, same, within = [], [], [], True, 0.0
-    fdb.call = counting
+    for m in mods:
+        m.call = counting
     try:
         for _ in range(repeats):
             del calls[:]
@@ -117,7 +119,8 @@ def bench(vqa, n, e, repeats, warmup=2):
             lists = [len(tk._ahead["match_rows"]) + len(tk._ahead["near_rows"]) for tk in tickets]
             c.append(form())
     finally:
-        fdb.call = real_call
+        for m in mods:
+            m.call = real_call
     db.close()
     pass_calls = ["vq_db_query_round_batch"]
     behind = lambda names: [x for x in names if x not in pass_calls and x != "vq_host_alloc"]        # noqa: E731

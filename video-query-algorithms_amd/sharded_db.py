@@ -51,6 +51,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from .batch_rounds import entry_arrays
 from .shard import all_gather_counts, all_gather_rows, merge_topk, shard_range
 
 OP_CLOSE, OP_RESTRICT, OP_SET_QUERY, OP_QUERY_FROM_ROW, OP_SCAN, OP_RESCORE, OP_SIMS, OP_SCORES, OP_GRID, OP_SELECT, OP_TOPK, \
@@ -787,16 +788,8 @@ class ShardedFeatureDB:
         from .hyperparameter import raw_loss_surface
         self._batch_round_ready("batch_round_fit")
         queries = self._round_queries("batch_round_fit", queries)
+        queries, rs, ys, wg, th, G, T = entry_arrays(self.S, queries, rows, labels, w_grids, th_grids, (ballasts,))
         k = len(queries)
-        if not len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == k:
-            raise ValueError("one rows / labels / w_grid / th_grid / ballast per query")
-        wg = [np.ascontiguousarray(g, dtype=np.float64) for g in w_grids]
-        th = [np.asarray(v, dtype=np.float64).reshape(-1) for v in th_grids]
-        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
-        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
-        G, T = (int(wg[0].shape[0]) if wg[0].ndim == 2 else -1), int(th[0].size)
-        if any(g.ndim != 2 or g.shape != (G, self.S) for g in wg) or any(v.size != T for v in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
-            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
         if not (1 <= G <= 64 and 1 <= T <= 64):
             raise ValueError("the grids of a batched fit hold 1 to 64 weights and thresholds (got %d, %d)" % (G, T))
         if any(r.size and (r.min() < 0 or r.max() >= self.n) for r in rs):
@@ -860,17 +853,9 @@ class ShardedFeatureDB:
         queries = self._round_queries("batch_round_update", queries)
         k = len(queries)
         eps = [float(eps)] * k if np.ndim(eps) == 0 else [float(e) for e in eps]
-        if not len(rows) == len(labels) == len(w_grids) == len(th_grids) == len(ballasts) == len(seconds) == len(eps) == len(reaches) == len(user_rows) == k:
-            raise ValueError("one rows / labels / w_grid / th_grid / ballast / second / reach / user_rows per query")
-        wg = [np.ascontiguousarray(g, dtype=np.float64) for g in w_grids]
-        th = [np.asarray(v, dtype=np.float64).reshape(-1) for v in th_grids]
-        rs = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
-        ys = [np.asarray(y, dtype=np.float64).reshape(-1) for y in labels]
+        queries, rs, ys, wg, th, G, T = entry_arrays(self.S, queries, rows, labels, w_grids, th_grids, (ballasts, seconds, eps, reaches, user_rows))
         us = [np.zeros(0, dtype=np.int64) if u is None else np.asarray(u, dtype=np.int64).reshape(-1) for u in user_rows]
         seconds = [int(s) for s in seconds]
-        G, T = (int(wg[0].shape[0]) if wg[0].ndim == 2 else -1), int(th[0].size)
-        if any(g.ndim != 2 or g.shape != (G, self.S) for g in wg) or any(v.size != T for v in th) or any(r.shape != y.shape for r, y in zip(rs, ys)):
-            raise ValueError("w_grids must be [G,%d] and th_grids [T] with one G and T for the call, and one label per row" % self.S)
         if not (1 <= G <= 64 and 1 <= T <= 64):
             raise ValueError("the grids of a batched update hold 1 to 64 weights and thresholds (got %d, %d)" % (G, T))
         if any(r.size and (r.min() < 0 or r.max() >= self.n) for r in rs + us):
