@@ -125,3 +125,82 @@ def bench_view(n=1_000_000, s=2, e=5, d=1024, frac=10, run=100, reps=40, dtype=n
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "view":
     bench_view(s=2, e=5)
     bench_view(s=2, e=3)
+
+
+def _timed(fn, tm):
+    call("vq_timer_start", tm, None)
+    fn()
+    call("vq_timer_stop", tm, None)
+    ms = C.c_float()
+    call("vq_timer_elapsed_ms", tm, C.byref(ms))
+    return ms.value
+
+
+def bench_tiled64(n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None):
+    """A float64 database on its rows against the same database in the tiled64 layout, in ONE process: two handles of the same seed,
+    timed in turn (bench_view's pattern) behind a warm-up, `reps` (>= 10) times each -- the one-query scan, then the 16-query pass.
+    GB/s is the algorithmic bytes (the rows + 8 B of score per clip) over device-event time; the share is of 8 TB/s.  The row-major
+    figures of the same run are the baseline.  ``out``: a JSON file with every sample."""
+    import json
+    import time
+    assert reps >= 10
+    w = [1.0, 1.5][:s]
+    rows = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=np.float64)
+    tiled = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=np.float64)
+    t0 = time.perf_counter()
+    tiled.set_layout(tiled.tiled_layout)              # synchronous: one sweep of the block each way through 256 MB of scratch
+    convert_ms = (time.perf_counter() - t0) * 1e3
+    assert tiled.layout == "tiled64" and rows.layout == "rows"
+    handles = (("rows", rows), ("tiled64", tiled))
+    for _name, db in handles:
+        db.set_query_from_row(7, want=False)
+    tm = C.c_void_p()
+    call("vq_timer_create", C.byref(tm))
+    nbytes = n * s * e * d * 8 + n * 8
+    res = {"n": n, "S": s, "E": e, "D": d, "dtype": "float64", "bytes": nbytes, "reps": reps, "convert_ms": convert_ms, "scan": {}, "batch": {}}
+    print("fp64 N=%d S=%d E=%d (%.1f GB): rows -> tiled64 in %.0f ms (%.2f TB/s of the block, read + written once each)"
+          % (n, s, e, nbytes / 1e9, convert_ms, 2 * nbytes / convert_ms / 1e9), flush=True)
+    for _name, db in handles:
+        for _ in range(3):
+            db.scan(weights=w)
+    times = {name: [] for name, _db in handles}
+    for _ in range(reps):
+        for name, db in handles:
+            times[name].append(_timed(lambda: db.scan(weights=w), tm))
+    for name, _db in handles:
+        med, best = sorted(times[name])[reps // 2], min(times[name])
+        res["scan"][name] = {"ms": times[name], "median_ms": med, "best_ms": best, "median_gbs": nbytes / med / 1e6, "best_gbs": nbytes / best / 1e6,
+                             "median_share_of_8tbs": nbytes / med / 1e6 / 8000}
+        print("  one-query scan %-7s: %.3f ms median (%.3f best) -> %.0f GB/s median, %.0f best (%.3f of 8 TB/s)"
+              % (name, med, best, nbytes / med / 1e6, nbytes / best / 1e6, nbytes / med / 1e6 / 8000), flush=True)
+    rng = np.random.default_rng(0)
+    t = rng.standard_normal((q, s, e, d)) / d
+    wq = 0.5 + rng.random((q, s))
+    first = {}
+    for name, db in handles:
+        first[name] = db.scan_batch(t, wq)              # warm-up, drained by the copy back
+        db.scan_batch(t, wq, want=False)
+        db.scan_batch(t[:1], wq[:1])
+    assert (first["rows"] == first["tiled64"]).all()    # the same bits: what is timed is the same computation
+    times = {name: [] for name, _db in handles}
+    for _ in range(reps):
+        for name, db in handles:
+            times[name].append(_timed(lambda: db.scan_batch(t, wq, want=False), tm))
+    dbb = n * s * e * d * 8
+    for name, _db in handles:
+        med, best = sorted(times[name])[reps // 2], min(times[name])
+        res["batch"][name] = {"ms": times[name], "median_ms": med, "best_ms": best, "queries_per_s": q / med * 1e3, "median_share_of_8tbs": dbb / med / 1e6 / 8000}
+        print("  16-query pass  %-7s: %.3f ms median (%.3f best) -> %.0f queries/s, DB bytes %.2f TB/s (%.3f of 8 TB/s)"
+              % (name, med, best, q / med * 1e3, dbb / med / 1e9, dbb / med / 1e9 / 8), flush=True)
+    rows.close()
+    tiled.close()
+    if out:
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "tiled64":
+    # tools/quick_sim_bench.py tiled64 [n s e [out.json]]: one shape per process (each under a time limit of its own)
+    a = sys.argv[2:]
+    bench_tiled64(*(int(v) for v in a[:3]), out=a[3] if len(a) > 3 else None)

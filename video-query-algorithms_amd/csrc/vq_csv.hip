@@ -40,13 +40,8 @@ struct CsvArgs {
     unsigned fail_cap;
     int64_t line0;             // first line of this launch
     int lds_text;              // bytes of LDS for the staged line (multiple of 16); the offset table follows
-    int dtype, tiled, NV, slot, D;
+    int dtype, unit, NV, slot, D;     // unit: elements per 16-byte unit of a tiled block, 0 = row-major (feat_index, csrc/vq_tile_index.h)
 };
-
-// element (row, slot v, k) of the block: the address rule of vq_sim.hip (row-major [N][S*E][D]; tiled [tile of 16][S*E][D/4][clip][4])
-__host__ __device__ inline int64_t elem_index(bool tiled, int64_t row, int NV, int v, int D, int k) {
-    return tiled ? (((row >> 4) * NV + v) * (int64_t)(D / 4) + (k >> 2)) * 64 + (row & 15) * 4 + (k & 3) : (row * NV + v) * (int64_t)D + k;
-}
 
 // the double's bits as the database stores them; false: a finite value that binary16 cannot hold (nothing stored)
 __host__ __device__ inline bool storage_bits(int dtype, uint64_t bits, uint64_t* out) {
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void csv_rows_kernel(CsvArgs a) {
         bool ok = vq_dec_parse(t + b, t + en, &bits) == VQ_DEC_OK;
         if (ok) ok = storage_bits(a.dtype, bits, &out);
         if (ok) {
-            store_elem(a.feats, a.dtype, elem_index(a.tiled != 0, row, a.NV, a.slot, D, j), out);
+            store_elem(a.feats, a.dtype, feat_index(a.unit, row, a.NV, a.slot, D, j), out);
         } else {
             const unsigned k = atomicAdd(&a.counters[0], 1u);
             if (k < a.fail_cap) a.fail_list[k] = make_int2((int)line, j);
@@ -212,7 +207,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
     std::vector<int64_t> pidx;
     std::vector<uint64_t> pval;
     int64_t resolved = 0;
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;
+    const int unit = db->unit();
     const int NV = db->S * db->E, slot = stream * db->E + split;
 
     for (size_t c = 0; c + 1 < cuts.size(); ++c) {
@@ -232,7 +227,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
         a.fail_cap = fail_cap;
         a.lds_text = lds_text;
         a.dtype = db->dtype;
-        a.tiled = tiled ? 1 : 0;
+        a.unit = unit;
         a.NV = NV;
         a.slot = slot;
         a.D = D;
@@ -272,7 +267,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
                     if (!storage_bits(db->dtype, bits, &out))
                         return fail(VQ_E_INVALID, "line %lld field %d: %.*s does not fit float16 (largest finite value 65504)", (long long)(li + 2), field,
                                     (int)std::min<int64_t>(40, fe - fb), fb);
-                    pidx[k] = elem_index(tiled, rows_host[li], NV, slot, D, list[k].y);
+                    pidx[k] = feat_index(unit, rows_host[li], NV, slot, D, list[k].y);
                     pval[k] = out;
                 }
                 VQ_HIP(d_pidx.grow((size_t)fail_cap * 8));

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "vq_common.h"
+#include "vq_tile_index.h"
 
 constexpr int kBatchSlots = 16;            // queries of a batched scan or round
 constexpr int64_t kRoundPrefix = 1024;     // rows of each list that a round copies back next to the counts
@@ -62,8 +63,12 @@ struct vq_db {
     void* feats = nullptr;
     bool owns_feats = true;
     // VQ_LAYOUT_ROWS: [N][S][E][D].  VQ_LAYOUT_TILED (fp32, own memory): [tile of 16 clips][S*E][D/4][clip][4] in the SAME block (a
-    // tile's 16 rows and its tiled form cover the same bytes; the block is allocated for whole tiles) -- vq_db_set_layout
+    // tile's 16 rows and its tiled form cover the same bytes; the block is allocated for whole tiles) -- vq_db_set_layout.
+    // VQ_LAYOUT_TILED64 (fp64): the same with the 16-byte unit of doubles, [tile][S*E][D/2][clip][2] (csrc/vq_tile_index.h)
     int layout = VQ_LAYOUT_ROWS;
+    bool tiled() const { return layout != VQ_LAYOUT_ROWS; }
+    int unit() const { return tiled() ? vq::tile_unit_of((int)elem()) : 0; }      // elements per 16-byte unit of the layout; 0: rows
+    int tiled_layout() const { return dtype == VQ_F32 ? VQ_LAYOUT_TILED : dtype == VQ_F64 ? VQ_LAYOUT_TILED64 : VQ_LAYOUT_ROWS; }   // the tiled layout of the storage type (rows: none)
     bool feats_exposed = false;      // adopted memory, or the raw pointer was handed out: the library no longer controls the layout
     uint8_t* present = nullptr;
     double* t = nullptr;        // [S*E*D]
@@ -127,7 +132,7 @@ struct vq_db {
     struct RowView {
         bool defined = false;
         int64_t m = 0;               // rows in the view
-        int64_t ntiles = 0;          // tiles of 16 clips it touches (fp32 databases of a tiled-capable shape; else no tile tables)
+        int64_t ntiles = 0;          // tiles of 16 clips it touches (fp32 / fp64 databases of a tiled-capable shape; else no tile tables)
         int64_t* rows = nullptr;     // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
         int64_t* tiles = nullptr;
         int64_t* pos = nullptr;

@@ -959,7 +959,7 @@ int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_h
                (long long)off[9], (long long)block_bytes);
     DeviceGuard g(db->device);
     const int64_t n = db->n, sm = start[Q];
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;
+    const bool tiled = db->tiled();
     uint32_t whole = 0, members = 0;                  // queries over the whole database | queries whose row list goes into the plan
     int64_t member_rows = 0, max_m = 0;
     for (int q = 0; q < Q; ++q) {

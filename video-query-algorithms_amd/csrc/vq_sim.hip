@@ -337,12 +337,48 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(std::conditional_t<VI
 // VIEW: the wave walks the TOUCHED tiles of a row view (item it -> tile items[it]: wave-uniform, scalar loads, the index two items on
 // fetched a tile ahead) and a lane stores its clip's results at pos[16 it + col] when that is not -1 (ScanViewArgs; the entry of the
 // wave's next tile is fetched while this one is multiplied); loads and arithmetic are the full scan's.
-template <int S, int E, int CH, int G, bool VIEW = false>
+// fp64 (VQ_LAYOUT_TILED64, [tile][slice][k / 2][clip][2]): the same walk with the unit of doubles (TileVec).  Load i of a lane is at
+// i * 128 + l * 2 doubles -- again 1 KB of contiguous memory per wave instruction -- and holds k = 8 i + 2 (l / 16) + 0..1: 128 loads per
+// slice, each two fp64 FMAs against ONE 16-byte query read (fp32: four conversions, four FMAs, two reads per 16 bytes of features).
+// The loop over the groups stays rolled and its query offset is the loop counter's: unrolled, the query reads (which do not depend on
+// the tile) would be hoisted into registers across tiles -- scan_kernel's LEAN trap.  72-110 VGPRs, no scratch (profiles/README.md).
+template <typename T>
+struct TileVec;                        // the 16 bytes a lane of scan_tiled_kernel loads: U elements, and their share of the dot
+template <>
+struct TileVec<float> {
+    static constexpr int U = 4;
+    float4 v;
+    __device__ __forceinline__ void load(const float* p) { v = stream_load4(p); }
+    __device__ __forceinline__ double dot(const double* tq, double p) const {
+        const double2 ta = *reinterpret_cast<const double2*>(tq);
+        const double2 tb = *reinterpret_cast<const double2*>(tq + 2);
+        p = fma((double)v.x, ta.x, p);
+        p = fma((double)v.y, ta.y, p);
+        p = fma((double)v.z, tb.x, p);
+        p = fma((double)v.w, tb.y, p);
+        return p;
+    }
+};
+template <>
+struct TileVec<double> {
+    static constexpr int U = 2;
+    vq_d2 v;
+    __device__ __forceinline__ void load(const double* p) { v = __builtin_nontemporal_load(reinterpret_cast<const vq_d2*>(p)); }
+    __device__ __forceinline__ double dot(const double* tq, double p) const {
+        const double2 ta = *reinterpret_cast<const double2*>(tq);
+        p = fma(v.x, ta.x, p);
+        p = fma(v.y, ta.y, p);
+        return p;
+    }
+};
+
+template <typename T, int S, int E, int CH, int G, bool VIEW = false>
 __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double t_lds[];    // [NV][D], natural order
     constexpr int NV = S * E;
     constexpr int D = CH * 256;
-    constexpr int LOADS = D / 16;                                     // 1 KB loads of a wave per slice
+    constexpr int U = TileVec<T>::U, WL = 64 * U;                     // elements of a lane's load, of a wave's (1 KB)
+    constexpr int LOADS = D * 16 / WL;                                // 1 KB loads of a wave per slice: D / 16 (fp32), D / 8 (fp64)
     constexpr int GROUPS = LOADS / G;
     static_assert(LOADS % G == 0, "group size must divide the slice");
     for (int i = threadIdx.x; i < NV * D; i += blockDim.x) t_lds[i] = a.t[i];
@@ -354,13 +390,13 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
     int64_t ntiles = (a.n + 15) / 16;
     if constexpr (VIEW) ntiles = a.n_items;                          // work items: the touched tiles
     constexpr int64_t tile_elems = (int64_t)NV * 16 * D;
-    const float* feats = static_cast<const float*>(a.feats) + lane * 4;
+    const T* feats = static_cast<const T*>(a.feats) + lane * U;
     double w[S];
     if (a.w) {
 #pragma unroll
         for (int s = 0; s < S; ++s) w[s] = a.w[s];
     }
-    float4 cur[G], nxt[G];
+    TileVec<T> cur[G], nxt[G];
     int64_t tile = wave;
     int64_t tr = 0, trn = 0, on = -1;                                  // VIEW: the tiles of item `tile` and of the wave's next item; this lane's position
     if constexpr (VIEW) {
@@ -373,7 +409,7 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
     }
     if (tile < ntiles) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) cur[j] = stream_load4(feats + (VIEW ? tr : tile) * tile_elems + j * 256);
+        for (int j = 0; j < G; ++j) cur[j].load(feats + (VIEW ? tr : tile) * tile_elems + j * WL);
     }
     while (tile < ntiles) {
         const int64_t tn = tile + nwaves;
@@ -382,9 +418,9 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
             trnn = a.items[min(tn + nwaves, ntiles - 1)];
             onn = a.pos[min(tn, ntiles - 1) * 16 + col];
         }
-        const float* x = feats + (VIEW ? tr : tile) * tile_elems;
+        const T* x = feats + (VIEW ? tr : tile) * tile_elems;
         // after the wave's last tile the ring is refilled from the tile just read: the refill stays unconditional
-        const float* xn = tn < ntiles ? feats + (VIEW ? trn : tn) * tile_elems : x;
+        const T* xn = tn < ntiles ? feats + (VIEW ? trn : tn) * tile_elems : x;
         const int64_t c = (VIEW ? tr : tile) * 16 + col;
         const int64_t o = VIEW ? on : c;                               // where this lane's clip reports
         const bool mine = kk == 0 && (VIEW ? o >= 0 : c < a.n);
@@ -393,22 +429,15 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
         int cnt = 0;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            const double* tq = t_lds + v * D + 4 * kk;
+            const double* tq = t_lds + v * D + U * kk;
             double p = 0.0;
 #pragma unroll 1
             for (int g = 0; g < GROUPS; ++g) {
-                const float* src = (v + 1 < NV || g + 1 < GROUPS) ? x + ((int64_t)v * GROUPS + g + 1) * (G * 256) : xn;
+                const T* src = (v + 1 < NV || g + 1 < GROUPS) ? x + ((int64_t)v * GROUPS + g + 1) * (G * WL) : xn;
 #pragma unroll
-                for (int j = 0; j < G; ++j) nxt[j] = stream_load4(src + j * 256);
+                for (int j = 0; j < G; ++j) nxt[j].load(src + j * WL);
 #pragma unroll
-                for (int j = 0; j < G; ++j) {
-                    const double2 ta = *reinterpret_cast<const double2*>(tq + 16 * (g * G + j));
-                    const double2 tb = *reinterpret_cast<const double2*>(tq + 16 * (g * G + j) + 2);
-                    p = fma((double)cur[j].x, ta.x, p);
-                    p = fma((double)cur[j].y, ta.y, p);
-                    p = fma((double)cur[j].z, tb.x, p);
-                    p = fma((double)cur[j].w, tb.y, p);
-                }
+                for (int j = 0; j < G; ++j) p = cur[j].dot(tq + 4 * U * (g * G + j), p);
 #pragma unroll
                 for (int j = 0; j < G; ++j) cur[j] = nxt[j];
             }
@@ -464,6 +493,10 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
 #define VQ_TILED_GROUP 4
 #endif
 constexpr int kTiledGroup = VQ_TILED_GROUP;     // 1 KB loads a wave of scan_tiled_kernel keeps in flight behind the ones it multiplies
+#ifndef VQ_TILED_GROUP64
+#define VQ_TILED_GROUP64 4
+#endif
+constexpr int kTiledGroup64 = VQ_TILED_GROUP64; // the same for fp64 (VQ_LAYOUT_TILED64)
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
 
@@ -523,7 +556,18 @@ struct ChunkP<double, P> {
             v[m][1] = *reinterpret_cast<const double2*>(p + 16 * m + 2);
         }
     }
-    __device__ __forceinline__ void load_tiled(const double* p) { load(p); }   // never used: the mirror is fp32 only
+    // VQ_LAYOUT_TILED64: piece m = units 8 m + 2 kk and 8 m + 2 kk + 1 of the slice, 32 doubles apart (p = slice + 64 kk + 2 col); per
+    // instruction four runs (one per kk) of 256 contiguous bytes -- whole lines, read once: non-temporal.  Pieces 256 doubles apart.
+    __device__ __forceinline__ void load_tiled(const double* p) {
+#pragma unroll
+        for (int m = 0; m < P; ++m) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const vq_d2 r = __builtin_nontemporal_load(reinterpret_cast<const vq_d2*>(p + 256 * m + 32 * h));
+                v[m][h] = make_double2(r.x, r.y);
+            }
+        }
+    }
     __device__ __forceinline__ double at(int m, int e) const { return (e & 1) ? v[m][e >> 1].y : v[m][e >> 1].x; }
 };
 
@@ -539,7 +583,7 @@ struct ChunkP<__half, P> {
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) v[m] = *reinterpret_cast<const h8*>(p + 32 * m);
     }
-    __device__ __forceinline__ void load_tiled(const __half* p) { load(p); }   // never used: the tiled layout is fp32 only
+    __device__ __forceinline__ void load_tiled(const __half* p) { load(p); }   // never used: the tiled layouts are fp32 / fp64 only
     __device__ __forceinline__ double at(int m, int e) const { return half_to_double(v[m >> 1][4 * (m & 1) + e]); }
 };
 
@@ -556,48 +600,52 @@ __device__ __forceinline__ int batch_query_pos(int k) {
 // of 32, so slot = (q % 4) + 8 (q / 4) + 4 kk + const is a bijection onto 0..31.
 __device__ __forceinline__ int query_row(int q, int D) { return q * D + (q & 3) + 8 * (q >> 2); }
 
-// The 16-query pass's view of an fp32 database: [tile of 16 clips][slice][k / 4][clip][4] -- every load instruction of a wave then
-// takes 1 KB of contiguous memory (whole 128-byte lines: the non-temporal hint pays), where the row-major layout gives it 64 bytes of
-// each of 16 clips 40 KB apart.  One workgroup per (tile, slice): the 16 rows come in whole (a wave reads 1 KB of one clip per
-// instruction), turn in LDS and go out in the tiled order.  Rows past n repeat the last clip (the pass never stores them).
-__global__ __launch_bounds__(256) void mirror_build_kernel(const float* feats, float* mirror, int64_t n, int NV, int D) {
-    extern __shared__ __attribute__((aligned(16))) float tile_lds[];          // [16][D + 4]
+// The 16-query pass's view of a database: [tile of 16 clips][slice][k / U][clip][U], U elements = 16 bytes (4 floats, 2 doubles:
+// csrc/vq_tile_index.h) -- every load instruction of a wave then takes 1 KB of contiguous memory (fp64: four runs of 256 bytes; whole
+// 128-byte lines either way: the non-temporal hint pays), where the row-major layout gives it 64 bytes of each of 16 clips 40 KB
+// apart.  The two conversions move 16-byte units and do not look inside them, so ONE pair of kernels serves both storage types: du =
+// units per vector (D / 4 for fp32, D / 2 for fp64).  One workgroup per (tile, slice): the 16 rows come in whole (a wave reads 1 KB of
+// one clip per instruction), turn in LDS ([16][du + 1] units: 65 792 bytes for fp32, 131 328 for fp64 at D = 1024) and go out in the
+// tiled order.  Rows past n repeat the last clip (the pass never stores them).
+__global__ __launch_bounds__(256) void mirror_build_kernel(const vq_f4* feats, vq_f4* mirror, int64_t n, int NV, int du) {
+    extern __shared__ __attribute__((aligned(16))) vq_f4 tile_lds[];          // [16][du + 1]
     const int64_t tile = blockIdx.x / NV;
     const int v = (int)(blockIdx.x - tile * NV);
-    const int d4 = D / 4, row = D + 4;
-    for (int i = threadIdx.x; i < 16 * d4; i += 256) {
-        const int c = i / d4, g = i - c * d4;
+    const int row = du + 1;
+    for (int i = threadIdx.x; i < 16 * du; i += 256) {
+        const int c = i / du, g = i - c * du;
         const int64_t clip = min(tile * 16 + c, n - 1);
-        *reinterpret_cast<float4*>(tile_lds + c * row + 4 * g) = stream_load4(feats + (clip * NV + v) * (int64_t)D + 4 * g);
+        tile_lds[c * row + g] = __builtin_nontemporal_load(feats + (clip * NV + v) * (int64_t)du + g);
     }
     __syncthreads();
-    float* out = mirror + (tile * NV + v) * 16 * (int64_t)D;
-    for (int j = threadIdx.x; j < 16 * d4; j += 256) {
+    vq_f4* out = mirror + (tile * NV + v) * 16 * (int64_t)du;
+    for (int j = threadIdx.x; j < 16 * du; j += 256) {
         const int g = j >> 4, c = j & 15;
-        *reinterpret_cast<float4*>(out + 4 * (int64_t)j) = *reinterpret_cast<const float4*>(tile_lds + c * row + 4 * g);
+        out[j] = tile_lds[c * row + g];
     }
 }
 
 // the inverse of mirror_build_kernel: one workgroup per (tile, slice) of a tiled block -> the 16 row segments (rows past n: none)
-__global__ __launch_bounds__(256) void untile_kernel(const float* tiled, float* rows, int64_t n, int NV, int D) {
-    extern __shared__ __attribute__((aligned(16))) float tile_lds[];          // [16][D + 4]
+__global__ __launch_bounds__(256) void untile_kernel(const vq_f4* tiled, vq_f4* rows, int64_t n, int NV, int du) {
+    extern __shared__ __attribute__((aligned(16))) vq_f4 tile_lds[];          // [16][du + 1]
     const int64_t tile = blockIdx.x / NV;
     const int v = (int)(blockIdx.x - tile * NV);
-    const int d4 = D / 4, row = D + 4;
-    const float* in = tiled + (tile * NV + v) * 16 * (int64_t)D;
-    for (int j = threadIdx.x; j < 16 * d4; j += 256) {
+    const int row = du + 1;
+    const vq_f4* in = tiled + (tile * NV + v) * 16 * (int64_t)du;
+    for (int j = threadIdx.x; j < 16 * du; j += 256) {
         const int g = j >> 4, c = j & 15;
-        *reinterpret_cast<float4*>(tile_lds + c * row + 4 * g) = *reinterpret_cast<const float4*>(in + 4 * (int64_t)j);
+        tile_lds[c * row + g] = in[j];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 16 * d4; i += 256) {
-        const int c = i / d4, g = i - c * d4;
+    for (int i = threadIdx.x; i < 16 * du; i += 256) {
+        const int c = i / du, g = i - c * du;
         const int64_t clip = tile * 16 + c;
-        if (clip < n) *reinterpret_cast<float4*>(rows + (clip * NV + v) * (int64_t)D + 4 * g) = *reinterpret_cast<const float4*>(tile_lds + c * row + 4 * g);
+        if (clip < n) rows[(clip * NV + v) * (int64_t)du + g] = tile_lds[c * row + g];
     }
 }
 
-// vq_db_upload into a tiled database: staged row-major rows -> their places in the tiles (16 bytes per thread)
+// vq_db_upload into a tiled database: staged row-major rows -> their places in the tiles (16 bytes per thread; d4 = the 16-byte units
+// of a vector: D / 4 for fp32, D / 2 for fp64)
 __global__ void scatter_rows_tiled_kernel(const float4* staged, float4* tiled, int64_t row0, int64_t nrows, int NV, int d4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t per_row = (int64_t)NV * d4;
@@ -674,7 +722,8 @@ struct ViewWalk {
     __device__ __forceinline__ int64_t phys_tile(int64_t tile) const { return a.items ? (int64_t)uniform_load(a.items + tile) : tile; }
     // this lane's pointer into slice v of work item `tile`: 64-bit, sixteen arbitrary rows can lie more than 2^32 elements apart
     __device__ __forceinline__ const T* ptr(int64_t tile, int v) const {
-        if constexpr (TILED) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 4);
+        if constexpr (TILED && sizeof(T) == 8) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 2);      // units of 2 doubles
+        else if constexpr (TILED) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 4);
         else return feats + (int64_t)pick16(rows_of(tile), col) * clip_elems + ((int64_t)v * D + KL * kk);
     }
     __device__ __forceinline__ ViewTile tile(int64_t tile) const {
@@ -750,6 +799,7 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
         return TILED ? feats + (tile * NV + v) * 16 * D : feats + tile * 16 * clip_elems + (int64_t)v * D;
     };
     auto lane_off = [&](int64_t tile) -> uint32_t {
+        if constexpr (TILED && sizeof(T) == 8) return (uint32_t)(kk * 64 + col * 2);      // VQ_LAYOUT_TILED64: units of 2 doubles
         if (TILED) return (uint32_t)(kk * 64 + col * 4);
         const int last = (int)min((int64_t)15, a.n - 1 - tile * 16);
         return (uint32_t)(min(col, last) * (int)clip_elems + KL * kk);
@@ -1071,25 +1121,21 @@ __global__ void loss_surface_kernel(const double* avg, const double* w_grid, con
 }
 
 // target_clip.py:311-313: t = r / (r . r), one block per (s,e) vector of row `row`, fp64 throughout.
-// element k of vector (row, v): row-major, or inside the tiled layout [tile][v][k / 4][row % 16][4]
-__device__ __forceinline__ int64_t feat_index(bool tiled, int64_t row, int v, int k, int NV, int D) {
-    return tiled ? (((row >> 4) * NV + v) * (int64_t)(D / 4) + (k >> 2)) * 64 + (row & 15) * 4 + (k & 3) : (row * NV + v) * (int64_t)D + k;
-}
-
+// element k of vector (row, v) in the database's layout: feat_index (csrc/vq_tile_index.h), unit = vq_db::unit()
 template <typename T>
-__global__ __launch_bounds__(256) void scale_query_kernel(const T* feats, int64_t row, int NV, int D, double* t, bool tiled) {
+__global__ __launch_bounds__(256) void scale_query_kernel(const T* feats, int64_t row, int NV, int D, double* t, int unit) {
     __shared__ double part[4];
     const int v = blockIdx.x;
     double p = 0.0;
     for (int k = threadIdx.x; k < D; k += blockDim.x) {
-        const double x = widen(feats[feat_index(tiled, row, v, k, NV, D)]);
+        const double x = widen(feats[feat_index(unit, row, NV, v, D, k)]);
         p = fma(x, x, p);
     }
     p = wave_sum(p);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = p;
     __syncthreads();
     const double rr = ((part[0] + part[1]) + part[2]) + part[3];
-    for (int k = threadIdx.x; k < D; k += blockDim.x) t[(int64_t)v * D + k] = widen(feats[feat_index(tiled, row, v, k, NV, D)]) / rr;
+    for (int k = threadIdx.x; k < D; k += blockDim.x) t[(int64_t)v * D + k] = widen(feats[feat_index(unit, row, NV, v, D, k)]) / rr;
 }
 
 // counter-based synthetic rows (shared with oracle/sim_oracle.py::synth_features)
@@ -1280,7 +1326,7 @@ __global__ void gather_rows_kernel(const U* feats, const int64_t* rows, int64_t 
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cnt * row_vec16) return;
     const int64_t r = i / row_vec16, k = i - r * row_vec16;
-    if (tiled_nv) {                                   // fp32, tiled: piece g of (clip, v) is one 16-byte unit of the tile
+    if (tiled_nv) {                                   // tiled: piece g of (clip, v) is one 16-byte unit of the tile (tiled_d4 of them per vector)
         const int v = (int)(k / tiled_d4), g = (int)(k - (int64_t)v * tiled_d4);
         const int64_t clip = rows[r];
         out[i] = feats[(((clip >> 4) * tiled_nv + v) * tiled_d4 + g) * 16 + (clip & 15)];
@@ -1333,14 +1379,14 @@ int vq::gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const voi
     char* base = (char*)db->grid_buf;
     if (!rows_dev) VQ_HIP(hipMemcpyAsync(base, rows_host, (size_t)L * 8, hipMemcpyHostToDevice, db->stream));
     const int64_t* rows = rows_dev ? rows_dev : (const int64_t*)base;
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;
+    const bool tiled = db->tiled();
     if (row_bytes % 16) {
         const int64_t vec = row_bytes / 8;
         gather_rows_kernel<uint2><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint2*)db->feats, rows, L, vec, (uint2*)(base + rb), 0, 0);
     } else {
         const int64_t vec = row_bytes / 16;
         gather_rows_kernel<uint4><<<cdiv((int64_t)L * vec, 256), 256, 0, db->stream>>>((const uint4*)db->feats, rows, L, vec, (uint4*)(base + rb),
-                                                                                      tiled ? db->S * db->E : 0, db->D / 4);
+                                                                                      tiled ? db->S * db->E : 0, tiled ? db->D / db->unit() : 0);
     }
     VQ_CHECK_LAUNCH();
     *dense = base + rb;
@@ -1351,9 +1397,10 @@ int vq::gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const voi
 // through a scratch block (rows -> scratch in the new order -> back).  One sweep of reads and writes each way; caller holds the lock.
 static int convert_layout(vq_db* db, int to) {
     const int NV = db->S * db->E;
-    const int64_t ntiles = (db->n + 15) / 16, tile_bytes = (int64_t)16 * NV * db->D * 4;
+    const int du = db->D * (int)db->elem() / 16;                           // 16-byte units of a vector: what the two kernels move
+    const int64_t ntiles = (db->n + 15) / 16, tile_bytes = (int64_t)16 * NV * db->D * (int64_t)db->elem();
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)(256u << 20) / tile_bytes));
-    float* scratch = nullptr;
+    char* scratch = nullptr;
     hipError_t e = hipMalloc((void**)&scratch, (size_t)(per * tile_bytes));
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
@@ -1361,7 +1408,7 @@ static int convert_layout(vq_db* db, int to) {
         e = hipMalloc((void**)&scratch, (size_t)(per * tile_bytes));
     }
     if (e != hipSuccess) return fail(VQ_E_NOMEM, "no room for the %lld MB conversion block: %s", (long long)(per * tile_bytes >> 20), hipGetErrorString(e));
-    const size_t lds = 16 * (size_t)(db->D + 4) * sizeof(float);         // 65 792 bytes at D = 1024: above the 64 KB default limit
+    const size_t lds = 16 * (size_t)(du + 1) * 16;                         // 65 792 bytes (fp32) / 131 328 (fp64) at D = 1024: above the 64 KB default limit
     {   // raised per (kernel, device) like every other large-LDS launch (vq_common.h); the caller holds a DeviceGuard
         const auto raise = [&]() -> int {
             VQ_DYN_LDS(mirror_build_kernel, lds);
@@ -1377,15 +1424,15 @@ static int convert_layout(vq_db* db, int to) {
     int rc = VQ_OK;
     for (int64_t t0 = 0; t0 < ntiles && rc == VQ_OK; t0 += per) {
         const int64_t k = std::min(per, ntiles - t0);
-        float* block = (float*)db->feats + t0 * 16 * NV * db->D;
+        char* block = (char*)db->feats + t0 * tile_bytes;
         const int64_t rows_here = std::min<int64_t>(db->n - t0 * 16, k * 16);
-        if (to == VQ_LAYOUT_TILED)
-            mirror_build_kernel<<<(unsigned)(k * NV), 256, lds, db->stream>>>(block, scratch, rows_here, NV, db->D);
+        if (to != VQ_LAYOUT_ROWS)
+            mirror_build_kernel<<<(unsigned)(k * NV), 256, lds, db->stream>>>((const vq_f4*)block, (vq_f4*)scratch, rows_here, NV, du);
         else
-            untile_kernel<<<(unsigned)(k * NV), 256, lds, db->stream>>>(block, scratch, rows_here, NV, db->D);
+            untile_kernel<<<(unsigned)(k * NV), 256, lds, db->stream>>>((const vq_f4*)block, (vq_f4*)scratch, rows_here, NV, du);
         e = hipGetLastError();
         // tiled -> rows leaves the rows past n of the last tile unwritten in the scratch block: copy whole rows only
-        const size_t bytes = to == VQ_LAYOUT_TILED ? (size_t)(k * tile_bytes) : (size_t)rows_here * NV * db->D * 4;
+        const size_t bytes = to != VQ_LAYOUT_ROWS ? (size_t)(k * tile_bytes) : (size_t)(rows_here * (tile_bytes / 16));
         if (e == hipSuccess) e = hipMemcpyAsync(block, scratch, bytes, hipMemcpyDeviceToDevice, db->stream);
         if (e != hipSuccess) rc = fail(VQ_E_HIP, "layout conversion failed: %s", hipGetErrorString(e));
     }
@@ -1561,12 +1608,12 @@ int vq_db_upload(vq_db* db, int64_t row0, int64_t nrows, const void* feats_host)
     std::lock_guard<std::mutex> lk(db->mu);
     DeviceGuard g(db->device);
     const size_t row_bytes = (size_t)db->S * db->E * db->D * db->elem();
-    if (db->layout == VQ_LAYOUT_TILED) {
+    if (db->tiled()) {
         // rows land in a staging block and are dealt into their tiles by a kernel, a bounded chunk at a time
         const int64_t chunk = std::max<int64_t>(1, (int64_t)(64u << 20) / (int64_t)row_bytes);
         void* stage = nullptr;
         VQ_HIP(vq::malloc_trim(&stage, (size_t)std::min<int64_t>(chunk, std::max<int64_t>(nrows, 1)) * row_bytes));
-        const int NV = db->S * db->E, d4 = db->D / 4;
+        const int NV = db->S * db->E, d4 = db->D / db->unit();           // 16-byte units of a vector
         for (int64_t r = 0; r < nrows; r += chunk) {
             const int64_t k = std::min(chunk, nrows - r);
             hipError_t e = hipMemcpyAsync(stage, (const char*)feats_host + r * row_bytes, k * row_bytes, hipMemcpyHostToDevice, db->stream);
@@ -1648,9 +1695,10 @@ int vq_db_generate(vq_db* db, uint64_t seed, int64_t global_row0, const float* s
     VQ_CHECK_LAUNCH();
     VQ_HIP(hipStreamSynchronize(db->stream));
     db->have_avg = db->have_scores = db->have_sims = false;
-    if (db->layout == VQ_LAYOUT_TILED) {          // the generator writes rows; a tiled database gets its layout back
+    if (db->tiled()) {                            // the generator writes rows; a tiled database gets its layout back
+        const int was = db->layout;
         db->layout = VQ_LAYOUT_ROWS;
-        return convert_layout(db, VQ_LAYOUT_TILED);
+        return convert_layout(db, was);
     }
     return VQ_OK;
 }
@@ -1714,11 +1762,11 @@ int vq_db_set_query_from_row(vq_db* db, int64_t row, double* t_out_host) {
     DeviceGuard g(db->device);
     const int NV = db->S * db->E;
     if (db->dtype == VQ_F16)
-        scale_query_kernel<__half><<<NV, 256, 0, db->stream>>>((const __half*)db->feats, row, NV, db->D, db->t, false);
+        scale_query_kernel<__half><<<NV, 256, 0, db->stream>>>((const __half*)db->feats, row, NV, db->D, db->t, db->unit());
     else if (db->dtype == VQ_F32)
-        scale_query_kernel<float><<<NV, 256, 0, db->stream>>>((const float*)db->feats, row, NV, db->D, db->t, db->layout == VQ_LAYOUT_TILED);
+        scale_query_kernel<float><<<NV, 256, 0, db->stream>>>((const float*)db->feats, row, NV, db->D, db->t, db->unit());
     else
-        scale_query_kernel<double><<<NV, 256, 0, db->stream>>>((const double*)db->feats, row, NV, db->D, db->t, false);
+        scale_query_kernel<double><<<NV, 256, 0, db->stream>>>((const double*)db->feats, row, NV, db->D, db->t, db->unit());
     VQ_CHECK_LAUNCH();
     if (t_out_host) {
         VQ_HIP(hipMemcpyAsync(t_out_host, db->t, (size_t)NV * db->D * 8, hipMemcpyDeviceToHost, db->stream));
@@ -1738,9 +1786,9 @@ static int launch_scan_t(vq_db* db, const A& a) {
     const size_t lds = (size_t)S * E * CH * 256 * 8;
     int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
     if (per_cu < 1) per_cu = 1;
-    if (db->layout == VQ_LAYOUT_TILED) {
-        if constexpr (sizeof(T) == 4) {
-            auto kern = scan_tiled_kernel<S, E, CH, kTiledGroup, VIEW>;
+    if (db->tiled()) {
+        if constexpr (sizeof(T) != 2) {
+            auto kern = scan_tiled_kernel<T, S, E, CH, sizeof(T) == 8 ? kTiledGroup64 : kTiledGroup, VIEW>;
             VQ_DYN_LDS(kern, lds);
             int64_t want = ((a.n + 15) / 16 + 3) / 4;   // 4 waves (tiles in flight) per block
             if constexpr (VIEW) want = (a.n_items + 3) / 4;
@@ -1749,7 +1797,7 @@ static int launch_scan_t(vq_db* db, const A& a) {
             VQ_CHECK_LAUNCH();
             return VQ_OK;
         }
-        return fail(VQ_E_STATE, "internal: a tiled database is fp32");
+        return fail(VQ_E_STATE, "internal: a tiled database is fp32 or fp64");
     }
     // a database whose clips are a few per wave: the lean instantiation, three waves per SIMD (VQ_SCAN_LEAN=0|1 forces one or the other)
     static const int force_lean = getenv("VQ_SCAN_LEAN") ? atoi(getenv("VQ_SCAN_LEAN")) : -1;
@@ -1821,7 +1869,7 @@ static int launch_scan_dtype(vq_db* db, const ScanArgs& a) {
     ScanViewArgs va;
     static_cast<ScanArgs&>(va) = a;
     va.pos = nullptr;
-    if (db->layout == VQ_LAYOUT_TILED) {
+    if (db->tiled()) {
         if (!v.tiles) return fail(VQ_E_STATE, "internal: a row view without tile tables on a tiled database");
         va.items = v.tiles;
         va.pos = v.pos;
@@ -1913,7 +1961,7 @@ template <bool ROUND>
 static int launch_fused_pass(vq_db* db, int Q, const double* d_t, const double* d_w, double* d_scores, double* d_avg) {
     const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;   // sixteen swizzled query rows
     const int ch = db->D / 256;
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;      // whole 128-byte lines per load instruction, non-temporal: 0.75 of the HBM peak against 0.71
+    const bool tiled = db->tiled();                        // whole 128-byte lines per load instruction, non-temporal: 0.75 of the HBM peak against 0.71
     BatchFusedArgs f;
     f.feats = db->feats;
     f.t = d_t;
@@ -2103,13 +2151,15 @@ int vq_db_layout(vq_db* db, int32_t* layout) {
 
 int vq_db_set_layout(vq_db* db, int32_t layout) {
     VQ_REQUIRE(db, "db is NULL");
-    VQ_REQUIRE(layout == VQ_LAYOUT_ROWS || layout == VQ_LAYOUT_TILED, "layout must be VQ_LAYOUT_ROWS or VQ_LAYOUT_TILED");
+    VQ_REQUIRE(layout == VQ_LAYOUT_ROWS || layout == VQ_LAYOUT_TILED || layout == VQ_LAYOUT_TILED64,
+               "layout must be VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED or VQ_LAYOUT_TILED64");
     std::lock_guard<std::mutex> lk(db->mu);
     if (layout == db->layout) return VQ_OK;
-    if (layout == VQ_LAYOUT_TILED) {
-        if (db->dtype != VQ_F32 || !fast_scan_shape(db))
-            return fail(VQ_E_UNSUPPORTED, "the tiled layout exists for fp32 databases (not fp16 / fp64) with D = 1024, S <= 2, E <= 5 (got dtype %d, D %d, S %d, E %d)", db->dtype,
-                        db->D, db->S, db->E);
+    if (layout != VQ_LAYOUT_ROWS) {
+        // each storage type has ONE tiled layout (the unit is the 16 bytes a lane loads): TILED is fp32's, TILED64 is fp64's, fp16 has none
+        if (layout != db->tiled_layout() || !fast_scan_shape(db))
+            return fail(VQ_E_UNSUPPORTED, "the tiled layouts exist for fp32 (VQ_LAYOUT_TILED) and fp64 (VQ_LAYOUT_TILED64) databases, not fp16, with D = 1024, S <= 2, E <= 5 (layout %d: got dtype %d, D %d, S %d, E %d)",
+                        layout, db->dtype, db->D, db->S, db->E);
         if (!db->owns_feats || db->feats_exposed)
             return fail(VQ_E_STATE, "the feature block is not the library's alone (adopted, or its address was handed out): it stays row-major");
     }
@@ -2364,10 +2414,10 @@ static int fetch_selected(vq_db* db, int64_t* match_rows_host, int64_t cap_match
 }  // extern "C"
 
 // ---- the pass of a batched round over a row view per query (csrc/vq_rounds.hip, include/vq_amd_round_views.h) -------------------------
-// the VIEW instantiation of the 16-query pass for a database: the tiled layout exists for fp32 rows of 1024 elements only (vq_db_set_layout)
+// the VIEW instantiation of the 16-query pass for a database: the tiled layouts exist for fp32 / fp64 rows of 1024 elements only (vq_db_set_layout)
 template <typename T, int CH, int TW>
 static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
-    if constexpr (std::is_same_v<T, float> && CH == 4) {
+    if constexpr (sizeof(T) != 2 && CH == 4) {
         if (tiled) return pres ? batch_view_kernel<T, CH, TW, true, 8, true> : batch_view_kernel<T, CH, TW, false, 8, true>;
     }
     return pres ? batch_view_kernel<T, CH, TW, true, 8, false> : batch_view_kernel<T, CH, TW, false, 8, false>;
@@ -2378,8 +2428,8 @@ static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
 int vq::launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
     const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;
     const int ch = db->D / 256;
-    const bool tiled = db->layout == VQ_LAYOUT_TILED;
-    if (tiled && !(db->dtype == VQ_F32 && ch == 4)) return fail(VQ_E_UNSUPPORTED, "a tiled database holds float32 rows of 1024 elements");
+    const bool tiled = db->tiled();
+    if (tiled && !(db->dtype != VQ_F16 && ch == 4)) return fail(VQ_E_UNSUPPORTED, "a tiled database holds float32 or float64 rows of 1024 elements");
     constexpr int TW = 2;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((max_tiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
     // every (T, CH, mask, layout) is launched by a case of tests/test_view_round_gpu.py (the table above VIEW_KERNELS there): a new one
@@ -2547,7 +2597,7 @@ int vq_db_rows_define(vq_db* db, const int64_t* rows_host, int64_t m, int32_t* v
     // the tiled form of the same view, built whenever the database could be tiled: a view defined on rows survives vq_db_set_layout
     std::vector<int64_t> host(rows_host, rows_host + m);
     int64_t ntiles = 0;
-    if (db->dtype == VQ_F32 && fast_scan_shape(db)) {
+    if (db->tiled_layout() != VQ_LAYOUT_ROWS && fast_scan_shape(db)) {
         for (int64_t i = 0; i < m; ++i) ntiles += (i == 0 || (rows_host[i] >> 4) != (rows_host[i - 1] >> 4)) ? 1 : 0;
         host.resize((size_t)(m + ntiles + ntiles * 16), -1);
         int64_t* tiles = host.data() + m;

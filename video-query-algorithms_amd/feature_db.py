@@ -59,6 +59,10 @@ class SearchSetView:
             return False
 
 
+# the layouts of vq_db_set_layout by name (include/vq_amd.h); the values also travel as they are in ShardedFeatureDB's OP_LAYOUT
+_LAYOUTS = {"rows": _lib.VQ_LAYOUT_ROWS, "tiled": _lib.VQ_LAYOUT_TILED, "tiled64": _lib.VQ_LAYOUT_TILED64}
+_LAYOUT_NAMES = {v: k for k, v in _LAYOUTS.items()}
+
 def whole_view(db) -> SearchSetView:
     """The trivial view of a database object (FeatureDB, ShardedFeatureDB, or a look-alike with ``clip_ids`` and ``row_of``)."""
     n = len(db.clip_ids)
@@ -277,7 +281,7 @@ class FeatureDB(BatchRounds):
         converting a value (src/api/api_load_records.py:45-58) and without a store on disk.  Same walk: videos sorted by name, a
         video's clips in clip-number order, ids ``clip_id_base + row + 1``; a (clip, stream, split) without a row is absent and reads
         back as zeros.  Pass one indexes the files and keeps only their clip numbers; pass two loads them.  ``clips`` is the
-        ``(video, clip)`` of every row; ``csv_host_fields`` counts the fields the host had to resolve.  ``layout="tiled"`` (fp32) tiles the
+        ``(video, clip)`` of every row; ``csv_host_fields`` counts the fields the host had to resolve.  ``layout="tiled"`` (fp32) or ``"tiled64"`` (fp64) tiles the
         block first, so the values land in their tiles.  A value that the database's type cannot hold (float16: |x| >= 65520) or that
         is no number raises ``ValueError`` naming file, line and field."""
         import os
@@ -386,15 +390,25 @@ class FeatureDB(BatchRounds):
         return int(host.value)
 
     def set_layout(self, layout: str):
-        """"rows" ([N][S][E][D]) or "tiled" ([tile of 16 clips][S*E][D/4][clip][4]: the order in which every load of the scans
-        takes whole lines; fp32 only, D = 1024, S <= 2, E <= 5).  In place, one sweep of the block: call once after loading."""
-        call("vq_db_set_layout", self._h, {"rows": _lib.VQ_LAYOUT_ROWS, "tiled": _lib.VQ_LAYOUT_TILED}[layout])
+        """"rows" ([N][S][E][D]), "tiled" ([tile of 16 clips][S*E][D/4][clip][4]: the order in which every load of the scans
+        takes whole lines; float32 only) or "tiled64" (the same for float64: [tile][S*E][D/2][clip][2]); both need D = 1024, S <= 2,
+        E <= 5 and each is refused for the other's dtype (:attr:`tiled_layout` names the one this database takes).  In place, one
+        sweep of the block: call once after loading.  Never chosen for the caller: the layouts agree to rounding, not bit for bit."""
+        call("vq_db_set_layout", self._h, _LAYOUTS[layout])
 
     @property
     def layout(self) -> str:
         v = C.c_int32()
         call("vq_db_layout", self._h, C.byref(v))
-        return "tiled" if v.value == _lib.VQ_LAYOUT_TILED else "rows"
+        return _LAYOUT_NAMES[v.value]
+
+    @property
+    def tiled_layout(self):
+        """The name of the tiled layout this database can take -- "tiled" (float32), "tiled64" (float64) -- or ``None`` (float16,
+        or a shape without the tiled kernels): what to hand :meth:`set_layout` without switching on the dtype."""
+        if self.dtype == np.float16 or not (self.D == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
+            return None
+        return "tiled64" if self.dtype == np.float64 else "tiled"
 
     def adopt_device(self, dev_ptr: int, keepalive=None):
         """Use caller-owned device memory (e.g. a torch tensor holding all-gathered blocks)."""
