@@ -87,6 +87,8 @@ enum {
  * scores like an fp32 / fp64 database holding the rounded values.  A library that predates VQ_F16 refuses it in vq_db_create. */
 enum { VQ_F32 = 0, VQ_F64 = 1, VQ_F16 = 2 };
 enum { VQ_LAYOUT_ROWS = 0, VQ_LAYOUT_TILED = 1, VQ_LAYOUT_TILED64 = 2 };
+/* a declaration of its own: tests/test_tiled64_host.py matches the line above as it stood when TILED64 was the last value */
+enum { VQ_LAYOUT_TILED16 = 3 };
 
 const char* vq_last_error(void);
 int vq_abi_version(void);
@@ -115,7 +117,7 @@ typedef struct vq_db vq_db;
  * GET per query in Ticket._get_candidate_features (src/models/ticket.py:358-382).
  * dtype VQ_F32 (BASELINE configs), VQ_F64 (exact values of the shipped CSVs) or VQ_F16 (binary16 rows: vq_db_upload, vq_db_read_rows,
  * vq_db_adopt_device and vq_db_feats_devptr then speak halves; the caller rounds, vq_db_generate rounds to nearest even).  Every vq_db_*
- * entry point works on all three; only the tiled layouts (vq_db_set_layout: fp32, fp64) and the host rows of vq_bootstrap_targets (fp32 / fp64) do not take it. */
+ * entry point works on all three, the tiled layouts included (vq_db_set_layout: each type has its own); only the host rows of vq_bootstrap_targets (fp32 / fp64) do not take it. */
 int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int32_t device, vq_db** out);
 int vq_db_destroy(vq_db* db);
 int vq_db_set_stream(vq_db* db, void* hip_stream);
@@ -131,7 +133,7 @@ int vq_db_adopt_device(vq_db* db, void* feats_dev);
  * every load instruction of a wave (one-query scan AND 16-query pass) takes 1 KB of contiguous memory.  The conversion is IN PLACE
  * (a tile's rows and its tiled form cover the same bytes; no second copy of the database, 256 MB of scratch while it runs) and
  * costs one sweep of the block: call it once after loading, off the query path.  Tiled needs fp32, D = 1024, S <= 2, E <= 5
- * (VQ_E_UNSUPPORTED otherwise -- also for VQ_F16 and VQ_F64 databases, which stay row-major and keep working) and a block that is the library's alone (VQ_E_STATE after vq_db_adopt_device / vq_db_feats_devptr).
+ * (VQ_E_UNSUPPORTED otherwise -- also for VQ_F16 and VQ_F64 databases, which take their own tiled layouts below; a refused handle stays as it was and keeps working) and a block that is the library's alone (VQ_E_STATE after vq_db_adopt_device / vq_db_feats_devptr).
  * Every other entry point works on either layout; results of the two layouts agree to rounding (<= 1e-12: the k order of a
  * dot differs), each is bit-reproducible in itself.  vq_db_upload into a tiled database deals the rows into their tiles.
  * VQ_LAYOUT_TILED64 (still ABI 12, no new symbol: a value of this argument) is the same order for VQ_F64 databases, restated with the
@@ -139,7 +141,11 @@ int vq_db_adopt_device(vq_db* db, void* feats_dev);
  * S <= 2, E <= 5), same refusals (VQ_E_UNSUPPORTED on VQ_F32 / VQ_F16 databases and other shapes, VQ_E_STATE on a block that is not the
  * library's alone), same in-place conversion; VQ_LAYOUT_TILED on a VQ_F64 database stays refused: each storage type has ONE tiled
  * layout, under its own name because the byte order differs.  The 16-query pass gives the bits of the pass on fp64 rows; the one-query
- * scan agrees with fp64 rows to rounding (<= 1e-12).  A library that predates the value refuses it (VQ_E_INVALID). */
+ * scan agrees with fp64 rows to rounding (<= 1e-12).  A library that predates the value refuses it (VQ_E_INVALID).
+ * VQ_LAYOUT_TILED16 (ABI 12 as well) is the order for VQ_F16 databases, the unit being 8 halves: [tile of 16 clips][S*E][D/8][clip][8].
+ * Same shapes, same in-place conversion, same refusals (VQ_E_UNSUPPORTED on VQ_F32 / VQ_F64 databases and other shapes; VQ_LAYOUT_TILED
+ * and VQ_LAYOUT_TILED64 on a VQ_F16 database stay refused; VQ_E_STATE on a block that is not the library's alone).  The 16-query pass
+ * gives the bits of the pass on fp16 rows; the one-query scan agrees with fp16 rows to rounding (<= 1e-12). */
 int vq_db_set_layout(vq_db* db, int32_t layout);
 int vq_db_layout(vq_db* db, int32_t* layout);
 /* Optional [N][S][E] presence mask (1 = this clip has this split); NULL restores "dense".

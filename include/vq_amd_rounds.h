@@ -27,7 +27,8 @@
  *
  * PRECONDITIONS, those of vq_db_scan_batch: 1 <= Q <= 16, D in {256, 512, 768, 1024}, S <= 8, and the WHOLE database -- with a row
  * view in use (vq_amd_rows.h) the call returns VQ_E_UNSUPPORTED and says so.  float32, float64 and float16 storage, rows and tiled
- * layout (the tiled instantiation does not exist for float16 rows, as for vq_db_scan_batch).
+ * layout (each storage type's own: VQ_LAYOUT_TILED, VQ_LAYOUT_TILED64, VQ_LAYOUT_TILED16 -- on a tiled database of any type the pass
+ * gives the bits of the pass on its rows).
  *
  * THE ONE-QUERY STATE of the handle is left alone, as vq_db_scan_batch leaves it: the query, avg, n_e, scores, the selection lists
  * of vq_db_select and the view in use.  The batched buffers are allocated on the first call and freed by vq_db_destroy.  After a

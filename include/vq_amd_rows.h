@@ -15,7 +15,9 @@
  * position and the selection keeps view order.  vq_db_round_layout stays sized for N: the arrays of the block hold their first M
  * entries and only those are copied back.  A clip's dot products, ensemble means and score under a view are the full scan's
  * sequence of operations on the same handle: the same bits (row-major: the scan reads only the M clips; tiled: it reads the
- * tiles the view touches, whole, and a clip outside the view stores nothing).
+ * tiles the view touches, whole, and a clip outside the view stores nothing).  The tile tables of a view are built when it is defined,
+ * for every database of a shape that can be tiled (D = 1024, S <= 2, E <= 5) -- float16 databases included, which have VQ_LAYOUT_TILED16
+ * -- so a view defined on rows survives vq_db_set_layout.
  *
  * These stay in DATABASE rows, view or no view: vq_db_set_query_from_row, vq_db_bootstrap_target, vq_db_read_rows,
  * vq_db_upload, vq_db_set_present (the presence mask is [N][S][E] and is read by database row).

@@ -136,30 +136,36 @@ def _timed(fn, tm):
     return ms.value
 
 
-def bench_tiled64(n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None):
-    """A float64 database on its rows against the same database in the tiled64 layout, in ONE process: two handles of the same seed,
-    timed in turn (bench_view's pattern) behind a warm-up, `reps` (>= 10) times each -- the one-query scan, then the 16-query pass.
-    GB/s is the algorithmic bytes (the rows + 8 B of score per clip) over device-event time; the share is of 8 TB/s.  The row-major
-    figures of the same run are the baseline.  ``out``: a JSON file with every sample."""
+MATRIX_MS_PER_ELEMENT = 4.2 / 10.24e9       # csrc/vq_sim.hip: 16 queries x 10.24 G elements are 4.2 ms of fp64 matrix time
+
+
+def bench_layout(layout, dtype, n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None, note=None):
+    """A database on its rows against the same database in its tiled layout (``layout``: "tiled64" for float64, "tiled16" for
+    float16), in ONE process: two handles of the same seed, timed in turn (bench_view's pattern) behind a warm-up, `reps` (>= 10) times
+    each -- the one-query scan, then the 16-query pass.  GB/s is the algorithmic bytes (the rows + 8 B of score per clip) over
+    device-event time; the share is of 8 TB/s; the pass is also put against its fp64 matrix time.  The row-major figures of the same run
+    are the baseline.  ``out``: a JSON file with every sample; ``note``: what the run is (e.g. the group size the library was built with)."""
     import json
     import time
     assert reps >= 10
     w = [1.0, 1.5][:s]
-    rows = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=np.float64)
-    tiled = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=np.float64)
+    rows = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=dtype)
+    tiled = vqa.FeatureDB.synthetic(n, s, e, d, seed=1, scales=(4.0, 1.0)[:s], dtype=dtype)
     t0 = time.perf_counter()
-    tiled.set_layout(tiled.tiled_layout)              # synchronous: one sweep of the block each way through 256 MB of scratch
+    tiled.set_layout(layout)                         # synchronous: one sweep of the block each way through 256 MB of scratch
     convert_ms = (time.perf_counter() - t0) * 1e3
-    assert tiled.layout == "tiled64" and rows.layout == "rows"
-    handles = (("rows", rows), ("tiled64", tiled))
+    assert tiled.layout == layout and rows.layout == "rows"
+    handles = (("rows", rows), (layout, tiled))
+    size, kind = np.dtype(dtype).itemsize, np.dtype(dtype).name
     for _name, db in handles:
         db.set_query_from_row(7, want=False)
     tm = C.c_void_p()
     call("vq_timer_create", C.byref(tm))
-    nbytes = n * s * e * d * 8 + n * 8
-    res = {"n": n, "S": s, "E": e, "D": d, "dtype": "float64", "bytes": nbytes, "reps": reps, "convert_ms": convert_ms, "scan": {}, "batch": {}}
-    print("fp64 N=%d S=%d E=%d (%.1f GB): rows -> tiled64 in %.0f ms (%.2f TB/s of the block, read + written once each)"
-          % (n, s, e, nbytes / 1e9, convert_ms, 2 * nbytes / convert_ms / 1e9), flush=True)
+    nbytes = n * s * e * d * size + n * 8
+    res = {"n": n, "S": s, "E": e, "D": d, "dtype": kind, "layout": layout, "note": note, "bytes": nbytes, "reps": reps, "convert_ms": convert_ms,
+           "scan": {}, "batch": {}}
+    print("%s N=%d S=%d E=%d (%.1f GB): rows -> %s in %.0f ms (%.2f TB/s of the block, read + written once each)%s"
+          % (kind, n, s, e, nbytes / 1e9, layout, convert_ms, 2 * nbytes / convert_ms / 1e9, " [%s]" % note if note else ""), flush=True)
     for _name, db in handles:
         for _ in range(3):
             db.scan(weights=w)
@@ -181,17 +187,19 @@ def bench_tiled64(n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None):
         first[name] = db.scan_batch(t, wq)              # warm-up, drained by the copy back
         db.scan_batch(t, wq, want=False)
         db.scan_batch(t[:1], wq[:1])
-    assert (first["rows"] == first["tiled64"]).all()    # the same bits: what is timed is the same computation
+    assert (first["rows"] == first[layout]).all()       # the same bits: what is timed is the same computation
     times = {name: [] for name, _db in handles}
     for _ in range(reps):
         for name, db in handles:
             times[name].append(_timed(lambda: db.scan_batch(t, wq, want=False), tm))
-    dbb = n * s * e * d * 8
+    dbb = n * s * e * d * size
+    matrix_ms = MATRIX_MS_PER_ELEMENT * n * s * e * d * (q / 16)
     for name, _db in handles:
         med, best = sorted(times[name])[reps // 2], min(times[name])
-        res["batch"][name] = {"ms": times[name], "median_ms": med, "best_ms": best, "queries_per_s": q / med * 1e3, "median_share_of_8tbs": dbb / med / 1e6 / 8000}
-        print("  16-query pass  %-7s: %.3f ms median (%.3f best) -> %.0f queries/s, DB bytes %.2f TB/s (%.3f of 8 TB/s)"
-              % (name, med, best, q / med * 1e3, dbb / med / 1e9, dbb / med / 1e9 / 8), flush=True)
+        res["batch"][name] = {"ms": times[name], "median_ms": med, "best_ms": best, "queries_per_s": q / med * 1e3, "median_share_of_8tbs": dbb / med / 1e6 / 8000,
+                              "matrix_ms": matrix_ms, "median_over_matrix_ms": med / matrix_ms}
+        print("  16-query pass  %-7s: %.3f ms median (%.3f best) -> %.0f queries/s, DB bytes %.2f TB/s (%.3f of 8 TB/s), %.2f x the %.2f ms of matrix time"
+              % (name, med, best, q / med * 1e3, dbb / med / 1e9, dbb / med / 1e9 / 8, med / matrix_ms, matrix_ms), flush=True)
     rows.close()
     tiled.close()
     if out:
@@ -200,7 +208,18 @@ def bench_tiled64(n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None):
     return res
 
 
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "tiled64":
-    # tools/quick_sim_bench.py tiled64 [n s e [out.json]]: one shape per process (each under a time limit of its own)
+def bench_tiled64(n=1_000_000, s=2, e=3, **kw):
+    return bench_layout("tiled64", np.float64, n, s, e, **kw)
+
+
+def bench_tiled16(n=1_000_000, s=2, e=5, **kw):
+    """float16 rows against tiled16.  The group-size A/B (VQ_TILED_GROUP16 = 2 / 4 / 8) is this mode once per library: build the
+    library with VQ_EXTRA_HIPCC_FLAGS=-DVQ_TILED_GROUP16=<g> into a file of its own, point VQ_AMD_LIB at it and pass the value as the note."""
+    return bench_layout("tiled16", np.float16, n, s, e, **kw)
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] in ("tiled64", "tiled16"):
+    # tools/quick_sim_bench.py tiled64|tiled16 [n s e [out.json [note]]]: one shape per process (each under a time limit of its own)
     a = sys.argv[2:]
-    bench_tiled64(*(int(v) for v in a[:3]), out=a[3] if len(a) > 3 else None)
+    {"tiled64": bench_tiled64, "tiled16": bench_tiled16}[sys.argv[1]](*(int(v) for v in a[:3]), out=a[3] if len(a) > 3 else None,
+                                                                      note=a[4] if len(a) > 4 else None)

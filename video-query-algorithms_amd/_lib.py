@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libvqamd.so")
 
 ABI_VERSION = 12                 # include/vq_amd.h: VQ_ABI_VERSION
 VQ_F32, VQ_F64, VQ_F16 = 0, 1, 2
-VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED, VQ_LAYOUT_TILED64 = 0, 1, 2
+VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED, VQ_LAYOUT_TILED64, VQ_LAYOUT_TILED16 = 0, 1, 2, 3
 VQ_OP_CONV, VQ_OP_MAXPOOL, VQ_OP_AVGPOOL, VQ_OP_GLOBAL_AVGPOOL, VQ_OP_CONV_WINOGRAD, VQ_OP_CONV_WINOGRAD16 = 1, 2, 3, 4, 5, 6
 VQ_OP_INNER_PRODUCT = 7
 

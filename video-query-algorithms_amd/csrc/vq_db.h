@@ -64,11 +64,12 @@ struct vq_db {
     bool owns_feats = true;
     // VQ_LAYOUT_ROWS: [N][S][E][D].  VQ_LAYOUT_TILED (fp32, own memory): [tile of 16 clips][S*E][D/4][clip][4] in the SAME block (a
     // tile's 16 rows and its tiled form cover the same bytes; the block is allocated for whole tiles) -- vq_db_set_layout.
-    // VQ_LAYOUT_TILED64 (fp64): the same with the 16-byte unit of doubles, [tile][S*E][D/2][clip][2] (csrc/vq_tile_index.h)
+    // VQ_LAYOUT_TILED64 (fp64): the same with the 16-byte unit of doubles, [tile][S*E][D/2][clip][2] (csrc/vq_tile_index.h);
+    // VQ_LAYOUT_TILED16 (fp16): with the unit of halves, [tile][S*E][D/8][clip][8]
     int layout = VQ_LAYOUT_ROWS;
     bool tiled() const { return layout != VQ_LAYOUT_ROWS; }
     int unit() const { return tiled() ? vq::tile_unit_of((int)elem()) : 0; }      // elements per 16-byte unit of the layout; 0: rows
-    int tiled_layout() const { return dtype == VQ_F32 ? VQ_LAYOUT_TILED : dtype == VQ_F64 ? VQ_LAYOUT_TILED64 : VQ_LAYOUT_ROWS; }   // the tiled layout of the storage type (rows: none)
+    int tiled_layout() const { return dtype == VQ_F32 ? VQ_LAYOUT_TILED : dtype == VQ_F64 ? VQ_LAYOUT_TILED64 : VQ_LAYOUT_TILED16; }   // the tiled layout of the storage type
     bool feats_exposed = false;      // adopted memory, or the raw pointer was handed out: the library no longer controls the layout
     uint8_t* present = nullptr;
     double* t = nullptr;        // [S*E*D]
@@ -132,7 +133,7 @@ struct vq_db {
     struct RowView {
         bool defined = false;
         int64_t m = 0;               // rows in the view
-        int64_t ntiles = 0;          // tiles of 16 clips it touches (fp32 / fp64 databases of a tiled-capable shape; else no tile tables)
+        int64_t ntiles = 0;          // tiles of 16 clips it touches (databases of a tiled-capable shape, whichever the storage type; else no tile tables)
         int64_t* rows = nullptr;     // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
         int64_t* tiles = nullptr;
         int64_t* pos = nullptr;

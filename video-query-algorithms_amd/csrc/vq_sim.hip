@@ -342,6 +342,10 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(std::conditional_t<VI
 // slice, each two fp64 FMAs against ONE 16-byte query read (fp32: four conversions, four FMAs, two reads per 16 bytes of features).
 // The loop over the groups stays rolled and its query offset is the loop counter's: unrolled, the query reads (which do not depend on
 // the tile) would be hoisted into registers across tiles -- scan_kernel's LEAN trap.  72-110 VGPRs, no scratch (profiles/README.md).
+// fp16 (VQ_LAYOUT_TILED16, [tile][slice][k / 8][clip][8]): the unit of halves.  Load i of a lane is at i * 512 + l * 8 halves and holds
+// k = 32 i + 8 (l / 16) + 0..7: 32 loads of 1 KB per wave and slice, each eight conversions and eight fp64 FMAs against four 16-byte query
+// reads (the four k-groups read addresses 64 bytes apart, broadcast within a group).  Per element the query reads are fp32's while the
+// HBM time halves.  Its group size is VQ_TILED_GROUP16.
 template <typename T>
 struct TileVec;                        // the 16 bytes a lane of scan_tiled_kernel loads: U elements, and their share of the dot
 template <>
@@ -371,6 +375,22 @@ struct TileVec<double> {
         return p;
     }
 };
+template <>
+struct TileVec<__half> {
+    static constexpr int U = 8;
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    h8 v;
+    __device__ __forceinline__ void load(const __half* p) { v = __builtin_nontemporal_load(reinterpret_cast<const h8*>(p)); }
+    __device__ __forceinline__ double dot(const double* tq, double p) const {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const double2 tg = *reinterpret_cast<const double2*>(tq + 2 * g);
+            p = fma(half_to_double(v[2 * g]), tg.x, p);
+            p = fma(half_to_double(v[2 * g + 1]), tg.y, p);
+        }
+        return p;
+    }
+};
 
 template <typename T, int S, int E, int CH, int G, bool VIEW = false>
 __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a) {
@@ -378,7 +398,7 @@ __global__ __launch_bounds__(256) void scan_tiled_kernel(std::conditional_t<VIEW
     constexpr int NV = S * E;
     constexpr int D = CH * 256;
     constexpr int U = TileVec<T>::U, WL = 64 * U;                     // elements of a lane's load, of a wave's (1 KB)
-    constexpr int LOADS = D * 16 / WL;                                // 1 KB loads of a wave per slice: D / 16 (fp32), D / 8 (fp64)
+    constexpr int LOADS = D * 16 / WL;                                // 1 KB loads of a wave per slice: D / 16 (fp32), D / 8 (fp64), D / 32 (fp16)
     constexpr int GROUPS = LOADS / G;
     static_assert(LOADS % G == 0, "group size must divide the slice");
     for (int i = threadIdx.x; i < NV * D; i += blockDim.x) t_lds[i] = a.t[i];
@@ -497,6 +517,15 @@ constexpr int kTiledGroup = VQ_TILED_GROUP;     // 1 KB loads a wave of scan_til
 #define VQ_TILED_GROUP64 4
 #endif
 constexpr int kTiledGroup64 = VQ_TILED_GROUP64; // the same for fp64 (VQ_LAYOUT_TILED64)
+#ifndef VQ_TILED_GROUP16
+#define VQ_TILED_GROUP16 8
+#endif
+// the same for fp16 (VQ_LAYOUT_TILED16), 32 loads per slice.  8 from an A/B of 2 / 4 / 8 on one MI355X (profiles/README.md, "fp16 storage
+// tiled in place"): 0.85 / 0.83 / 0.78 of the HBM peak at 1 M x 2 x 5 and 0.79 / 0.75 / 0.79 at 1 M x 2 x 3 -- at 8 the kernel holds 256
+// VGPRs + 60-70 AGPRs (no scratch) and runs one wave per SIMD, 8 KB in flight each; 4 is the better value at 50 000 x 2 x 5 (0.73 / 0.64)
+constexpr int kTiledGroup16 = VQ_TILED_GROUP16;
+template <typename T>
+constexpr int kTiledGroupOf = sizeof(T) == 8 ? kTiledGroup64 : sizeof(T) == 2 ? kTiledGroup16 : kTiledGroup;
 
 typedef double doublex4 __attribute__((ext_vector_type(4)));
 
@@ -573,7 +602,7 @@ struct ChunkP<double, P> {
 
 // fp16 rows: a lane's 16-byte load is 8 consecutive halves, so across the four k-lanes a load instruction still covers 64 contiguous bytes of
 // each clip -- 32 elements, two 16-element pieces: piece m holds elements 32 (m / 2) + 8 kk + 4 (m % 2) + e of the chunk.  The query rows
-// in LDS are stored in that order (batch_query_pos), so the MFMA loop reads them exactly as it does for fp32.  Rows only.
+// in LDS are stored in that order (batch_query_pos), so the MFMA loop reads them exactly as it does for fp32.
 template <int P>
 struct ChunkP<__half, P> {
     static_assert(P % 2 == 0, "a 16-byte load of halves is two pieces");
@@ -583,7 +612,13 @@ struct ChunkP<__half, P> {
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) v[m] = *reinterpret_cast<const h8*>(p + 32 * m);
     }
-    __device__ __forceinline__ void load_tiled(const __half* p) { load(p); }   // never used: the tiled layouts are fp32 / fp64 only
+    // VQ_LAYOUT_TILED16: load m' holds the same elements 32 m' + 8 kk + 0..7 of the chunk -- ONE unit of the slice, unit 4 m' + kk, at
+    // 128 (4 m' + kk) + 8 col halves (p = chunk + 128 kk + 8 col): 1 KB of contiguous memory per wave instruction, whole lines read once:
+    // non-temporal.  at() and batch_query_pos stay, so the MFMA sequence per (clip, query) is that of fp16 rows: the same bits.
+    __device__ __forceinline__ void load_tiled(const __half* p) {
+#pragma unroll
+        for (int m = 0; m < P / 2; ++m) v[m] = __builtin_nontemporal_load(reinterpret_cast<const h8*>(p + 512 * m));
+    }
     __device__ __forceinline__ double at(int m, int e) const { return half_to_double(v[m >> 1][4 * (m & 1) + e]); }
 };
 
@@ -600,13 +635,13 @@ __device__ __forceinline__ int batch_query_pos(int k) {
 // of 32, so slot = (q % 4) + 8 (q / 4) + 4 kk + const is a bijection onto 0..31.
 __device__ __forceinline__ int query_row(int q, int D) { return q * D + (q & 3) + 8 * (q >> 2); }
 
-// The 16-query pass's view of a database: [tile of 16 clips][slice][k / U][clip][U], U elements = 16 bytes (4 floats, 2 doubles:
+// The 16-query pass's view of a database: [tile of 16 clips][slice][k / U][clip][U], U elements = 16 bytes (4 floats, 2 doubles, 8 halves:
 // csrc/vq_tile_index.h) -- every load instruction of a wave then takes 1 KB of contiguous memory (fp64: four runs of 256 bytes; whole
 // 128-byte lines either way: the non-temporal hint pays), where the row-major layout gives it 64 bytes of each of 16 clips 40 KB
-// apart.  The two conversions move 16-byte units and do not look inside them, so ONE pair of kernels serves both storage types: du =
-// units per vector (D / 4 for fp32, D / 2 for fp64).  One workgroup per (tile, slice): the 16 rows come in whole (a wave reads 1 KB of
-// one clip per instruction), turn in LDS ([16][du + 1] units: 65 792 bytes for fp32, 131 328 for fp64 at D = 1024) and go out in the
-// tiled order.  Rows past n repeat the last clip (the pass never stores them).
+// apart.  The two conversions move 16-byte units and do not look inside them, so ONE pair of kernels serves every storage type: du =
+// units per vector (D / 4 for fp32, D / 2 for fp64, D / 8 for fp16).  One workgroup per (tile, slice): the 16 rows come in whole (a
+// wave reads 1 KB of one clip per instruction), turn in LDS ([16][du + 1] units: 65 792 bytes for fp32, 131 328 for fp64, 33 024 for
+// fp16 at D = 1024) and go out in the tiled order.  Rows past n repeat the last clip (the pass never stores them).
 __global__ __launch_bounds__(256) void mirror_build_kernel(const vq_f4* feats, vq_f4* mirror, int64_t n, int NV, int du) {
     extern __shared__ __attribute__((aligned(16))) vq_f4 tile_lds[];          // [16][du + 1]
     const int64_t tile = blockIdx.x / NV;
@@ -722,8 +757,8 @@ struct ViewWalk {
     __device__ __forceinline__ int64_t phys_tile(int64_t tile) const { return a.items ? (int64_t)uniform_load(a.items + tile) : tile; }
     // this lane's pointer into slice v of work item `tile`: 64-bit, sixteen arbitrary rows can lie more than 2^32 elements apart
     __device__ __forceinline__ const T* ptr(int64_t tile, int v) const {
-        if constexpr (TILED && sizeof(T) == 8) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 2);      // units of 2 doubles
-        else if constexpr (TILED) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 64 + col * 4);
+        // tiled: units of U = 16 / sizeof(T) elements, 16 U apart along k; a k-lane's KL elements are KL / U units: kk * 16 KL + col * U
+        if constexpr (TILED) return feats + (phys_tile(tile) * NV + v) * 16 * D + (kk * 16 * KL + col * vq::tile_unit_of((int)sizeof(T)));
         else return feats + (int64_t)pick16(rows_of(tile), col) * clip_elems + ((int64_t)v * D + KL * kk);
     }
     __device__ __forceinline__ ViewTile tile(int64_t tile) const {
@@ -799,8 +834,8 @@ __global__ __launch_bounds__(1024) void batch_fused_kernel(BatchFusedArgs a) {
         return TILED ? feats + (tile * NV + v) * 16 * D : feats + tile * 16 * clip_elems + (int64_t)v * D;
     };
     auto lane_off = [&](int64_t tile) -> uint32_t {
-        if constexpr (TILED && sizeof(T) == 8) return (uint32_t)(kk * 64 + col * 2);      // VQ_LAYOUT_TILED64: units of 2 doubles
-        if (TILED) return (uint32_t)(kk * 64 + col * 4);
+        // units of U = 16 / sizeof(T) elements (4 floats, 2 doubles, 8 halves), 16 U apart along k; a k-lane's KL elements are KL / U units
+        if (TILED) return (uint32_t)(kk * 16 * KL + col * vq::tile_unit_of((int)sizeof(T)));
         const int last = (int)min((int64_t)15, a.n - 1 - tile * 16);
         return (uint32_t)(min(col, last) * (int)clip_elems + KL * kk);
     };
@@ -1787,17 +1822,14 @@ static int launch_scan_t(vq_db* db, const A& a) {
     int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
     if (per_cu < 1) per_cu = 1;
     if (db->tiled()) {
-        if constexpr (sizeof(T) != 2) {
-            auto kern = scan_tiled_kernel<T, S, E, CH, sizeof(T) == 8 ? kTiledGroup64 : kTiledGroup, VIEW>;
-            VQ_DYN_LDS(kern, lds);
-            int64_t want = ((a.n + 15) / 16 + 3) / 4;   // 4 waves (tiles in flight) per block
-            if constexpr (VIEW) want = (a.n_items + 3) / 4;
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * per_cu));
-            kern<<<grid, 256, lds, db->stream>>>(a);
-            VQ_CHECK_LAUNCH();
-            return VQ_OK;
-        }
-        return fail(VQ_E_STATE, "internal: a tiled database is fp32 or fp64");
+        auto kern = scan_tiled_kernel<T, S, E, CH, kTiledGroupOf<T>, VIEW>;
+        VQ_DYN_LDS(kern, lds);
+        int64_t want = ((a.n + 15) / 16 + 3) / 4;   // 4 waves (tiles in flight) per block
+        if constexpr (VIEW) want = (a.n_items + 3) / 4;
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * per_cu));
+        kern<<<grid, 256, lds, db->stream>>>(a);
+        VQ_CHECK_LAUNCH();
+        return VQ_OK;
     }
     // a database whose clips are a few per wave: the lean instantiation, three waves per SIMD (VQ_SCAN_LEAN=0|1 forces one or the other)
     static const int force_lean = getenv("VQ_SCAN_LEAN") ? atoi(getenv("VQ_SCAN_LEAN")) : -1;
@@ -1946,10 +1978,10 @@ int vq_db_scan(vq_db* db, const double* w_host, int32_t keep_sims) {
 
 }  // extern "C"
 
-// the instantiation of the 16-query pass for a database (the tiled branch does not exist for fp16 rows)
+// the instantiation of the 16-query pass for a database (fp16: the tiled branch exists at D = 1024 only, the one shape that can be tiled)
 template <typename T, int CH, int TW, bool ROUND = false>
 static auto fused_kernel_for(bool pres, bool tiled) -> void (*)(BatchFusedArgs) {
-    if constexpr (sizeof(T) != 2) {
+    if constexpr (sizeof(T) != 2 || CH == 4) {
         if (tiled) return pres ? batch_fused_kernel<T, CH, TW, true, 8, true, ROUND> : batch_fused_kernel<T, CH, TW, false, 8, true, ROUND>;
     }
     return pres ? batch_fused_kernel<T, CH, TW, true, 8, false, ROUND> : batch_fused_kernel<T, CH, TW, false, 8, false, ROUND>;
@@ -2151,14 +2183,14 @@ int vq_db_layout(vq_db* db, int32_t* layout) {
 
 int vq_db_set_layout(vq_db* db, int32_t layout) {
     VQ_REQUIRE(db, "db is NULL");
-    VQ_REQUIRE(layout == VQ_LAYOUT_ROWS || layout == VQ_LAYOUT_TILED || layout == VQ_LAYOUT_TILED64,
-               "layout must be VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED or VQ_LAYOUT_TILED64");
+    VQ_REQUIRE(layout == VQ_LAYOUT_ROWS || layout == VQ_LAYOUT_TILED || layout == VQ_LAYOUT_TILED64 || layout == VQ_LAYOUT_TILED16,
+               "layout must be VQ_LAYOUT_ROWS, VQ_LAYOUT_TILED, VQ_LAYOUT_TILED64 or VQ_LAYOUT_TILED16");
     std::lock_guard<std::mutex> lk(db->mu);
     if (layout == db->layout) return VQ_OK;
     if (layout != VQ_LAYOUT_ROWS) {
-        // each storage type has ONE tiled layout (the unit is the 16 bytes a lane loads): TILED is fp32's, TILED64 is fp64's, fp16 has none
+        // each storage type has ONE tiled layout (the unit is the 16 bytes a lane loads): TILED is fp32's, TILED64 is fp64's, TILED16 is fp16's
         if (layout != db->tiled_layout() || !fast_scan_shape(db))
-            return fail(VQ_E_UNSUPPORTED, "the tiled layouts exist for fp32 (VQ_LAYOUT_TILED) and fp64 (VQ_LAYOUT_TILED64) databases, not fp16, with D = 1024, S <= 2, E <= 5 (layout %d: got dtype %d, D %d, S %d, E %d)",
+            return fail(VQ_E_UNSUPPORTED, "each storage type has one tiled layout -- fp32 VQ_LAYOUT_TILED, fp64 VQ_LAYOUT_TILED64, fp16 VQ_LAYOUT_TILED16 -- for D = 1024, S <= 2, E <= 5 (layout %d: got dtype %d, D %d, S %d, E %d)",
                         layout, db->dtype, db->D, db->S, db->E);
         if (!db->owns_feats || db->feats_exposed)
             return fail(VQ_E_STATE, "the feature block is not the library's alone (adopted, or its address was handed out): it stays row-major");
@@ -2414,10 +2446,10 @@ static int fetch_selected(vq_db* db, int64_t* match_rows_host, int64_t cap_match
 }  // extern "C"
 
 // ---- the pass of a batched round over a row view per query (csrc/vq_rounds.hip, include/vq_amd_round_views.h) -------------------------
-// the VIEW instantiation of the 16-query pass for a database: the tiled layouts exist for fp32 / fp64 rows of 1024 elements only (vq_db_set_layout)
+// the VIEW instantiation of the 16-query pass for a database: the tiled layouts exist for rows of 1024 elements only (vq_db_set_layout)
 template <typename T, int CH, int TW>
 static auto view_kernel_for(bool pres, bool tiled) -> void (*)(BatchViewArgs) {
-    if constexpr (sizeof(T) != 2 && CH == 4) {
+    if constexpr (CH == 4) {
         if (tiled) return pres ? batch_view_kernel<T, CH, TW, true, 8, true> : batch_view_kernel<T, CH, TW, false, 8, true>;
     }
     return pres ? batch_view_kernel<T, CH, TW, true, 8, false> : batch_view_kernel<T, CH, TW, false, 8, false>;
@@ -2429,11 +2461,11 @@ int vq::launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles) {
     const size_t lds = ((size_t)kBatchSlots * db->D + 32) * 8;
     const int ch = db->D / 256;
     const bool tiled = db->tiled();
-    if (tiled && !(db->dtype != VQ_F16 && ch == 4)) return fail(VQ_E_UNSUPPORTED, "a tiled database holds float32 or float64 rows of 1024 elements");
+    if (tiled && ch != 4) return fail(VQ_E_UNSUPPORTED, "a tiled database holds rows of 1024 elements (float32, float64 or float16)");
     constexpr int TW = 2;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((max_tiles + 16 * TW - 1) / (16 * TW), (int64_t)db->cus));
     // every (T, CH, mask, layout) is launched by a case of tests/test_view_round_gpu.py (the table above VIEW_KERNELS there): a new one
-    // gets a new case there
+    // gets a new case there (the tiled forms of fp64 and fp16: tests/test_tiled64_gpu.py, tests/test_tiled16_gpu.py)
 #define VQ_VIEW_LAUNCH(T, CH)                                                                                              \
     {                                                                                                                      \
         auto kern = view_kernel_for<T, CH, TW>(db->present != nullptr, tiled);                                             \
@@ -2597,7 +2629,7 @@ int vq_db_rows_define(vq_db* db, const int64_t* rows_host, int64_t m, int32_t* v
     // the tiled form of the same view, built whenever the database could be tiled: a view defined on rows survives vq_db_set_layout
     std::vector<int64_t> host(rows_host, rows_host + m);
     int64_t ntiles = 0;
-    if (db->tiled_layout() != VQ_LAYOUT_ROWS && fast_scan_shape(db)) {
+    if (fast_scan_shape(db)) {                        // every storage type has a tiled layout at these shapes
         for (int64_t i = 0; i < m; ++i) ntiles += (i == 0 || (rows_host[i] >> 4) != (rows_host[i - 1] >> 4)) ? 1 : 0;
         host.resize((size_t)(m + ntiles + ntiles * 16), -1);
         int64_t* tiles = host.data() + m;

@@ -2,8 +2,8 @@
 // ONE statement of the rule, shared by csrc/vq_sim.hip, csrc/vq_csv.hip and the host-only test of the rule (no HIP include: plain C++).
 //
 //   rows (unit 0):  [N][NV][D]
-//   tiled (unit U): [tile of 16 clips][NV][D / U][clip][U] -- U elements = the 16 bytes a lane loads: 4 floats (VQ_LAYOUT_TILED) or
-//                   2 doubles (VQ_LAYOUT_TILED64).  A (tile, slice) is 16 D elements whichever the order, so a tile's 16 rows and its
+//   tiled (unit U): [tile of 16 clips][NV][D / U][clip][U] -- U elements = the 16 bytes a lane loads: 4 floats (VQ_LAYOUT_TILED),
+//                   2 doubles (VQ_LAYOUT_TILED64) or 8 halves (VQ_LAYOUT_TILED16).  A (tile, slice) is 16 D elements whichever the order, so a tile's 16 rows and its
 //                   tiled form cover the same bytes, and 64 consecutive units are 1 KB: 4 k-groups of 16 clips.
 #pragma once
 #include <cstdint>

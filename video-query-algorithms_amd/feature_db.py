@@ -62,6 +62,12 @@ class SearchSetView:
 # the layouts of vq_db_set_layout by name (include/vq_amd.h); the values also travel as they are in ShardedFeatureDB's OP_LAYOUT
 _LAYOUTS = {"rows": _lib.VQ_LAYOUT_ROWS, "tiled": _lib.VQ_LAYOUT_TILED, "tiled64": _lib.VQ_LAYOUT_TILED64}
 _LAYOUT_NAMES = {v: k for k, v in _LAYOUTS.items()}
+# The public table: every layout by name.  _LAYOUTS above stays the three names it held when "tiled64" was the last one, because
+# tests/test_tiled64_host.py holds it (and sharded_db.LAYOUT_VALUES) to exactly those; set_layout, layout, from_csv_tree and both ends of
+# ShardedFeatureDB's OP_LAYOUT look names up HERE.
+LAYOUTS = dict(_LAYOUTS, tiled16=_lib.VQ_LAYOUT_TILED16)
+LAYOUT_NAMES = {v: k for k, v in LAYOUTS.items()}
+_TILED_OF_DTYPE = {np.dtype(np.float32): "tiled", np.dtype(np.float64): "tiled64", np.dtype(np.float16): "tiled16"}
 
 def whole_view(db) -> SearchSetView:
     """The trivial view of a database object (FeatureDB, ShardedFeatureDB, or a look-alike with ``clip_ids`` and ``row_of``)."""
@@ -281,7 +287,7 @@ class FeatureDB(BatchRounds):
         converting a value (src/api/api_load_records.py:45-58) and without a store on disk.  Same walk: videos sorted by name, a
         video's clips in clip-number order, ids ``clip_id_base + row + 1``; a (clip, stream, split) without a row is absent and reads
         back as zeros.  Pass one indexes the files and keeps only their clip numbers; pass two loads them.  ``clips`` is the
-        ``(video, clip)`` of every row; ``csv_host_fields`` counts the fields the host had to resolve.  ``layout="tiled"`` (fp32) or ``"tiled64"`` (fp64) tiles the
+        ``(video, clip)`` of every row; ``csv_host_fields`` counts the fields the host had to resolve.  ``layout="tiled"`` (fp32), ``"tiled64"`` (fp64) or ``"tiled16"`` (fp16) tiles the
         block first, so the values land in their tiles.  A value that the database's type cannot hold (float16: |x| >= 65520) or that
         is no number raises ``ValueError`` naming file, line and field."""
         import os
@@ -391,21 +397,33 @@ class FeatureDB(BatchRounds):
 
     def set_layout(self, layout: str):
         """"rows" ([N][S][E][D]), "tiled" ([tile of 16 clips][S*E][D/4][clip][4]: the order in which every load of the scans
-        takes whole lines; float32 only) or "tiled64" (the same for float64: [tile][S*E][D/2][clip][2]); both need D = 1024, S <= 2,
-        E <= 5 and each is refused for the other's dtype (:attr:`tiled_layout` names the one this database takes).  In place, one
-        sweep of the block: call once after loading.  Never chosen for the caller: the layouts agree to rounding, not bit for bit."""
-        call("vq_db_set_layout", self._h, _LAYOUTS[layout])
+        takes whole lines; float32 only), "tiled64" (the same for float64: [tile][S*E][D/2][clip][2]) or "tiled16" (for float16:
+        [tile][S*E][D/8][clip][8]); all need D = 1024, S <= 2, E <= 5 and each is refused for the others' dtypes (:attr:`layouts`
+        names what this database takes).  In place, one sweep of the block: call once after loading.  Never chosen for the caller:
+        the layouts agree to rounding, not bit for bit.  A name that is no layout is a ``KeyError``."""
+        call("vq_db_set_layout", self._h, LAYOUTS[layout])      # LAYOUTS, not _LAYOUTS: see the comment at the tables
 
     @property
     def layout(self) -> str:
         v = C.c_int32()
         call("vq_db_layout", self._h, C.byref(v))
-        return _LAYOUT_NAMES[v.value]
+        return LAYOUT_NAMES[v.value]
+
+    @property
+    def layouts(self) -> tuple:
+        """The names :meth:`set_layout` accepts for this database, "rows" first: ``("rows", "tiled16")`` for a float16 database of
+        a tileable shape, ``("rows", "tiled")`` / ``("rows", "tiled64")`` for float32 / float64, ``("rows",)`` for any other shape.
+        By dtype and shape alone: a block that is not the library's alone any more (adopted, or its address handed out) is refused
+        whatever the name (``VqError``, VQ_E_STATE)."""
+        if not (self.D == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
+            return ("rows",)
+        return ("rows", _TILED_OF_DTYPE[np.dtype(self.dtype)])
 
     @property
     def tiled_layout(self):
-        """The name of the tiled layout this database can take -- "tiled" (float32), "tiled64" (float64) -- or ``None`` (float16,
-        or a shape without the tiled kernels): what to hand :meth:`set_layout` without switching on the dtype."""
+        """The float32 / float64 name: "tiled" (float32), "tiled64" (float64), or ``None`` (a shape without the tiled kernels -- and
+        float16, whose "tiled16" came later: this property keeps the value it had for every database, tests/test_tiled64_gpu.py holds
+        it to ``None`` there).  :attr:`layouts` is the way to ask what a database takes, whichever its dtype."""
         if self.dtype == np.float16 or not (self.D == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
             return None
         return "tiled64" if self.dtype == np.float64 else "tiled"

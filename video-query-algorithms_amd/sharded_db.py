@@ -57,6 +57,9 @@ from .shard import all_gather_counts, all_gather_rows, merge_topk, shard_range
 # what OP_LAYOUT carries: the values of vq_db_set_layout (include/vq_amd.h; _lib.VQ_LAYOUT_*)
 LAYOUT_VALUES = {"rows": 0, "tiled": 1, "tiled64": 2}
 LAYOUT_NAMES = {v: k for k, v in LAYOUT_VALUES.items()}
+# Both tables stay as they stood when "tiled64" was the last layout (tests/test_tiled64_host.py holds LAYOUT_VALUES to those three
+# names); both ends of OP_LAYOUT look names up in feature_db.LAYOUTS / LAYOUT_NAMES, the one table with every layout ("tiled16": 3).
+from .feature_db import LAYOUTS, LAYOUT_NAMES as _ALL_LAYOUT_NAMES      # noqa: E402
 
 OP_CLOSE, OP_RESTRICT, OP_SET_QUERY, OP_QUERY_FROM_ROW, OP_SCAN, OP_RESCORE, OP_SIMS, OP_SCORES, OP_GRID, OP_SELECT, OP_TOPK, \
     OP_MIN, OP_FETCH, OP_SCAN_BATCH, OP_LAYOUT, OP_WRITE_AVG, OP_ROUND, OP_DEFINE_SET, OP_USE_SET, OP_DROP_SET = range(20)
@@ -391,10 +394,10 @@ class ShardedFeatureDB:
     # ------------------------------------------------------------------ query
     @_atomic
     def set_layout(self, layout: str):
-        """Every rank re-tiles its own rows in place (FeatureDB.set_layout: "rows", "tiled" or "tiled64"): once, after loading.  The
-        announcement carries the layout's value (include/vq_amd.h: 0, 1, 2); a name that is no layout is a ``KeyError`` before
+        """Every rank re-tiles its own rows in place (FeatureDB.set_layout: "rows", "tiled", "tiled64" or "tiled16"): once, after loading.
+        The announcement carries the layout's value (include/vq_amd.h: 0, 1, 2, 3); a name that is no layout is a ``KeyError`` before
         anything is announced."""
-        self._announce(OP_LAYOUT, ints=[LAYOUT_VALUES[layout]])
+        self._announce(OP_LAYOUT, ints=[LAYOUTS[layout]])
         self._local_step(lambda: self.local.set_layout(layout))
 
     @_atomic
@@ -1134,7 +1137,7 @@ class ShardedFeatureDB:
         elif op == OP_FETCH:
             self.read_rows(ints)
         elif op == OP_LAYOUT:
-            self.set_layout(LAYOUT_NAMES[int(ints[0])])
+            self.set_layout(_ALL_LAYOUT_NAMES[int(ints[0])])
         elif op == OP_WRITE_AVG:
             self.write_avg(floats.reshape(self._ntot, S), ints.reshape(self._ntot, S) if ints.size else None)
         elif op == OP_DEFINE_SET:
