@@ -11,7 +11,7 @@ for r in csv.DictReader(open(stats)):
            else "scan_tiled_kernel" if "scan_tiled_kernel" in name else "scan_kernel (row-major block, before the in-place tiling)" if "scan_kernel" in name
            else "batch_fused_kernel (16-query pass)" if "batch_fused" in name and "true>" in name
            else "batch_fused_kernel on the row-major block" if "batch_fused" in name
-           else "pool/gavgpool/preprocess/consensus" if any(k in name for k in ("pool_kernel", "gavgpool", "preprocess", "consensus"))
+           else "pool/gavgpool/preprocess/consensus" if any(k in name for k in ("pool_kernel", "pool_fast_kernel", "gavgpool", "preprocess", "consensus"))
            else "other")
     f = fam.setdefault(key, [0, 0.0])
     f[0] += int(r["Calls"])

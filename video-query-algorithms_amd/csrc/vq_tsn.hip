@@ -887,12 +887,14 @@ __global__ __launch_bounds__(256) void pool_gemm_kernel(ConvArgs a) {
 // pooling (Caffe semantics: ceil-mode output size; MAX ignores padding; AVE divides by the window
 // clipped to the padded extent and accumulates h-major in fp32)
 // ------------------------------------------------------------------------------------------------
-// PoolArgs / pool_one: vq_tsn_kernels.h (shared with the grouped Winograd launch, which also carries a level's pooling)
+// PoolArgs / pool_one / pool_unit: vq_tsn_kernels.h (shared with the grouped Winograd launch, which also carries a level's pooling)
 template <bool IS_MAX>
 __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < a.total) pool_one<IS_MAX>(a, i);
 }
+// a.mode != 0 (pool_plan): the window-specialised path, kPoolPerWG outputs per workgroup -- the code a grouped launch runs
+__global__ __launch_bounds__(256) void pool_fast_kernel(PoolArgs a) { pool_unit_any(a, blockIdx.x); }
 
 // global average pool (Caffe AVE, kernel = whole map): sequential fp32 sum over h, w then / (H*W)
 __global__ void gavgpool_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int HW, int Cs_in, int coff_in,
@@ -968,14 +970,18 @@ __global__ __launch_bounds__(64) void inner_product_kernel(const float* __restri
 // are fewer output tiles than compute units, and one wave per SIMD cannot hide its own load latency): the slices' partial
 // sums are added in slice order, then bias and ReLU -- a fixed order for every batch size and tiling, so the rule "which
 // layers are split" (layer geometry only) keeps the features independent of how crops are batched.
-__global__ void splitk_combine_kernel(const float* __restrict__ part, int ksplit, size_t slice_stride, int M, int Cout,
-                                      const float* __restrict__ bias, int relu, float* __restrict__ out, int Cs_out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c4 = Cout / 4;
-    if (i >= (int64_t)M * c4) return;
-    const int m = (int)(i / c4), n = (int)(i - (int64_t)m * c4) * 4;
-    floatx4 v = *reinterpret_cast<const floatx4*>(part + (size_t)m * Cout + n);
-    for (int q = 1; q < ksplit; ++q) v += *reinterpret_cast<const floatx4*>(part + q * slice_stride + (size_t)m * Cout + n);
+// Workgroup (blockIdx.x, blockIdx.y) = 4 rows x 64 channel quads, one wave per row: no division, and 32-bit element offsets (the
+// launch checks M * Cout and M * Cs_out against 2^31).
+__global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __restrict__ part, int ksplit, size_t slice_stride, int M, int Cout,
+                                                             const float* __restrict__ bias, int relu, float* __restrict__ out, int Cs_out) {
+    const unsigned m = blockIdx.x * 4u + (threadIdx.x >> 6), n = (blockIdx.y * 64u + (threadIdx.x & 63u)) * 4u;
+    if (m >= (unsigned)M || n >= (unsigned)Cout) return;
+    const unsigned at = m * (unsigned)Cout + n;
+    floatx4 v = *reinterpret_cast<const floatx4*>(part + at);
+    for (int q = 1; q < ksplit; ++q) {
+        part += slice_stride;
+        v += *reinterpret_cast<const floatx4*>(part + at);
+    }
     v += *reinterpret_cast<const floatx4*>(bias + n);
     if (relu) {
         v[0] = fmaxf(v[0], 0.f);
@@ -983,7 +989,7 @@ __global__ void splitk_combine_kernel(const float* __restrict__ part, int ksplit
         v[2] = fmaxf(v[2], 0.f);
         v[3] = fmaxf(v[3], 0.f);
     }
-    *reinterpret_cast<floatx4*>(out + (size_t)m * Cs_out + n) = v;
+    *reinterpret_cast<floatx4*>(out + (m * (unsigned)Cs_out + n)) = v;
 }
 
 // global average pool + segment consensus in one pass: a snippet's global_pool value is formed exactly
@@ -1389,8 +1395,8 @@ static int launch_conv_layer(const vq_tsn* net, const Launch& ln, int li, int n_
     if (rc != VQ_OK) return rc;
     const vq_tensor_desc& td = net->plan.tensors[L.dst];
     float* out = net->slots[L.dst] + (size_t)ln.crop0 * td.h * td.w * td.c + L.dst_coff;
-    const int64_t work = (int64_t)a.M * (L.cout / 4);
-    VQ_LAUNCH(splitk_combine_kernel, (unsigned)cdiv(work, 256), 256, 0, combine.stream, combine.ev_start, combine.ev_stop,
+    VQ_REQUIRE((int64_t)a.M * L.cout < (1ll << 31) && (int64_t)a.M * td.c < (1ll << 31), "layer %d: K-split combine pass beyond 32-bit offsets (split the batch)", li);
+    VQ_LAUNCH(splitk_combine_kernel, dim3((unsigned)cdiv(a.M, 4), (unsigned)cdiv(L.cout / 4, 64)), 256, 0, combine.stream, combine.ev_start, combine.ev_stop,
               net->split_scratch + (size_t)a.out_row0 * L.cout, a.ksplit, net->split_slice_floats, a.M, L.cout, net->blob + L.b_off, L.relu, out, td.c);
     VQ_CHECK_LAUNCH();
     return VQ_OK;
@@ -1448,6 +1454,11 @@ static void fill_pool_args(const vq_tsn* net, const Launch& ln, int li, int n_cr
     a.total = (int64_t)n_crops * td.h * td.w * (L.cin / 4);
     a.bias = (L.op == VQ_OP_AVGPOOL && L.has_bias) ? net->blob + L.b_off : nullptr;
     a.relu = (L.op == VQ_OP_AVGPOOL) ? L.relu : 0;
+    // the specialised path addresses both slots with 32-bit byte offsets; slots beyond that keep the generic path (mode 0)
+    const size_t in_bytes = (size_t)n_crops * ts.h * ts.w * ts.c * sizeof(float), out_bytes = (size_t)n_crops * td.h * td.w * td.c * sizeof(float);
+    a.in_bytes = in_bytes <= 0x7FFFFFF0u ? (unsigned)in_bytes : 0u;
+    a.out_bytes = out_bytes <= 0x7FFFFFF0u ? (unsigned)out_bytes : 0u;
+    pool_plan(a, n_crops);
 }
 
 // The Winograd layers among `members` (independent of each other) plus the pooling layers among them as one launch.
@@ -1653,7 +1664,9 @@ static int run_layer(const vq_tsn* net, const Launch& ln, int li, int n_crops, i
         PoolArgs a;
         fill_pool_args(net, ln, li, n_crops, a);
         const int64_t blocks = (a.total + 255) / 256;
-        if (L.op == VQ_OP_MAXPOOL)
+        if (a.mode)
+            VQ_LAUNCH(pool_fast_kernel, (unsigned)((a.total + kPoolPerWG - 1) / kPoolPerWG), 256, 0, ln.stream, ln.ev_start, ln.ev_stop, a);
+        else if (L.op == VQ_OP_MAXPOOL)
             VQ_LAUNCH(pool_kernel<true>, (unsigned)blocks, 256, 0, ln.stream, ln.ev_start, ln.ev_stop, a);
         else
             VQ_LAUNCH(pool_kernel<false>, (unsigned)blocks, 256, 0, ln.stream, ln.ev_start, ln.ev_stop, a);

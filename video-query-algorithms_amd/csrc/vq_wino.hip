@@ -561,6 +561,10 @@ void wino_f2x2_3x3_kernel(WinoGroup g) {
         const PoolArgs& pa = g.pool[q];
         const int unit = b - pa.unit0;
         if (unit >= pa.n_units) return;
+        if (pa.mode) {
+            pool_unit_any(pa, (unsigned)unit);
+            return;
+        }
 #pragma unroll
         for (int r = 0; r < kPoolPerWG / 256; ++r) {
             const int64_t i = (int64_t)unit * kPoolPerWG + r * 256 + threadIdx.x;
