@@ -1,4 +1,4 @@
-"""Test infrastructure for the dot products in front of the ranking kernels (csrc/vq_sim.hip: scan_kernel, scan_tiled_kernel,
+"""Test infrastructure for the dot products in front of the ranking kernels (csrc/vq_sim.hip, csrc/vq_sim_batch.hip: scan_kernel, scan_tiled_kernel,
 scan_generic_kernel, batch_fused_kernel, batch_view_kernel): hard feature vectors with an EXACT reference and a DERIVED tolerance.
 tests/test_dot_cases.py checks this table on the CPU, tests/test_dot_hard_gpu.py and tests/_dot_hard_child.py run the kernels on it.
 

@@ -1,4 +1,4 @@
-"""Test infrastructure (GPU box): one table of tests/_dot_cases.py through one path of csrc/vq_sim.hip -- shared by
+"""Test infrastructure (GPU box): one table of tests/_dot_cases.py through one path of csrc/vq_sim.hip or csrc/vq_sim_batch.hip -- shared by
 tests/test_dot_hard_gpu.py (this process) and tests/_dot_hard_child.py (one process per forced scan_kernel instantiation).
 
 Every function returns a ``Visit``: the worst |err| / bound per family and how many scans ran, so that a test can assert what it

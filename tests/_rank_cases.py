@@ -1,5 +1,5 @@
 """Test infrastructure, no GPU: the table of hard score rows for the one-query ranking kernels (select_small / select_count / scan /
-scatter, topk_small / topk_hist / topk_pick, gather_scores in csrc/vq_sim.hip, the shared steps in csrc/vq_select.h).
+scatter, topk_small / topk_hist / topk_pick, gather_scores in csrc/vq_rank.hip, the shared steps in csrc/vq_select.h).
 
 A case is (family, variant, n) -> a float64 row, deterministic per (family, n); ``bands_of`` and ``ks_of`` give the (threshold, lower)
 bands and the k values a row is ranked under.  ``skipped_of`` / ``skipped_bands`` list what a size cannot hold BY CONSTRUCTION (a tie

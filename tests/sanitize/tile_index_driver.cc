@@ -15,7 +15,7 @@
 
 #include "vq_tile_index.h"
 
-static int64_t fp32_rule(int64_t row, int NV, int v, int D, int k) {      // as written in csrc/vq_sim.hip (feat_index) before
+static int64_t fp32_rule(int64_t row, int NV, int v, int D, int k) {      // as written in the feature database's unit (feat_index) before
     return (((row >> 4) * NV + v) * (int64_t)(D / 4) + (k >> 2)) * 64 + (row & 15) * 4 + (k & 3);
 }
 

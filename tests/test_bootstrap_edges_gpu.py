@@ -1,4 +1,4 @@
-"""GPU: the bootstrap kernel (csrc/vq_boot.hip) and scale_query_kernel (csrc/vq_sim.hip) at the edges, to the accuracy of their own
+"""GPU: the bootstrap kernel (csrc/vq_boot.hip) and scale_query_kernel (csrc/vq_db.hip) at the edges, to the accuracy of their own
 arithmetic.  tests/test_bootstrap_gpu.py holds them to the reference's recorded fixtures within 1e-8 (the conditioning of those
 fixtures through explicit 1024 x 1024 inverses); here the bound is what fp64 roundings of ONE formula can differ by.
 

@@ -1,4 +1,4 @@
-"""GPU: every dot-product kernel of csrc/vq_sim.hip on the hard rows of tests/_dot_cases.py -- mixed signs, cancellation, storage-type
+"""GPU: every dot-product kernel of csrc/vq_sim.hip and csrc/vq_sim_batch.hip on the hard rows of tests/_dot_cases.py -- mixed signs, cancellation, storage-type
 subnormals, values next to the largest finite one, 24 binades of range, signed zeros and single non-zeros at the lane, chunk and piece
 boundaries, infinities and NaNs -- against the exact dot with the derived bound D 2^-53 sum|x_k t_k| (no measured constant), classes for
 the non-finite rows, n_e exactly, scores bit for bit from the device's avg, a second run the same bits, row views bit for bit the full scan.

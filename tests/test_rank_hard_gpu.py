@@ -1,4 +1,4 @@
-"""GPU: the one-query ranking kernels of csrc/vq_sim.hip (select_small / select_count / select_scan / select_scatter, topk_small /
+"""GPU: the one-query ranking kernels of csrc/vq_rank.hip (select_small / select_count / select_scan / select_scatter, topk_small /
 topk_hist / topk_pick and the compaction with limit1, gather_scores) on the hard score rows of tests/_rank_cases.py, at every size cut.
 
 The rows are PLANTED: written over the handle's scores on the device (FeatureDB.device_tensor("scores")), read back, and every

@@ -72,11 +72,12 @@ def test_the_main_header_brings_the_round_topk_along_in_plain_c():
 
 
 def test_order_key_has_one_definition():
-    """The key of a ranking and the selection helpers both units use live in one header that both include."""
+    """The key of a ranking and the selection helpers live in one header that every unit using them includes (csrc/vq_db.hip takes the
+    block size of the selection scratch from it)."""
     csrc = os.path.join(ROOT, "video-query-algorithms_amd", "csrc")
     found = [fn for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h")) and re.search(r"uint64_t\s+order_key\s*\(", open(os.path.join(csrc, fn)).read())]
     assert found == ["vq_select.h"]
-    for unit in ("vq_sim.hip", "vq_rounds.hip", "vq_round_topk.hip"):
+    for unit in ("vq_rank.hip", "vq_db.hip", "vq_rounds.hip", "vq_round_topk.hip"):
         assert '#include "vq_select.h"' in open(os.path.join(csrc, unit)).read(), unit
 
 

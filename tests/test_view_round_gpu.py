@@ -88,7 +88,7 @@ CASES = [
 # one case per (dtype, D, mask) at n = 203, Q = 5, row-major: with the cases above these launch every VIEW instantiation
 SMALL = [(dt, 5, 203, 2, 2, d, m, "rows", ["all_but_one", "mod37", "run", "edges", "empty"])
          for dt in (np.float16, np.float32, np.float64) for d in (256, 512, 768, 1024) for m in (False, True)]
-# The instantiations launch_view_pass (csrc/vq_sim.hip) can choose -- batch_view_kernel<T, D / 256, 2, masked, 8, tiled>:
+# The instantiations launch_view_pass (csrc/vq_sim_batch.hip) can choose -- batch_view_kernel<T, D / 256, 2, masked, 8, tiled>:
 # 24 row-major ones, every (dtype, D, mask), launched by the SMALL cases (and again by CASES), and the two tiled ones (float32, D = 1024,
 # plain / masked), launched by the two tiled CASES.  A new storage type, width or layout there gets a new case and a new entry here.
 VIEW_KERNELS = {(dt, d, m, "rows") for dt in (np.float16, np.float32, np.float64) for d in (256, 512, 768, 1024) for m in (False, True)}

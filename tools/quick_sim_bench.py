@@ -136,7 +136,7 @@ def _timed(fn, tm):
     return ms.value
 
 
-MATRIX_MS_PER_ELEMENT = 4.2 / 10.24e9       # csrc/vq_sim.hip: 16 queries x 10.24 G elements are 4.2 ms of fp64 matrix time
+MATRIX_MS_PER_ELEMENT = 4.2 / 10.24e9       # csrc/vq_sim_batch.hip: 16 queries x 10.24 G elements are 4.2 ms of fp64 matrix time
 
 
 def bench_layout(layout, dtype, n=1_000_000, s=2, e=3, d=1024, q=16, reps=12, out=None, note=None):

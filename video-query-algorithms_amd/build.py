@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/vq_sim.hip", "csrc/vq_tsn.hip", "csrc/vq_wino.hip", "csrc/vq_boot.hip", "csrc/vq_frames.hip", "csrc/vq_comm.hip", "csrc/vq_flow.hip",
+SOURCES = ["csrc/vq_sim.hip", "csrc/vq_sim_batch.hip", "csrc/vq_rank.hip", "csrc/vq_db.hip", "csrc/vq_tsn.hip", "csrc/vq_wino.hip", "csrc/vq_boot.hip", "csrc/vq_frames.hip", "csrc/vq_comm.hip", "csrc/vq_flow.hip",
            "csrc/vq_jpeg.hip", "csrc/vq_csv.hip", "csrc/vq_rounds.hip", "csrc/vq_round_targets.hip", "csrc/vq_round_topk.hip"]
 # host-only translation units (no HIP include): plain C++, also built with sanitizers by tests/sanitize/Makefile
 HOST_SOURCES = ["csrc/host/vq_csv.cc", "csrc/host/vq_jpeg_host.cc", "csrc/host/vq_corners.cc", "csrc/host/vq_block_pool.cc", "csrc/host/vq_tsn_plan.cc", "csrc/host/vq_flow_host.cc", "csrc/host/vq_csv_read.cc"]

@@ -1,5 +1,5 @@
 // What the host-only translation units (csrc/host/*.cc: no HIP include, buildable by plain g++ with sanitizers) share with the
-// rest of the library: the error plumbing.  vq::last_error_ref() lives in vq_sim.hip for the product and in
+// rest of the library: the error plumbing.  vq::last_error_ref() lives in vq_db.hip for the product and in
 // tests/sanitize/host_main.cc for the sanitizer builds.
 #pragma once
 #include <cstdarg>

@@ -90,6 +90,23 @@ struct PerDeviceOnce {
 __device__ __forceinline__ double widen(double x) { return x; }
 __device__ __forceinline__ double widen(float x) { return (double)x; }
 __device__ __forceinline__ double widen(__half x) { return (double)__half2float(x); }
+// binary16 -> binary64 is exact (through binary32, subnormals included): an fp16 database scores like the fp64 arithmetic on its values
+__device__ __forceinline__ double half_to_double(_Float16 h) { return (double)(float)h; }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// The one-query scan reads the database once, whole 1 KB per wave instruction, and it is far larger than every cache: its loads
+// carry the non-temporal hint (6.15 ms per pass at cfg 4 instead of 6.8-7.0 on the same box: 6.66 TB/s).
+typedef float vq_f4 __attribute__((ext_vector_type(4)));
+typedef double vq_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 stream_load4(const float* p) {
+    const vq_f4 r = __builtin_nontemporal_load(reinterpret_cast<const vq_f4*>(p));
+    return make_float4(r.x, r.y, r.z, r.w);
+}
 
 // csrc/vq_boot.hip: closed-form target bootstrapping on rows that already live on the device.  row_off [P][stride]
 // element offsets into base_dev (the n_valid[p] validated matches first, then the n_invalid[p] non-matches).
@@ -97,7 +114,7 @@ int bootstrap_from_device_rows(const void* base_dev, int dtype, const std::vecto
                                const int32_t* n_invalid, int P, int D, double mu, hipStream_t stream, double* targets_host,
                                double* targets_dev_copy);
 
-// csrc/vq_sim.hip: copy the n scores of the last scan to dst_dev on `st`, ORDERED BEHIND that scan (which ran on the handle's
+// csrc/vq_db.hip: copy the n scores of the last scan to dst_dev on `st`, ORDERED BEHIND that scan (which ran on the handle's
 // own stream): an event recorded on the handle's stream, waited for by `st`.  VQ_E_STATE without a scan.  Takes the handle's lock.
 int db_copy_scores_ordered(vq_db* db, double* dst_dev, int64_t* n_out, hipStream_t st);
 

@@ -282,7 +282,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
             l0 = l1;
         }
     }
-    db->have_avg = db->have_scores = db->have_sims = false;
+    db->stale();
     if (host_fields) *host_fields = resolved;
     return VQ_OK;
 }

@@ -1,8 +1,11 @@
-// The handle of a resident feature database (vq_db_*): what csrc/vq_sim.hip keeps per database, shared with the device loader of
-// feature CSV files (csrc/vq_csv.hip), which stores into the handle's block under the handle's lock, and with the units of the
-// batched rounds (csrc/vq_rounds.hip, csrc/vq_round_targets.hip, csrc/vq_round_topk.hip).
+// The handle of a resident feature database (vq_db_*): what csrc/vq_db.hip keeps per database, shared with the scans
+// (csrc/vq_sim.hip, csrc/vq_sim_batch.hip), the ranking (csrc/vq_rank.hip), the device loader of feature CSV files (csrc/vq_csv.hip),
+// which stores into the handle's block under the handle's lock, and the units of the batched rounds (csrc/vq_rounds.hip,
+// csrc/vq_round_targets.hip, csrc/vq_round_topk.hip).  Every device block is held by an owner (vq_common.h): the handle has no free
+// function and is deleted with its device current.  The plain pointers next to the owners point INTO one of them.
 #pragma once
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "vq_common.h"
@@ -28,7 +31,7 @@ struct BatchRound {
     int64_t m(int i) const { return start[i + 1] - start[i]; }
 };
 
-// The arguments of the 16-query passes (batch_fused_kernel, batch_view_kernel: csrc/vq_sim.hip).
+// The arguments of the 16-query passes (batch_fused_kernel, batch_view_kernel: csrc/vq_sim_batch.hip).
 struct BatchFusedArgs {
     const void* feats;
     const double* t;          // [Q][NV][D]
@@ -60,8 +63,13 @@ struct vq_db {
     int64_t n = 0;
     int S = 0, E = 0, D = 0, dtype = VQ_F32;
     int cus = 256;
-    void* feats = nullptr;
+    void* feats = nullptr;           // the one block that may be adopted (vq_db_adopt_device): raw, released by release_feats alone
     bool owns_feats = true;
+    void release_feats() {
+        if (owns_feats && feats) (void)hipFree(feats);
+        feats = nullptr;
+    }
+    ~vq_db() { release_feats(); }
     // VQ_LAYOUT_ROWS: [N][S][E][D].  VQ_LAYOUT_TILED (fp32, own memory): [tile of 16 clips][S*E][D/4][clip][4] in the SAME block (a
     // tile's 16 rows and its tiled form cover the same bytes; the block is allocated for whole tiles) -- vq_db_set_layout.
     // VQ_LAYOUT_TILED64 (fp64): the same with the 16-byte unit of doubles, [tile][S*E][D/2][clip][2] (csrc/vq_tile_index.h);
@@ -71,70 +79,63 @@ struct vq_db {
     int unit() const { return tiled() ? vq::tile_unit_of((int)elem()) : 0; }      // elements per 16-byte unit of the layout; 0: rows
     int tiled_layout() const { return dtype == VQ_F32 ? VQ_LAYOUT_TILED : dtype == VQ_F64 ? VQ_LAYOUT_TILED64 : VQ_LAYOUT_TILED16; }   // the tiled layout of the storage type
     bool feats_exposed = false;      // adopted memory, or the raw pointer was handed out: the library no longer controls the layout
-    uint8_t* present = nullptr;
-    double* t = nullptr;        // [S*E*D]
+    vq::DeviceMem<uint8_t> present;
+    vq::DeviceMem<double> t;    // [S*E*D] | w
     bool have_query = false, have_avg = false, have_scores = false, have_sims = false;
-    double* w = nullptr;        // [8]
-    double* sims = nullptr;     // lazily [N][S][E]
+    void stale() { have_avg = have_scores = have_sims = false; }      // what the handle holds was computed from other inputs
+    double* w = nullptr;        // [8], inside t
+    vq::DeviceMem<double> sims; // lazily [N][S][E]
     double* avg = nullptr;      // [N][S]
     int32_t* ne = nullptr;      // [N][S]
     double* scores = nullptr;   // [N]
     // avg | ne | scores | sel_result | match prefix | near prefix are ONE device allocation (round_dev), in the order of the host
     // block of vq_db_query_round: a round's results go back in one copy
-    char* round_dev = nullptr;
+    vq::DeviceMem<char> round_dev;
     int64_t round_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // byte offsets of avg, ne, scores, result, matchp, nearp; [6] = total
     int64_t* matchp = nullptr;       // first kRoundPrefix rows of the last selection's match list
     int64_t* nearp = nullptr;
     // selection scratch
-    int nblk = 0;
-    int2* blk_cnt = nullptr;
-    double* blk_max = nullptr;
-    int64_t* blk_arg = nullptr;
+    vq::DeviceMem<int2> blk_cnt;
+    vq::DeviceMem<double> blk_max;
+    vq::DeviceMem<int64_t> blk_arg;
     int64_t* sel_result = nullptr;   // [3] device
-    int64_t* rows0 = nullptr;        // [N]
-    int64_t* rows1 = nullptr;        // [N]
+    vq::DeviceMem<int64_t> rows0, rows1;     // [N] each
     int64_t last_n0 = 0, last_n1 = 0;
-    uint64_t* tk_state = nullptr;    // [2]
-    unsigned int* tk_hist = nullptr; // [256]
-    double* batch_buf = nullptr;     // batched scan: queries [Q][NV][D] | weights [Q][S] | (two-kernel form: sims [NV][Q][N]) | scores [Q][N]
-    double* batch_scores = nullptr;  // where the scores of the last batched scan start inside batch_buf
-    int64_t batch_cap = 0;           // doubles
+    vq::DeviceMem<uint64_t> tk_state;        // [2]
+    vq::DeviceMem<unsigned int> tk_hist;     // [256]
+    vq::DeviceMem<double> batch_buf; // batched scan: queries [Q][NV][D] | weights [Q][S] | (two-kernel form: sims [NV][Q][N]) | scores [Q][N]
+    double* batch_scores = nullptr;  // where the scores of the last batched pass start, inside batch_buf or bround_dev
     int batch_q = 0;                 // queries of the last batched scan
     // Batched rounds (csrc/vq_rounds.hip; include/vq_amd_rounds.h, vq_amd_round_views.h, vq_amd_round_fit.h): ONE lazy allocation that
     // starts with the image of the host block (queries | weights | bands | n_e | avg | scores | results | prefixes: what comes and goes
     // in one copy each way) followed by the full match / near lists and the per-block scratch of the three-pass selection; `round` says
     // where each of these sits for the last round.
-    char* bround_dev = nullptr;
-    int64_t bround_cap = 0;          // bytes
-    hipEvent_t bround_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // flag 8: start | pass done | selection done | copies done
+    vq::DeviceMem<char> bround_dev;
+    vq::Event bround_ev[4];          // flag 8: start | pass done | selection done | copies done
     BatchRound round;
     // View rounds (vq_db_query_round_views, include/vq_amd_round_views.h): the plan's device block, allocated on the first one --
     // inv [16][stride] i32 | union rows [stride + 16] i32 | touched tiles [stride / 16] i32 | counts [2] i64 | start [17] i64 | the
     // per-block counts of the compaction [tiles / 256] int2 -- and what the last one covered
-    char* vround_plan = nullptr;
+    vq::DeviceMem<char> vround_plan;
     bool vround_have = false;
     int64_t vround_union = 0, vround_tiles = 0;
-    double* grid_buf = nullptr;      // scratch for grid / gathers
-    int64_t grid_cap = 0;
+    vq::DeviceMem<char> grid_buf;    // scratch for grid / gathers
     // Batched targets (vq_db_batch_targets, include/vq_amd_round_targets.h; csrc/vq_round_targets.hip): the image of the call's block |
     // the pools' Gram matrices | the coefficients of every draw | a status per (draw, slot), and the scratch area of the draws whose
     // systems do not fit into local memory.  Both grow on demand and go with the handle.
-    char* targets_buf = nullptr;
-    int64_t targets_cap = 0;         // bytes
-    double* targets_ws = nullptr;
-    int64_t targets_ws_cap = 0;      // bytes
+    vq::DeviceMem<char> targets_buf;
+    vq::DeviceMem<double> targets_ws;
     // Batched top-k (vq_db_batch_round_topk, include/vq_amd_round_topk.h; csrc/vq_round_topk.hip): the image of the call's block | the
     // survivors of the long pieces | the state and the histograms of the eight radix passes | the block counts of the compaction.
     // Allocated by the first call, grows on demand, goes with the handle.
-    char* btopk_buf = nullptr;
-    int64_t btopk_cap = 0;           // bytes
+    vq::DeviceMem<char> btopk_buf;
     // Row views (vq_db_rows_define): resident index lists, one device block each.  `active` is the view the one-query path runs over
     // (-1: the whole database) and `na` the number of clips it then covers -- M, or N: what every result-side entry point counts with.
     struct RowView {
         bool defined = false;
         int64_t m = 0;               // rows in the view
         int64_t ntiles = 0;          // tiles of 16 clips it touches (databases of a tiled-capable shape, whichever the storage type; else no tile tables)
-        int64_t* rows = nullptr;     // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
+        vq::DeviceMem<int64_t> rows; // [m] | tiles [ntiles] | pos [ntiles][16]: ONE allocation, rows first
         int64_t* tiles = nullptr;
         int64_t* pos = nullptr;
     };
@@ -146,21 +147,47 @@ struct vq_db {
 
 namespace vq {
 
-// csrc/vq_sim.hip: rows (by number) -> a dense row-major [L][S][E][D] block in the handle's gather scratch, whatever the layout; the
+// The one dispatch on the storage type: f(T{}) with T = __half, float or double, the element type of the handle's feature block.
+template <typename F>
+int with_dtype(const vq_db* db, F&& f) {
+    switch (db->dtype) {
+        case VQ_F16: return f(__half{});
+        case VQ_F32: return f(float{});
+        case VQ_F64: return f(double{});
+    }
+    return fail(VQ_E_STATE, "internal: database of unknown dtype %d", db->dtype);
+}
+// ... and on the 256-element chunks of a vector, D / 256 in {1, 2, 3, 4}: f(std::integral_constant<int, CH>{}); the caller has checked D
+template <typename F>
+int with_chunks(const vq_db* db, F&& f) {
+    switch (db->D / 256) {
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+    }
+    return f(std::integral_constant<int, 1>{});
+}
+
+// csrc/vq_db.hip: rows (by number) -> a dense row-major [L][S][E][D] block in the handle's gather scratch, whatever the layout; the
 // caller holds the handle's lock and has its device current.  rows_dev: the same L row numbers already on the device (ordered on the
 // handle's stream) -- they are then read there and nothing is uploaded.  Shared with csrc/vq_round_targets.hip.
 int gather_rows_device(vq_db* db, const int64_t* rows_host, int L, const void** dense, const int64_t* rows_dev = nullptr);
 
-// csrc/vq_sim.hip, for the rounds of csrc/vq_rounds.hip; the caller holds the handle's lock, has its device current and has checked
-// the shape (D in {256,512,768,1024}, S <= 8).  The 16-query pass of a round over the whole database: d_t [Q][NV][D], d_w [Q][8] ->
-// d_scores [Q][n], d_avg [Q][n][S].  The pass over the union of a round's views; max_tiles bounds the tiles its plan can hold.  The
-// handle's gather scratch, grown to at least `bytes`.
+// csrc/vq_sim.hip: the one-query scan over the row view in use (none: the whole database) on the handle's stream, from the handle's
+// query into its avg / ne and, with_scores, under the handle's weights into its scores; keep_sims: the per-split similarities too
+// (the handle's sims block exists).  The caller holds the handle's lock and has its device current, here and below.
+int launch_scan(vq_db* db, bool with_scores, bool keep_sims);
+
+// csrc/vq_rank.hip: the handle's scores again from its avg under its weights; the stable partition of the scores by a threshold and
+// a lower bound (res = n_match, n_near, near_argmax copied back and waited for, or null: they stay on the device; with_prefix: the
+// first kRoundPrefix rows of both lists next to them, for vq_db_query_round).
+int launch_rescore(vq_db* db);
+int select_threshold(vq_db* db, double threshold, double lower, int64_t res[3], bool with_prefix = false);
+
+// csrc/vq_sim_batch.hip, for the rounds of csrc/vq_rounds.hip; the caller has checked the shape (D in {256,512,768,1024}, S <= 8).
+// The 16-query pass of a round over the whole database: d_t [Q][NV][D], d_w [Q][8] -> d_scores [Q][n], d_avg [Q][n][S].  The pass
+// over the union of a round's views; max_tiles bounds the tiles its plan can hold.
 int launch_round_pass(vq_db* db, int Q, const double* d_t, const double* d_w, double* d_scores, double* d_avg);
 int launch_view_pass(vq_db* db, BatchViewArgs f, int64_t max_tiles);
-int ensure_grid_buf(vq_db* db, int64_t bytes);
-
-// csrc/vq_rounds.hip: what the batched rounds allocated on the handle (their device block, the plan of the view rounds, the events of
-// the timed ones) goes; for db_free, with the handle's device current.
-void free_round_state(vq_db* db);
 
 }  // namespace vq

@@ -258,18 +258,6 @@ __global__ __launch_bounds__(256) void targets_combine_kernel(TargetsArgs a) {
     a.target[o] = t;
 }
 
-// at least `bytes` in a buffer the handle owns; what it held is gone when it had to grow.  Caller holds the lock, device current.
-template <typename P>
-int grow(P** buf, int64_t* cap, int64_t bytes) {
-    if (*cap >= bytes) return VQ_OK;
-    if (*buf) VQ_HIP(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    VQ_HIP(vq::malloc_trim((void**)buf, (size_t)bytes));
-    *cap = bytes;
-    return VQ_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -382,15 +370,11 @@ int vq_db_batch_targets(vq_db* db, int32_t n_queries, int64_t n_pool_rows, int32
 
     DeviceGuard g(db->device);
     const int64_t gram_at = off[9], coef_at = gram_at + up64(a.gram_off[Q] * 8), pstat_at = coef_at + up64((int64_t)NV * n_entries * 8);
-    int rc = grow(&db->targets_buf, &db->targets_cap, pstat_at + up64((int64_t)n_draws * NV * 4));
-    if (rc != VQ_OK) return rc;
-    if (n_ws) {
-        rc = grow(&db->targets_ws, &db->targets_ws_cap, (int64_t)ws_groups * ws_need * 8);
-        if (rc != VQ_OK) return rc;
-    }
+    VQ_HIP(db->targets_buf.grow((size_t)(pstat_at + up64((int64_t)n_draws * NV * 4))));
+    if (n_ws) VQ_HIP(db->targets_ws.grow((size_t)ws_groups * ws_need * 8));
     char* base = db->targets_buf;
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)(any_previous ? off[7] : off[6]), hipMemcpyHostToDevice, db->stream));      // adjacent: one copy
-    rc = gather_rows_device(db, nullptr, (int)n_pool_rows, &a.dense, (const int64_t*)(base + off[2]));
+    int rc = gather_rows_device(db, nullptr, (int)n_pool_rows, &a.dense, (const int64_t*)(base + off[2]));
     if (rc != VQ_OK) return rc;
     a.NV = NV;
     a.D = D;

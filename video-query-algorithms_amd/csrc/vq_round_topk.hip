@@ -93,7 +93,7 @@ __device__ __forceinline__ int pow2_at_least(int v) {
 }
 
 // ---- short pieces: one workgroup per query ----------------------------------------------------------------------------------------
-// topk_small_kernel (csrc/vq_sim.hip) per query of the round, with the final order made here: keys in LDS, eight histogram passes
+// topk_small_kernel (csrc/vq_rank.hip) per query of the round, with the final order made here: keys in LDS, eight histogram passes
 // separated by barriers, the stable compaction into LDS, a bitonic sort of the at most kTopkSmallK survivors, the stores.
 __global__ __launch_bounds__(kTopkSmallThreads) void topk_batch_small_kernel(TopkBatchArgs a) {
     const int q = blockIdx.x;
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void topk_batch_hist_kernel(TopkBatchArgs a, i
     if (h[tid]) atomicAdd(&a.hist[(pass * kTopkSlots + q) * 256 + tid], h[tid]);
 }
 
-// the count / scan / scatter compaction of csrc/vq_sim.hip with predicate mode 1, the pivot of each query read on the device
+// the count / scan / scatter compaction of csrc/vq_rank.hip with predicate mode 1, the pivot of each query read on the device
 __global__ __launch_bounds__(SEL_BLOCK) void topk_batch_count_kernel(TopkBatchArgs a) {
     const int q = blockIdx.y, b0 = a.bstart[q];
     if ((int)blockIdx.x >= a.bstart[q + 1] - b0) return;
@@ -388,16 +388,6 @@ __global__ __launch_bounds__(kTopkSortThreads) void topk_batch_sort_kernel(TopkB
     if (tid == 0) a.count[q] = total;
 }
 
-int grow(char** buf, int64_t* cap, int64_t bytes) {
-    if (*cap >= bytes) return VQ_OK;
-    if (*buf) VQ_HIP(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    VQ_HIP(vq::malloc_trim((void**)buf, (size_t)bytes));
-    *cap = bytes;
-    return VQ_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -459,10 +449,7 @@ int vq_db_batch_round_topk(vq_db* db, int32_t n_queries, int64_t k_max, void* bl
     DeviceGuard g(db->device);
     const int64_t cand_at = off[4], state_at = cand_at + up64((int64_t)kTopkSlots * k_max * 8), total_at = state_at + up64(9 * kTopkSlots * 2 * 8);
     const int64_t hist_at = total_at + up64(kTopkSlots * 2 * 8), cnt_at = hist_at + up64(8 * kTopkSlots * 256 * 4);
-    {
-        const int rc = grow(&db->btopk_buf, &db->btopk_cap, cnt_at + up64((int64_t)a.bstart[kTopkSlots] * 8));
-        if (rc != VQ_OK) return rc;
-    }
+    VQ_HIP(db->btopk_buf.grow((size_t)(cnt_at + up64((int64_t)a.bstart[kTopkSlots] * 8))));
     char* base = db->btopk_buf;
     VQ_HIP(hipMemcpyAsync(base + off[0], host + off[0], (size_t)(off[1] - off[0]), hipMemcpyHostToDevice, db->stream));      // the k's
     a.scores = (const double*)(db->bround_dev + db->round.off[5]);

@@ -10,7 +10,7 @@
 // start[q + 1] of the concatenated avg / scores / list arrays.  A whole-database round is the round whose pieces all have N rows.
 // The partition of the score pieces has one kernel family and one launcher (launch_partition) for every kind of round and for every
 // run of queries that vq_db_batch_round_rescore partitions again.  The 16-query passes themselves are the scan kernels of
-// csrc/vq_sim.hip (vq::launch_round_pass, vq::launch_view_pass).
+// csrc/vq_sim_batch.hip (vq::launch_round_pass, vq::launch_view_pass).
 #include <algorithm>
 #include <cstring>
 
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void view_ne_kernel(ViewPlanArgs a, const uint
     }
 }
 
-// ---- the weight fit and the rescore of vq_db_loss_surface / vq_db_rescore (csrc/vq_sim.hip) for the queries of a batched round, on the
+// ---- the weight fit and the rescore of vq_db_loss_surface / vq_db_rescore (csrc/vq_rank.hip) for the queries of a batched round, on the
 // avg that round left on the device (include/vq_amd_round_fit.h) ----
 // loss_surface_kernel for every query with labels in ONE launch: block (g, q) = grid weight g of query q, over the avg entries of that
 // query (qoff[q] on).  The labels walk through LDS in chunks of kFitChunk: all threads fill the chunk's scores, then thread t adds the
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kPickThreads) void review_band_batch_kernel(UpdateB
     a.pick[q * 8 + 4] = lower;
 }
 
-// grid_kernel (csrc/vq_sim.hip) for the queries of a batched round: thread (q = blockIdx.y, i = g L_q + l) scores row rows[l] of query
+// grid_kernel (csrc/vq_rank.hip) for the queries of a batched round: thread (q = blockIdx.y, i = g L_q + l) scores row rows[l] of query
 // q's avg piece (qoff[q] on) under w_grid[q][g] into the query's [G][L_q] piece of `out`, which starts at entry G lstart[q].  A query
 // without rows has no thread that passes the bound.
 struct GridBatchArgs {
@@ -563,27 +563,15 @@ static int check_round_call(const vq_db* db, int n_queries, int flags, bool view
 
 // the device block of round r and, for a timed round, the four events; what the block held is gone when it had to grow
 static int ensure_round_block(vq_db* db, const BatchRound& r, bool timed) {
-    if (db->bround_cap < r.need) {
-        if (db->bround_dev && (char*)db->batch_scores >= db->bround_dev && (char*)db->batch_scores < db->bround_dev + db->bround_cap) {
-            db->batch_scores = nullptr;               // the scores of the round before lived in the block that goes
-            db->batch_q = 0;
-        }
-        if (db->bround_dev) VQ_HIP(hipFree(db->bround_dev));
-        db->bround_dev = nullptr;
-        db->bround_cap = 0;
-        VQ_HIP(vq::malloc_trim((void**)&db->bround_dev, (size_t)r.need));
-        db->bround_cap = r.need;
+    const char* dev = db->bround_dev;
+    if (db->bround_dev.bytes < (size_t)r.need && dev && (char*)db->batch_scores >= dev && (char*)db->batch_scores < dev + db->bround_dev.bytes) {
+        db->batch_scores = nullptr;                   // the scores of the round before lived in the block that goes
+        db->batch_q = 0;
     }
+    VQ_HIP(db->bround_dev.grow((size_t)r.need));
     if (timed && !db->bround_ev[0])
-        for (auto& ev : db->bround_ev) VQ_HIP(hipEventCreate(&ev));
+        for (Event& ev : db->bround_ev) VQ_HIP(ev.create());
     return VQ_OK;
-}
-
-void vq::free_round_state(vq_db* db) {
-    if (db->bround_dev) (void)hipFree(db->bround_dev);
-    if (db->vround_plan) (void)hipFree(db->vround_plan);
-    for (hipEvent_t ev : db->bround_ev)
-        if (ev) (void)hipEventDestroy(ev);
 }
 
 // The partition of the score pieces of queries q0 .. q1 of round r in the handle's block, under the bands d_band [q1 - q0 + 1][2] (on
@@ -992,7 +980,7 @@ int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_h
     const int nblk_u = cdiv(db_tiles, SEL_BLOCK);
     const int64_t p_rows = (int64_t)kBatchSlots * stride * 4, p_tiles = p_rows + up64((stride + 16) * 4), p_counts = p_tiles + up64(db_tiles * 4);
     const int64_t p_start = p_counts + 64, p_blk = p_start + up64(17 * 8), p_need = p_blk + (int64_t)nblk_u * 8 + 64;
-    if (!db->vround_plan) VQ_HIP(vq::malloc_trim((void**)&db->vround_plan, (size_t)p_need));
+    VQ_HIP(db->vround_plan.grow((size_t)p_need));
     char* plan = db->vround_plan;
     char* dev = db->bround_dev;
     if (timed) VQ_HIP(hipEventRecord(db->bround_ev[0], db->stream));
@@ -1000,7 +988,7 @@ int vq_db_query_round_views(vq_db* db, int32_t n_queries, const int32_t* views_h
     // the plan
     ViewPlanArgs pa;
     for (int q = 0; q < kBatchSlots; ++q) {
-        pa.rows[q] = (members >> q) & 1u ? db->views[views_host[q]].rows : nullptr;
+        pa.rows[q] = (members >> q) & 1u ? db->views[views_host[q]].rows.get() : nullptr;
         pa.m[q] = r.m(q);
         pa.start[q] = start[q];
     }
@@ -1134,11 +1122,8 @@ int vq_db_batch_round_fit(vq_db* db, int32_t n_queries, int32_t n_grid, int32_t 
                        (long long)(l - a.lstart[q]), (long long)r.m(q));
     if (n_labels == 0) return VQ_OK;                  // every query skipped: nothing to launch
     DeviceGuard g(db->device);
-    {
-        const int rc = ensure_grid_buf(db, off[7]);
-        if (rc != VQ_OK) return rc;
-    }
-    char* base = (char*)db->grid_buf;
+    VQ_HIP(db->grid_buf.grow((size_t)off[7]));
+    char* base = db->grid_buf;
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[6], hipMemcpyHostToDevice, db->stream));      // grids | ballast | L | rows | labels: adjacent
     a.avg = (const double*)(db->bround_dev + r.off[4]);
     a.w_grid = (const double*)(base + off[0]);
@@ -1190,12 +1175,9 @@ int vq_db_batch_round_rescore(vq_db* db, int32_t mask, void* block, int64_t bloc
     }
     DeviceGuard g(db->device);
     const int64_t up_bytes = off[3] - off[1];         // weights | bands of the round's block: adjacent
-    {
-        const int rc = ensure_grid_buf(db, up_bytes);
-        if (rc != VQ_OK) return rc;
-    }
+    VQ_HIP(db->grid_buf.grow((size_t)up_bytes));
     // staged beside the round's image, whose weights and bands of the other queries stay what the round saw
-    char* stage = (char*)db->grid_buf;
+    char* stage = db->grid_buf;
     VQ_HIP(hipMemcpyAsync(stage, host + off[1], (size_t)up_bytes, hipMemcpyHostToDevice, db->stream));
     const double* d_band = (const double*)(stage + (off[2] - off[1]));
     {
@@ -1300,11 +1282,8 @@ static int run_batch_update(vq_db* db, bool tables, int32_t n_queries, int32_t n
     if (mask == 0) return VQ_OK;                      // every slot skipped: nothing to launch
     DeviceGuard g(db->device);
     const int64_t stage_w = off[15], stage_band = stage_w + kBatchSlots * 8 * 8;             // behind the block's image: weights | bands
-    {
-        const int rc = ensure_grid_buf(db, stage_band + kBatchSlots * 2 * 8);
-        if (rc != VQ_OK) return rc;
-    }
-    char* base = (char*)db->grid_buf;
+    VQ_HIP(db->grid_buf.grow((size_t)(stage_band + kBatchSlots * 2 * 8)));
+    char* base = db->grid_buf;
     // ONE upload: the fit's inputs, the surface piece (given, or about to be overwritten) and the update's inputs are adjacent
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[13], hipMemcpyHostToDevice, db->stream));
     const bool have_rows = max_m > 0;                 // false: only empty views, which have neither labels nor scores nor lists
@@ -1411,11 +1390,8 @@ int vq_db_batch_round_avg_rows(vq_db* db, int32_t n_queries, int64_t n_rows, voi
     }
     if (n_rows == 0) return VQ_OK;                    // every query skipped: nothing to launch
     DeviceGuard g(db->device);
-    {
-        const int rc = ensure_grid_buf(db, off[3]);
-        if (rc != VQ_OK) return rc;
-    }
-    char* base = (char*)db->grid_buf;
+    VQ_HIP(db->grid_buf.grow((size_t)off[3]));
+    char* base = db->grid_buf;
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[2], hipMemcpyHostToDevice, db->stream));      // L | rows: adjacent
     a.avg = (const double*)(db->bround_dev + r.off[4]);
     a.rows = (const int64_t*)(base + off[1]);
@@ -1478,11 +1454,8 @@ int vq_db_batch_round_grid(vq_db* db, int32_t n_queries, int32_t n_grid, int64_t
     }
     if (n_rows == 0) return VQ_OK;                    // every query skipped: nothing to launch
     DeviceGuard g(db->device);
-    {
-        const int rc = ensure_grid_buf(db, off[4]);
-        if (rc != VQ_OK) return rc;
-    }
-    char* base = (char*)db->grid_buf;
+    VQ_HIP(db->grid_buf.grow((size_t)off[4]));
+    char* base = db->grid_buf;
     VQ_HIP(hipMemcpyAsync(base, host, (size_t)off[3], hipMemcpyHostToDevice, db->stream));      // grid | L | rows: adjacent
     a.avg = (const double*)(db->bround_dev + r.off[4]);
     a.w_grid = (const double*)(base + off[0]);

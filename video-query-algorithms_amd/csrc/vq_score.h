@@ -1,4 +1,4 @@
-// The score of a clip from its stream means, shared by the scans of csrc/vq_sim.hip and the batched fit and rescore of
+// The score of a clip from its stream means, shared by the scans of csrc/vq_sim.hip, the ranking of csrc/vq_rank.hip and the batched fit and rescore of
 // csrc/vq_rounds.hip.  One definition; every unit that includes it is compiled with -ffp-contract=off.
 #pragma once
 #include "vq_common.h"

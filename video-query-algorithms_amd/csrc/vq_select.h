@@ -1,4 +1,4 @@
-// What the selection kernels of csrc/vq_sim.hip (vq_db_select, vq_db_topk) share with the partitions of the batched rounds
+// What the selection kernels of csrc/vq_rank.hip (vq_db_select, vq_db_topk) share with the partitions of the batched rounds
 // (csrc/vq_rounds.hip) and the batched top-k of csrc/vq_round_topk.hip: the order-mapped key of a score, the two predicates of the
 // stable compaction, the block scan of its two counters, the four blocks of the stable partition, and the two wave-level steps of the
 // MSB-first radix select (the histogram add and the pick of the next digit).  One definition each, as with csrc/vq_gauss_jordan.h.
@@ -60,7 +60,7 @@ __device__ __forceinline__ int2 block_scan_excl2(int2 v, int2* total) {
     return make_int2(base.x + inc.x - v.x, base.y + inc.y - v.y);
 }
 
-// ---- the stable partition of a score array (ticket.py:325-340), as the blocks that the one-query kernels of csrc/vq_sim.hip and the
+// ---- the stable partition of a score array (ticket.py:325-340), as the blocks that the one-query kernels of csrc/vq_rank.hip and the
 // batched ones of csrc/vq_rounds.hip are made of ----
 // pass 1: per-block counts of both classes + block-local first-argmax of class 1 (near band)
 __device__ __forceinline__ void select_count_block(const double* scores, int64_t n, SelPred pred, int2* blk_cnt, double* blk_max,

@@ -1,5 +1,5 @@
 // Where element k of vector (row, slice v) of a feature block sits, for every layout of a resident database (vq_db_set_layout): the
-// ONE statement of the rule, shared by csrc/vq_sim.hip, csrc/vq_csv.hip and the host-only test of the rule (no HIP include: plain C++).
+// ONE statement of the rule, shared by csrc/vq_db.hip, csrc/vq_csv.hip and the host-only test of the rule (no HIP include: plain C++).
 //
 //   rows (unit 0):  [N][NV][D]
 //   tiled (unit U): [tile of 16 clips][NV][D / U][clip][U] -- U elements = the 16 bytes a lane loads: 4 floats (VQ_LAYOUT_TILED),

@@ -71,7 +71,7 @@ class Hyperparameter:
                 ticket._own_similarities()      # a resident database shared between tickets: this ticket's similarities (ticket.py)
             if on_device:
                 # the 40 rescorings AND the 40 x 31 loss surface in one launch: per cell the reference's fp64 operations, the labelled clips
-                # added one at a time in the dict's order (csrc/vq_sim.hip: loss_surface_kernel) -- what the numpy lines below do on the host
+                # added one at a time in the dict's order (csrc/vq_rank.hip: loss_surface_kernel) -- what the numpy lines below do on the host
                 surface = db.loss_surface(candidates, rows, [float(v) for v in labels], self.threshold_grid, self.ballast)
             else:
                 graded = db.scores_grid(candidates, rows)                           # [40][L] in one launch
