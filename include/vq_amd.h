@@ -23,6 +23,8 @@
  *     VQ_DEVICE_POOL_GB=<n>        device blocks of closed TSN extractors kept for the next one of the same shape (default 40, 0 = off)
  *     VQ_TSN_SPLIT=<n> | a,b,..    sub-batches of a forward on separate HIP streams (default 2; 1 = one stream)
  *     VQ_SCAN_LEAN=0|1             force the register-lean / register-resident instantiation of the row-major scan (default: by database shape)
+ *     VQ_SCAN_SHORT=0|1            force the generic / the short-row scan kernel on every handle created with VQ_DIM_SHORT_ROWS whose stored
+ *                                  D <= 128 (vq_amd_dim.h; default: the short-row kernel; the two agree to rounding, not bit for bit)
  *     VQ_TSN_AUTOTUNE=0|1          0: batch sizes without a tiling table run the occupancy heuristic (nothing is ever timed); 1: the tables
  *                                  shipped beside the library are left out and every size is timed in its first forward; unset: shipped
  *                                  tables, and a timing sweep only for sizes further than 1.6x from every table
@@ -622,5 +624,6 @@ int vq_broadcast_query(vq_comm* comm, void* buf_dev, int64_t bytes, int32_t root
 #include "vq_amd_round_topk.h" /* the k best clips of every query of a batched round, ranked on the device in one call (additive to ABI 12) */
 #include "vq_amd_round_grid.h" /* the scores of chosen rows of a batched round under a grid of weights: what a sharded fit combines (additive to ABI 12) */
 #include "vq_amd_round_update.h" /* a group's whole weight update -- fit, pick, rescore, review bands, partition -- in one call (additive to ABI 12) */
+#include "vq_amd_dim.h"       /* any vector length d on rows stored at a zero-padded pitch D; the short-row scan kernel (additive to ABI 12) */
 #include "vq_amd_round_shard.h" /* the avg rows of a batched round, and the whole weight update on given avg tables: a sharded update in one operation (additive to ABI 12) */
 #endif /* VQ_AMD_H */

@@ -218,6 +218,69 @@ def bench_tiled16(n=1_000_000, s=2, e=5, **kw):
     return bench_layout("tiled16", np.float16, n, s, e, **kw)
 
 
+def bench_short(n, dtype, s=2, e=3, d=101, alternations=4, reps=10, seed=1):
+    """scan_short_kernel against scan_generic_kernel on the same rows of logical length ``d`` (stored at d rounded up to a multiple of
+    4), in one process: two handles of the same data, one created with VQ_DIM_SHORT_ROWS and one with VQ_DIM_PADDED alone
+    (include/vq_amd_dim.h; the environment is not touched), timed in turn -- ``alternations`` (>= 3) blocks of ``reps`` scans each,
+    behind a warm-up of both.  The generic kernel is the baseline: what a hand-padded plain database runs.  Per kernel: the median of
+    each block, the median and the spread (max - min) of those block medians, GB/s and the share of 8 TB/s over the bytes stored (pads
+    included: they are read) plus 8 B of score per clip.  The two kernels must agree to 1e-12 on what they computed here."""
+    assert alternations >= 3
+    size = np.dtype(dtype).itemsize
+    handles = (("generic", vqa.FeatureDB(n, s, e, d, dtype=dtype, short_rows=False)), ("short", vqa.FeatureDB(n, s, e, d, dtype=dtype, short_rows=True)))
+    rng = np.random.default_rng(seed)
+    chunk = max(1, (256 << 20) // (s * e * d * 4))
+    for r in range(0, n, chunk):
+        k = min(chunk, n - r)
+        x = np.abs(rng.standard_normal((k, s, e, d), dtype=np.float32)).astype(dtype)
+        for _name, db in handles:
+            db.upload(r, x)
+    w = [1.0, 1.5][:s]
+    tm = C.c_void_p()
+    call("vq_timer_create", C.byref(tm))
+    first = {}
+    for name, db in handles:
+        db.set_query_from_row(7, want=False)
+        for _ in range(3):
+            db.scan(weights=w)
+        first[name] = db.scores()
+    agree = float(np.abs(first["short"] - first["generic"]).max())
+    assert agree <= 1e-12, agree
+    blocks = {name: [] for name, _db in handles}
+    for _ in range(alternations):
+        for name, db in handles:
+            ms = sorted(_timed(lambda: db.scan(weights=w), tm) for _ in range(reps))
+            blocks[name].append(ms[reps // 2])
+    pitch = handles[0][1].Dp
+    nbytes = n * s * e * pitch * size + n * 8
+    res = {"n": n, "S": s, "E": e, "d": d, "stored_D": pitch, "dtype": np.dtype(dtype).name, "bytes": nbytes, "alternations": alternations,
+           "reps_per_block": reps, "max_abs_score_difference": agree, "kernels": {}}
+    for name, _db in handles:
+        b = blocks[name]
+        med = sorted(b)[len(b) // 2]
+        res["kernels"][name] = {"block_median_ms": b, "median_ms": med, "spread_ms": max(b) - min(b), "gbs": nbytes / med / 1e6,
+                                "share_of_8tbs": nbytes / med / 1e6 / 8000}
+        print("short-row A/B N=%d %dx%dx%d %s %-7s: %.4f ms (block medians %s, spread %.4f) -> %.0f GB/s (%.3f of 8 TB/s)"
+              % (n, s, e, d, np.dtype(dtype).name, name, med, " ".join("%.4f" % v for v in b), max(b) - min(b), nbytes / med / 1e6,
+                 nbytes / med / 1e6 / 8000), flush=True)
+    g, sh = res["kernels"]["generic"], res["kernels"]["short"]
+    res["short_faster_by_ms"] = g["median_ms"] - sh["median_ms"]
+    res["short_wins_beyond_spread"] = bool(g["median_ms"] - sh["median_ms"] > max(g["spread_ms"], sh["spread_ms"]))
+    for _name, db in handles:
+        db.close()
+    return res
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "short":
+    # tools/quick_sim_bench.py short [out.json]: 10 000 and 1 000 000 clips x 2 x 3 x 101, float32 and float64
+    import json
+    results = [bench_short(n, dt) for n in (10_000, 1_000_000) for dt in (np.float32, np.float64)]
+    if len(sys.argv) > 2:
+        with open(sys.argv[2], "w") as f:
+            json.dump({"what": "scan_short_kernel (a handle with VQ_DIM_SHORT_ROWS) against scan_generic_kernel (VQ_DIM_PADDED alone) on the same rows, in turn",
+                       "results": results}, f, indent=1)
+
+
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] in ("tiled64", "tiled16"):
     # tools/quick_sim_bench.py tiled64|tiled16 [n s e [out.json [note]]]: one shape per process (each under a time limit of its own)
     a = sys.argv[2:]

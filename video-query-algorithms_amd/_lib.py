@@ -168,6 +168,9 @@ ROUND_SHARD_SIGNATURES = {
     "vq_db_batch_update_given_layout": [_P, _I32, _I32, _I32, _I64, _I64, _P],
     "vq_db_batch_round_update_given": [_P, _I32, _I32, _I32, _I64, _I64, _P, _I64, _P, _I64, _I32],
 }
+# include/vq_amd_dim.h: any vector length d on rows stored at a zero-padded pitch D, and the short-row scan kernel -- additive to ABI 12
+# with no new entry point: two flag bits OR-ed into vq_db_create's dtype argument
+VQ_DIM_PADDED, VQ_DIM_SHORT_ROWS = 256, 512
 _SPECIAL = {"vq_last_error": ([], C.c_char_p), "vq_abi_version": ([], C.c_int)}
 
 _lib = None

@@ -41,6 +41,7 @@ struct CsvArgs {
     int64_t line0;             // first line of this launch
     int lds_text;              // bytes of LDS for the staged line (multiple of 16); the offset table follows
     int dtype, unit, NV, slot, D;     // unit: elements per 16-byte unit of a tiled block, 0 = row-major (feat_index, csrc/vq_tile_index.h)
+    int pitch;                 // D = the fields of a line (the database's logical length), pitch = its stored length: equal unless the handle was created with VQ_DIM_PADDED
 };
 
 // the double's bits as the database stores them; false: a finite value that binary16 cannot hold (nothing stored)
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void csv_rows_kernel(CsvArgs a) {
         bool ok = vq_dec_parse(t + b, t + en, &bits) == VQ_DEC_OK;
         if (ok) ok = storage_bits(a.dtype, bits, &out);
         if (ok) {
-            store_elem(a.feats, a.dtype, feat_index(a.unit, row, a.NV, a.slot, D, j), out);
+            store_elem(a.feats, a.dtype, feat_index(a.unit, row, a.NV, a.slot, a.pitch, j), out);
         } else {
             const unsigned k = atomicAdd(&a.counters[0], 1u);
             if (k < a.fail_cap) a.fail_list[k] = make_int2((int)line, j);
@@ -155,7 +156,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
     if (int rc = csv_index(text_host, bytes, true, &ix, &n)) return rc;
     VQ_REQUIRE(n == n_rows, "the file has %lld data rows, rows_host names %lld", (long long)n, (long long)n_rows);
     if (n == 0) return VQ_OK;
-    VQ_REQUIRE(ix.dim == db->D, "the file's rows have %d values, the database's %d", ix.dim, db->D);
+    VQ_REQUIRE(ix.dim == db->d, "the file's rows have %d values, the database's %d", ix.dim, db->d);
     {
         std::vector<int64_t> named;
         named.reserve((size_t)n);
@@ -167,7 +168,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
         const auto dup = std::adjacent_find(named.begin(), named.end());
         VQ_REQUIRE(dup == named.end(), "rows_host names row %lld twice", (long long)(dup == named.end() ? 0 : *dup));
     }
-    const int D = db->D;
+    const int D = db->d, pitch = db->D;        // fields per line | elements between stored vectors (the pads stay as they are: +0.0)
     int64_t longest = 0;
     for (int64_t i = 0; i < n; ++i) longest = std::max(longest, csv_line_end(text_host + ix.line_off[i], text_host + ix.line_off[i + 1]) - (text_host + ix.line_off[i]));
     if (longest > 65000 - 4 * (int64_t)D)
@@ -231,6 +232,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
         a.NV = NV;
         a.slot = slot;
         a.D = D;
+        a.pitch = pitch;
         // the whole chunk in one launch; if it hands back more fields than the list holds, again in pieces that cannot
         int64_t piece = lines;
         for (int64_t l0 = 0; l0 < lines;) {
@@ -267,7 +269,7 @@ int vq_db_load_csv(vq_db* db, const char* text_host, int64_t bytes, int32_t stre
                     if (!storage_bits(db->dtype, bits, &out))
                         return fail(VQ_E_INVALID, "line %lld field %d: %.*s does not fit float16 (largest finite value 65504)", (long long)(li + 2), field,
                                     (int)std::min<int64_t>(40, fe - fb), fb);
-                    pidx[k] = feat_index(unit, rows_host[li], NV, slot, D, list[k].y);
+                    pidx[k] = feat_index(unit, rows_host[li], NV, slot, pitch, list[k].y);
                     pval[k] = out;
                 }
                 VQ_HIP(d_pidx.grow((size_t)fail_cap * 8));

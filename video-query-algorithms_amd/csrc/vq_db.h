@@ -62,6 +62,11 @@ struct vq_db {
     hipStream_t stream = nullptr;
     int64_t n = 0;
     int S = 0, E = 0, D = 0, dtype = VQ_F32;
+    // include/vq_amd_dim.h: d = the logical length of a vector, D = the stored pitch (d rounded up to a multiple of 4; the pads d..D-1
+    // of every stored vector and of the query are +0.0).  d == D on every handle created without VQ_DIM_PADDED.  short_rows: the handle
+    // was created with VQ_DIM_SHORT_ROWS (scan_short_kernel at D <= 128)
+    int d = 0;
+    bool short_rows = false;
     int cus = 256;
     void* feats = nullptr;           // the one block that may be adopted (vq_db_adopt_device): raw, released by release_feats alone
     bool owns_feats = true;

@@ -74,6 +74,17 @@ __global__ void scatter_rows_tiled_kernel(const float4* staged, float4* tiled, i
     tiled[((tile * NV + v) * d4 + g) * 16 + (clip & 15)] = staged[i];
 }
 
+// upload_unpadded (vq_db_upload on a padded handle): staged vectors of d elements -> vectors at pitch D, the pads d .. D - 1 written as +0.0 (all bits clear in every
+// storage type).  U = the unsigned integer of the element's size; one element per thread, a wave's stores are contiguous.
+template <typename U>
+__global__ void pad_rows_kernel(const U* staged, U* padded, int64_t nvec, int d, int D) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nvec * D) return;
+    const int64_t v = i / D;
+    const int k = (int)(i - v * D);
+    padded[i] = k < d ? staged[v * d + k] : (U)0;
+}
+
 // target_clip.py:311-313: t = r / (r . r), one block per (s,e) vector of row `row`, fp64 throughout.
 // element k of vector (row, v) in the database's layout: feat_index (csrc/vq_tile_index.h), unit = vq_db::unit()
 template <typename T>
@@ -280,13 +291,11 @@ int vq_timer_destroy(void* timer) {
     return VQ_OK;
 }
 
-int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int32_t device, vq_db** out) {
-    VQ_REQUIRE(out, "out is NULL");
-    *out = nullptr;
-    VQ_REQUIRE(n > 0 && S > 0 && E > 0 && D > 0, "n, S, E, D must be positive (got %lld, %d, %d, %d)", (long long)n, S, E, D);
-    VQ_REQUIRE(S <= 8, "at most 8 streams are supported (got %d)", S);
-    VQ_REQUIRE(S * E <= 64, "S*E must be <= 64 (got %d)", S * E);
-    VQ_REQUIRE(D % 4 == 0, "D must be a multiple of 4 (got %d)", D);
+}  // extern "C"
+
+// vq_db_create without and with the flags of include/vq_amd_dim.h: a handle of logical length d stored at pitch D (d <= D, D % 4 == 0; the
+// caller has checked both, and S and E); clear: the whole feature block starts as +0.0, not only the rows past n of the last tile
+static int create_db(int64_t n, int32_t S, int32_t E, int32_t d, int32_t D, int32_t dtype, int32_t device, bool short_rows, bool clear, vq_db** out) {
     VQ_REQUIRE(dtype == VQ_F32 || dtype == VQ_F64 || dtype == VQ_F16, "dtype must be VQ_F32, VQ_F64 or VQ_F16");
     VQ_REQUIRE(n < (1ll << 31) * (long long)SEL_CHUNK, "n too large");
     int ndev = 0;
@@ -300,6 +309,8 @@ int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int3
     db->S = S;
     db->E = E;
     db->D = D;
+    db->d = d;
+    db->short_rows = short_rows;
     db->dtype = dtype;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) db->cus = prop.multiProcessorCount;
@@ -312,7 +323,12 @@ int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int3
     };
     const auto alloc = [&](auto& block, size_t bytes) { return nomem(block.grow(bytes), bytes); };
     int rc = nomem(malloc_trim(&db->feats, fbytes), fbytes);
-    if (rc == VQ_OK && n % 16) (void)hipMemset((char*)db->feats + (size_t)n * S * E * D * db->elem(), 0, fbytes - (size_t)n * S * E * D * db->elem());
+    if (rc == VQ_OK && clear) {
+        const hipError_t e = hipMemset(db->feats, 0, fbytes);
+        if (e != hipSuccess) return fail(VQ_E_HIP, "clearing the feature block failed: %s", hipGetErrorString(e));
+    } else if (rc == VQ_OK && n % 16) {
+        (void)hipMemset((char*)db->feats + (size_t)n * S * E * D * db->elem(), 0, fbytes - (size_t)n * S * E * D * db->elem());
+    }
     if (rc == VQ_OK) rc = alloc(db->t, tbytes + 64);
     if (rc == VQ_OK) rc = alloc(db->round_dev, (size_t)db->round_off[6]);
     if (rc == VQ_OK) rc = alloc(db->blk_cnt, nblk * sizeof(int2));
@@ -332,6 +348,26 @@ int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int3
     db->nearp = (int64_t*)(db->round_dev + db->round_off[5]);
     *out = db.release();
     return VQ_OK;
+}
+
+extern "C" {
+
+int vq_db_create(int64_t n, int32_t S, int32_t E, int32_t D, int32_t dtype, int32_t device, vq_db** out) {
+    VQ_REQUIRE(out, "out is NULL");
+    *out = nullptr;
+    VQ_REQUIRE(n > 0 && S > 0 && E > 0 && D > 0, "n, S, E, D must be positive (got %lld, %d, %d, %d)", (long long)n, S, E, D);
+    VQ_REQUIRE(S <= 8, "at most 8 streams are supported (got %d)", S);
+    VQ_REQUIRE(S * E <= 64, "S*E must be <= 64 (got %d)", S * E);
+    // include/vq_amd_dim.h: the bits above the storage type.  With VQ_DIM_PADDED (VQ_DIM_SHORT_ROWS implies it) D is the logical
+    // length, stored at the next multiple of 4 in a cleared block; without, every check and every byte is what it was
+    const int32_t flags = dtype & ~0xFF;
+    if (flags == 0) {
+        VQ_REQUIRE(D % 4 == 0, "D must be a multiple of 4 (got %d)", D);
+        return create_db(n, S, E, D, D, dtype, device, false, false, out);
+    }
+    VQ_REQUIRE((flags & ~(VQ_DIM_PADDED | VQ_DIM_SHORT_ROWS)) == 0, "dtype carries unknown flag bits (got %d): VQ_DIM_PADDED, VQ_DIM_SHORT_ROWS", dtype);
+    VQ_REQUIRE(D <= (1 << 30), "D too large (got %d)", D);
+    return create_db(n, S, E, D, (D + 3) / 4 * 4, dtype & 0xFF, device, (flags & VQ_DIM_SHORT_ROWS) != 0, true, out);
 }
 
 int vq_db_destroy(vq_db* db) {
@@ -359,8 +395,11 @@ int vq_db_shape(vq_db* db, int64_t* n, int32_t* S, int32_t* E, int32_t* D, int32
     return VQ_OK;
 }
 
+static int upload_unpadded(vq_db* db, int64_t row0, int64_t nrows, const void* rows_host);
+
 int vq_db_upload(vq_db* db, int64_t row0, int64_t nrows, const void* feats_host) {
     VQ_REQUIRE(db && feats_host, "NULL argument");
+    if (db->d != db->D) return upload_unpadded(db, row0, nrows, feats_host);      // include/vq_amd_dim.h: rows of d elements, padded on the device
     VQ_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= db->n, "rows [%lld,%lld) outside [0,%lld)", (long long)row0,
                (long long)(row0 + nrows), (long long)db->n);
     std::lock_guard<std::mutex> lk(db->mu);
@@ -386,6 +425,48 @@ int vq_db_upload(vq_db* db, int64_t row0, int64_t nrows, const void* feats_host)
         VQ_HIP(hipMemcpyAsync((char*)db->feats + row0 * row_bytes, feats_host, nrows * row_bytes, hipMemcpyHostToDevice,
                               db->stream));
         VQ_HIP(hipStreamSynchronize(db->stream));
+    }
+    db->stale();
+    return VQ_OK;
+}
+
+// vq_db_upload on a handle with d != D: rows_host [nrows][S][E][d], unpadded
+static int upload_unpadded(vq_db* db, int64_t row0, int64_t nrows, const void* rows_host) {
+    VQ_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= db->n, "rows [%lld,%lld) outside [0,%lld)", (long long)row0,
+               (long long)(row0 + nrows), (long long)db->n);
+    std::lock_guard<std::mutex> lk(db->mu);
+    DeviceGuard g(db->device);
+    const int NV = db->S * db->E;
+    const size_t row_bytes = (size_t)NV * db->D * db->elem(), raw_bytes = (size_t)NV * db->d * db->elem();
+    // the unpadded rows land in a staging block, a bounded chunk at a time, and are written at pitch by a kernel: straight into their
+    // rows, or (a tiled database) into a second staging block that is dealt into the tiles as vq_db_upload deals it
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)(64u << 20) / (int64_t)row_bytes);
+    const size_t most = (size_t)std::min<int64_t>(chunk, std::max<int64_t>(nrows, 1));
+    DeviceMem<char> raw;
+    DeviceMem<float4> stage;
+    VQ_HIP(raw.grow(most * raw_bytes));
+    if (db->tiled()) VQ_HIP(stage.grow(most * row_bytes));
+    const int d4 = db->tiled() ? db->D / db->unit() : 0;
+    for (int64_t r = 0; r < nrows; r += chunk) {
+        const int64_t k = std::min(chunk, nrows - r), nvec = k * NV;
+        char* dst = db->tiled() ? (char*)stage.get() : (char*)db->feats + (size_t)(row0 + r) * row_bytes;
+        hipError_t e = hipMemcpyAsync(raw, (const char*)rows_host + (size_t)r * raw_bytes, (size_t)k * raw_bytes, hipMemcpyHostToDevice, db->stream);
+        if (e == hipSuccess) {
+            const unsigned blocks = (unsigned)cdiv(nvec * db->D, 256);
+            if (db->dtype == VQ_F64)
+                pad_rows_kernel<uint64_t><<<blocks, 256, 0, db->stream>>>((const uint64_t*)raw.get(), (uint64_t*)dst, nvec, db->d, db->D);
+            else if (db->dtype == VQ_F32)
+                pad_rows_kernel<uint32_t><<<blocks, 256, 0, db->stream>>>((const uint32_t*)raw.get(), (uint32_t*)dst, nvec, db->d, db->D);
+            else
+                pad_rows_kernel<uint16_t><<<blocks, 256, 0, db->stream>>>((const uint16_t*)raw.get(), (uint16_t*)dst, nvec, db->d, db->D);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && db->tiled()) {
+            scatter_rows_tiled_kernel<<<cdiv(k * NV * d4, 256), 256, 0, db->stream>>>(stage, (float4*)db->feats, row0 + r, k, NV, d4);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(db->stream);      // the staging blocks are reused by the next chunk
+        if (e != hipSuccess) return fail(VQ_E_HIP, "upload of unpadded rows failed: %s", hipGetErrorString(e));
     }
     db->stale();
     return VQ_OK;
@@ -423,6 +504,7 @@ int vq_db_set_present(vq_db* db, const uint8_t* present_host) {
 
 int vq_db_generate(vq_db* db, uint64_t seed, int64_t global_row0, const float* scales_host) {
     VQ_REQUIRE(db && scales_host, "NULL argument");
+    if (db->d != db->D) return fail(VQ_E_UNSUPPORTED, "the generator fills whole vectors: not for a logical length %d stored at pitch %d (include/vq_amd_dim.h)", db->d, db->D);
     std::lock_guard<std::mutex> lk(db->mu);
     DeviceGuard g(db->device);
     float* scales_dev = reinterpret_cast<float*>(db->w);   // 64 bytes of scratch; w is rewritten by every scan

@@ -292,6 +292,106 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(std::conditional_t<VI
     }
 }
 
+// score_from_avg with the stream count a constant of each call: the loop over av / w unrolls and both stay in registers (the same
+// operations in the same order whichever the case)
+__device__ __forceinline__ double score_from_avg_streams(const double* av, const double* w, int S) {
+    switch (S) {
+        case 1: return score_from_avg(av, w, 1);
+        case 2: return score_from_avg(av, w, 2);
+        case 3: return score_from_avg(av, w, 3);
+        case 4: return score_from_avg(av, w, 4);
+        case 5: return score_from_avg(av, w, 5);
+        case 6: return score_from_avg(av, w, 6);
+        case 7: return score_from_avg(av, w, 7);
+    }
+    return score_from_avg(av, w, 8);
+}
+
+// Short rows (include/vq_amd_dim.h: handles created with VQ_DIM_SHORT_ROWS, stored D <= 128, rows layout): scan_generic_kernel gives
+// a whole wave to one vector -- at D = 104 only 26 of its 64 lanes load -- and reads the query from global memory.  Here a wave
+// works on 64 / L clips at once, L = 1 << lg = the smallest power of two >= D / 4 (1 .. 32): lane group lane / L owns clip
+// c0 + lane / L, lane j = lane % L holds elements 4 j .. 4 j + 3 of the current vector (nothing when 4 j >= D: its share of the dot
+// is +0.0).  The query is an LDS image [NV][D] of doubles in natural order (at most 64 x 128 x 8 = 64 KB: the launch raises the
+// limit); lane j reads its four values with two 16-byte reads, every group the same addresses (broadcast).  The next vector
+// (possibly of the group's next clip) is in flight while the current one is multiplied and reduced, as in scan_kernel.  A dot is
+// summed over the group by __shfl_xor over L / 2 .. 1, which stays inside the group and leaves the sum in every lane of it, so the
+// bookkeeping per clip (ClipAcc) is group-uniform and lane j == 0 stores.  A group whose clip is >= n neither loads nor stores.
+// VIEW: c walks the positions of a row view, r is the database row read; results go to positions, presence bits are the row's.
+template <typename T, bool VIEW = false>
+__global__ __launch_bounds__(256) void scan_short_kernel(std::conditional_t<VIEW, ScanViewArgs, ScanArgs> a, int lg) {
+    extern __shared__ __attribute__((aligned(16))) double t_lds[];    // [NV][D], natural order
+    const int NV = a.S * a.E, D = a.D;
+    for (int i = threadIdx.x; i < NV * D; i += blockDim.x) t_lds[i] = a.t[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, L = 1 << lg, G = 64 >> lg;
+    const int grp = lane >> lg, j = lane & (L - 1);
+    const bool act = 4 * j < D;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t step = (int64_t)gridDim.x * (blockDim.x >> 6) * G;  // clips between two rounds of the grid
+    const T* feats = static_cast<const T*>(a.feats) + 4 * j;
+    const double* tq = t_lds + 4 * j;
+    const int64_t clip_elems = (int64_t)NV * D;
+    double w[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) w[s] = (a.w && s < a.S) ? a.w[s] : 0.0;
+
+    Quad<T> cur{}, nxt{};
+    int64_t c = wave * G + grp;
+    bool live = c < a.n;
+    int64_t r = c;                                                     // the row read; c stays where the results go
+    if constexpr (VIEW) r = live ? a.items[c] : 0;
+    if (live && act) cur.load(feats + r * clip_elems);
+    for (int64_t c0 = wave * G; c0 < a.n; c0 += step) {                // wave-uniform: every lane takes part in the shuffles
+        const int64_t cn = c + step;
+        const bool live_n = cn < a.n;
+        int64_t rn = cn;
+        if constexpr (VIEW) rn = live_n ? a.items[cn] : 0;
+        ClipAcc st;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) st.av[s] = 0.0;
+        int s = 0, e = 0;
+        for (int v = 0; v < NV; ++v) {
+            const bool more = v + 1 < NV;
+            const T* nb = more ? feats + r * clip_elems + (int64_t)(v + 1) * D : feats + rn * clip_elems;
+            if ((more ? live : live_n) && act) nxt.load(nb);
+            double p = 0.0;
+            if (act) {
+                const double2 ta = *reinterpret_cast<const double2*>(tq + v * D);
+                const double2 tb = *reinterpret_cast<const double2*>(tq + v * D + 2);
+                p = fma(cur.x0(), ta.x, p);
+                p = fma(cur.x1(), ta.y, p);
+                p = fma(cur.x2(), tb.x, p);
+                p = fma(cur.x3(), tb.y, p);
+            }
+            if (lg > 4) p += __shfl_xor(p, 16, 64);
+            if (lg > 3) p += __shfl_xor(p, 8, 64);
+            if (lg > 2) p += __shfl_xor(p, 4, 64);
+            if (lg > 1) p += __shfl_xor(p, 2, 64);
+            if (lg > 0) p += __shfl_xor(p, 1, 64);
+            if (live) {
+                if constexpr (VIEW) clip_add_view(a, st, c, r, s, e, p, j);
+                else clip_add(a, st, c, s, e, p, j);
+            }
+            if (++e == a.E) {
+                if (live) {
+                    const double m = clip_close_stream(a, st, c, s, j);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (k == s) st.av[k] = m;
+                }
+                e = 0;
+                ++s;
+            }
+            cur = nxt;
+        }
+        if (a.w && live && j == 0) a.scores[c] = score_from_avg_streams(st.av, w, a.S);
+        c = cn;
+        r = rn;
+        live = live_n;
+    }
+}
+
 // The one-query scan over a TILED database (vq_db_set_layout): [tile of 16 clips][slice][k / 4][clip][4], fp32.  A wave owns a tile:
 // lane l = (clip l % 16, k quarter l / 16), and because piece g = 4 i + l / 16 of the slice sits at g * 64 + (l % 16) * 4 floats, load i
 // of a lane is at i * 256 + l * 4 -- a wave instruction still takes 1 KB of contiguous memory and a whole tile (all its slices) is ONE
@@ -527,6 +627,22 @@ static int launch_scan_shape(vq_db* db, const A& a) {
 #undef C_
     }
     if (db->layout != VQ_LAYOUT_ROWS) return fail(VQ_E_STATE, "internal: tiled layout on a shape without a tiled scan kernel");
+    // a handle created with VQ_DIM_SHORT_ROWS (include/vq_amd_dim.h), stored D <= 128: the short-row kernel, unless the environment
+    // (VQ_SCAN_SHORT=0) forces the generic one; every other handle runs what it ever ran
+    static const int env_short = getenv("VQ_SCAN_SHORT") ? atoi(getenv("VQ_SCAN_SHORT")) : -1;
+    if (db->short_rows && db->D <= 128 && env_short != 0) {
+        int lg = 0;
+        while ((4 << lg) < db->D) ++lg;                                // L = 1 << lg lanes per clip, 64 >> lg clips per wave
+        const size_t lds = (size_t)db->S * db->E * db->D * 8;           // <= 64 x 128 x 8 = 64 KB
+        void (*kern)(A, int) = scan_short_kernel<T, std::is_same_v<A, ScanViewArgs>>;
+        VQ_DYN_LDS(kern, 65536);
+        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+        const int64_t per_block = 4 * (int64_t)(64 >> lg);             // 4 waves of 64 / L clips
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.n + per_block - 1) / per_block, (int64_t)db->cus * per_cu));
+        kern<<<grid, 256, lds, db->stream>>>(a, lg);
+        VQ_CHECK_LAUNCH();
+        return VQ_OK;
+    }
     const int64_t want = (a.n + 3) / 4;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)db->cus * 8));
     scan_generic_kernel<T, std::is_same_v<A, ScanViewArgs>><<<grid, 256, 0, db->stream>>>(a);

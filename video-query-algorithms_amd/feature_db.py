@@ -69,6 +69,12 @@ LAYOUTS = dict(_LAYOUTS, tiled16=_lib.VQ_LAYOUT_TILED16)
 LAYOUT_NAMES = {v: k for k, v in LAYOUTS.items()}
 _TILED_OF_DTYPE = {np.dtype(np.float32): "tiled", np.dtype(np.float64): "tiled64", np.dtype(np.float16): "tiled16"}
 
+def _pad_for(dim):
+    """What the constructors that take data of any length pass as ``short_rows``: True for a length that is no multiple of 4 (stored
+    padded, short rows on their own kernel), None for any other (the plain database of ever)."""
+    return True if dim is not None and int(dim) % 4 != 0 else None
+
+
 def whole_view(db) -> SearchSetView:
     """The trivial view of a database object (FeatureDB, ShardedFeatureDB, or a look-alike with ``clip_ids`` and ``row_of``)."""
     n = len(db.clip_ids)
@@ -83,10 +89,19 @@ def search_set_rows(db, clip_ids) -> np.ndarray:
 class FeatureDB(BatchRounds):
     """N clips x S streams x E ensemble slots x D floats, resident on ``device``.  ``dtype`` is how the block is STORED: float32, float64
     or (opt-in) float16 -- half the bytes per query and per clip; values are rounded once on the way in and every result is what the
-    fp64 arithmetic gives on the rounded values."""
+    fp64 arithmetic gives on the rounded values.
+
+    ``dim`` is any length >= 1 (the 101 class scores of ``fc-action`` as well as 1024 pooled activations).  ``D`` is that logical length,
+    what every array the caller hands in or gets back has; ``Dp`` is the stored pitch, ``D`` rounded up to a multiple of 4, with
+    +0.0 pads that the methods below write on the way in and cut on the way out (include/vq_amd_dim.h).  The plain constructor keeps
+    what it ever did -- ``vq_db_create`` as it was, a ``dim`` that is no multiple of 4 is a ``VqError`` -- and padding is asked for:
+    ``short_rows=True`` makes the handle with ``VQ_DIM_PADDED | VQ_DIM_SHORT_ROWS`` (stored ``Dp <= 128`` then scans with the short-row
+    kernel), ``short_rows=False`` with ``VQ_DIM_PADDED`` alone when ``dim % 4 != 0`` (the generic kernel) and plainly otherwise.
+    ``from_arrays``, ``from_records``, ``from_store`` and ``from_csv_tree`` ask for ``short_rows=True`` whenever their data's length is no
+    multiple of 4.  Out of scope on a padded database (``D != Dp``): ``scan_batch``, the batched rounds, ``synthetic``."""
 
     def __init__(self, n: int, n_streams: int, n_splits: int, dim: int = 1024, dtype=np.float32, device: int = 0,
-                 clip_ids: Sequence[int] | None = None):
+                 clip_ids: Sequence[int] | None = None, short_rows: bool | None = None):
         # before anything can fail, so that close() always finds them: the handle, and the pools of page-locked blocks of every
         # call that takes one -- made here, not on first use, so that the first calls of two threads share them
         self._h = C.c_void_p()
@@ -97,7 +112,13 @@ class FeatureDB(BatchRounds):
         if self.dtype not in _VQ_DTYPE:
             raise TypeError("FeatureDB dtype must be float32, float64 or float16")
         self.device = int(device)
-        call("vq_db_create", self.n, self.S, self.E, self.D, _VQ_DTYPE[self.dtype], self.device, C.byref(self._h))
+        self.Dp = (self.D + 3) // 4 * 4
+        flags = 0
+        if short_rows:
+            flags = _lib.VQ_DIM_PADDED | _lib.VQ_DIM_SHORT_ROWS
+        elif short_rows is False and self.D % 4 != 0:
+            flags = _lib.VQ_DIM_PADDED
+        call("vq_db_create", self.n, self.S, self.E, self.D, _VQ_DTYPE[self.dtype] | flags, self.device, C.byref(self._h))
         self.clip_ids = (np.arange(1, self.n + 1, dtype=np.int64) if clip_ids is None
                          else np.asarray(clip_ids, dtype=np.int64).copy())
         if self.clip_ids.shape != (self.n,):
@@ -119,6 +140,25 @@ class FeatureDB(BatchRounds):
         self._whole = None
         self._na = self.n
         self._round_off = self._layout(ONE_ROUND, "vq_db_round_layout")
+
+    # ------------------------------------------------------------------ logical length and stored pitch
+    def _padded(self, t: np.ndarray) -> np.ndarray:
+        """[..., D] float64 -> the contiguous [..., Dp] block the library takes, +0.0 in the pads (the array itself when D == Dp)."""
+        if self.D == self.Dp:
+            return t
+        out = np.zeros(t.shape[:-1] + (self.Dp,), dtype=np.float64)
+        out[..., :self.D] = t
+        return out
+
+    def _logical(self, a: np.ndarray) -> np.ndarray:
+        """[..., Dp] as the library wrote it -> [..., D], contiguous."""
+        return a if self.D == self.Dp else np.ascontiguousarray(a[..., :self.D])
+
+    def _layout(self, pieces: dict, name: str, *args):
+        # every batched call lays its block out first: a padded database takes one-query rounds only (include/vq_amd_dim.h)
+        if self.D != self.Dp and name != "vq_db_round_layout":
+            raise ValueError("batched rounds are out of scope for a database of length %d stored at pitch %d" % (self.D, self.Dp))
+        return BatchRounds._layout(self, pieces, name, *args)
 
     # ------------------------------------------------------------------ search sets
     def define_search_set(self, set_id, clip_ids):
@@ -195,7 +235,7 @@ class FeatureDB(BatchRounds):
         if dtype is None and feats.dtype not in (np.float32, np.float64):
             feats = feats.astype(np.float32)
         n, s, e, d = feats.shape
-        db = cls(n, s, e, d, feats.dtype if dtype is None else dtype, device, clip_ids)
+        db = cls(n, s, e, d, feats.dtype if dtype is None else dtype, device, clip_ids, short_rows=_pad_for(d))
         db.upload(0, feats)
         if present is not None:
             db.set_present(present)
@@ -249,7 +289,7 @@ class FeatureDB(BatchRounds):
                 feats[rows, si, ei] = np.asarray(list(d.values()), dtype=host_dtype)
                 present[rows, si, ei] = 1
         db = cls(n, len(stream_list), n_slots, dim, dtype, device,
-                 np.fromiter(order.keys(), dtype=np.int64, count=n))
+                 np.fromiter(order.keys(), dtype=np.int64, count=n), short_rows=_pad_for(dim))
         db.stream_names = stream_list
         db.slot_splits = slot_splits
         db.upload(0, feats)
@@ -268,7 +308,7 @@ class FeatureDB(BatchRounds):
         rows = n_all - row0 if rows is None else int(rows)
         if row0 < 0 or rows <= 0 or row0 + rows > n_all:
             raise ValueError("rows [%d,%d) outside the store's %d clips" % (row0, row0 + rows, n_all))
-        db = cls(rows, feats.shape[1], feats.shape[2], feats.shape[3], feats.dtype, device, ids[row0:row0 + rows])
+        db = cls(rows, feats.shape[1], feats.shape[2], feats.shape[3], feats.dtype, device, ids[row0:row0 + rows], short_rows=_pad_for(feats.shape[3]))
         for r in range(0, rows, chunk_rows):
             k = min(chunk_rows, rows - r)
             db.upload(r, np.ascontiguousarray(feats[row0 + r:row0 + r + k]))
@@ -333,7 +373,7 @@ class FeatureDB(BatchRounds):
                             rows[[i for i, r in enumerate(rows.tolist()) if last[r] != i]] = -1
                         jobs.append((path, si, ei, rows))
             row0 += len(clips)
-        db = cls(n, len(streams), len(splits), dim, dtype, device, clip_id_base + np.arange(1, n + 1, dtype=np.int64))
+        db = cls(n, len(streams), len(splits), dim, dtype, device, clip_id_base + np.arange(1, n + 1, dtype=np.int64), short_rows=_pad_for(dim))
         if layout != "rows":
             db.set_layout(layout)
         db.clips, db.csv_host_fields = names, 0
@@ -362,7 +402,10 @@ class FeatureDB(BatchRounds):
     def synthetic(cls, n: int, n_streams: int, n_splits: int, dim: int = 1024, seed: int = 0,
                   scales: Sequence[float] = (4.0, 1.0), row0: int = 0, dtype=np.float32, device: int = 0,
                   clip_ids=None) -> "FeatureDB":
-        """Rows generated on the device by the counter-based hash (oracle.sim_oracle.synth_features)."""
+        """Rows generated on the device by the counter-based hash (oracle.sim_oracle.synth_features); ``dim`` a multiple of 4 (the
+        generator fills whole stored vectors)."""
+        if int(dim) % 4 != 0:
+            raise ValueError("synthetic rows need dim % 4 == 0 (got %d)" % dim)
         db = cls(n, n_streams, n_splits, dim, dtype, device, clip_ids)
         sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float32))
         if sc.shape != (n_streams,):
@@ -380,6 +423,7 @@ class FeatureDB(BatchRounds):
         a = np.ascontiguousarray(feats, dtype=self.dtype)
         if a.shape[1:] != (self.S, self.E, self.D):
             raise ValueError("rows must be [n,%d,%d,%d]" % (self.S, self.E, self.D))
+        # D != Dp: the library takes the unpadded rows and writes them at pitch with zero pads on the device (include/vq_amd_dim.h)
         call("vq_db_upload", self._h, int(row0), a.shape[0], _np_ptr(a))
 
     def load_csv(self, data, stream: int, split: int, rows, chunk_bytes: int = 0) -> int:
@@ -415,7 +459,7 @@ class FeatureDB(BatchRounds):
         a tileable shape, ``("rows", "tiled")`` / ``("rows", "tiled64")`` for float32 / float64, ``("rows",)`` for any other shape.
         By dtype and shape alone: a block that is not the library's alone any more (adopted, or its address handed out) is refused
         whatever the name (``VqError``, VQ_E_STATE)."""
-        if not (self.D == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
+        if not (self.Dp == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):      # the stored pitch: D = 1021 .. 1024
             return ("rows",)
         return ("rows", _TILED_OF_DTYPE[np.dtype(self.dtype)])
 
@@ -424,7 +468,7 @@ class FeatureDB(BatchRounds):
         """The float32 / float64 name: "tiled" (float32), "tiled64" (float64), or ``None`` (a shape without the tiled kernels -- and
         float16, whose "tiled16" came later: this property keeps the value it had for every database, tests/test_tiled64_gpu.py holds
         it to ``None`` there).  :attr:`layouts` is the way to ask what a database takes, whichever its dtype."""
-        if self.dtype == np.float16 or not (self.D == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
+        if self.dtype == np.float16 or not (self.Dp == 1024 and 1 <= self.S <= 2 and 1 <= self.E <= 5):
             return None
         return "tiled64" if self.dtype == np.float64 else "tiled"
 
@@ -504,9 +548,9 @@ class FeatureDB(BatchRounds):
     def read_rows(self, rows: Sequence[int]) -> np.ndarray:
         """Feature rows [L,S,E,D] back on the host (database dtype)."""
         r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        out = np.empty((r.size, self.S, self.E, self.D), dtype=self.dtype)
+        out = np.empty((r.size, self.S, self.E, self.Dp), dtype=self.dtype)
         call("vq_db_read_rows", self._h, _np_ptr(r) if r.size else None, int(r.size), _np_ptr(out))
-        return out
+        return self._logical(out)
 
     def scores_at(self, rows: Sequence[int]) -> np.ndarray:
         r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
@@ -519,15 +563,16 @@ class FeatureDB(BatchRounds):
         t = np.ascontiguousarray(t, dtype=np.float64)
         if t.shape != (self.S, self.E, self.D):
             raise ValueError("query must be [%d,%d,%d]" % (self.S, self.E, self.D))
+        t = self._padded(t)
         with self.lock:
             call("vq_db_set_query", self._h, _np_ptr(t))
 
     def set_query_from_row(self, row: int, want: bool = True):
         """t = r/(r.r) of a resident row (target_clip.py:311-313), computed on the device."""
-        out = np.empty((self.S, self.E, self.D), dtype=np.float64) if want else None
+        out = np.empty((self.S, self.E, self.Dp), dtype=np.float64) if want else None
         with self.lock:
             call("vq_db_set_query_from_row", self._h, int(row), _np_ptr(out) if want else None)
-        return out
+        return self._logical(out) if want else None
 
     def bootstrap_target(self, valid_rows: Sequence[int], invalid_rows: Sequence[int] = (), mu: float = 0.0,
                          set_query: bool = True) -> np.ndarray:
@@ -535,11 +580,11 @@ class FeatureDB(BatchRounds):
         device; see csrc/vq_boot.hip).  With ``set_query`` they become the query of the next scan."""
         v = np.ascontiguousarray(valid_rows, dtype=np.int64)
         iv = np.ascontiguousarray(invalid_rows, dtype=np.int64)
-        out = np.empty((self.S, self.E, self.D), dtype=np.float64)
+        out = np.empty((self.S, self.E, self.Dp), dtype=np.float64)
         with self.lock:
             call("vq_db_bootstrap_target", self._h, _np_ptr(v), int(v.size), _np_ptr(iv) if iv.size else None, int(iv.size), float(mu),
                  _np_ptr(out), 1 if set_query else 0)
-        return out
+        return self._logical(out)
 
     def scan(self, weights: Sequence[float] | None = None, keep_sims: bool = False):
         """One pass over the DB (ticket.py:120-163 [+ 165-180 when weights are given])."""
@@ -557,6 +602,8 @@ class FeatureDB(BatchRounds):
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if t.ndim != 4 or t.shape[1:] != (self.S, self.E, self.D) or w.shape != (t.shape[0], self.S):
             raise ValueError("targets must be [Q,%d,%d,%d] and weights [Q,%d]" % (self.S, self.E, self.D, self.S))
+        if self.D != self.Dp:
+            raise ValueError("scan_batch is out of scope for a database of length %d stored at pitch %d" % (self.D, self.Dp))
         out = np.empty((t.shape[0], self.n), dtype=np.float64) if want else None
         call("vq_db_scan_batch", self._h, t.shape[0], _np_ptr(t), _np_ptr(w), _np_ptr(out) if want else None)
         return out
@@ -575,7 +622,10 @@ class FeatureDB(BatchRounds):
         S = self.S
         flags = 0
         if t is not None:
-            view("t", np.float64, (S, self.E, self.D))[...] = t
+            tv = view("t", np.float64, (S, self.E, self.Dp))
+            tv[..., :self.D] = t
+            if self.D != self.Dp:
+                tv[..., self.D:] = 0.0                        # the block is reused: the pads are written every time
             flags |= 1
         if weights is not None:
             view("weights", np.float64, (S,))[...] = weights
