@@ -379,7 +379,7 @@ enum {
      * 1x1 slots; w_off addresses W as [cout][cin] (Caffe's blob order), b_off the bias [cout]; cin, src_coff and w_off are multiples
      * of 4, cout and dst_coff are free (101 classes).  The bias is always added: has_bias must be 1 (refused otherwise) and b_off is
      * checked against the blob like w_off.  A launch of its own without tiling choices (its rows of a tiling table are
-     * zeros); the summation order of an output depends on cin alone (csrc/vq_tsn.hip: inner_product_kernel), never on the batch.
+     * zeros); the summation order of an output depends on cin alone (csrc/vq_tsn_ops.hip: inner_product_kernel), never on the batch.
      * Added without a new ABI version: a description that does not use it means what it meant. */
     VQ_OP_INNER_PRODUCT = 7
 };

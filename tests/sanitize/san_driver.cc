@@ -564,6 +564,26 @@ static int run() {
     PLAN_CHECK(vq::nearest_size(V{48, 80}, 64) == 48 && vq::nearest_size(V{80, 48}, 64) == 80);      // the first of equals
     PLAN_CHECK(vq::nearest_size(V{16}, 10) == 16 && vq::nearest_size(V{10}, 16) == 10);              // exactly 1.6x
     PLAN_CHECK(vq::nearest_size(V{17}, 10) == 0 && vq::nearest_size(V{10}, 17) == 0 && vq::nearest_size(V{}, 10) == 0);
+    // 6. the creation-time switches: the VQ_TSN_SPLIT and VQ_TSN_TILE grammars (expected values: the parsing vq_tsn_create did itself)
+    {
+        auto split = [](const char* v) { return vq::parse_tsn_options(nullptr, nullptr, nullptr, nullptr, nullptr, v, nullptr); };
+        auto is = [](const vq::TsnOptions& o, const V& parts) { return o.n_split == (int)parts.size() && o.split_parts == parts; };
+        PLAN_CHECK(is(split(nullptr), V{1, 1}));
+        PLAN_CHECK(is(split("1"), V{1}) && is(split("3"), V{1, 1, 1}) && is(split("2,1"), V{2, 1}));
+        PLAN_CHECK(is(split("0"), V{1}) && is(split("9"), V(8, 1)));                                  // clamped to 1 .. 8
+        PLAN_CHECK(is(split("0,0"), V{1, 1}) && is(split(","), V{1}) && is(split("a,b"), V{1, 1}));    // an entry below 1 counts as 1
+        PLAN_CHECK(is(split("1,2,3,4,5,6,7,8,9,10"), V{1, 2, 3, 4, 5, 6, 7, 8}));                     // cut to 8 sub-batches
+        auto tile = [](const char* v) { return vq::parse_tsn_options(nullptr, nullptr, nullptr, nullptr, v, nullptr, nullptr); };
+        auto has = [](const vq::TsnOptions& o, bool set, int bm, int bn, int bk, int pipe) {
+            return o.tile_set == set && o.tile[0] == bm && o.tile[1] == bn && o.tile[2] == bk && o.tile[3] == pipe;
+        };
+        PLAN_CHECK(has(tile(nullptr), false, 0, 0, 32, 0) && has(tile("x"), false, 0, 0, 32, 0));
+        PLAN_CHECK(has(tile("64x64"), true, 64, 64, 32, 0) && has(tile("128x64x16"), true, 128, 64, 16, 0) && has(tile("128x64x16x1"), true, 128, 64, 16, 1));
+        const vq::TsnOptions d = vq::parse_tsn_options(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        PLAN_CHECK(d.autotune && d.group_wino && d.group_pool && !d.poison && d.splitk);
+        const vq::TsnOptions f = vq::parse_tsn_options("0", "0", "0", "1", nullptr, nullptr, "0");
+        PLAN_CHECK(!f.autotune && !f.group_wino && !f.group_pool && f.poison && !f.splitk);
+    }
     printf("plan: ok (%d checks of validate_plan, %d mutations)\n", distinct, (int)(sizeof kMutations / sizeof kMutations[0]));
     return 0;
 }

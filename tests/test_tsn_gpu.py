@@ -95,7 +95,7 @@ def test_conv_bn_relu_layer(tsn, monkeypatch, cin, h, cout, k, s, p, n, tile):
 
 def test_maps_wider_than_the_reciprocal_range_run_the_plain_kernel(tsn, monkeypatch):
     """The pipelined kernel decodes a workgroup's pixels with 22-bit reciprocals (exact for output maps up to ~1 980 pixels wide, a sufficient
-    condition checked on the host: csrc/vq_tsn.hip:pixel_walk_ok); a 2 048-pixel-wide map asked for on a pipelined tiling runs the plain
+    condition checked on the host: csrc/vq_tsn_conv.hip:pixel_walk_ok); a 2 048-pixel-wide map asked for on a pipelined tiling runs the plain
     kernel of the same tiling instead.  A 1x1 convolution + BN + ReLU is a per-pixel function: the oracle is run on the first and the last
     two rows of the map; all tilings give the same bits."""
     bi, net = tsn

@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 N = 96                                          # the cfg-2 batch: 32 clips x 3 snippets
 T = 3
 PICK = list(range(N))                           # every crop: both sub-batches, their edges (47 | 48) and the ragged last M tiles
-# every tiling of the direct kernel's table, in the external form [bm, bn, bk, pipe] (csrc/vq_tsn.hip: kTiles)
+# every tiling of the direct kernel's table, in the external form [bm, bn, bk, pipe] (csrc/vq_tsn_conv.hip: kTiles)
 DIRECT = [(bm, bn, bk, pipe) for pipe in (0, 1) for bm, bn in ((128, 128), (128, 96), (128, 64), (64, 128), (64, 64), (128, 32), (32, 128))
           for bk in (32, 16)] + [(64, 256, 16, 0), (64, 256, 8, 3), (64, 64, 8, 3), (128, 64, 8, 3)]
 WINO = [(128, 32, 8, 2), (128, 64, 8, 2), (64, 32, 16, 2), (64, 64, 16, 2)]

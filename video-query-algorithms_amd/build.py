@@ -8,11 +8,11 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/vq_sim.hip", "csrc/vq_sim_batch.hip", "csrc/vq_rank.hip", "csrc/vq_db.hip", "csrc/vq_tsn.hip", "csrc/vq_wino.hip", "csrc/vq_boot.hip", "csrc/vq_frames.hip", "csrc/vq_comm.hip", "csrc/vq_flow.hip",
+SOURCES = ["csrc/vq_sim.hip", "csrc/vq_sim_batch.hip", "csrc/vq_rank.hip", "csrc/vq_db.hip", "csrc/vq_tsn.hip", "csrc/vq_tsn_conv.hip", "csrc/vq_tsn_ops.hip", "csrc/vq_wino.hip", "csrc/vq_boot.hip", "csrc/vq_frames.hip", "csrc/vq_comm.hip", "csrc/vq_flow.hip",
            "csrc/vq_jpeg.hip", "csrc/vq_csv.hip", "csrc/vq_rounds.hip", "csrc/vq_round_targets.hip", "csrc/vq_round_topk.hip"]
 # host-only translation units (no HIP include): plain C++, also built with sanitizers by tests/sanitize/Makefile
 HOST_SOURCES = ["csrc/host/vq_csv.cc", "csrc/host/vq_jpeg_host.cc", "csrc/host/vq_corners.cc", "csrc/host/vq_block_pool.cc", "csrc/host/vq_tsn_plan.cc", "csrc/host/vq_flow_host.cc", "csrc/host/vq_csv_read.cc"]
-HEADERS = ["csrc/vq_common.h", "csrc/vq_tsn_kernels.h", "csrc/vq_div9.h","csrc/host/vq_host.h", "csrc/host/vq_jpeg_host.h", "csrc/host/vq_corners.h", "csrc/host/vq_block_pool.h", "csrc/host/vq_tsn_plan.h", "csrc/host/vq_flow_host.h", "../include/vq_amd.h", "../include/vq_amd_rows.h", "../include/vq_amd_csv.h", "../include/vq_amd_rounds.h", "../include/vq_amd_round_views.h", "../include/vq_amd_round_fit.h", "../include/vq_amd_round_targets.h", "../include/vq_amd_round_topk.h", "../include/vq_amd_round_grid.h", "../include/vq_amd_round_update.h", "../include/vq_amd_round_shard.h", "../include/vq_amd_dim.h",
+HEADERS = ["csrc/vq_common.h", "csrc/vq_tsn_kernels.h", "csrc/vq_tsn_conv.h", "csrc/vq_div9.h","csrc/host/vq_host.h", "csrc/host/vq_jpeg_host.h", "csrc/host/vq_corners.h", "csrc/host/vq_block_pool.h", "csrc/host/vq_tsn_plan.h", "csrc/host/vq_flow_host.h", "../include/vq_amd.h", "../include/vq_amd_rows.h", "../include/vq_amd_csv.h", "../include/vq_amd_rounds.h", "../include/vq_amd_round_views.h", "../include/vq_amd_round_fit.h", "../include/vq_amd_round_targets.h", "../include/vq_amd_round_topk.h", "../include/vq_amd_round_grid.h", "../include/vq_amd_round_update.h", "../include/vq_amd_round_shard.h", "../include/vq_amd_dim.h",
            "csrc/vq_db.h", "csrc/vq_tile_index.h", "csrc/vq_gauss_jordan.h", "csrc/vq_select.h", "csrc/vq_score.h", "csrc/vq_decimal.h", "csrc/vq_pow5_table.h", "csrc/host/vq_csv_read.h"]
 OUT = os.path.join(HERE, "libvqamd.so")
 # -ffp-contract=off: score arithmetic must round like the reference's numpy scalars; FMAs are explicit

@@ -1,4 +1,4 @@
-// The process-wide pool of device blocks closed extractors leave for the next one (csrc/vq_tsn.hip): which block of which size on
+// The process-wide pool of device blocks closed extractors leave for the next one (csrc/vq_tsn.hip: device_pool, vq::PoolBlock): which block of which size on
 // which device is held, under a byte cap.  Pure bookkeeping over opaque pointers -- the hipMalloc / hipFree calls stay with the
 // caller -- so that it is a host-only translation unit the sanitizer builds can hammer from many threads.
 #pragma once

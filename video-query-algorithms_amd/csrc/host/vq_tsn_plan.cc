@@ -4,7 +4,9 @@
 #include "vq_tsn_plan.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define VQ_REQUIRE(cond, ...)                                            \
     do {                                                                 \
@@ -325,6 +327,37 @@ BatchCut cut_batch(const TsnPlan& plan, int n_crops, int T, const std::vector<in
     }
     cut.fused_consensus = whole;
     return cut;
+}
+
+TsnOptions parse_tsn_options(const char* autotune, const char* group, const char* group_pool, const char* poison, const char* tile,
+                             const char* split, const char* splitk) {
+    TsnOptions o;
+    if (autotune) o.autotune = atoi(autotune) != 0;
+    if (group) o.group_wino = atoi(group) != 0;
+    if (group_pool) o.group_pool = atoi(group_pool) != 0;
+    if (poison) o.poison = atoi(poison) != 0;
+    if (splitk) o.splitk = atoi(splitk) != 0;
+    if (tile) o.tile_set = sscanf(tile, "%dx%dx%dx%d", &o.tile[0], &o.tile[1], &o.tile[2], &o.tile[3]) >= 2;
+    if (split && strchr(split, ',')) {
+        o.split_parts.clear();
+        for (const char* q = split; *q;) {
+            o.split_parts.push_back(std::max(atoi(q), 1));
+            q = strchr(q, ',');
+            if (!q) break;
+            ++q;
+        }
+        o.n_split = std::min<int>((int)o.split_parts.size(), 8);
+        o.split_parts.resize(o.n_split);
+    } else {
+        o.n_split = std::min(std::max(split ? atoi(split) : 2, 1), 8);
+        o.split_parts.assign(o.n_split, 1);
+    }
+    return o;
+}
+
+TsnOptions tsn_options_from_env() {
+    return parse_tsn_options(getenv("VQ_TSN_AUTOTUNE"), getenv("VQ_TSN_GROUP"), getenv("VQ_TSN_GROUP_POOL"), getenv("VQ_TSN_POISON"),
+                             getenv("VQ_TSN_TILE"), getenv("VQ_TSN_SPLIT"), getenv("VQ_TSN_SPLITK"));
 }
 
 int nearest_size(const std::vector<int>& sizes, int n_crops) {

@@ -1,6 +1,6 @@
 // What the TSN executor (csrc/vq_tsn.hip) decides without touching the GPU: the validation of a layer plan against its tensor table,
 // the launch sequence, which convolutions run split over K, how a batch is cut into sub-batches, and which tuned batch size stands in
-// for another.  Host-only translation unit (no HIP include), so that tests/sanitize/san_driver.cc can drive every check of it under
+// for another, and the creation-time switches of the environment.  Host-only translation unit (no HIP include), so that tests/sanitize/san_driver.cc can drive every check of it under
 // the sanitizers; the constants both sides need live here once (csrc/vq_tsn_kernels.h includes this header for them).
 #pragma once
 #include <cstddef>
@@ -21,7 +21,7 @@ constexpr int kWinoMaxJobs = 4;
 constexpr int kWinoMaxPools = 2;
 
 // ... except the x-major space-to-depth stem (7x7 / stride 2 over c channels): four kernel rows of 7 x-taps x 2 rows x c floats each,
-// every row padded to whole 16-byte chunks, walked side by side (launch_conv_layer)
+// every row padded to whole 16-byte chunks, walked side by side (csrc/vq_tsn.hip: launch_conv_layer)
 inline int stem_rows_kp(int c) { return 4 * ((14 * c + 3) / 4 * 4); }
 
 // k*k*Cin of a convolution in ALGORITHMIC terms: a layer that reads slot 0 counts the un-padded input channels and,
@@ -76,6 +76,23 @@ void build_items(TsnPlan& plan, bool group_wino, bool group_pool);
 
 // plan.ksplit, plan.split_crop_floats, plan.max_cout: which direct convolutions run split over K (none when !enabled).
 void choose_ksplit(TsnPlan& plan, bool enabled);
+
+// The switches vq_tsn_create reads from the environment, parsed once (include/vq_amd.h documents them).
+struct TsnOptions {
+    bool autotune = true;          // VQ_TSN_AUTOTUNE != 0
+    bool group_wino = true;        // VQ_TSN_GROUP != 0: independent Winograd layers share a launch
+    bool group_pool = true;        // VQ_TSN_GROUP_POOL != 0: a level's pooling rides in its Winograd launch
+    bool poison = false;           // VQ_TSN_POISON != 0: NaN-fill every activation slot before a forward
+    bool splitk = true;            // VQ_TSN_SPLITK != 0: the 7 x 7 layers run split over K (choose_ksplit)
+    bool tile_set = false;         // VQ_TSN_TILE = "BMxBN[xBK[xP]]" (P = 1: pipelined kernel) gave at least BM and BN:
+    int tile[4] = {0, 0, 32, 0};   // ... [bm, bn, bk, pipe], which the executor resolves with tile_index
+    int n_split = 2;               // VQ_TSN_SPLIT = "n": n equal sub-batches (1 .. 8), or "a,b,..": up to 8 sub-batches of these
+    std::vector<int> split_parts = {1, 1};   // relative sizes ("2,1": 2/3 and 1/3 of the crops; an entry below 1 counts as 1)
+};
+// From the values of the seven variables, each null when unset
+TsnOptions parse_tsn_options(const char* autotune, const char* group, const char* group_pool, const char* poison, const char* tile,
+                             const char* split, const char* splitk);
+TsnOptions tsn_options_from_env();
 
 inline int parts_sum(const std::vector<int>& split_parts) {
     int sum = 0;

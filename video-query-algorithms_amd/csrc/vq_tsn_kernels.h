@@ -1,4 +1,5 @@
-// Kernel entry points shared between the TSN executor (vq_tsn.hip) and separately compiled kernel files.
+// What the TSN executor (vq_tsn.hip) and its separately compiled kernel files (vq_tsn_conv.hip, vq_tsn_ops.hip, vq_wino.hip) share:
+// device helpers, the pooling path, the Winograd launch, and the host launches of the small kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -336,6 +337,24 @@ constexpr int kWinoVariants = 2;   // output-channel blocks of 32 per workgroup:
 // ev_start / ev_stop (both or neither): events that receive the kernel's own begin / end timestamps
 // (hipExtLaunchKernelGGL) for per-launch profiling.  Returns a VQ_* status.
 int launch_wino_group(WinoGroup& g, int variant, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+
+// vq_tsn_ops.hip: one host launch per small kernel; each returns a VQ_* status.  ev_start / ev_stop: as for launch_wino_group.
+// n uint8 NHWC crops at src -> the fp32 input slot at dst (channels padded, or space-to-depth: vq_input_desc), minus mean
+int launch_preprocess(const uint8_t* src, float* dst, int n, const vq_input_desc& in, const vq_tensor_desc& t0, const float* mean,
+                      hipStream_t stream);
+// one pooling layer (after pool_plan): the window-specialised path where a.mode says so, else one thread per output
+int launch_pool(const PoolArgs& a, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+int launch_gavgpool(const float* in, float* out, int n, int HW, int Cs_in, int coff_in, int C, int Cs_out, int coff_out, hipStream_t stream,
+                    hipEvent_t ev_start, hipEvent_t ev_stop);
+// global pool + segment consensus of B whole clips of T <= kMaxFusedT snippets
+int launch_gavgpool_consensus(const float* in, float* out, double* feat, int B, int T, int HW, int Cs_in, int coff_in, int C, int Cs_out,
+                              int coff_out, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+int launch_inner_product(const float* x, int x_stride, const float* W, const float* bias, float* y, int y_stride, int M, int K, int N,
+                         hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+// the slices of a K-split convolution added in slice order, + bias, ReLU (M * Cout and M * Cs_out below 2^31: the caller checks)
+int launch_splitk_combine(const float* part, int ksplit, size_t slice_stride, int M, int Cout, const float* bias, int relu, float* out,
+                          int Cs_out, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+int launch_consensus(const float* per_snippet, double* feat, int B, int T, int D, int Cs, hipStream_t stream);
 
 // A launch whose begin / end timestamps land in two events when they are given: the timestamps come from the
 // dispatch packet itself, so the measured interval is the kernel alone (what rocprofv3 reports) and no extra

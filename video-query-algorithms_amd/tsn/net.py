@@ -19,7 +19,7 @@ from .. import _lib
 from .._lib import ConvSegment, InputDesc, LayerDesc, TensorDesc, call
 from .bn_inception import Graph, Plan
 
-BK = 32                      # K granularity of the implicit-GEMM kernel (csrc/vq_tsn.hip)
+BK = 32                      # K granularity of the implicit-GEMM kernel (csrc/vq_tsn_conv.hip)
 RGB_MEAN = (104.0, 117.0, 123.0)      # BGR order, as cv2.imread delivers frames
 FLOW_MEAN = (128.0,) * 10
 _OPS = {"conv": _lib.VQ_OP_CONV, "maxpool": _lib.VQ_OP_MAXPOOL, "avgpool": _lib.VQ_OP_AVGPOOL,
